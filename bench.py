@@ -16,6 +16,11 @@ changes is that the device may run kernels of neighbouring steps side by side (o
 VALU-bound first layers under another batch's MFMA-bound layers).  Per-kernel figures (roofline, --layers) are taken in a serial
 leg right after the timed region (one batch at a time, the kernel alone on the device) and the serial throughput is reported
 next to `value` ("serial"); --inflight 1 makes the timed region itself serial, as in rounds 1 and 2.
+
+A plain run does only what the headline needs: set-up, pre-roll and warm-up, the K timed steps, the outputs of the last timed
+step (--dump-outputs DIR) and the result line.  Everything else it can measure or check -- the no-pre-roll region, the serial
+leg, roofline and per-layer figures, the latency-plan, sustained-rate, energy and config[1] legs, the determinism self-check, the
+MI355_ACC_REF_F32 leg and the CPU baselines -- runs only with --full.
 """
 import argparse
 import ctypes
@@ -41,7 +46,7 @@ def parse_args():
     ap.add_argument("--graph", action="store_true", help="replay the layer loop as a hipGraph (no per-layer events)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-images", type=int, default=8, help="bounded CPU-baseline sample (images through the reference)")
-    ap.add_argument("--layers", action="store_true", help="print the per-layer table to stderr")
+    ap.add_argument("--layers", action="store_true", help="print the per-layer table to stderr (implies --full: the table comes from its legs)")
     ap.add_argument("--cpu-omp", action="store_true", help="(default since round 4; kept for old command lines)")
     ap.add_argument("--no-cpu-omp", action="store_true", help="skip the all-cores leg of the CPU baseline (the reference's MULTI_CORE=1 OpenMP build)")
     ap.add_argument("--cpu-omp-images", type=int, default=4, help="bounded sample of the all-cores leg")
@@ -72,7 +77,14 @@ def parse_args():
                          "100+ plain steps measures 0.244 (profiles/r05_warmup_curve.log); reported as `preroll_steps`")
     ap.add_argument("--selfcheck-passes", type=int, default=48,
                     help="determinism self-check before the warmup steps: that many passes over the input, yolo-output checksums compared (0: off)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (no-pre-roll region, serial leg, roofline, latency-plan / sustained / energy / config[1] "
+                         "legs, determinism self-check, MI355_ACC_REF_F32 leg, CPU baselines); a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the yolo outputs of the last timed step (float32, [batch][outputs]) as DIR/yolo_L<i>.npy")
+    a = ap.parse_args()
+    a.full = a.full or a.layers
+    return a
 
 
 METRICS = {"yolov3-tiny_quant.cfg": "images/sec yolov3-tiny INT8 416x416", "yolov3_quant.cfg": "images/sec yolov3 (full, 75 conv + 23 quantized shortcut) INT8 608x608"}
@@ -236,6 +248,28 @@ def microbench_config1(binding, iters=30):
             "us_per_launch": round(t * 1e6, 2), "achieved": round(ops / t / 1e12, 1), "unit": "TOP/s", "peak": round(PEAK_INT8_TOPS, 1),
             "frac": round(ops / t / 1e12 / PEAK_INT8_TOPS, 4), "ops_per_launch": ops, "launches": iters, "kernel_family": fam,
             "note": "HIP events on the launch stream around back-to-back launches, alone on the device, after the timed region; never part of `value`"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(net, binding, out_dir):
+    """--dump-outputs: what a caller of forward_network_gpu receives from the step `net` ran last -- the float32 outputs of every yolo
+    layer, [batch][outputs] -- as out_dir/yolo_L<i>.npy.  Past DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded
+    sample of its elements (sorted flat indices, so two builds of the project compare element for element).  Returns {name: shape}."""
+    import numpy as np
+    arrays = {f"yolo_L{i}": net.pull(i)["f32"].reshape(net.batch, -1) for i, inf in enumerate(net.info) if inf["type"] == binding.T_YOLO}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.size * DUMP_LIMIT_BYTES // total)
+            idx = np.sort(np.random.default_rng(1234).choice(a.size, keep, replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32))
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def flush_c_stdio():
@@ -484,7 +518,7 @@ def main():
     # (round 6, ADVICE r05 / VERDICT r05 #5: the rounds 1-4 protocol -- W warm-up steps, then K timed steps, nothing in front of them -- once, BEFORE the
     # pre-roll, so that the line carries both figures of the same run: `no_preroll` is comparable with BENCH_r01-r04, `value` with r05 on)
     no_preroll = None
-    if args.preroll > 0 and not args.no_preroll_leg:
+    if args.full and args.preroll > 0 and not args.no_preroll_leg:
         for i in range(args.warmup):
             nets[i % len(nets)].forward()
         barrier()
@@ -523,7 +557,7 @@ def main():
         net.profile_begin(n, prof_stride, phase)
         return n
 
-    prof_steps = arm_events((args.steps + ninfl - 1) // ninfl) if (ninfl == 1 or args.inflight_events) else arm_events(0)
+    prof_steps = arm_events((args.steps + ninfl - 1) // ninfl) if args.full and (ninfl == 1 or args.inflight_events) else arm_events(0)
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -541,6 +575,9 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
     flight_prof = net.profile_read() if (prof_steps and rank == 0) else None
+    dumped = None
+    if args.dump_outputs and rank == 0:  # the last timed step ran on instance (steps - 1) % ninfl; nothing has run on it since
+        dumped = dump_outputs(nets[(args.steps - 1) % ninfl], binding, args.dump_outputs)
 
     # ---- serial leg (only with several batches in flight): the same steps on ONE instance, nothing else on the device.  A kernel that
     # shares the CUs with another batch's kernels runs longer than alone, so per-kernel durations -- the roofline, the per-layer
@@ -548,7 +585,7 @@ def main():
     serial = None
     ser_dt = dt
     ser_steps = args.steps
-    if ninfl > 1:
+    if args.full and ninfl > 1:
         ser_steps = max(args.serial_steps, 2)
         prof_steps = arm_events(ser_steps)
         barrier()
@@ -567,7 +604,7 @@ def main():
     # whole-chip kernels of rounds 1-2 (128 x 384 row-image tiles, conv_ws3), so that their roofline stays on record next to
     # the half-CU kernels'.  Never part of `value`.
     latency_leg = None
-    if ninfl > 1 and plan == 1 and rank == 0 and world == 1 and not args.graph and not args.no_extra_legs:
+    if args.full and ninfl > 1 and plan == 1 and rank == 0 and world == 1 and not args.graph and not args.no_extra_legs:
         net.set("plan", 0)
         for _ in range(4):
             net.forward()
@@ -588,7 +625,7 @@ def main():
     # wall time / number of launches = what one launch costs the chip when the chip is kept full of this kernel -- no launch gap, fill or
     # tail between dependent launches, which is how the kernel runs in the timed region.  (tools/layer_flood.py does this for every layer.)
     sustained = sustained33 = energy = None
-    extra_legs = ninfl > 1 and rank == 0 and world == 1 and not args.graph and not args.no_extra_legs  # (world > 1: every other rank would sit in the final barrier meanwhile)
+    extra_legs = args.full and ninfl > 1 and rank == 0 and world == 1 and not args.graph and not args.no_extra_legs  # (world > 1: every other rank would sit in the final barrier meanwhile)
     s33_layers = [i for i, inf in enumerate(net.info) if inf["type"] == binding.T_CONV and inf["size"] == 3 and inf["stride"] == 1 and inf["c"] > 3]
     if extra_legs and (rows_layers or s33_layers):
         per = {}
@@ -687,7 +724,7 @@ def main():
     # resident input on every instance at once (their passes overlap on the device like the timed steps), a device-side order-independent checksum
     # of the yolo outputs after each pass; a pass that differs from the first fails the run.  After the timed region and its legs, never inside them.
     selfcheck = None
-    if args.selfcheck_passes > 0 and not args.graph:
+    if args.full and args.selfcheck_passes > 0 and not args.graph:
         for nk in nets:
             nk.selfcheck(args.selfcheck_passes)
         bad = sum(nk.selfcheck_result() for nk in nets)
@@ -862,7 +899,7 @@ def main():
     # MI355_ACC_REF_F32 = the verification kernel that emulates the reference's sequential fp32 accumulation (one thread per
     # output); same net, same batch, separate instance, never part of `value`.
     ref_f32 = None
-    if rank == 0 and world == 1 and not force_dist and not args.no_ref_f32 and os.path.basename(args.cfg).startswith("yolov3-tiny"):
+    if args.full and rank == 0 and world == 1 and not force_dist and not args.no_ref_f32 and os.path.basename(args.cfg).startswith("yolov3-tiny"):
         rnet = binding.Net(args.cfg, wts, batch=B, gpu=local_rank, accum=binding.ACC_REF_F32)
         rnet.prepare_fixed(1.0 / 255.0, 0)
         rnet.push_input(x)
@@ -879,7 +916,7 @@ def main():
                            "tests/test_gpu_parity.py::test_yolov3_tiny_416_ref_f32_equals_reference_hashes); verification mode, not the product path"}
 
     cpu = cpu_omp = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cfg, wts, args.cpu_images)
         if not args.no_cpu_omp and cpu and cpu["kind"] == "reference":
             # the reference's own all-cores build (Makefile MULTI_CORE=1: `#pragma omp parallel for` over the GEMM's output rows,
@@ -923,7 +960,8 @@ def main():
                                         else "eager launches, no events inside the timed region (per-kernel figures come from the serial leg after it)")),
                           "weight_broadcast_ms": round(bcast_ms, 3)},
                "roofline": roof, "serial": serial, "cpu_baseline": cpu if world == 1 else "see the n_gpus=1 line (timed on rank 0 at N=1 only)",
-               "accum_ref_f32_mode": ref_f32, "selfcheck": selfcheck}
+               "accum_ref_f32_mode": ref_f32, "selfcheck": selfcheck, "full": args.full,
+               "dumped_outputs": {"dir": args.dump_outputs, "arrays": dumped} if dumped is not None else None}
         if cpu_omp:
             out["cpu_baseline_omp"] = cpu_omp
         if layers:

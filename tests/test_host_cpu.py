@@ -339,14 +339,14 @@ def test_reference_side_binding_compiles_against_the_real_header(tmp_path):
         assert hasattr(L, "refdrv_mi355_bind") and hasattr(L, "mi355_bind_network") and hasattr(L, "forward_network_mi355")
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/cfg/yolov3_tiny_quant_channelwise.cfg"), reason="reference checkout absent (GPU box)")
-def test_host_parser_swallows_the_reference_s_shipped_cfg(tmp_path, cfg_dir):
+def test_host_parser_swallows_the_reference_s_shipped_cfg(tmp_path, cfg_dir, golden_dir):
     """the repo's cfgs are regenerated (tools/make_cfg.py, training keys stripped); host/parser.c must also take
     the reference's OWN file (ref cfg/yolov3_tiny_quant_channelwise.cfg through ref src/parser.c:579-674's key set: `# Training`
     comments, `start_quantization_step`, spaced `saturation = 1.5`, blank lines), and the same file with CRLF line ends.  Checked:
-    the 24 layer shapes of SURVEY.md section 8 and equality with the parse of the regenerated relu6 cfg."""
+    the 24 layer shapes of SURVEY.md section 8 and equality with the parse of the regenerated relu6 cfg.  The file is stored
+    byte for byte as the fixture tests/golden/yolov3_tiny_quant_channelwise.cfg."""
     from yolo_quantization_amd import binding
-    ref_cfg = "/root/reference/cfg/yolov3_tiny_quant_channelwise.cfg"
+    ref_cfg = os.path.join(golden_dir, "yolov3_tiny_quant_channelwise.cfg")
     crlf = tmp_path / "crlf.cfg"
     crlf.write_bytes(open(ref_cfg, "rb").read().replace(b"\r\n", b"\n").replace(b"\n", b"\r\n"))
     keys = ("type", "c", "h", "w", "n", "size", "stride", "pad", "out_c", "out_h", "out_w", "activation", "batch_normalize", "quantized", "quant_stop", "outputs")

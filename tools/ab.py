@@ -71,7 +71,7 @@ for rnd in range(a.rounds):
                 cells.append(f"{c[0]} s {c[2]} f {c[3]}")
             print(f"round {rnd} {name:12s} " + "  ".join(cells), flush=True)
         elif a.what == "bench":
-            cmd = [sys.executable, "bench.py", "--steps", str(a.steps), "--warmup", "30", "--no-cpu-baseline", "--no-ref-f32", "--inflight", kv.get("inflight", "4")] + extra
+            cmd = [sys.executable, "bench.py", "--steps", str(a.steps), "--warmup", "30", "--full", "--no-cpu-baseline", "--no-ref-f32", "--inflight", kv.get("inflight", "4")] + extra
             out, _ = run(cmd, env)
             try:
                 d = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])

@@ -13,10 +13,10 @@ tests)
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 | tee $O/smoke.log ;;
 bench)
   # the driver's command, then a long run with the per-layer table; one batch at a time under the latency plan for the round 1-2 kernels
-  timeout 900 python bench.py --steps 20 --warmup 5 2>$O/bench_driver_cmd.err | tee $O/bench_driver_cmd.json | cut -c1-400
-  timeout 900 python bench.py --steps 300 --warmup 30 --layers 2>$O/bench.err | tee $O/bench.json | cut -c1-300
+  timeout 900 python bench.py --steps 20 --warmup 5 --full 2>$O/bench_driver_cmd.err | tee $O/bench_driver_cmd.json | cut -c1-400
+  timeout 900 python bench.py --steps 300 --warmup 30 --full --layers 2>$O/bench.err | tee $O/bench.json | cut -c1-300
   cp gpurun_out/bench_layers_n1.json $O/bench_layers_throughput_plan.json
-  timeout 600 python bench.py --steps 300 --warmup 30 --inflight 1 --layers --no-cpu-baseline --no-ref-f32 2>$O/bench_if1.err | tee $O/bench_inflight1.json | cut -c1-300
+  timeout 600 python bench.py --steps 300 --warmup 30 --inflight 1 --full --layers --no-cpu-baseline --no-ref-f32 2>$O/bench_if1.err | tee $O/bench_inflight1.json | cut -c1-300
   cp gpurun_out/bench_layers_n1.json $O/bench_layers_latency_plan.json ;;
 sq)
   # SQ counters per kernel (instruction counts, busy cycles): two passes, one batch at a time under each plan's kernels
@@ -57,7 +57,7 @@ pmc)
   python tools/pmc_traffic.py $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_traffic.json | head -12
   rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE ;;
 bench608)
-  timeout 900 python bench.py --cfg cfg/yolov3_quant.cfg --batch 32 --steps 30 --warmup 3 --layers --selfcheck-passes 4 --serial-steps 8 2>$O/bench608.err > $O/bench608.json; python -c "import json; d=json.load(open('$O/bench608.json')); print('yolov3-608', d['value'], d['ms_per_step'], d['serial'])"
+  timeout 900 python bench.py --cfg cfg/yolov3_quant.cfg --batch 32 --steps 30 --warmup 3 --full --layers --selfcheck-passes 4 --serial-steps 8 2>$O/bench608.err > $O/bench608.json; python -c "import json; d=json.load(open('$O/bench608.json')); print('yolov3-608', d['value'], d['ms_per_step'], d['serial'])"
   grep "\[layer\]" $O/bench608.err > $O/bench608_layers.log; tail -3 $O/bench608.err ;;
 dist)
   BENCH_FORCE_DIST=1 timeout 600 python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-ref-f32 2>$O/bench_dist1.err > $O/bench_dist1.json; python -c "import json; d=json.loads(open('$O/bench_dist1.json').read().strip().splitlines()[-1]); print('force-dist', d['value'], d['config']['weight_broadcast_ms'])" ;;
