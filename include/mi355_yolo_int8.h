@@ -137,7 +137,10 @@ int mi355_tensor_to_nchw(const mi355_tensor *t, uint8_t *nchw, void *stream);
  * `zero_point_uint8` table ref: src/blas.c:290-300 and GEMM pass 2 ref: src/convolutional_layer.c:721 are
  * folded into per-channel constants).  weights_uint8: [n][c*k*k] in the reference's (ci,ky,kx) order
  * (ref: src/parser.c:1146), zp_w: [n].  Returns the packed blob size; writes it when `blob` != NULL.
- * The blob is position independent (offsets only) so it can be broadcast to other GPUs as bytes. */
+ * The blob is position independent (offsets only) so it can be broadcast to other GPUs as bytes.
+ * Accepted shapes: n >= 1, c >= 1, 1 <= ksize <= 11 (0 / MI355_EINVAL otherwise).  3x3 layers on c % 16 == 0 or on the
+ * 3-channel image and 1x1 layers on c % 16 == 0 get the specialised kernels' packing; every other shape the general
+ * kernel's (conv_kxk.hip), whose layout depends on (n, c, ksize) only, not on stride or padding. */
 size_t mi355_conv_pack_size(int n, int c, int ksize);
 int mi355_conv_pack(int n, int c, int ksize, const uint8_t *weights_uint8, const uint8_t *zp_w,
                     const int32_t *biases_int32, const double *M_value, const double *shift_value, void *blob);
@@ -151,7 +154,11 @@ int mi355_conv_pack(int n, int c, int ksize, const uint8_t *weights_uint8, const
 int mi355_conv_pack_epilogue(int n, int c, int ksize, int activation, int zp_act, void *blob);
 
 typedef struct mi355_conv_desc {
-    int n, c, ksize, stride, pad; /* filters, input channels, 1|3, 1|2, ksize/2 (stride 2: plain exact-mode convs, c % 16 == 0) */
+    int n, c, ksize, stride, pad; /* filters, input channels, kernel size 1..11, stride >= 1, padding >= 0 (the cfg's pad=1 means
+                                   * ksize/2).  The specialised 3x3 / 1x1 shapes (see mi355_conv_pack) run at stride 1 | 2 with
+                                   * pad = ksize/2 in exact mode (stride 2: 3x3, c % 16 == 0) and at any stride / padding in
+                                   * ref-f32 mode; every other shape at any stride and padding in both modes.  1x1 layers:
+                                   * stride 1, pad 0 only (the reference's 1x1 path is not a convolution otherwise). */
     int activation;               /* MI355_ACT_* */
     int store_mode;               /* MI355_STORE_* */
     int accum_mode;               /* MI355_ACC_* */

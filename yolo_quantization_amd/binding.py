@@ -183,9 +183,10 @@ class DevTensor:
         return C.byref(self.t)
 
 
-def conv_pack(wq, zp_w, c, ksize, biases_int32, M_value, shift_value, activation=None, zp_act=None):
+def conv_pack(wq, zp_w, c, ksize, biases_int32, M_value, shift_value, activation=None, zp_act=None, pad=None):
     """Host-side packing -> numpy uint8 blob.  With activation / zp_act the blob also gets the conv + maxpool kernels' epilogue
-    table (mi355_conv_pack_epilogue); without, those kernels derive the constants per workgroup (same bytes)."""
+    table (mi355_conv_pack_epilogue); without, those kernels derive the constants per workgroup (same bytes).  The packing
+    depends on (n, c, ksize) only: `pad` is accepted for symmetry with conv_forward and not used."""
     wq = np.ascontiguousarray(wq, np.uint8)
     n = wq.shape[0]
     sz = shim().mi355_conv_pack_size(n, c, ksize)
@@ -204,14 +205,15 @@ def conv_pack(wq, zp_w, c, ksize, biases_int32, M_value, shift_value, activation
 
 
 def conv_forward(x: DevTensor, wq, zp_w, ksize, biases_int32, M_value, shift_value, zp_in, zp_act, s_act,
-                 activation, store=STORE_WRAP, accum=ACC_EXACT, want_acc=True, want_f32=False, stride=1):
-    """One quantized conv layer through the C-ABI. Returns dict(u8 NCHW, int32 [B,n,HW], f32)."""
+                 activation, store=STORE_WRAP, accum=ACC_EXACT, want_acc=True, want_f32=False, stride=1, pad=None):
+    """One quantized conv layer through the C-ABI. Returns dict(u8 NCHW, int32 [B,n,HW], f32).  pad=None: ksize // 2."""
     n = wq.shape[0]
     c = x.t.C
     blob = DevBuf.from_numpy(conv_pack(wq, zp_w, c, ksize, biases_int32, M_value, shift_value))
     wraw = DevBuf.from_numpy(np.ascontiguousarray(wq, np.uint8))
     zraw = DevBuf.from_numpy(np.ascontiguousarray(zp_w, np.uint8))
-    pad = ksize // 2
+    if pad is None:
+        pad = ksize // 2
     OH, OW = (x.t.H + 2 * pad - ksize) // stride + 1, (x.t.W + 2 * pad - ksize) // stride + 1
     y = DevTensor(x.t.B, OH, OW, n, zp_act)
     cnt = x.t.B * n * OH * OW

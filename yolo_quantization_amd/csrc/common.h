@@ -29,7 +29,8 @@ struct ConvBlobHeader {
     uint64_t total;
     uint64_t off_shift;  // int32[mpad]: right shift s when shift_value == 2^-s exactly for every channel (pow2 == 1)
     int32_t pow2;        // 1: every shift_value is an exact power of two 2^-s with 0 <= s <= 31 (the reference's case)
-    int32_t pad_;
+    int32_t generic;     // 1: conv_kxk.hip packing (shapes outside the other kernels): wp = [mpad/32][ksteps][64 lanes][16 B] A fragments,
+                         // cb = unit bytes per tap (4 | 8 | 16), nchunks = channel chunks, spc = K-steps per chunk
     uint64_t off_mprime; // f64[mpad]: M_value * shift_value (exact product when pow2)
     uint64_t off_cwb;    // int32[mpad]: cw + biases_int32 (the two per-channel additive constants folded)
     uint64_t off_ws;     // conv_small.hip shapes only (3x3, c 16|32 with n 32|64, c 64 with n 64..128), else 0: A fragments of
@@ -37,6 +38,8 @@ struct ConvBlobHeader {
                          // c 32: 9 taps; c 64: 18 steps, two per tap)
     uint64_t off_ept;    // EptHeader + EptEntry[mpad] (+ the first layer's 4 KiB LEAKY byte table): the pooled kernels' per-channel epilogue
                          // constants for ONE (activation, zero point), written by mi355_conv_pack_epilogue; key 0 = not prepared
+    uint64_t off_gen;    // conv_kxk.hip A fragments [round_up(n, 128) / 32][ksteps][64 lanes][16 B] (K layout: kargs.h kxk_geom), or 0.
+                         // generic blobs: == off_wp; 3x3 blobs: a section behind the specialised kernels' data (their strides / paddings)
 };
 
 // ---------------------------------------------------------------------------------------------------------

@@ -120,6 +120,44 @@ struct LayoutArgs {
     int B, H, W, C, cs, lead;
 };
 
+// conv_kxk.hip: the general-shape convolution (any size 1..11, stride, padding, channel count) and its ref-f32 twin
+struct KxkArgs {
+    const uint8_t *x;        // input tensor: cs == 4 plain image cells, else biased PHWC (cs % 16 == 0)
+    int in_cs, in_lead;
+    int B, H, W, c;          // input map and channels
+    int n, ksize, stride, pad, OH, OW;
+    const int8_t *wk;        // packed A fragments [mpad / 32][ksteps][64 lanes][16 B] (ConvBlobHeader.generic)
+    int unit, nchunks, spc, ksteps;  // K layout: unit = channel bytes per tap (4 | 8 | 16), spc = K-steps per channel chunk
+    const int32_t *cw, *dzp, *bias, *cwb;
+    const double *mval, *sval, *mprime;
+    const ConvBlobHeader *hdr;  // device copy (pow2 flag)
+    const uint8_t *w_u8, *zp_w; // ref-f32 kernel: raw reference weights [n][c k k], zero points
+    uint8_t *y;
+    int out_cs, out_lead;
+    int32_t *acc_out;
+    float *y_f32;
+    int zp_in, zp_act, act, store_mode;
+    float s_act;
+    int tw_sh, tiles_x, tiles_y, mgroups, ph, pw;  // tile geometry (set by the launcher)
+};
+int conv_kxk_launch(KxkArgs &a, hipStream_t st);
+int conv_ref_f32_general_launch(KxkArgs &a, hipStream_t st);
+// K of the general kernel is (channel chunk, tap, channel in the chunk) with `unit` channel bytes per tap: few-channel layers pack 4 or 8
+// channels of a tap densely (the 3-channel image: 4-byte cells), the others 16-channel chunks (the last one padded with zero weights)
+inline int kxk_unit(int c) { return c <= 4 ? 4 : (c <= 8 ? 8 : 16); }
+struct KxkGeom { int unit, nchunks, spc, ksteps, mpad; };
+inline KxkGeom kxk_geom(int n, int c, int ksize)
+{
+    KxkGeom g;
+    g.unit = kxk_unit(c);
+    const int tpl = 16 / g.unit;                      // taps per 16-byte lane fragment
+    g.nchunks = g.unit == 16 ? (c + 15) / 16 : 1;
+    g.spc = (ksize * ksize + 2 * tpl - 1) / (2 * tpl);  // K-steps per chunk: 2 lane halves of tpl taps each
+    g.ksteps = g.nchunks * g.spc;
+    g.mpad = ((n + 127) / 128) * 128;                 // rows padded to the largest M tile
+    return g;
+}
+
 int yolo_detections_launch(const float *out, int B, int n, int classes, int h, int w, const float *biases, const int *mask,
                            int netw, int neth, int imw, int imh, float thresh, int relative, float *recs, int max_recs,
                            int *counts, hipStream_t st);

@@ -319,15 +319,30 @@ static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 static thread_local int g_last_kernel = 0;
 extern "C" int mi355_last_conv_kernel(void) { return g_last_kernel; }
 
+// every shape the specialised kernels do not take (size 1..11, any channel count) gets conv_kxk.hip's packing (header.generic)
+static bool specialised_shape(int c, int ksize) { return (ksize == 1 || ksize == 3) && ((c == 3 && ksize == 3) || c % 16 == 0); }
+
 static int blob_layout(int n, int c, int ksize, ConvBlobHeader *h)
 {
-    if (n <= 0 || c <= 0 || (ksize != 1 && ksize != 3)) return MI355_EINVAL;
+    if (n <= 0 || c <= 0 || ksize < 1 || ksize > 11) return MI355_EINVAL;
     memset(h, 0, sizeof(*h));
     h->magic = MI355_BLOB_MAGIC;
     h->n = n; h->c = c; h->ksize = ksize;
     h->ktrue = c * ksize * ksize;
     size_t off = align16(sizeof(ConvBlobHeader));
-    if (c == 3 && ksize == 3) {
+    const KxkGeom kg = kxk_geom(n, c, ksize);
+    const size_t gen_bytes = (size_t)(kg.mpad / 32) * kg.ksteps * 1024;
+    if (!specialised_shape(c, ksize)) {
+        // conv_kxk.hip: A fragments [mpad / 32][ksteps][64 lanes][16 B]; rows padded to the largest M tile (128)
+        h->generic = 1;
+        h->mpad = kg.mpad;
+        h->cb = kg.unit;
+        h->nchunks = kg.nchunks;
+        h->upc = ksize * ksize;
+        h->spc = kg.spc;
+        h->ksteps = kg.ksteps;
+        h->off_wp = off; h->off_gen = off; off = align16(off + gen_bytes);
+    } else if (c == 3 && ksize == 3) {
         h->first = 1;
         h->mpad = ((n + 3) / 4) * 4;
         h->cb = 4; h->nchunks = 1; h->upc = 9; h->spc = 9; h->ksteps = 9;
@@ -351,6 +366,10 @@ static int blob_layout(int n, int c, int ksize, ConvBlobHeader *h)
     h->off_shift = off; off = align16(off + (size_t)h->mpad * 4);
     h->off_mprime = off; off = align16(off + (size_t)h->mpad * 8);
     h->off_cwb = off; off = align16(off + (size_t)h->mpad * 4);
+    if (h->generic) {
+        h->total = off;
+        return MI355_OK;
+    }
     if (conv1x1_ws_eligible(n, c, ksize)) {  // conv1x1.hip: [n/32 quads][c/32 K-steps][64 lanes][16 B]
         h->off_ws = off;
         off = align16(off + (size_t)((n + 31) / 32) * (c / 32) * 1024);
@@ -369,6 +388,10 @@ static int blob_layout(int n, int c, int ksize, ConvBlobHeader *h)
         off = align16(off + sizeof(EptHeader) + (size_t)h->mpad * sizeof(EptEntry) + (size_t)LUTQ_N +
                       (h->first ? (size_t)((n + 15) / 16) * 64 * sizeof(L0Lane) : 0));
     }
+    if (ksize == 3) {  // the general kernel's fragments for the strides / paddings the 3x3 kernels refuse, behind everything they read
+        h->off_gen = off;
+        off = align16(off + gen_bytes);
+    }
     h->total = off;
     return MI355_OK;
 }
@@ -384,7 +407,7 @@ int mi355_conv_pack(int n, int c, int ksize, const uint8_t *wq, const uint8_t *z
                     const double *M_value, const double *shift_value, void *blob)
 {
     ConvBlobHeader h;
-    if (blob_layout(n, c, ksize, &h) != MI355_OK) return einval("conv_pack: need ksize 1|3 and c==3 or c%16==0");
+    if (blob_layout(n, c, ksize, &h) != MI355_OK) return einval("conv_pack: need n >= 1, c >= 1 and 1 <= ksize <= 11");
     if (!wq || !zp_w || !biases_int32 || !M_value || !shift_value || !blob) return einval("conv_pack: null");
     char *base = (char *)blob;
     memset(base, 0, (size_t)h.total);
@@ -415,10 +438,26 @@ int mi355_conv_pack(int n, int c, int ksize, const uint8_t *wq, const uint8_t *z
         dzp[oc] = d;
         long sw = 0;
         for (int k = 0; k < K; ++k) sw += (int)wq[(size_t)oc * K + k] - 128;
-        cw[oc] = (int32_t)(128 * sw + 128L * K * d);  // 128*sum(w') + 128*K*d   (|.| < 2^28 for K <= 9216)
+        cw[oc] = (int32_t)(uint32_t)(128 * sw + 128L * K * d);  // 128*sum(w') + 128*K*d   (|.| < 2^28 for K <= 9216; modulo 2^32 beyond, like the accumulators)
         ((int32_t *)(base + h.off_cwb))[oc] = (int32_t)((uint32_t)cw[oc] + (uint32_t)biases_int32[oc]);
         ((double *)(base + h.off_mprime))[oc] = M_value[oc] * shift_value[oc];
     }
+    if (h.off_gen) {  // conv_kxk.hip: lane (row lane % 32, half kh = lane / 32) of K-step g; byte e = tap slot (2 st + kh) tpl + e / U, channel e % U
+        int8_t *wp = (int8_t *)(base + h.off_gen);
+        const KxkGeom kg = kxk_geom(n, c, ksize);
+        const int U = kg.unit, tpl = 16 / U, kk = ksize * ksize;
+        for (int mt = 0; mt < kg.mpad / 32; ++mt)
+            for (int g = 0; g < kg.ksteps; ++g)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int oc = 32 * mt + (lane & 31), kh = lane >> 5, ch = g / kg.spc, st = g % kg.spc;
+                    int8_t *dst = wp + ((size_t)(mt * kg.ksteps + g) * 64 + lane) * 16;
+                    for (int e = 0; e < 16; ++e) {
+                        const int t = (2 * st + kh) * tpl + e / U, ci = ch * U + e % U;
+                        dst[e] = (oc < n && t < kk && ci < c) ? (int8_t)(wq[(size_t)oc * K + (ci * ksize + t / ksize) * ksize + t % ksize] ^ 0x80) : 0;
+                    }
+                }
+    }
+    if (h.generic) return MI355_OK;
     if (h.first) {
         uint32_t *wp = (uint32_t *)(base + h.off_wp);
         for (int oc = 0; oc < n; ++oc)
@@ -592,12 +631,75 @@ int mi355_conv_pack_epilogue(int n, int c, int ksize, int activation, int zp_act
 }
 
 // ------------------------------------------------------------------------------------------------ convolution
+// The shapes outside the specialised kernels (conv_kxk.hip): plain convolutions of size 1..11 at any stride and padding, exact mode
+// on the generic packing, ref-f32 mode on any packing.  No fused form: MI355_EINVAL, nothing launched, and the caller runs the
+// layer after the conv on its own.
+static int conv_generic_forward(const mi355_conv_desc *d, const mi355_tensor *x, const void *blob, const uint8_t *w_u8,
+                                const uint8_t *zp_w, const mi355_tensor *y, int32_t *acc_out, float *y_f32, hipStream_t st,
+                                bool fused)
+{
+    if (fused) return einval("conv_forward: fused maxpool / upsample / yolo / shortcut forms exist for the specialised shapes only");
+    if (d->stride < 1 || d->pad < 0) return einval("conv_forward: need stride >= 1 and pad >= 0");
+    if (d->ksize == 1 && (d->stride != 1 || d->pad != 0))
+        return einval("conv_forward: stride 2 exists for plain exact-mode 3x3 convs with c % 16 == 0 only (the reference's 1x1 path "
+                      "feeds the input to the GEMM unsampled, src/convolutional_layer.c:711-716)");
+    const long OHl = ((long)x->H + 2L * d->pad - d->ksize) / d->stride + 1, OWl = ((long)x->W + 2L * d->pad - d->ksize) / d->stride + 1;
+    if (x->H + 2L * d->pad < d->ksize || x->W + 2L * d->pad < d->ksize || OHl < 1 || OWl < 1)
+        return einval("conv_forward: the padded map is smaller than the kernel");
+    const int OH = (int)OHl, OW = (int)OWl;
+    if (x->C != d->c) return einval("conv_forward: x.C != desc.c");
+    if (y && (y->C != d->n || y->B != x->B || y->H != OH || y->W != OW || !y->data)) return einval("conv_forward: y shape");
+    if (x->cs == 1) return einval("conv_forward: the planar (cs==1) layout is accepted for the exact-mode 3-channel first layer only");
+    if (x->cs != 4 && x->cs % 16) return einval("conv_forward: x.cs must be 4 or a multiple of 16");
+    ConvBlobHeader h;
+    if (blob_layout(d->n, d->c, d->ksize, &h) != MI355_OK) return einval("conv_forward: shape");
+    const char *base = (const char *)blob;
+    KxkArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = (const uint8_t *)x->data; a.in_cs = x->cs; a.in_lead = x->lead;
+    a.B = x->B; a.H = x->H; a.W = x->W; a.c = d->c;
+    a.n = d->n; a.ksize = d->ksize; a.stride = d->stride; a.pad = d->pad; a.OH = OH; a.OW = OW;
+    a.cw = (const int32_t *)(base + h.off_cw); a.dzp = (const int32_t *)(base + h.off_dzp);
+    a.bias = (const int32_t *)(base + h.off_bias); a.cwb = (const int32_t *)(base + h.off_cwb);
+    a.mval = (const double *)(base + h.off_mval); a.sval = (const double *)(base + h.off_sval);
+    a.mprime = (const double *)(base + h.off_mprime);
+    a.hdr = (const ConvBlobHeader *)base;
+    a.w_u8 = w_u8; a.zp_w = zp_w;
+    a.y = y ? (uint8_t *)y->data : nullptr; a.out_cs = y ? y->cs : 0; a.out_lead = y ? y->lead : 0;
+    a.acc_out = acc_out; a.y_f32 = y_f32;
+    a.zp_in = d->zp_in; a.zp_act = d->zp_act; a.act = d->activation; a.store_mode = d->store_mode; a.s_act = d->s_act;
+    if (d->accum_mode == MI355_ACC_REF_F32) {
+        if (!w_u8 || !zp_w) return einval("conv_forward: ref-f32 mode needs the raw weights_uint8 / zp_w");
+        g_last_kernel = 6;
+        return conv_ref_f32_general_launch(a, st);
+    }
+    if (!h.off_gen) return einval("conv_forward: this blob carries no general-kernel fragments");
+    const KxkGeom kg = kxk_geom(d->n, d->c, d->ksize);
+    a.wk = (const int8_t *)(base + h.off_gen);
+    a.unit = kg.unit; a.nchunks = kg.nchunks; a.spc = kg.spc; a.ksteps = kg.ksteps;
+    if ((uintptr_t)x->data % (uintptr_t)kg.unit)
+        return einval("conv_forward: the general kernel reads unit-sized channel groups: x.data (a channel window of x included) must be "
+                      "aligned to 4 bytes for c <= 4, 8 for c <= 8, 16 otherwise");
+    const int rc = conv_kxk_launch(a, st);
+    if (rc == MI355_EINVAL) return einval("conv_forward: no tile of the general kernel fits this shape in LDS (stride too large for the kernel size)");
+    g_last_kernel = 9;
+    return rc;
+}
+
 static int conv_forward_impl(const mi355_conv_desc *d, const mi355_tensor *x, const void *blob, const uint8_t *w_u8,
                              const uint8_t *zp_w, const mi355_tensor *y, const mi355_tensor *ypool, int32_t *acc_out,
                              float *y_f32, void *stream, float *yolo_out = nullptr, int yolo_classes = 0, int up = 1,
                              const mi355_tensor *res = nullptr, int sc_ka = 0, int sc_kb = 0, int sc_k0 = 0)
 {
     if (!d || !x || !x->data || !blob) return einval("conv_forward: null");
+    if (d->ksize < 1 || d->ksize > 11) return einval("conv_forward: size must be 1..11 (larger kernels are not supported)");
+    {  // the general kernels: shapes the specialised kernels do not take, and the strides / paddings they refuse
+        const bool legacy_geom = d->stride == 1 && ((d->ksize == 3 && d->pad == 1) || (d->ksize == 1 && d->pad == 0));
+        const bool legacy_exact = legacy_geom || (d->stride == 2 && d->ksize == 3 && d->pad == 1 && d->c % 16 == 0);
+        if (!specialised_shape(d->c, d->ksize) || !(d->accum_mode == MI355_ACC_REF_F32 ? legacy_geom : legacy_exact))
+            return conv_generic_forward(d, x, blob, w_u8, zp_w, y, acc_out, y_f32, (hipStream_t)stream,
+                                        ypool || up != 1 || yolo_out || res);
+    }
     if (d->stride != 1 && d->stride != 2) return einval("conv_forward: stride must be 1 or 2");
     if (d->stride == 2 && (d->ksize != 3 || ypool || up != 1 || yolo_out || d->accum_mode != MI355_ACC_EXACT || d->c % 16))
         return einval("conv_forward: stride 2 exists for plain exact-mode 3x3 convs with c % 16 == 0 only (the reference's 1x1 path "

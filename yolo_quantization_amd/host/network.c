@@ -310,10 +310,16 @@ void quantization_prep_host(network *net, float in_scale, uint8_t in_zp)
         layer *l = &net->layers[i];
         if (l->type != CONVOLUTIONAL) continue;
         prep_conv_layer(net, i);
+        /* a 3-filter conv stores 4-byte cells of plain bytes (the image's layout); only a convolution reads those */
+        if (l->n == 3 && ((i + 1 < net->n && net->layers[i + 1].type != CONVOLUTIONAL && net->layers[i + 1].type != ROUTE) ||
+                          output_read_elsewhere(net, i))) {
+            fprintf(stderr, "layer %d: a 3-filter convolution can only feed another convolution\n", i);
+            error("unsupported layer after a 3-filter convolution");
+        }
         size_t sz = mi355_conv_pack_size(l->n, l->c, l->size);
         if (!sz) {
             fprintf(stderr, "layer %d: conv %dx%d, %d->%d channels is not supported by the gfx950 kernels "
-                            "(need size 1|3 and c==3 or c%%16==0)\n", i, l->size, l->size, l->c, l->n);
+                            "(sizes above 11 are refused)\n", i, l->size, l->size, l->c, l->n);
             error("unsupported convolution shape");
         }
         free(l->blob_host);
