@@ -80,6 +80,7 @@ struct layer {
     float *anchors; /* the reference calls this l.biases for yolo layers */
     float *anchors_gpu, *det_recs_gpu; /* on-device box decode (network_yolo_detections_gpu): anchors, records, counts */
     int *mask_gpu, *det_counts_gpu, det_cap;
+    int *det_sizes_gpu; /* [2][batch] source widths, heights (network_yolo_detections_gpu_sizes) */
 
     /* host mirrors of the outputs, reference layout (filled by pull_layer_output) */
     float *output;               /* [batch][outputs] float (quant_stop convs, yolo) */
@@ -174,6 +175,19 @@ struct network {
     int prof_cap, prof_used;
     int prof_stride, prof_calls; /* events are recorded on every prof_stride-th forward (they cost ~2.4 us per layer) ... */
     int prof_phase;              /* ... the ones with call index % prof_stride == prof_phase */
+    /* per-image input quantisation (set_input_quantization_per_image): layer 0 runs on a bank of blobs, one per distinct
+     * (scale, zero point) of the batch; the bank's slots are a cache keyed by (scale bits, zero point).  A replica owns its own. */
+    int per_image;
+    void *pi_bank_gpu, *pi_bank_host; /* [pi_cap] layer-0 blobs, pi_entry_bytes apart (host: staging of the uploads) */
+    size_t pi_entry_bytes;
+    int pi_cap;
+    uint32_t *pi_key_scale;     /* [pi_cap] float bits of the slot's input scale */
+    int *pi_key_zp;             /* [pi_cap] its zero point, -1: empty */
+    long *pi_stamp;             /* [pi_cap] last batch that used the slot */
+    long pi_tick;
+    void *pi_idx_gpu, *pi_idx_host; /* [B] int32 entry | [B] float scale | [B] uint8 zero point */
+    float *pi_mm_gpu, *pi_mm_host;  /* [B][2] max, min */
+    int pi_packed;              /* bank entries packed by the last batch (the others came from the cache) */
 };
 
 /* ---- construction / IO ------------------------------------------------------------------------------------ */
@@ -198,6 +212,17 @@ void quantization_weights_and_activations_gpu(network *net, const float *input_g
  * into batch slot `slot` of the network's float input, then the layer-0 quantiser over the whole batch. */
 void network_letterbox_input_gpu(network *net, int slot, const float *im_gpu, int imw, int imh);
 void network_quantize_input_gpu(network *net);
+/* Per-image input quantisation, opt-in (off: image 0 defines the scale of the whole batch, as before).  On: every image of a batch is
+ * quantised with its own min / max, scale and zero point, and layer 0 runs with that image's constants (mi355_conv_forward_per_image):
+ * slot b of every layer equals the batch-1 run on image b.  The quantisers above honour it.  Returns 0, or MI355_EINVAL with a message
+ * when layer 0 is not a 3 -> n 3x3 stride-1 convolution (the general kernel is not served per image) or the network holds no raw
+ * layer-0 weights to derive the constants from.  A replica made afterwards inherits the mode and keeps its own bank. */
+int set_input_quantization_per_image(network *net, int on);
+/* layer 0's blob for input scale s / zero point zp into dst (mi355_conv_pack_size bytes): one bank entry, derived by the host prep
+ * exactly as the per-image quantisers derive it; the network's layer-0 record is unchanged afterwards.  Host only (no device). */
+void network_layer0_entry(network *net, float s, uint8_t zp, void *dst);
+/* the (scale, zero point) of every image of the last per-image batch: scale[batch], zp[batch] */
+void network_input_quantization(network *net, float *scale, uint8_t *zp);
 /* the host half of the prep only (per-channel integers + packed blobs, no device needed) */
 void quantization_prep_host(network *net, float in_scale, uint8_t in_zp);
 
@@ -230,6 +255,9 @@ void pull_layer_output(network *net, int i);
  * the reference's loop), counts: [batch] detections found (records beyond max_recs are dropped). */
 void network_yolo_detections_gpu(network *net, int i, int imw, int imh, float thresh, int relative, float *recs,
                                  int max_recs, int *counts);
+/* the same with one source image size per batch slot (imw[b], imh[b]: host arrays) for correct_yolo_boxes */
+void network_yolo_detections_gpu_sizes(network *net, int i, const int *imw, const int *imh, float thresh, int relative, float *recs,
+                                       int max_recs, int *counts);
 
 /* ---- detections (what `detector test` does after network_predict; ref: include/darknet.h:658-669) -------------------- */
 typedef struct { float x, y, w, h; } box;

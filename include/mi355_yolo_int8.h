@@ -221,6 +221,23 @@ int mi355_conv_upsample_forward(const mi355_conv_desc *desc, const mi355_tensor 
 int mi355_conv_shortcut_forward(const mi355_conv_desc *desc, const mi355_tensor *x, const void *blob, const mi355_tensor *from,
                                 const mi355_tensor *y_sum, int32_t Ka, int32_t Kb, uint8_t zp_from, uint8_t zp_out, void *stream);
 
+/* Layer 0 with one input scale / zero point PER IMAGE.  Only layer 0 depends on the input scale (ref: src/blas.c:300-333), so each image
+ * needs its own layer-0 constants: a BANK is E blobs of this layer at a fixed byte stride entry_bytes (a multiple of 16, at least
+ * mi355_conv_pack_size), each the mi355_conv_pack (+ mi355_conv_pack_epilogue) output for one (s_in, zp_in) -- same weights, zero
+ * points and activation in every entry.  Image b uses entry entry_of_image[b] (int32, device) and pads with zp_in_of_image[b] (uint8,
+ * device); desc.zp_in is ignored.  Images with equal (s_in, zp_in) may share an entry.  Every slot's bytes equal the shared-scale call
+ * at batch 1 on that image with that image's blob.  Because the kernel arguments point at the bank and the index arrays, a captured
+ * graph stays valid when their contents change.  Served by the first-layer kernels only: 3 -> n, 3x3, stride 1, pad 1 (exact mode:
+ * the MFMA kernels for 16 / 32 filters on even maps, the VALU kernels otherwise; ref-f32 mode: the emulation kernel); any other
+ * shape returns MI355_EINVAL up front.  Pad cells of a cs == 4 tensor are never read by these calls (the bottom pad row of image b
+ * is the top pad row of image b + 1, which cannot hold two zero points): out-of-image taps take the image's zero point in registers. */
+int mi355_conv_forward_per_image(const mi355_conv_desc *desc, const mi355_tensor *x, const void *bank, size_t entry_bytes,
+                                 const int32_t *entry_of_image, const uint8_t *zp_in_of_image, const uint8_t *w_u8,
+                                 const uint8_t *zp_w, const mi355_tensor *y, int32_t *acc_out, float *y_f32, void *stream);
+int mi355_conv_pool_forward_per_image(const mi355_conv_desc *desc, const mi355_tensor *x, const void *bank, size_t entry_bytes,
+                                      const int32_t *entry_of_image, const uint8_t *zp_in_of_image, const mi355_tensor *y,
+                                      const mi355_tensor *ypool, void *stream);
+
 /* Tile configuration override for benchmarking (0 = auto). */
 int mi355_conv_set_tile(int bm, int bn);
 /* Development switches.  Bits 0..8 are timing ablations of the K loop (no DMA / no s_barrier / no MFMA / ...), compiled
@@ -271,6 +288,13 @@ int mi355_letterbox_forward(const float *im_f32, int imw, int imh, int c, float 
  * (double)zero_point), 0, 255), the reference's evaluation order (:160-165). */
 int mi355_image_minmax(const float *x_f32, long count, float *minmax, void *stream);
 int mi355_image_quantize(const float *x_f32, long count, float scale, int zero_point, uint8_t *out_u8, void *stream);
+/* Per-image input quantisation (opt-in; the calls above keep "image 0 defines the scale"): B images of count_per_image floats each.
+ * mi355_image_minmax_batched: minmax[2 b], minmax[2 b + 1] = mi355_image_minmax of image b (same seeds, NaN handling, comparisons), one
+ * launch.  mi355_image_quantize_per_image: image b quantised with scale_dev[b], zp_dev[b] -- read from DEVICE memory, so that a captured
+ * graph stays valid for the next batch's scales -- in mi355_image_quantize's evaluation order.  B <= 65535. */
+int mi355_image_minmax_batched(const float *x_f32, int B, long count_per_image, float *minmax, void *stream);
+int mi355_image_quantize_per_image(const float *x_f32, int B, long count_per_image, const float *scale_dev, const uint8_t *zp_dev,
+                                   uint8_t *out_u8, void *stream);
 /* *sum_dev += an order-independent 64-bit checksum of `dwords` 32-bit words at buf (device pointers; zero *sum_dev first).  The
  * host's determinism self-check compares it between passes over the same input (network_selfcheck, darknet_q.h). */
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream);
@@ -287,6 +311,11 @@ int mi355_yolo_forward(const float *in, float *out, int B, int n, int classes, i
 int mi355_yolo_detections(const float *yolo_out, int B, int n, int classes, int H, int W, const float *anchors,
                           const int *mask, int netw, int neth, int imw, int imh, float thresh, int relative, float *recs,
                           int max_recs, int *counts, void *stream);
+
+/* mi355_yolo_detections with one letterbox source size per image: imw_dev[b], imh_dev[b] (int, device memory). */
+int mi355_yolo_detections_sizes(const float *yolo_out, int B, int n, int classes, int H, int W, const float *anchors,
+                                const int *mask, int netw, int neth, const int *imw_dev, const int *imh_dev, float thresh,
+                                int relative, float *recs, int max_recs, int *counts, void *stream);
 
 #ifdef __cplusplus
 }

@@ -96,6 +96,13 @@ def shim():
         L.mi355_image_minmax.argtypes = [vp, C.c_long, vp, vp]
         L.mi355_letterbox_forward.argtypes = [vp, ci, ci, ci, vp, ci, ci, vp]
         L.mi355_image_quantize.argtypes = [vp, C.c_long, C.c_float, ci, vp, vp]
+        L.mi355_image_minmax_batched.argtypes = [vp, ci, C.c_long, vp, vp]
+        L.mi355_image_quantize_per_image.argtypes = [vp, ci, C.c_long, vp, vp, vp, vp]
+        L.mi355_conv_forward_per_image.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.c_size_t, vp, vp, vp, vp,
+                                                   C.POINTER(Tensor), vp, vp, vp]
+        L.mi355_conv_pool_forward_per_image.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.c_size_t, vp, vp,
+                                                        C.POINTER(Tensor), C.POINTER(Tensor), vp]
+        L.mi355_yolo_detections_sizes.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, C.c_float, ci, vp, ci, vp, vp]
         _shim = L
     return _shim
 
@@ -293,6 +300,16 @@ def host():
         L.network_load_packed.argtypes = [vp, C.c_char_p]
         L.dnq_layer_conv_kernel.argtypes = [vp, ci]
         L.dnq_layer_conv_kernel.restype = ci
+        L.set_input_quantization_per_image.argtypes = [vp, ci]
+        L.set_input_quantization_per_image.restype = ci
+        L.network_input_quantization.argtypes = [vp, vp, vp]
+        L.network_yolo_detections_gpu_sizes.argtypes = [vp, ci, vp, vp, C.c_float, ci, vp, ci, vp]
+        L.dnq_net_pi_packed.argtypes = [vp]
+        L.dnq_net_pi_entry_bytes.argtypes = [vp]
+        L.dnq_net_pi_entry_bytes.restype = C.c_long
+        L.network_layer0_entry.argtypes = [vp, C.c_float, C.c_uint8, vp]
+        L.dnq_net_graph.argtypes = [vp]
+        L.dnq_net_graph.restype = vp
         _host = L
     return _host
 
@@ -350,6 +367,7 @@ class Net:
         r.keep_head_float = self.keep_head_float
         r.n, r.batch, r.inputs, r.info = self.n, self.batch, self.inputs, self.info
         r._parent = self  # keeps the parent alive
+        r.per_image = getattr(self, "per_image", False)
         return r
 
     def prepare_fixed(self, in_scale=1.0 / 255.0, in_zp=0):
@@ -358,13 +376,36 @@ class Net:
     def prepare_host_only(self, in_scale=1.0 / 255.0, in_zp=0):
         self.H.quantization_prep_host(self.h, np.float32(in_scale), in_zp)
 
+    def set_input_per_image(self, on=True):
+        """Per-image input quantisation (darknet_q.h set_input_quantization_per_image): every image of a batch gets its own
+        scale / zero point and layer-0 constants.  Off (the default): image 0 defines the scale of the batch.  Raises
+        MI355Error when layer 0 cannot be served per image.  While it is on, the prepare_from_* calls return
+        (uint8 input, scale[batch], zero_point[batch])."""
+        rc = self.H.set_input_quantization_per_image(self.h, int(bool(on)))
+        if rc != 0:
+            raise MI355Error(f"set_input_quantization_per_image: code {rc} (layer 0 is not served per image)")
+        self.per_image = bool(on)
+
+    def input_quantization(self):
+        """(scale[batch] float32, zero_point[batch] uint8) the last batch was quantised with."""
+        s = np.zeros(self.batch, np.float32)
+        z = np.zeros(self.batch, np.uint8)
+        self.H.network_input_quantization(self.h, s.ctypes.data, z.ctypes.data)
+        return s, z
+
+    def _prepared(self, xq):
+        if getattr(self, "per_image", False):
+            s, z = self.input_quantization()
+            return xq, s, z
+        return xq
+
     def prepare_from_float(self, x_float):
         """Reference flow: dynamic layer-0 quantiser on the float image(s) (src/blas.c:279)."""
         x = np.ascontiguousarray(x_float, np.float32).ravel()
         assert x.size == self.batch * self.inputs
         C.memmove(self.H.dnq_net_input_float(self.h), x.ctypes.data, x.nbytes)
         self.H.quantization_weights_and_activations(self.h)
-        return _as(self.H.dnq_net_input_host(self.h), self.batch * self.inputs, C.c_uint8).copy()
+        return self._prepared(_as(self.H.dnq_net_input_host(self.h), self.batch * self.inputs, C.c_uint8).copy())
 
     def prepare_from_float_gpu(self, x_float):
         """The same with the quantiser on the device: the floats are uploaded as they are, min / max and the per-element
@@ -378,7 +419,7 @@ class Net:
         check(shim().mi355_d2h(out.ctypes.data, self.input_gpu_ptr(), out.nbytes, None), "d2h")
         check(shim().mi355_stream_sync(None), "sync")
         buf.free()
-        return out
+        return self._prepared(out)
 
     def prepare_from_images_gpu(self, images):
         """Device input path: every image (float32 [c][h][w], any size) is uploaded, letterboxed into its batch slot and
@@ -397,7 +438,7 @@ class Net:
         check(shim().mi355_stream_sync(None), "sync")
         for b in bufs:
             b.free()
-        return out
+        return self._prepared(out)
 
     def push_input(self, x_u8):
         x = np.ascontiguousarray(x_u8, np.uint8).ravel()
@@ -458,6 +499,36 @@ class Net:
         self.H.network_yolo_detections_gpu(self.h, i, imw, imh, C.c_float(thresh), int(relative), recs.ctypes.data, max_recs,
                                            counts.ctypes.data)
         return counts, recs
+
+    def detections_sizes(self, i, classes, imw, imh, thresh, relative, max_recs):
+        """detections() with one source image size per batch slot: imw, imh are sequences of `batch` ints."""
+        recs = np.zeros((self.batch, max_recs, 6 + classes), np.float32)
+        counts = np.zeros(self.batch, np.int32)
+        w = np.ascontiguousarray(imw, np.int32)
+        h = np.ascontiguousarray(imh, np.int32)
+        assert w.size == self.batch and h.size == self.batch
+        self.H.network_yolo_detections_gpu_sizes(self.h, i, w.ctypes.data, h.ctypes.data, C.c_float(thresh), int(relative),
+                                                 recs.ctypes.data, max_recs, counts.ctypes.data)
+        return counts, recs
+
+    def layer0_entry(self, scale, zp):
+        """Host-side bank entry of layer 0 for one (input scale, zero point): the bytes the per-image path uploads for it."""
+        info = self.info[0]
+        out = np.zeros(int(shim().mi355_conv_pack_size(info["n"], info["c"], info["size"])), np.uint8)
+        self.H.network_layer0_entry(self.h, C.c_float(scale), int(zp), out.ctypes.data)
+        return out
+
+    def bank_entry_bytes(self):
+        """per-image mode: byte stride of the layer-0 bank (0 before the first per-image batch)"""
+        return int(self.H.dnq_net_pi_entry_bytes(self.h))
+
+    def graph_handle(self):
+        """the captured graph of the layer loop, or None (use_graph networks capture on their first forward)"""
+        return self.H.dnq_net_graph(self.h)
+
+    def bank_packed(self):
+        """per-image mode: bank entries packed by the last batch (the others were cached)"""
+        return int(self.H.dnq_net_pi_packed(self.h))
 
     def selfcheck(self, passes):
         """queue `passes` forward passes over the resident input with a device-side checksum of the yolo outputs after each

@@ -11,15 +11,19 @@
 #include <type_traits>
 
 
-__global__ __launch_bounds__(256) void conv_first_u8_kernel(const AuxArgs a)
+// PI (per-image input quantisation): a thread's image selects its bank entry (kargs.h bank_entry); the weights in LDS are entry 0's
+// (every entry holds the same weights), and out-of-image taps take the image's own zero point instead of the shared pad cells.
+template <bool PI>
+__global__ __launch_bounds__(256) void conv_first_u8_kernel(const AuxArgs a0)
 {
     extern __shared__ uint32_t wl[];  // [n][9] weights then [n] zp_w
-    for (int i = threadIdx.x; i < a.n * 9; i += blockDim.x) wl[i] = a.wfirst[i];
+    for (int i = threadIdx.x; i < a0.n * 9; i += blockDim.x) wl[i] = a0.wfirst[i];
     __syncthreads();
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= a.total_n) return;
-    const int hw = a.H * a.W, W1 = a.W + 1;
+    if (n >= a0.total_n) return;
+    const int hw = a0.H * a0.W, W1 = a0.W + 1;
     const int b = n / hw, rem = n - b * hw;
+    const AuxArgs &a = bank_entry<PI>(a0, b);
     const int y = rem / a.W, xx = rem - y * a.W;
     const int cell = a.in_lead + (b * (a.H + 1) + (y + 1)) * W1 + xx;
     const uint32_t *xc = reinterpret_cast<const uint32_t *>(a.x);
@@ -29,6 +33,8 @@ __global__ __launch_bounds__(256) void conv_first_u8_kernel(const AuxArgs a)
     for (int t = 0; t < 9; ++t) {
         const int dy = t / 3 - 1, dx = t % 3 - 1;
         xin[t] = xc[cell + dy * W1 + dx];
+        if constexpr (PI)
+            if ((unsigned)(y + dy) >= (unsigned)a.H || (unsigned)(xx + dx) >= (unsigned)a.W) xin[t] = (uint32_t)a.zp_in * 0x00010101u;
         sumx = __builtin_amdgcn_udot4(xin[t], 0x00010101u, sumx, false);
     }
     const int ocell = a.out_lead + (b * (a.H + 1) + (y + 1)) * W1 + xx;
@@ -53,16 +59,18 @@ __global__ __launch_bounds__(256) void conv_first_u8_kernel(const AuxArgs a)
     }
 }
 
-__global__ __launch_bounds__(256) void conv_ref_f32_kernel(const AuxArgs a)
+template <bool PI>
+__global__ __launch_bounds__(256) void conv_ref_f32_kernel(const AuxArgs a0)
 {
-    const int hw = a.H * a.W;
-    const long total = (long)a.B * a.n * hw;
+    const int hw = a0.H * a0.W;
+    const long total = (long)a0.B * a0.n * hw;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     // pixel fastest so that a wave reads neighbouring cells
     const int rem = (int)(idx % hw);
-    const int oc = (int)((idx / hw) % a.n);
-    const int b = (int)(idx / ((long)hw * a.n));
+    const int oc = (int)((idx / hw) % a0.n);
+    const int b = (int)(idx / ((long)hw * a0.n));
+    const AuxArgs &a = bank_entry<PI>(a0, b);  // PI: the image's bank entry and zero point (the pad value below)
     const int y = rem / a.W, xx = rem - y * a.W;
     const int W1 = a.W + 1;
     const int K = a.c * a.ksize * a.ksize;
@@ -104,27 +112,30 @@ __global__ __launch_bounds__(256) void conv_ref_f32_kernel(const AuxArgs a)
 // computes the four pre-pool pixels (4x4 input window), requantises them (compile-time activation / store mode,
 // folded multiplier) and writes the bytewise max.  Removes the 2.77 MB/image pre-pool write + re-read.  The pre-pool
 // tensor is still written when `a.y` is given (parity runs keep the reference's per-layer tensors).
-template <int ACT, bool SAT>
-__global__ __launch_bounds__(256) void conv_first_pool_u8_kernel(const AuxArgs a)
+// PI (per-image input quantisation): as in conv_first_u8_kernel; the wrap-safe ranges in LDS would be the workgroup's first entry's, so
+// every window takes the plain path (requantise the four values, then the max: the same bytes)
+template <int ACT, bool SAT, bool PI>
+__global__ __launch_bounds__(256) void conv_first_pool_u8_kernel(const AuxArgs a0)
 {
     extern __shared__ uint32_t wl[];  // [n][9] weights (c0,c1,c2,0) per tap, then [n] lo, [n] hi wrap-safe ranges
-    int32_t *slo = reinterpret_cast<int32_t *>(wl + a.n * 9), *shi = slo + a.n;
-    for (int i = threadIdx.x; i < a.n * 9; i += blockDim.x) wl[i] = a.wfirst[i];
+    int32_t *slo = reinterpret_cast<int32_t *>(wl + a0.n * 9), *shi = slo + a0.n;
+    for (int i = threadIdx.x; i < a0.n * 9; i += blockDim.x) wl[i] = a0.wfirst[i];
     // Max-pool commutes with the requantisation while no byte of the window wraps (see conv_small.hip): [lo, hi] is
     // the per-channel range of accumulators (bias included) that cannot wrap; pre-pool stores keep the plain path.
-    const bool commute = !a.y && a.hdr->pow2 == 1;
-    if (threadIdx.x < a.n) {
+    const bool commute = !PI && !a0.y && a0.hdr->pow2 == 1;
+    if (!PI && threadIdx.x < a0.n) {
         int32_t lo = -2147483647 - 1, hi = 2147483647;
-        if (!SAT) small_safe_range<ACT>(a.mprime[threadIdx.x], a.zp_act, lo, hi);
+        if (!SAT) small_safe_range<ACT>(a0.mprime[threadIdx.x], a0.zp_act, lo, hi);
         slo[threadIdx.x] = lo;
         shi[threadIdx.x] = hi;
     }
     __syncthreads();
-    const int OH = a.H >> 1, OW = a.W >> 1;
-    const int total = a.B * OH * OW;
+    const int OH = a0.H >> 1, OW = a0.W >> 1;
+    const int total = a0.B * OH * OW;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const int b = idx / (OH * OW), rem = idx - b * (OH * OW);
+    const AuxArgs &a = bank_entry<PI>(a0, b);
     const int oy = rem / OW, ox = rem - oy * OW;
     const int W1 = a.W + 1;
     const int cell00 = a.in_lead + (b * (a.H + 1) + (2 * oy + 1)) * W1 + 2 * ox;  // pre-pool pixel (2oy, 2ox)
@@ -133,7 +144,11 @@ __global__ __launch_bounds__(256) void conv_first_pool_u8_kernel(const AuxArgs a
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) xin[r][c] = xc[cell00 + (r - 1) * W1 + (c - 1)];
+        for (int c = 0; c < 4; ++c) {
+            xin[r][c] = xc[cell00 + (r - 1) * W1 + (c - 1)];
+            if constexpr (PI)
+                if ((unsigned)(2 * oy + r - 1) >= (unsigned)a.H || (unsigned)(2 * ox + c - 1) >= (unsigned)a.W) xin[r][c] = (uint32_t)a.zp_in * 0x00010101u;
+        }
     int32_t sumx[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
@@ -164,7 +179,7 @@ __global__ __launch_bounds__(256) void conv_first_pool_u8_kernel(const AuxArgs a
             }
             const int32_t mx = max(max(accb[r][0], accb[r][1]), max(accb[r][2], accb[r][3]));
             const int32_t mn = min(min(accb[r][0], accb[r][1]), min(accb[r][2], accb[r][3]));
-            bad |= (mx > shi[oc]) | (mn < slo[oc]);
+            if constexpr (!PI) bad |= (mx > shi[oc]) | (mn < slo[oc]);  // (PI: the ranges are not staged, windows take the plain path)
             amax[r][0] = mx;
         }
         int32_t m[4];
@@ -200,7 +215,7 @@ __global__ __launch_bounds__(256) void conv_first_pool_u8_kernel(const AuxArgs a
     }
 }
 
-template <int ACT>
+template <int ACT, bool PI>
 static int conv_first_pool_launch_act(AuxArgs &a, hipStream_t st)
 {
     const int bs = 256;
@@ -208,10 +223,15 @@ static int conv_first_pool_launch_act(AuxArgs &a, hipStream_t st)
     const int grid = (total + bs - 1) / bs;
     const size_t lds = a.n * 11 * sizeof(uint32_t);
     if (a.store_mode == MI355_STORE_SATURATE)
-        hipLaunchKernelGGL((conv_first_pool_u8_kernel<ACT, true>), dim3(grid), dim3(bs), lds, st, a);
+        hipLaunchKernelGGL((conv_first_pool_u8_kernel<ACT, true, PI>), dim3(grid), dim3(bs), lds, st, a);
     else
-        hipLaunchKernelGGL((conv_first_pool_u8_kernel<ACT, false>), dim3(grid), dim3(bs), lds, st, a);
+        hipLaunchKernelGGL((conv_first_pool_u8_kernel<ACT, false, PI>), dim3(grid), dim3(bs), lds, st, a);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
+}
+template <int ACT>
+static int conv_first_pool_launch_act(AuxArgs &a, hipStream_t st)
+{
+    return a.entry_of_image ? conv_first_pool_launch_act<ACT, true>(a, st) : conv_first_pool_launch_act<ACT, false>(a, st);
 }
 
 // returns MI355_EINVAL when the fused form does not apply (caller runs the two layers separately)
@@ -227,7 +247,10 @@ int conv_first_launch(AuxArgs &a, hipStream_t st)
 {
     const int bs = 256;
     const int grid = (a.total_n + bs - 1) / bs;
-    hipLaunchKernelGGL(conv_first_u8_kernel, dim3(grid), dim3(bs), a.n * 9 * sizeof(uint32_t), st, a);
+    if (a.entry_of_image)
+        hipLaunchKernelGGL(conv_first_u8_kernel<true>, dim3(grid), dim3(bs), a.n * 9 * sizeof(uint32_t), st, a);
+    else
+        hipLaunchKernelGGL(conv_first_u8_kernel<false>, dim3(grid), dim3(bs), a.n * 9 * sizeof(uint32_t), st, a);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }
 
@@ -236,7 +259,10 @@ int conv_ref_f32_launch(AuxArgs &a, hipStream_t st)
     const int bs = 256;
     const long total = (long)a.B * a.n * a.H * a.W;
     const long grid = (total + bs - 1) / bs;
-    hipLaunchKernelGGL(conv_ref_f32_kernel, dim3((unsigned)grid), dim3(bs), 0, st, a);
+    if (a.entry_of_image)
+        hipLaunchKernelGGL(conv_ref_f32_kernel<true>, dim3((unsigned)grid), dim3(bs), 0, st, a);
+    else
+        hipLaunchKernelGGL(conv_ref_f32_kernel<false>, dim3((unsigned)grid), dim3(bs), 0, st, a);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }
 
@@ -298,10 +324,22 @@ extern "C" int mi355_debug_read_l0ph(long long *host)
 #define L0P_STORE() do { } while (0)
 #endif
 
-template <int ACT, bool SAT, int NM, bool PLANAR>
-__global__ __launch_bounds__(256, 4) void conv_first_mfma_pool_kernel(const AuxArgs a)
+// PI (per-image input quantisation, mi355_conv_pool_forward_per_image): the launcher gives every image pi_wpi workgroups of its own, so a
+// workgroup walks the tiles of ONE image (a tile never straddles images) and resolves that image's bank entry once, before the prologue:
+// the per-lane records, the byte table, the header and every per-channel pointer are the entry's, the pad value is the image's zero point.
+template <int ACT, bool SAT, int NM, bool PLANAR, bool PI>
+__global__ __launch_bounds__(256, 4) void conv_first_mfma_pool_kernel(const AuxArgs a0)
 {
     L0P_ENTRY;
+    // PI: workgroup -> (image, index among the image's workgroups); the workgroups of an image are consecutive in XCD order (below)
+    int pi_b = 0, pi_k = 0;
+    if constexpr (PI) {
+        const bool xw = (gridDim.x & 7) == 0 && !(a0.debug_flags & 2048);
+        const int L = xw ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+        pi_b = L / a0.pi_wpi;
+        pi_k = L - pi_b * a0.pi_wpi;
+    }
+    const AuxArgs &a = bank_entry<PI>(a0, pi_b);
     constexpr int ROWC = first_stage_rowc(PLANAR), XO = PLANAR ? 4 : 0;
     __shared__ __attribute__((aligned(16))) uint32_t img[2][18 * ROWC];
     // LEAKY, wrapping store: windows inside the safe range take activation + zero point + bias from a byte table (common.h)
@@ -358,6 +396,7 @@ __global__ __launch_bounds__(256, 4) void conv_first_mfma_pool_kernel(const AuxA
     // either inside the image or entirely pad (cells of the input zero point, ref: src/convolutional_layer.c:703-705).
     const int prow_ix = tid / 10, pq = tid - prow_ix * 10;
     const uint32_t zsplat = (uint32_t)a.zp_in * 0x01010101u;
+    [[maybe_unused]] const uint32_t zcell = (uint32_t)a.zp_in * 0x00010101u;  // PI, cell input: a pad cell (zp, zp, zp, 0)
     const size_t plane_sz = (size_t)a.H * a.W;
     const int planar_off = (prow_ix - 1) * a.W + 4 * pq - 4;  // byte offset of this thread's group from the tile's (16 ty, 32 tx)
     // the thread's group of colour plane k from (tile origin - one plane): never negative, 32 bits (the launcher refuses inputs of 2 GiB and more)
@@ -378,11 +417,11 @@ __global__ __launch_bounds__(256, 4) void conv_first_mfma_pool_kernel(const AuxA
     // XCD-aware order as before: workgroup id w runs on XCD w % 8 (each with its own L2); neighbouring tiles share the cache lines of their halo
     // columns / rows, so every XCD takes one CONTIGUOUS eighth of the tiles and its workgroups walk it side by side.
     const bool xcd_walk = (gridDim.x & 7) == 0 && !(a.debug_flags & 2048);
-    const int per_x = xcd_walk ? (ntiles + 7) >> 3 : ntiles;
-    const int tstride = xcd_walk ? (int)(gridDim.x >> 3) : (int)gridDim.x;
-    const int tbase_x = xcd_walk ? (int)(blockIdx.x & 7) * per_x : 0;
+    const int per_x = PI ? tpi : (xcd_walk ? (ntiles + 7) >> 3 : ntiles);
+    const int tstride = PI ? a.pi_wpi : (xcd_walk ? (int)(gridDim.x >> 3) : (int)gridDim.x);
+    const int tbase_x = PI ? pi_b * tpi : (xcd_walk ? (int)(blockIdx.x & 7) * per_x : 0);
     const int tend = min(tbase_x + per_x, ntiles);
-    const int tile0 = tbase_x + (xcd_walk ? (int)(blockIdx.x >> 3) : (int)blockIdx.x);
+    const int tile0 = tbase_x + (PI ? pi_k : (xcd_walk ? (int)(blockIdx.x >> 3) : (int)blockIdx.x));
     unsigned T_in, T_out, T_fl;
     int nt;
     {
@@ -440,6 +479,18 @@ __global__ __launch_bounds__(256, 4) void conv_first_mfma_pool_kernel(const AuxA
         } else {
 #pragma unroll
             for (int k = 0; k < 3; ++k) v[k] = xc[min(max((int)org + soff[k], 0), a.in_cells - 1)];
+            if constexpr (PI) {  // pad cells are shared between neighbouring images: out-of-image cells take THIS image's zero point
+                if (!(fl & 1u)) {
+                    const int tx = (int)((fl >> 2) & 1023u), ty = (int)((fl >> 12) & 1023u);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const int slot = min(tid + 256 * k, 18 * 34 - 1);
+                        const int r = slot / 34, c = slot - r * 34;
+                        const int y = 16 * ty - 1 + r, x = 32 * tx - 1 + c;
+                        if ((unsigned)y >= (unsigned)a.H || (unsigned)x >= (unsigned)a.W) v[k] = zcell;
+                    }
+                }
+            }
         }
     };
     auto stash = [&](int buf, const uint32_t(&v)[3]) {
@@ -874,9 +925,17 @@ __global__ __launch_bounds__(256, 4) void conv_first_mfma_pool_kernel(const AuxA
 // The same kernel without the pool: the first layer of the non-tiny networks (YOLOv3's 3 -> 32 at full resolution) stores
 // every conv pixel.  Same tiling (a lane's four MFMAs are the 2x2 block of conv pixels at (2 prow + jy, 2 pcol + jx)), all
 // sixteen values of a lane requantised, four 4-byte stores per m-tile.
-template <int ACT, bool SAT, int NM, bool PLANAR>
-__global__ __launch_bounds__(256, 4) void conv_first_mfma_kernel(const AuxArgs a)
+template <int ACT, bool SAT, int NM, bool PLANAR, bool PI>
+__global__ __launch_bounds__(256, 4) void conv_first_mfma_kernel(const AuxArgs a0)
 {
+    int pi_b = 0, pi_k = 0;  // PI: as in conv_first_mfma_pool_kernel, a workgroup walks the tiles of one image
+    if constexpr (PI) {
+        const bool xw = (gridDim.x & 7) == 0 && !(a0.debug_flags & 2048);
+        const int L = xw ? (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+        pi_b = L / a0.pi_wpi;
+        pi_k = L - pi_b * a0.pi_wpi;
+    }
+    const AuxArgs &a = bank_entry<PI>(a0, pi_b);
     constexpr int ROWC = first_stage_rowc(PLANAR), XO = PLANAR ? 4 : 0;
     __shared__ __attribute__((aligned(16))) uint32_t img[2][18 * ROWC];
     const int tid = threadIdx.x;
@@ -943,7 +1002,7 @@ __global__ __launch_bounds__(256, 4) void conv_first_mfma_kernel(const AuxArgs a
         p.tx = r - p.ty * tiles_x;
         return p;
     };
-    const Pos step = pos_of(((gridDim.x & 7) == 0 && !(a.debug_flags & 2048)) ? (int)(gridDim.x >> 3) : (int)gridDim.x);
+    const Pos step = pos_of(PI ? a.pi_wpi : (((gridDim.x & 7) == 0 && !(a.debug_flags & 2048)) ? (int)(gridDim.x >> 3) : (int)gridDim.x));
     auto advance = [&](Pos &p) {
         p.tx += step.tx;
         p.ty += step.ty;
@@ -976,6 +1035,15 @@ __global__ __launch_bounds__(256, 4) void conv_first_mfma_kernel(const AuxArgs a
             const int org = a.in_lead + (p.b * (a.H + 1) + 16 * p.ty) * W1 + 32 * p.tx - 1;  // image cell (0, 0)
 #pragma unroll
             for (int k = 0; k < 3; ++k) v[k] = xc[min(max(org + soff[k], 0), a.in_cells - 1)];
+            if constexpr (PI) {  // pad cells are shared between neighbouring images: out-of-image cells take THIS image's zero point
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const int slot = min(tid + 256 * k, 18 * 34 - 1);
+                    const int r = slot / 34, c = slot - r * 34;
+                    const int y = 16 * p.ty - 1 + r, x = 32 * p.tx - 1 + c;
+                    if ((unsigned)y >= (unsigned)a.H || (unsigned)x >= (unsigned)a.W) v[k] = (uint32_t)a.zp_in * 0x00010101u;
+                }
+            }
         }
     };
     auto stash = [&](int buf, const uint32_t(&v)[3]) {
@@ -1004,11 +1072,11 @@ __global__ __launch_bounds__(256, 4) void conv_first_mfma_kernel(const AuxArgs a
     // side: tile = xcd * per + idx, idx = b / 8 + k * (gridDim / 8).  (Plain b + k * gridDim put neighbours on different
     // XCDs: 2.3x - 3x the input bytes fetched, profiles/r01_v6_pmc_traffic.json, r02_v1_pmc_traffic.json.)
     const bool xcd_walk = (gridDim.x & 7) == 0 && !(a.debug_flags & 2048);
-    const int per_x = xcd_walk ? (ntiles + 7) >> 3 : ntiles;
-    const int tstride = xcd_walk ? (int)(gridDim.x >> 3) : (int)gridDim.x;
-    const int tbase_x = xcd_walk ? (int)(blockIdx.x & 7) * per_x : 0;
+    const int per_x = PI ? tpi : (xcd_walk ? (ntiles + 7) >> 3 : ntiles);
+    const int tstride = PI ? a.pi_wpi : (xcd_walk ? (int)(gridDim.x >> 3) : (int)gridDim.x);
+    const int tbase_x = PI ? pi_b * tpi : (xcd_walk ? (int)(blockIdx.x & 7) * per_x : 0);
     const int tend = min(tbase_x + per_x, ntiles);
-    int tile = tbase_x + (xcd_walk ? (int)(blockIdx.x >> 3) : (int)blockIdx.x);
+    int tile = tbase_x + (PI ? pi_k : (xcd_walk ? (int)(blockIdx.x >> 3) : (int)blockIdx.x));
     Pos cur = pos_of(tile), nxp = cur;
     uint32_t nxt[3];
     if (tile < tend) {
@@ -1111,34 +1179,55 @@ __global__ __launch_bounds__(256, 4) void conv_first_mfma_kernel(const AuxArgs a
     }
 }
 
-template <int ACT, int NM>
+template <int ACT, int NM, bool PI>
 static int first_mfma_launch_sat(AuxArgs &a, hipStream_t st, int grid)
 {
     if (a.planar) {
         if (a.store_mode == MI355_STORE_SATURATE)
-            hipLaunchKernelGGL((conv_first_mfma_pool_kernel<ACT, true, NM, true>), dim3(grid), dim3(256), 0, st, a);
+            hipLaunchKernelGGL((conv_first_mfma_pool_kernel<ACT, true, NM, true, PI>), dim3(grid), dim3(256), 0, st, a);
         else
-            hipLaunchKernelGGL((conv_first_mfma_pool_kernel<ACT, false, NM, true>), dim3(grid), dim3(256), 0, st, a);
+            hipLaunchKernelGGL((conv_first_mfma_pool_kernel<ACT, false, NM, true, PI>), dim3(grid), dim3(256), 0, st, a);
     } else if (a.store_mode == MI355_STORE_SATURATE)
-        hipLaunchKernelGGL((conv_first_mfma_pool_kernel<ACT, true, NM, false>), dim3(grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((conv_first_mfma_pool_kernel<ACT, true, NM, false, PI>), dim3(grid), dim3(256), 0, st, a);
     else
-        hipLaunchKernelGGL((conv_first_mfma_pool_kernel<ACT, false, NM, false>), dim3(grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((conv_first_mfma_pool_kernel<ACT, false, NM, false, PI>), dim3(grid), dim3(256), 0, st, a);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }
-
 template <int ACT, int NM>
+static int first_mfma_launch_sat(AuxArgs &a, hipStream_t st, int grid)
+{
+    return a.entry_of_image ? first_mfma_launch_sat<ACT, NM, true>(a, st, grid) : first_mfma_launch_sat<ACT, NM, false>(a, st, grid);
+}
+
+template <int ACT, int NM, bool PI>
 static int first_mfma_nopool_launch_sat(AuxArgs &a, hipStream_t st, int grid)
 {
     if (a.planar) {
         if (a.store_mode == MI355_STORE_SATURATE)
-            hipLaunchKernelGGL((conv_first_mfma_kernel<ACT, true, NM, true>), dim3(grid), dim3(256), 0, st, a);
+            hipLaunchKernelGGL((conv_first_mfma_kernel<ACT, true, NM, true, PI>), dim3(grid), dim3(256), 0, st, a);
         else
-            hipLaunchKernelGGL((conv_first_mfma_kernel<ACT, false, NM, true>), dim3(grid), dim3(256), 0, st, a);
+            hipLaunchKernelGGL((conv_first_mfma_kernel<ACT, false, NM, true, PI>), dim3(grid), dim3(256), 0, st, a);
     } else if (a.store_mode == MI355_STORE_SATURATE)
-        hipLaunchKernelGGL((conv_first_mfma_kernel<ACT, true, NM, false>), dim3(grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((conv_first_mfma_kernel<ACT, true, NM, false, PI>), dim3(grid), dim3(256), 0, st, a);
     else
-        hipLaunchKernelGGL((conv_first_mfma_kernel<ACT, false, NM, false>), dim3(grid), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((conv_first_mfma_kernel<ACT, false, NM, false, PI>), dim3(grid), dim3(256), 0, st, a);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
+}
+template <int ACT, int NM>
+static int first_mfma_nopool_launch_sat(AuxArgs &a, hipStream_t st, int grid)
+{
+    return a.entry_of_image ? first_mfma_nopool_launch_sat<ACT, NM, true>(a, st, grid) : first_mfma_nopool_launch_sat<ACT, NM, false>(a, st, grid);
+}
+
+// PI: every image gets wpi workgroups of its own (about the shared-scale grid in all, at most 64 tiles per workgroup, never more
+// workgroups than the image has tiles); returns the grid
+static long per_image_grid(AuxArgs &a, long tpi, long shared_grid)
+{
+    long wpi = (shared_grid + a.B - 1) / a.B;
+    if (wpi < (tpi + 63) / 64) wpi = (tpi + 63) / 64;
+    if (wpi > tpi) wpi = tpi;
+    a.pi_wpi = (int)wpi;
+    return wpi * a.B;
 }
 
 // first layer without a pool on the matrix pipe; MI355_EINVAL outside its domain (the caller uses the VALU kernel)
@@ -1152,7 +1241,12 @@ int conv_first_mfma_launch(AuxArgs &a, hipStream_t st)
     if (ntiles >= (1L << 31)) return MI355_EINVAL;
     a.fd_tx = fastdiv_make((uint32_t)((OW + 15) / 16));
     a.fd_tpi = fastdiv_make((uint32_t)(((OW + 15) / 16) * ((OH + 7) / 8)));
-    const int grid = (int)(ntiles < 1024 ? ntiles : 1024);
+    int grid = (int)(ntiles < 1024 ? ntiles : 1024);
+    if (a.entry_of_image) {
+        const long g = per_image_grid(a, ntiles / a.B, grid);
+        if (g >= (1L << 31)) return MI355_EINVAL;
+        grid = (int)g;
+    }
     if (a.n == 16) {
         if (a.act == MI355_ACT_LEAKY) return first_mfma_nopool_launch_sat<MI355_ACT_LEAKY, 1>(a, st, grid);
         if (a.act == MI355_ACT_RELU6) return first_mfma_nopool_launch_sat<MI355_ACT_RELU6, 1>(a, st, grid);
@@ -1184,6 +1278,7 @@ int conv_first_mfma_pool_launch(AuxArgs &a, hipStream_t st)
     long g = ntiles < grid_cap ? ntiles : grid_cap;
     const long need = (((ntiles + 7) / 8 + 63) / 64) * 8;
     if (g < need) g = need;
+    if (a.entry_of_image) g = per_image_grid(a, ntiles / a.B, g);
     if (g >= (1L << 31)) return MI355_EINVAL;
     const int grid = (int)g;
     if (a.n == 16) {

@@ -410,6 +410,140 @@ int letterbox_launch(const float *im, int imw, int imh, int c, float *out, int w
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }
 
+// Per-image input quantisation: the same two passes for B images of count_per_image floats each.  The min / max pass runs one grid row
+// (blockIdx.y) per image into mm[2 b], mm[2 b + 1] with image_minmax_kernel's seeds, comparisons and atomics; the quantiser reads image b's
+// (scale, zero point) from DEVICE memory, so a captured graph stays valid when the next batch brings other scales.
+__global__ __launch_bounds__(256) void image_minmax_seed_kernel(uint32_t *mm, int B)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 2 * B) mm[i] = (i & 1) ? 0x80000000u : 0u;  // +0.0f, -0.0f
+}
+
+__global__ __launch_bounds__(256) void image_minmax_batched_kernel(const float *x, long count, uint32_t *mm)
+{
+    const float *xi = x + (size_t)blockIdx.y * count;
+    uint32_t *mi = mm + 2 * (size_t)blockIdx.y;
+    float mx = 0.0f, mn = 0.0f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (long)gridDim.x * blockDim.x) {
+        const float v = xi[i];
+        mx = v > mx ? v : mx;
+        mn = v < mn ? v : mn;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float omx = __shfl_xor(mx, m), omn = __shfl_xor(mn, m);
+        mx = omx > mx ? omx : mx;
+        mn = omn < mn ? omn : mn;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (mx > 0.0f) atomicMax(reinterpret_cast<int *>(mi), __float_as_int(mx));
+        if (mn < 0.0f) atomicMax(mi + 1, (uint32_t)__float_as_int(mn));
+    }
+}
+
+__global__ __launch_bounds__(256) void image_quantize_per_image_kernel(const float *x, long count, const float *scale_dev,
+                                                                       const uint8_t *zp_dev, uint8_t *out)
+{
+    // four elements per thread, one grid row per image (image_quantize_kernel's expressions)
+    const long i4 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i4 >= count) return;
+    const float *xi = x + (size_t)blockIdx.y * count;
+    uint8_t *oi = out + (size_t)blockIdx.y * count;
+    const float scale = scale_dev[blockIdx.y];
+    const int zp = zp_dev[blockIdx.y];
+    float v[4];
+    if (i4 + 3 < count && (reinterpret_cast<size_t>(xi) & 15) == 0) {
+        const float4 t = *reinterpret_cast<const float4 *>(xi + i4);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = i4 + k < count ? xi[i4 + k] : 0.0f;
+    }
+    uint32_t packed = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float t = (float)(round((double)(v[k] / scale)) + (double)zp);  // ref :160-165
+        const int q = (int)t;
+        packed |= (uint32_t)(q < 0 ? 0 : (q > 255 ? 255 : q)) << (8 * k);
+    }
+    if (i4 + 3 < count && (reinterpret_cast<size_t>(oi) & 3) == 0) {
+        *reinterpret_cast<uint32_t *>(oi + i4) = packed;
+    } else {
+        for (int k = 0; k < 4 && i4 + k < count; ++k) oi[i4 + k] = (uint8_t)(packed >> (8 * k));
+    }
+}
+
+int image_minmax_batched_launch(const float *x, int B, long count, uint32_t *mm, hipStream_t st)
+{
+    hipLaunchKernelGGL(image_minmax_seed_kernel, dim3(nblk(2L * B)), dim3(256), 0, st, mm, B);
+    if (hipGetLastError() != hipSuccess) return MI355_EHIP;
+    const long want = (count + 255) / 256;
+    // about 2048 workgroups in all, at least one per image
+    const long cap = 2048 / B > 0 ? 2048 / B : 1;
+    const int gx = (int)(want < cap ? (want > 0 ? want : 1) : cap);
+    hipLaunchKernelGGL(image_minmax_batched_kernel, dim3(gx, B), dim3(256), 0, st, x, count, mm);
+    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
+}
+
+int image_quantize_per_image_launch(const float *x, int B, long count, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out,
+                                    hipStream_t st)
+{
+    hipLaunchKernelGGL(image_quantize_per_image_kernel, dim3(nblk((count + 3) / 4), B), dim3(256), 0, st, x, count, scale_dev, zp_dev, out);
+    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
+}
+
+// yolo_detections_kernel with one letterbox source size per image (imw_dev[b], imh_dev[b], device memory)
+__global__ __launch_bounds__(256) void yolo_detections_sizes_kernel(const float *out, int B, int n, int classes, int h, int w,
+                                                                    const float *biases, const int *mask, int netw, int neth,
+                                                                    const int *imw_dev, const int *imh_dev, float thresh, int relative,
+                                                                    float *recs, int max_recs, int *counts)
+{
+    const int hw = h * w, per = classes + 5, rl = 6 + classes;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)B * hw * n) return;
+    const int a = (int)(idx % n);
+    const int i = (int)((idx / n) % hw);
+    const int b = (int)(idx / ((long)n * hw));
+    const int imw = imw_dev[b], imh = imh_dev[b];
+    const float *p = out + ((size_t)b * n + a) * per * hw + i;
+    const float objectness = p[4 * hw];
+    if (objectness <= thresh) return;
+    const int slot = atomicAdd(counts + b, 1);
+    if (slot >= max_recs) return;
+    int new_w, new_h;
+    if (((float)netw / imw) < ((float)neth / imh)) { new_w = netw; new_h = (imh * netw) / imw; }
+    else { new_h = neth; new_w = (imw * neth) / imh; }
+    const int row = i / w, col = i % w;
+    float bx = (col + p[0 * hw]) / w;
+    float by = (row + p[1 * hw]) / h;
+    float bw = (float)(exp((double)p[2 * hw]) * biases[2 * mask[a]] / netw);
+    float bh = (float)(exp((double)p[3 * hw]) * biases[2 * mask[a] + 1] / neth);
+    bx = (float)((bx - (netw - new_w) / 2. / netw) / ((float)new_w / netw));
+    by = (float)((by - (neth - new_h) / 2. / neth) / ((float)new_h / neth));
+    bw *= (float)netw / new_w;
+    bh *= (float)neth / new_h;
+    if (!relative) { bx *= imw; bw *= imw; by *= imh; bh *= imh; }
+    float *r = recs + ((size_t)b * max_recs + slot) * rl;
+    r[0] = (float)(i * n + a);
+    r[1] = bx; r[2] = by; r[3] = bw; r[4] = bh;
+    r[5] = objectness;
+    for (int j = 0; j < classes; ++j) {
+        const float prob = objectness * p[(5 + j) * hw];
+        r[6 + j] = (prob > thresh) ? prob : 0.f;
+    }
+}
+
+int yolo_detections_sizes_launch(const float *out, int B, int n, int classes, int h, int w, const float *biases, const int *mask,
+                                 int netw, int neth, const int *imw_dev, const int *imh_dev, float thresh, int relative, float *recs,
+                                 int max_recs, int *counts, hipStream_t st)
+{
+    if (hipMemsetAsync(counts, 0, sizeof(int) * (size_t)B, st) != hipSuccess) return MI355_EHIP;
+    const long total = (long)B * h * w * n;
+    hipLaunchKernelGGL(yolo_detections_sizes_kernel, dim3(nblk(total)), dim3(256), 0, st, out, B, n, classes, h, w, biases, mask, netw,
+                       neth, imw_dev, imh_dev, thresh, relative, recs, max_recs, counts);
+    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
+}
+
 int image_minmax_launch(const float *x, long count, uint32_t *mm, hipStream_t st)
 {
     if (hipMemsetAsync(mm, 0, 4, st) != hipSuccess) return MI355_EHIP;                 // +0.0f

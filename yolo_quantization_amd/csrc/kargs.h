@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include <atomic>
+#include <type_traits>
 #include <mutex>
 
 struct ConvArgs {
@@ -84,7 +85,34 @@ struct AuxArgs {
     int debug_flags;            // mi355_debug_flags (2048: plain tile walk instead of the XCD-aware one, A/B runs)
     const EptHeader *ept;       // the blob's epilogue table (common.h) or null
     FastDiv fd_tpi, fd_tx;      // first-layer MFMA kernels: divisions by tiles per image / tiles per row
+    // per-image input quantisation (mi355_conv_forward_per_image): the blob pointers above are entry 0 of a bank of entries
+    // `entry_bytes` apart; image b uses entry entry_of_image[b] and the input zero point zp_of_image[b] (zp_in is unused).
+    // Read only by the kernels' PI instantiations.
+    const int32_t *entry_of_image;
+    const uint8_t *zp_of_image;
+    long entry_bytes;
+    int pi_wpi;                 // first-layer MFMA kernels, PI: workgroups per image (a workgroup walks the tiles of one image)
 };
+
+// The view of a per-image bank that image b sees: every per-entry pointer moved to entry entry_of_image[b], the image's own
+// input zero point.  Identity for the shared-scale instantiations (PI = false).  The packed weights are the same in every
+// entry (one layer, packed for different input scales), so kernels that stage them before knowing the image use entry 0's.
+template <bool PI>
+__device__ __forceinline__ std::conditional_t<PI, AuxArgs, const AuxArgs &> bank_entry(const AuxArgs &a, int b)
+{
+    if constexpr (!PI) {
+        return a;
+    } else {
+        AuxArgs e = a;
+        const long off = (long)a.entry_of_image[b] * a.entry_bytes;
+        auto mv = [off](auto *p) { return p ? reinterpret_cast<decltype(p)>(reinterpret_cast<const char *>(p) + off) : p; };
+        e.wfirst = mv(a.wfirst); e.dzp = mv(a.dzp); e.bias = mv(a.bias);
+        e.mval = mv(a.mval); e.sval = mv(a.sval); e.mprime = mv(a.mprime);
+        e.hdr = mv(a.hdr); e.cwb = mv(a.cwb); e.ept = mv(a.ept);
+        e.zp_in = a.zp_of_image[b];
+        return e;
+    }
+}
 
 struct PoolArgs {
     const uint8_t *x;
@@ -204,6 +232,12 @@ int fill_u32_launch(uint32_t *p, uint32_t v, long n, hipStream_t st);
 int letterbox_launch(const float *im, int imw, int imh, int c, float *out, int w, int h, hipStream_t st);
 int image_minmax_launch(const float *x, long count, uint32_t *mm, hipStream_t st);
 int image_quantize_launch(const float *x, long count, float scale, int zp, uint8_t *out, hipStream_t st);
+int image_minmax_batched_launch(const float *x, int B, long count, uint32_t *mm, hipStream_t st);
+int image_quantize_per_image_launch(const float *x, int B, long count, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out,
+                                    hipStream_t st);
+int yolo_detections_sizes_launch(const float *out, int B, int n, int classes, int h, int w, const float *biases, const int *mask,
+                                 int netw, int neth, const int *imw_dev, const int *imh_dev, float thresh, int relative, float *recs,
+                                 int max_recs, int *counts, hipStream_t st);
 int yolo_logistic_launch(const float *in, float *out, int B, int n, int classes, int hw, hipStream_t st);
 int checksum_u32_launch(const uint32_t *p, long n, unsigned long long *out, hipStream_t st);
 

@@ -686,12 +686,27 @@ static int conv_generic_forward(const mi355_conv_desc *d, const mi355_tensor *x,
     return rc;
 }
 
+// a per-image blob bank (mi355_conv_forward_per_image): blob = entry 0, entries entry_bytes apart
+struct PerImageBank {
+    size_t entry_bytes;
+    const int32_t *entry_of_image;
+    const uint8_t *zp_in_of_image;
+};
+
 static int conv_forward_impl(const mi355_conv_desc *d, const mi355_tensor *x, const void *blob, const uint8_t *w_u8,
                              const uint8_t *zp_w, const mi355_tensor *y, const mi355_tensor *ypool, int32_t *acc_out,
                              float *y_f32, void *stream, float *yolo_out = nullptr, int yolo_classes = 0, int up = 1,
-                             const mi355_tensor *res = nullptr, int sc_ka = 0, int sc_kb = 0, int sc_k0 = 0)
+                             const mi355_tensor *res = nullptr, int sc_ka = 0, int sc_kb = 0, int sc_k0 = 0,
+                             const PerImageBank *bank = nullptr)
 {
     if (!d || !x || !x->data || !blob) return einval("conv_forward: null");
+    if (bank) {  // per-image input quantisation: the first-layer kernels (conv_aux.hip) only
+        if (d->c != 3 || d->ksize != 3 || d->stride != 1 || d->pad != 1)
+            return einval("conv_forward_per_image: only a 3 -> n 3x3 stride-1 first layer (pad 1) is served per image; the general kernel is not");
+        if (!bank->entry_of_image || !bank->zp_in_of_image) return einval("conv_forward_per_image: null index arrays");
+        if (bank->entry_bytes % 16 || bank->entry_bytes < mi355_conv_pack_size(d->n, d->c, d->ksize))
+            return einval("conv_forward_per_image: entry_bytes must be a multiple of 16 and hold one mi355_conv_pack blob");
+    }
     if (d->ksize < 1 || d->ksize > 11) return einval("conv_forward: size must be 1..11 (larger kernels are not supported)");
     {  // the general kernels: shapes the specialised kernels do not take, and the strides / paddings they refuse
         const bool legacy_geom = d->stride == 1 && ((d->ksize == 3 && d->pad == 1) || (d->ksize == 1 && d->pad == 0));
@@ -748,6 +763,9 @@ static int conv_forward_impl(const mi355_conv_desc *d, const mi355_tensor *x, co
         a.ept = h.off_ept ? (const EptHeader *)(base + h.off_ept) : nullptr;
         a.ypool = ypool ? (uint8_t *)ypool->data : nullptr; a.pool_cs = ypool ? ypool->cs : 0;
         a.pool_lead = ypool ? ypool->lead : 0;
+        if (bank) {
+            a.entry_of_image = bank->entry_of_image; a.zp_of_image = bank->zp_in_of_image; a.entry_bytes = (long)bank->entry_bytes;
+        }
         if (d->accum_mode == MI355_ACC_REF_F32) {
             if (ypool) return einval("conv_pool_forward: not in ref-f32 mode");
             if (!w_u8 || !zp_w) return einval("conv_forward: ref-f32 mode needs the raw weights_uint8 / zp_w");
@@ -877,6 +895,23 @@ int mi355_conv_pool_forward(const mi355_conv_desc *d, const mi355_tensor *x, con
     return conv_forward_impl(d, x, blob, nullptr, nullptr, y, ypool, nullptr, nullptr, stream);
 }
 
+int mi355_conv_forward_per_image(const mi355_conv_desc *d, const mi355_tensor *x, const void *bank, size_t entry_bytes,
+                                 const int32_t *entry_of_image, const uint8_t *zp_in_of_image, const uint8_t *w_u8,
+                                 const uint8_t *zp_w, const mi355_tensor *y, int32_t *acc_out, float *y_f32, void *stream)
+{
+    const PerImageBank pb = {entry_bytes, entry_of_image, zp_in_of_image};
+    return conv_forward_impl(d, x, bank, w_u8, zp_w, y, nullptr, acc_out, y_f32, stream, nullptr, 0, 1, nullptr, 0, 0, 0, &pb);
+}
+
+int mi355_conv_pool_forward_per_image(const mi355_conv_desc *d, const mi355_tensor *x, const void *bank, size_t entry_bytes,
+                                      const int32_t *entry_of_image, const uint8_t *zp_in_of_image, const mi355_tensor *y,
+                                      const mi355_tensor *ypool, void *stream)
+{
+    if (!ypool) return einval("conv_pool_forward_per_image: ypool is null");
+    const PerImageBank pb = {entry_bytes, entry_of_image, zp_in_of_image};
+    return conv_forward_impl(d, x, bank, nullptr, nullptr, y, ypool, nullptr, nullptr, stream, nullptr, 0, 1, nullptr, 0, 0, 0, &pb);
+}
+
 // -------------------------------------------------------------------------------------------------------- glue
 int mi355_maxpool_forward(const mi355_tensor *x, const mi355_tensor *y, int size, int stride, int pad, void *stream)
 {
@@ -978,6 +1013,20 @@ int mi355_image_quantize(const float *x_f32, long count, float scale, int zero_p
     return image_quantize_launch(x_f32, count, scale, zero_point, out_u8, (hipStream_t)stream);
 }
 
+int mi355_image_minmax_batched(const float *x_f32, int B, long count_per_image, float *minmax, void *stream)
+{
+    if (!x_f32 || !minmax || B <= 0 || count_per_image <= 0 || B > 65535) return einval("image_minmax_batched: null / empty / B > 65535");
+    return image_minmax_batched_launch(x_f32, B, count_per_image, reinterpret_cast<uint32_t *>(minmax), (hipStream_t)stream);
+}
+
+int mi355_image_quantize_per_image(const float *x_f32, int B, long count_per_image, const float *scale_dev, const uint8_t *zp_dev,
+                                   uint8_t *out_u8, void *stream)
+{
+    if (!x_f32 || !out_u8 || !scale_dev || !zp_dev || B <= 0 || count_per_image <= 0 || B > 65535)
+        return einval("image_quantize_per_image: null / empty / B > 65535");
+    return image_quantize_per_image_launch(x_f32, B, count_per_image, scale_dev, zp_dev, out_u8, (hipStream_t)stream);
+}
+
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream)
 {
     if (!buf || !sum_dev || dwords < 0) return einval("checksum: null");
@@ -999,6 +1048,16 @@ int mi355_yolo_detections(const float *yolo_out, int B, int n, int classes, int 
         return einval("yolo_detections: bad argument");
     return yolo_detections_launch(yolo_out, B, n, classes, H, W, anchors, mask, netw, neth, imw, imh, thresh, relative, recs,
                                   max_recs, counts, (hipStream_t)stream);
+}
+
+int mi355_yolo_detections_sizes(const float *yolo_out, int B, int n, int classes, int H, int W, const float *anchors,
+                                const int *mask, int netw, int neth, const int *imw_dev, const int *imh_dev, float thresh,
+                                int relative, float *recs, int max_recs, int *counts, void *stream)
+{
+    if (!yolo_out || !anchors || !mask || !recs || !counts || !imw_dev || !imh_dev || B <= 0 || n <= 0 || classes < 0 || max_recs <= 0)
+        return einval("yolo_detections_sizes: bad argument");
+    return yolo_detections_sizes_launch(yolo_out, B, n, classes, H, W, anchors, mask, netw, neth, imw_dev, imh_dev, thresh, relative,
+                                        recs, max_recs, counts, (hipStream_t)stream);
 }
 
 }  // extern "C"

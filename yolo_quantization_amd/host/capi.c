@@ -105,3 +105,9 @@ int dnq_layer_shortcut(network *net, int i, int32_t *k)
     k[0] = net->layers[i].shortcut_Ka; k[1] = net->layers[i].shortcut_Kb; k[2] = net->layers[i].index;
     return 0;
 }
+
+/* per-image input quantisation: entries packed by the last batch, and the byte stride of the layer-0 bank */
+int dnq_net_pi_packed(network *net) { return net->pi_packed; }
+long dnq_net_pi_entry_bytes(network *net) { return (long)net->pi_entry_bytes; }
+/* the captured graph of the layer loop (NULL: none yet); tests compare it across batches to see that no re-capture happened */
+void *dnq_net_graph(network *net) { return net->graph; }

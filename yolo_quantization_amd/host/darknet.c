@@ -19,6 +19,8 @@
  * -gpus: replica 0 reads the weights file, the others receive the packed blobs by one RCCL broadcast over xGMI),
  * -inflight <N> (with -n <iters>: after the timed passes, the same passes dealt round-robin to N executors of the prepared
  * model -- network_replica: own activations and stream, shared packed weights; the 4th on the default stream -- and their rate).
+ * -list <file> (instead of <image>: one image path per line, dealt into batches of -batch, every image quantised with its own scale /
+ * zero point -- set_input_quantization_per_image -- and reported with the block `detector test` prints for it alone).
  *
  * Image input: binary PPM (P6) of ANY size (letterboxed like the reference does), a raw `.u8` file holding [c][h][w] bytes at
  * network size, or `synthetic:<seed>`.  JPEG/PNG decoding is third-party code in the reference (stb_image, SURVEY.md 2
@@ -115,12 +117,92 @@ static void dump_layer(const char *dir, network *net, int i)
 
 typedef struct {
     const char *datacfg, *cfgfile, *weightfile, *filename, *dumpdir, *packed_in, *packed_out;
+    const char *listfile;  /* -list: image paths, one per line, per-image input quantisation */
     float thresh, hier_thresh;
     int batch, accum, store, use_graph, iters, gpu, boxes, quiet, inflight;
     int rank, nranks;      /* -gpus with -bcast: this replica's rank; rank 0 reads the weights file, the others receive blobs */
     const void *comm_id;   /* shared 128-byte RCCL unique id (NULL: every replica reads the file) */
     double seconds; /* out: per forward pass */
 } detect_job;
+
+/* boxes of batch slot b (source image imw x imh), NMS, and draw_detections' console output */
+static void print_detections(const detect_job *job, network *net, int b, int imw, int imh, char **names, int nnames)
+{
+    int classes = 0;
+    for (int i = 0; i < net->n; ++i)
+        if (net->layers[i].type == YOLO) classes = net->layers[i].classes; /* ref: `l = net->layers[net->n-1]` (:910) */
+    if (!classes) return;
+    const float nms = .45f; /* ref :892 */
+    int nboxes = 0;
+    detection *dets = get_network_boxes_batch(net, b, imw, imh, job->thresh, job->hier_thresh, 0, 1, &nboxes);
+    printf("%d\n", nboxes);
+    printf("-----------------------\n");
+    if (nms) do_nms_sort(dets, nboxes, classes, nms);
+    for (int i = 0; i < nboxes; ++i) /* draw_detections' console output (src/image.c:246-257) */
+        for (int j = 0; j < classes; ++j)
+            if (dets[i].prob[j] > job->thresh) {
+                if (names && j < nnames) printf("%s: %.0f%%\n", names[j], dets[i].prob[j] * 100);
+                else printf("class %d: %.0f%%\n", j, dets[i].prob[j] * 100);
+                if (job->boxes)
+                    printf("box: class %d prob %.9g x %.9g y %.9g w %.9g h %.9g\n", j, dets[i].prob[j], dets[i].bbox.x,
+                           dets[i].bbox.y, dets[i].bbox.w, dets[i].bbox.h);
+            }
+    free_detections(dets, nboxes);
+}
+
+/* -list <file>: one image path per line (the reference's valid= lists), dealt into batches of -batch with every image quantised on
+ * its own (set_input_quantization_per_image).  Each image prints the block `detector test` prints for it alone.  The slots a short
+ * last batch leaves free repeat its last image (they are not printed). */
+static void test_detector_list(detect_job *job, network *net, char **names, int nnames)
+{
+    FILE *f = fopen(job->listfile, "r");
+    if (!f) file_error(job->listfile);
+    char **paths = NULL;
+    int np = 0;
+    char line[4096];
+    while (fgets(line, sizeof(line), f)) {
+        size_t n = strlen(line);
+        while (n && (line[n - 1] == '\n' || line[n - 1] == '\r' || line[n - 1] == ' ')) line[--n] = 0;
+        if (!n) continue;
+        paths = realloc(paths, sizeof(char *) * (size_t)(np + 1));
+        paths[np] = malloc(n + 1);
+        memcpy(paths[np++], line, n + 1);
+    }
+    fclose(f);
+    if (set_input_quantization_per_image(net, 1)) error("-list: layer 0 cannot quantise every image on its own");
+    const int B = net->batch;
+    int *imw = calloc((size_t)B, sizeof(int)), *imh = calloc((size_t)B, sizeof(int));
+    for (int first = 0; first < np; first += B) {
+        const int cnt = np - first < B ? np - first : B;
+        for (int b = 0; b < B; ++b) {
+            const char *path = paths[first + (b < cnt ? b : cnt - 1)];
+            image im = load_image_any(path, net->c, net->h, net->w);
+            float *im_gpu = NULL;
+            const size_t imbytes = (size_t)im.c * im.h * im.w * sizeof(float);
+            if (mi355_alloc((void **)&im_gpu, imbytes) || mi355_h2d(im_gpu, im.data, imbytes, net->stream)) {
+                fprintf(stderr, "MI355: %s\n", mi355_last_error());
+                error("cannot stage the image on the device");
+            }
+            network_letterbox_input_gpu(net, b, im_gpu, im.w, im.h);
+            if (mi355_stream_sync(net->stream)) error("sync");
+            mi355_free(im_gpu);
+            imw[b] = im.w; imh[b] = im.h;
+            free(im.data);
+        }
+        network_quantize_input_gpu(net);
+        const double t0 = what_time_is_it_now();
+        network_predict(net, net->input);
+        const double dt = what_time_is_it_now() - t0;
+        for (int b = 0; b < cnt; ++b) {
+            printf("%s: Predicted in %f seconds. (batch %d, %.1f images/s, gpu %d, accum=%s, parity=%s)\n", paths[first + b], dt, B,
+                   B / dt, job->gpu, job->accum == MI355_ACC_EXACT ? "exact" : "ref-f32", job->store == MI355_STORE_WRAP ? "wrap" : "saturate");
+            print_detections(job, net, b, imw[b], imh[b], names, nnames);
+        }
+    }
+    free(imw); free(imh);
+    for (int i = 0; i < np; ++i) free(paths[i]);
+    free(paths);
+}
 
 /* one network on one device: load, input path, predict, boxes, NMS, print */
 static void test_detector(detect_job *job)
@@ -156,6 +238,14 @@ static void test_detector(detect_job *job)
         mi355_comm_destroy(comm);
     }
 
+    if (job->listfile) {
+        if (mi355_init(job->gpu)) error("mi355_init");
+        test_detector_list(job, net, names, nnames);
+        for (int i = 0; i < nnames; ++i) free(names[i]);
+        free(names);
+        free_network(net);
+        return;
+    }
     image im = load_image_any(job->filename, net->c, net->h, net->w);
     /* input path on the device: the float image goes up once, letterbox_image + the layer-0 quantiser run in HBM */
     float *im_gpu = NULL;
@@ -198,27 +288,7 @@ static void test_detector(detect_job *job)
         for (int k = n - 1; k >= 1; --k) free_network(ex[k]);
     }
 
-    int classes = 0;
-    for (int i = 0; i < net->n; ++i)
-        if (net->layers[i].type == YOLO) classes = net->layers[i].classes; /* ref: `l = net->layers[net->n-1]` (:910) */
-    if (classes && !job->quiet) {
-        const float nms = .45f; /* ref :892 */
-        int nboxes = 0;
-        detection *dets = get_network_boxes(net, im.w, im.h, job->thresh, job->hier_thresh, 0, 1, &nboxes);
-        printf("%d\n", nboxes);
-        printf("-----------------------\n");
-        if (nms) do_nms_sort(dets, nboxes, classes, nms);
-        for (int i = 0; i < nboxes; ++i) /* draw_detections' console output (src/image.c:246-257) */
-            for (int j = 0; j < classes; ++j)
-                if (dets[i].prob[j] > job->thresh) {
-                    if (names && j < nnames) printf("%s: %.0f%%\n", names[j], dets[i].prob[j] * 100);
-                    else printf("class %d: %.0f%%\n", j, dets[i].prob[j] * 100);
-                    if (job->boxes)
-                        printf("box: class %d prob %.9g x %.9g y %.9g w %.9g h %.9g\n", j, dets[i].prob[j], dets[i].bbox.x,
-                               dets[i].bbox.y, dets[i].bbox.w, dets[i].bbox.h);
-                }
-        free_detections(dets, nboxes);
-    }
+    if (!job->quiet) print_detections(job, net, 0, im.w, im.h, names, nnames);
     if (job->dumpdir) for (int i = 0; i < net->n; ++i) dump_layer(job->dumpdir, net, i);
     mi355_free(im_gpu);
     free(im.data);
@@ -238,7 +308,7 @@ int main(int argc, char **argv)
     if (argc < 2) {
         fprintf(stderr, "usage: %s detector test <data> <cfg> <weights> <image> [-thresh t] [-i gpu | -gpus a,b,..] [-batch B] "
                         "[-accum exact|ref-f32] [-parity wrap|saturate] [-dump dir] [-graph] [-n iters] [-boxes] "
-                        "[-save_packed file] [-packed file] [-bcast] [-inflight N]\n", argv[0]);
+                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file]\n", argv[0]);
         return 0;
     }
     detect_job job;
@@ -260,12 +330,20 @@ int main(int argc, char **argv)
     const int bcast = find_arg(argc, argv, "-bcast");
     job.iters = atoi(find_char_arg(argc, argv, "-n", "1"));
     job.inflight = atoi(find_char_arg(argc, argv, "-inflight", "1"));
+    job.listfile = find_char_arg(argc, argv, "-list", NULL);
     if (job.iters < 1) job.iters = 1;
     if (job.batch < 1) job.batch = 1;
     job.accum = 0 == strcmp(accum_s, "ref-f32") ? MI355_ACC_REF_F32 : MI355_ACC_EXACT;
     job.store = 0 == strcmp(parity_s, "saturate") ? MI355_STORE_SATURATE : MI355_STORE_WRAP;
     if (strcmp(argv[1], "detector")) {
         fprintf(stderr, "Not an option: %s\n", argv[1]);
+        return 0;
+    }
+    if (job.listfile && (gpu_list || job.dumpdir || job.inflight > 1 || job.packed_in || job.packed_out))
+        error("-list runs on one device (-i) without -dump, -inflight, -packed or -save_packed");
+    if (job.listfile && argc >= 6 && argv[2] && !strcmp(argv[2], "test") && argv[3] && argv[4] && argv[5] && (argc < 7 || !argv[6])) {
+        job.datacfg = argv[3]; job.cfgfile = argv[4]; job.weightfile = argv[5]; job.filename = NULL;
+        test_detector(&job);
         return 0;
     }
     if (argc < 7 || !argv[2] || strcmp(argv[2], "test") || !argv[3] || !argv[4] || !argv[5] || !argv[6]) {

@@ -29,6 +29,39 @@ static void alloc_act_record(layer *l)
     l->activ_data_uint8_zero_point = calloc(1, sizeof(uint8_t));
 }
 
+/* Layer 0 under per-image input quantisation (set_input_quantization_per_image): the same launches on the network's bank of
+ * layer-0 blobs, one entry per image (mi355_conv_forward_per_image); fusion as in the shared-scale path below */
+static void forward_first_layer_per_image(layer l, network net, const mi355_conv_desc *d)
+{
+    const size_t eb = net.pi_entry_bytes;
+    const int32_t *entry = (const int32_t *)net.pi_idx_gpu;
+    const uint8_t *zp = (const uint8_t *)net.pi_idx_gpu + 8 * (size_t)net.batch;
+    layer *self = &net.layers[net.index];
+    mi355_tensor converted;
+    if (!net.pi_bank_gpu) error("per-image input: layer 0 runs before the batch was quantised (no bank)");
+    if (net.cur_t->cs == 1) { /* planar network input: in place where the kernel can, else converted once and for all */
+        int rc = MI355_EINVAL;
+        if (net.fused_pool_t) rc = mi355_conv_pool_forward_per_image(d, net.cur_t, net.pi_bank_gpu, eb, entry, zp, NULL, net.fused_pool_t, net.stream);
+        else if (!l.quant_stop_flag)
+            rc = mi355_conv_forward_per_image(d, net.cur_t, net.pi_bank_gpu, eb, entry, zp, NULL, NULL, &l.out_t, NULL, NULL, net.stream);
+        if (rc != MI355_EINVAL) { check_mi355(rc, "mi355_conv_forward_per_image (planar input)"); return; }
+        if (net.input_direct_p) *net.input_direct_p = 0;
+        converted = net.input_t;
+        check_mi355(mi355_nchw_to_tensor((const uint8_t *)net.cur_t->data, &converted, net.stream), "input layout");
+        net.cur_t = &converted;
+    }
+    if (net.fused_pool_t) {
+        const int rc = mi355_conv_pool_forward_per_image(d, net.cur_t, net.pi_bank_gpu, eb, entry, zp, l.fuse_pool_keep ? &l.out_t : NULL,
+                                                         net.fused_pool_t, net.stream);
+        if (rc != MI355_EINVAL) { check_mi355(rc, "mi355_conv_pool_forward_per_image"); return; }
+        self->fuse_next_pool = 0;
+    }
+    check_mi355(mi355_conv_forward_per_image(d, net.cur_t, net.pi_bank_gpu, eb, entry, zp, l.weights_uint8_gpu, l.weight_zero_point_gpu,
+                                             &l.out_t, net.dump_int32 ? l.output_int32_gpu : NULL, l.quant_stop_flag ? l.output_gpu : NULL,
+                                             net.stream),
+                "mi355_conv_forward_per_image");
+}
+
 /* ref: forward_convolutional_layer_quant_inputi_outputi, src/convolutional_layer.c:694-761 */
 static void forward_convolutional_layer_quant_gpu(layer l, network net)
 {
@@ -48,6 +81,7 @@ static void forward_convolutional_layer_quant_gpu(layer l, network net)
      * point means "no kernel fuses this shape" (nothing was launched): the flag is cleared in the network's layer array
      * (net.layers points at it; `l` is a by-value copy) and the convolution runs unfused below, the layer after it on its
      * own. */
+    if (net.per_image && net.index == 0) { forward_first_layer_per_image(l, net, &d); return; }
     layer *self = &net.layers[net.index];
     mi355_tensor converted;
     if (net.cur_t->cs == 1) { /* planar network input: try the in-place read; MI355_EINVAL -> convert, once and for all */
@@ -329,6 +363,8 @@ void free_layer_device(layer *l)
     if (l->anchors_gpu) mi355_free(l->anchors_gpu);
     if (l->mask_gpu) mi355_free(l->mask_gpu);
     if (l->det_recs_gpu) mi355_free(l->det_recs_gpu);
+    if (l->det_sizes_gpu) mi355_free(l->det_sizes_gpu);
+    l->det_sizes_gpu = NULL;
     if (l->det_counts_gpu) mi355_free(l->det_counts_gpu);
     l->anchors_gpu = NULL; l->mask_gpu = NULL; l->det_recs_gpu = NULL; l->det_counts_gpu = NULL; l->det_cap = 0;
     l->out_t.data = NULL; l->blob_gpu = NULL; l->weights_uint8_gpu = NULL; l->weight_zero_point_gpu = NULL;

@@ -10,6 +10,7 @@
  */
 #include <assert.h>
 #include <math.h>
+#include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -55,6 +56,7 @@ const char *get_layer_string(LAYER_TYPE t)
 }
 
 static void plan_fusion(network *net);
+static void pi_free(network *net);
 
 /* ------------------------------------------------------------------------------------------------- host prep */
 void quant_multi_smaller_than_one_to_scale_and_shift(float real_multiplier, int32_t *quantized_multiplier,
@@ -393,8 +395,21 @@ void quantization_weights_and_activations_fixed_input(network *net, float in_sca
     net->prepared = 1;
 }
 
+static void pi_bank_update(network *net, const float *scale, const uint8_t *zp);
+
 void quantization_weights_and_activations(network *net)
 {
+    if (net->per_image) { /* every image with its own min / max (the reference's batch-1 quantiser, ref :279, per image) */
+        float *s = malloc(sizeof(float) * (size_t)net->batch);
+        uint8_t *zp = malloc((size_t)net->batch);
+        for (int b = 0; b < net->batch; ++b)
+            quant_image_with_min_max(net->inputs, net->input + (size_t)b * net->inputs, net->input_uint8 + (size_t)b * net->inputs, &s[b], &zp[b]);
+        if (!net->prepared) quantization_weights_and_activations_fixed_input(net, s[0], zp[0]);
+        pi_bank_update(net, s, zp);
+        free(s); free(zp);
+        push_network_input_uint8(net, net->input_uint8);
+        return;
+    }
     /* ref :279: dynamic layer-0 quantiser on the float image in net->input (image 0 defines scale / zero point) */
     float s; uint8_t zp;
     quant_image_with_min_max(net->inputs, net->input, net->input_uint8, &s, &zp);
@@ -416,11 +431,14 @@ void quantization_weights_and_activations(network *net)
  * from the ones layer 0 was prepared with -- re-derives and re-uploads layer 0's multipliers and blob in place (no other
  * layer depends on the input scale); the per-element quantiser then runs on the device straight into the network's uint8
  * input.  Byte-identical to quantization_weights_and_activations() on the same floats. */
+static void quantize_per_image_gpu(network *net, const float *input_gpu);
+
 void quantization_weights_and_activations_gpu(network *net, const float *input_gpu)
 {
     if (!input_gpu) error("quantization_weights_and_activations_gpu: null input");
     check_mi355(mi355_init(net->gpu_index), "mi355_init");
     if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
+    if (net->per_image) { quantize_per_image_gpu(net, input_gpu); return; }
     if (!net->quant_mm_gpu) check_mi355(mi355_alloc((void **)&net->quant_mm_gpu, 2 * sizeof(float)), "alloc minmax");
     float mm[2];
     check_mi355(mi355_image_minmax(input_gpu, net->inputs, net->quant_mm_gpu, net->stream), "mi355_image_minmax");
@@ -455,6 +473,184 @@ void quantization_weights_and_activations_gpu(network *net, const float *input_g
                 "mi355_image_quantize");
 }
 
+/* ---------------------------------------------------------------------------------- per-image input quantisation
+ * Only layer 0 depends on the input scale (ref: src/blas.c:300-333).  The bank holds layer-0 blobs packed by the same code as
+ * the shared-scale path (prep_conv_layer + mi355_conv_pack + mi355_conv_pack_epilogue), so every entry is bit-identical to the
+ * blob a batch-1 run of its image would use.  Its slots double as a cache keyed by (scale bits, zero point): a slot is only
+ * repacked and re-uploaded when a batch brings a key the bank does not hold.  Uploads are asynchronous on the network's stream;
+ * the host staging of a slot is only rewritten after the next batch's min / max sync, when the previous upload is done. */
+static int l0_per_image_shape_ok(const layer *l)
+{
+    return l->type == CONVOLUTIONAL && l->c == 3 && l->size == 3 && l->stride == 1 && l->pad == 1;
+}
+
+static network *l0_source(network *net) { return net->replica_of ? net->replica_of : net; } /* who holds layer 0's raw weights */
+
+int set_input_quantization_per_image(network *net, int on)
+{
+    if (!on) {
+        if (net->per_image && net->graph) { mi355_graph_destroy(net->graph); net->graph = NULL; } /* captured with the per-image launches */
+        net->per_image = 0;
+        return 0;
+    }
+    const layer *l0 = &net->layers[0];
+    if (!l0_per_image_shape_ok(l0)) {
+        fprintf(stderr, "set_input_quantization_per_image: layer 0 (%s %dx%d stride %d, %d -> %d) is not served per image: only a "
+                        "3 -> n 3x3 stride-1 convolution with pad 1 runs on the first-layer kernels\n",
+                get_layer_string(l0->type), l0->size, l0->size, l0->stride, l0->c, l0->n);
+        return MI355_EINVAL;
+    }
+    const network *src = l0_source(net);
+    if (src->prepared && !src->has_host_weights && !src->has_l0_weights) {
+        fprintf(stderr, "set_input_quantization_per_image: this network holds no raw layer-0 weights to derive per-image constants from\n");
+        return MI355_EINVAL;
+    }
+    if (!net->per_image && net->graph) { mi355_graph_destroy(net->graph); net->graph = NULL; }
+    net->per_image = 1;
+    return 0;
+}
+
+void network_input_quantization(network *net, float *scale, uint8_t *zp)
+{
+    const int B = net->batch;
+    if (!net->per_image || !net->pi_idx_host) {
+        for (int b = 0; b < B; ++b) { scale[b] = net->layers[0].input_data_uint8_scales[0]; zp[b] = net->layers[0].input_data_uint8_zero_point[0]; }
+        return;
+    }
+    memcpy(scale, (char *)net->pi_idx_host + 4 * (size_t)B, sizeof(float) * (size_t)B);
+    memcpy(zp, (char *)net->pi_idx_host + 8 * (size_t)B, (size_t)B);
+}
+
+static void pi_free(network *net)
+{
+    if (net->pi_bank_gpu) mi355_free(net->pi_bank_gpu);
+    if (net->pi_idx_gpu) mi355_free(net->pi_idx_gpu);
+    if (net->pi_mm_gpu) mi355_free(net->pi_mm_gpu);
+    free(net->pi_bank_host); free(net->pi_idx_host); free(net->pi_mm_host);
+    free(net->pi_key_scale); free(net->pi_key_zp); free(net->pi_stamp);
+    net->pi_bank_gpu = net->pi_bank_host = net->pi_idx_gpu = net->pi_idx_host = NULL;
+    net->pi_mm_gpu = net->pi_mm_host = NULL;
+    net->pi_key_scale = NULL; net->pi_key_zp = NULL; net->pi_stamp = NULL;
+    net->pi_cap = 0;
+}
+
+static void pi_alloc(network *net)
+{
+    const int B = net->batch;
+    const layer *l0 = &l0_source(net)->layers[0];
+    const size_t eb = (mi355_conv_pack_size(l0->n, l0->c, l0->size) + 255) & ~(size_t)255;
+    if (net->pi_bank_gpu && net->pi_cap >= B && net->pi_entry_bytes == eb) return;
+    pi_free(net);
+    net->pi_cap = 2 * B < 8 ? 8 : 2 * B; /* a batch needs B slots at most; the rest keeps recent keys cached */
+    net->pi_entry_bytes = eb;
+    check_mi355(mi355_alloc(&net->pi_bank_gpu, eb * (size_t)net->pi_cap), "alloc layer-0 bank");
+    net->pi_bank_host = calloc((size_t)net->pi_cap, eb);
+    net->pi_key_scale = calloc((size_t)net->pi_cap, sizeof(uint32_t));
+    net->pi_key_zp = malloc(sizeof(int) * (size_t)net->pi_cap);
+    net->pi_stamp = calloc((size_t)net->pi_cap, sizeof(long));
+    for (int k = 0; k < net->pi_cap; ++k) net->pi_key_zp[k] = -1;
+    check_mi355(mi355_alloc(&net->pi_idx_gpu, 9 * (size_t)B), "alloc layer-0 index");
+    net->pi_idx_host = calloc(9, (size_t)B);
+    check_mi355(mi355_alloc((void **)&net->pi_mm_gpu, 2 * sizeof(float) * (size_t)B), "alloc minmax");
+    net->pi_mm_host = calloc(2 * (size_t)B, sizeof(float));
+}
+
+/* layer 0's blob for input scale s / zero point zp into dst: the shared-scale path's own code (prep_conv_layer, mi355_conv_pack,
+ * mi355_conv_pack_epilogue) on the network that holds the raw weights -- a replica's parent.  prep_conv_layer derives into the
+ * layer's record; every field it writes is saved before and restored after, under one process-wide lock (replicas of one parent may
+ * be quantised from several host threads), so the record reads as it did before the call. */
+static pthread_mutex_t pi_pack_mu = PTHREAD_MUTEX_INITIALIZER;
+
+static void pi_pack(network *net, float s, uint8_t zp, void *dst)
+{
+    network *src = l0_source(net);
+    layer *l0 = &src->layers[0];
+    if (!src->has_host_weights && !src->has_l0_weights) error("per-image input: no raw layer-0 weights to derive the constants from");
+    const size_t n = (size_t)l0->n;
+    pthread_mutex_lock(&pi_pack_mu);
+    /* the record prep_conv_layer rewrites, saved in one scratch block */
+    struct { void *p; size_t bytes; } f[] = {
+        {l0->mult_zero_point, n * sizeof(*l0->mult_zero_point)}, {l0->weights_sum_int, n * sizeof(*l0->weights_sum_int)},
+        {l0->M, n * sizeof(*l0->M)}, {l0->M0, n * sizeof(*l0->M0)}, {l0->M0_right_shift, n * sizeof(*l0->M0_right_shift)},
+        {l0->M0_right_shift_value, n * sizeof(*l0->M0_right_shift_value)}, {l0->M_value, n * sizeof(*l0->M_value)},
+        {l0->biases_int32, n * sizeof(*l0->biases_int32)}, {l0->input_data_uint8_scales, sizeof(float)},
+        {l0->input_data_uint8_zero_point, sizeof(uint8_t)}};
+    const int nf = (int)(sizeof(f) / sizeof(f[0]));
+    size_t total = 0;
+    for (int k = 0; k < nf; ++k) total += f[k].bytes;
+    char *save = malloc(total), *q = save;
+    for (int k = 0; k < nf; ++k) { memcpy(q, f[k].p, f[k].bytes); q += f[k].bytes; }
+    l0->input_data_uint8_scales[0] = s;
+    l0->input_data_uint8_zero_point[0] = zp;
+    prep_conv_layer(src, 0);
+    const int rc = mi355_conv_pack(l0->n, l0->c, l0->size, l0->weights_uint8, l0->weight_data_uint8_zero_point, l0->biases_int32,
+                                   l0->M_value, l0->M0_right_shift_value, dst);
+    const int rc2 = rc ? rc : mi355_conv_pack_epilogue(l0->n, l0->c, l0->size, l0->activation, l0->activ_data_uint8_zero_point[0], dst);
+    q = save;
+    for (int k = 0; k < nf; ++k) { memcpy(f[k].p, q, f[k].bytes); q += f[k].bytes; }
+    free(save);
+    pthread_mutex_unlock(&pi_pack_mu);
+    check_mi355(rc, "mi355_conv_pack");
+    check_mi355(rc2, "mi355_conv_pack_epilogue");
+}
+
+/* the same, exported for host-only checks: layer 0's bank entry for (s, zp) into dst (mi355_conv_pack_size bytes) */
+void network_layer0_entry(network *net, float s, uint8_t zp, void *dst) { pi_pack(net, s, zp, dst); }
+
+/* bank entries for this batch's (scale, zero point) pairs, the index arrays, all uploaded on the network's stream */
+static void pi_bank_update(network *net, const float *scale, const uint8_t *zp)
+{
+    const int B = net->batch;
+    pi_alloc(net);
+    const long tick = ++net->pi_tick;
+    int32_t *entry = (int32_t *)net->pi_idx_host;
+    float *sc = (float *)((char *)net->pi_idx_host + 4 * (size_t)B);
+    uint8_t *zq = (uint8_t *)net->pi_idx_host + 8 * (size_t)B;
+    net->pi_packed = 0;
+    for (int b = 0; b < B; ++b) {
+        uint32_t bits;
+        memcpy(&bits, &scale[b], 4);
+        int k = -1;
+        for (int j = 0; j < net->pi_cap && k < 0; ++j)
+            if (net->pi_key_zp[j] == zp[b] && net->pi_key_scale[j] == bits) k = j;
+        if (k < 0) { /* the least recently used slot this batch does not use */
+            for (int j = 0; j < net->pi_cap; ++j)
+                if (net->pi_stamp[j] != tick && (k < 0 || net->pi_stamp[j] < net->pi_stamp[k])) k = j;
+            char *h = (char *)net->pi_bank_host + (size_t)k * net->pi_entry_bytes;
+            pi_pack(net, scale[b], zp[b], h);
+            check_mi355(mi355_h2d((char *)net->pi_bank_gpu + (size_t)k * net->pi_entry_bytes, h, net->pi_entry_bytes, net->stream),
+                        "upload bank entry");
+            net->pi_key_scale[k] = bits;
+            net->pi_key_zp[k] = zp[b];
+            net->pi_packed++;
+        }
+        net->pi_stamp[k] = tick;
+        entry[b] = k;
+        sc[b] = scale[b];
+        zq[b] = zp[b];
+    }
+    check_mi355(mi355_h2d(net->pi_idx_gpu, net->pi_idx_host, 9 * (size_t)B, net->stream), "upload bank index");
+}
+
+static void quantize_per_image_gpu(network *net, const float *input_gpu)
+{
+    const int B = net->batch;
+    if (!net->pi_mm_gpu || net->pi_cap < B) pi_alloc(net);
+    check_mi355(mi355_image_minmax_batched(input_gpu, B, net->inputs, net->pi_mm_gpu, net->stream), "mi355_image_minmax_batched");
+    check_mi355(mi355_d2h(net->pi_mm_host, net->pi_mm_gpu, 2 * sizeof(float) * (size_t)B, net->stream), "minmax d2h");
+    check_mi355(mi355_stream_sync(net->stream), "sync"); /* the batch's one host sync: every earlier upload of the bank is done too */
+    float *s = malloc(sizeof(float) * (size_t)B);
+    uint8_t *zp = malloc((size_t)B);
+    for (int b = 0; b < B; ++b) image_scale_zero_point(net->pi_mm_host[2 * b + 1] + 0.0f, net->pi_mm_host[2 * b], &s[b], &zp[b]);
+    if (!net->prepared) quantization_weights_and_activations_fixed_input(net, s[0], zp[0]);
+    pi_bank_update(net, s, zp);
+    free(s); free(zp);
+    const char *idx = (const char *)net->pi_idx_gpu;
+    check_mi355(mi355_image_quantize_per_image(input_gpu, B, net->inputs, (const float *)(idx + 4 * (size_t)B),
+                                               (const uint8_t *)(idx + 8 * (size_t)B), net->input_uint8_gpu, net->stream),
+                "mi355_image_quantize_per_image");
+}
+
 void network_letterbox_input_gpu(network *net, int slot, const float *im_gpu, int imw, int imh)
 {
     if (slot < 0 || slot >= net->batch || !im_gpu) error("network_letterbox_input_gpu: bad slot / null image");
@@ -479,6 +675,7 @@ void set_batch_network(network *net, int b)
     if (net->replica_of) error("set_batch_network on a replica: re-batch the parent and make new replicas");
     if (net->n_replicas > 0) error("set_batch_network: free this network's replicas first (they borrow its packed weights on the device)");
     net->batch = b;
+    pi_free(net); /* the per-image bank and index arrays are sized by the batch */
     free(net->input); free(net->input_uint8);
     net->input = calloc((size_t)net->inputs * b, sizeof(float));
     net->input_uint8 = calloc((size_t)net->inputs * b, sizeof(uint8_t));
@@ -722,11 +919,9 @@ static int cmp_rec_rank(const void *a, const void *b)
     return (x > y) - (x < y);
 }
 
-void network_yolo_detections_gpu(network *net, int i, int imw, int imh, float thresh, int relative, float *recs,
-                                 int max_recs, int *counts)
+/* anchors, masks and room for max_recs records per image of yolo layer l on the device (kept on the layer) */
+static void det_buffers(network *net, layer *l, int max_recs)
 {
-    if (i < 0 || i >= net->n || net->layers[i].type != YOLO) error("network_yolo_detections_gpu: not a yolo layer");
-    layer *l = &net->layers[i];
     const int B = net->batch, rl = 6 + l->classes;
     if (!l->anchors_gpu) {
         check_mi355(mi355_alloc((void **)&l->anchors_gpu, sizeof(float) * 2 * (size_t)l->total), "alloc anchors");
@@ -740,9 +935,12 @@ void network_yolo_detections_gpu(network *net, int i, int imw, int imh, float th
         check_mi355(mi355_alloc((void **)&l->det_counts_gpu, sizeof(int) * (size_t)B), "alloc counts");
         l->det_cap = max_recs;
     }
-    check_mi355(mi355_yolo_detections(l->output_gpu, B, l->n, l->classes, l->h, l->w, l->anchors_gpu, l->mask_gpu, net->w,
-                                      net->h, imw, imh, thresh, relative, l->det_recs_gpu, max_recs, l->det_counts_gpu,
-                                      net->stream), "mi355_yolo_detections");
+}
+
+/* records of every image back to the host, each image's in reference order (ascending rank) */
+static void det_pull(network *net, layer *l, float *recs, int max_recs, int *counts)
+{
+    const int B = net->batch, rl = 6 + l->classes;
     check_mi355(mi355_d2h(counts, l->det_counts_gpu, sizeof(int) * (size_t)B, net->stream), "pull counts");
     check_mi355(mi355_stream_sync(net->stream), "sync");
     for (int b = 0; b < B; ++b) { /* only the records that exist cross PCIe; reference order = ascending rank */
@@ -753,6 +951,38 @@ void network_yolo_detections_gpu(network *net, int i, int imw, int imh, float th
         check_mi355(mi355_stream_sync(net->stream), "sync");
         qsort(dst, (size_t)k, sizeof(float) * rl, cmp_rec_rank);
     }
+}
+
+void network_yolo_detections_gpu(network *net, int i, int imw, int imh, float thresh, int relative, float *recs,
+                                 int max_recs, int *counts)
+{
+    if (i < 0 || i >= net->n || net->layers[i].type != YOLO) error("network_yolo_detections_gpu: not a yolo layer");
+    layer *l = &net->layers[i];
+    const int B = net->batch;
+    det_buffers(net, l, max_recs);
+    check_mi355(mi355_yolo_detections(l->output_gpu, B, l->n, l->classes, l->h, l->w, l->anchors_gpu, l->mask_gpu, net->w,
+                                      net->h, imw, imh, thresh, relative, l->det_recs_gpu, max_recs, l->det_counts_gpu,
+                                      net->stream), "mi355_yolo_detections");
+    det_pull(net, l, recs, max_recs, counts);
+}
+
+void network_yolo_detections_gpu_sizes(network *net, int i, const int *imw, const int *imh, float thresh, int relative, float *recs,
+                                       int max_recs, int *counts)
+{
+    if (i < 0 || i >= net->n || net->layers[i].type != YOLO) error("network_yolo_detections_gpu_sizes: not a yolo layer");
+    const int B = net->batch;
+    for (int b = 0; b < B; ++b)
+        if (imw[b] < 1 || imh[b] < 1) error("network_yolo_detections_gpu_sizes: image sizes must be positive");
+    layer *l = &net->layers[i];
+    det_buffers(net, l, max_recs);
+    if (!l->det_sizes_gpu) check_mi355(mi355_alloc((void **)&l->det_sizes_gpu, 2 * sizeof(int) * (size_t)B), "alloc sizes");
+    check_mi355(mi355_h2d(l->det_sizes_gpu, imw, sizeof(int) * (size_t)B, net->stream), "sizes");
+    check_mi355(mi355_h2d(l->det_sizes_gpu + B, imh, sizeof(int) * (size_t)B, net->stream), "sizes");
+    check_mi355(mi355_yolo_detections_sizes(l->output_gpu, B, l->n, l->classes, l->h, l->w, l->anchors_gpu, l->mask_gpu, net->w, net->h,
+                                            l->det_sizes_gpu, l->det_sizes_gpu + B, thresh, relative, l->det_recs_gpu, max_recs,
+                                            l->det_counts_gpu, net->stream),
+                "mi355_yolo_detections_sizes");
+    det_pull(net, l, recs, max_recs, counts); /* (its first sync also retires the size uploads from the caller's arrays) */
 }
 
 /* ------------------------------------------------------------------------------------ packed-weight exchange */
@@ -995,6 +1225,7 @@ network *network_replica_ex(network *parent, int default_stream)
     net->accum_mode = parent->accum_mode; net->store_mode = parent->store_mode;
     net->fuse_maxpool = parent->fuse_maxpool; net->keep_head_float = parent->keep_head_float;
     net->use_graph = parent->use_graph; net->input_direct_off = parent->input_direct_off;
+    net->per_image = parent->per_image; /* its own bank (allocated by its first per-image batch); layer 0's raw weights are the parent's */
     net->dump_int32 = 0;
     if (parent->accum_mode == MI355_ACC_REF_F32) error("network_replica: MI355_ACC_REF_F32 reads raw weights, which a replica does not hold");
     net->replica_of = parent;
@@ -1060,6 +1291,7 @@ void free_network(network *net)
     if (net->input_t.data) mi355_free(net->input_t.data);
     if (net->input_gpu) mi355_free(net->input_gpu);
     if (net->quant_mm_gpu) mi355_free(net->quant_mm_gpu);
+    pi_free(net);
     if (net->selfcheck_gpu) mi355_free(net->selfcheck_gpu);
     if (net->stream) mi355_stream_release(net->stream);
     free(net->layers); free(net->input); free(net->input_uint8); free(net->seen); free(net->cfg_path);
