@@ -254,6 +254,12 @@ int mi355_debug_flags(int flags);
  * conv + maxpool), 3 conv1x1.hip, 4 conv_ws3.hip, 5 conv_igemm.hip / conv_rows.hip / conv_rows16.hip, 6 fp32-accumulate emulation,
  * 7 conv_pool16.hip (16 -> 32 + maxpool with the packed epilogue table), 8 conv_small32.hip (32 -> 64 + maxpool). */
 int mi355_last_conv_kernel(void);
+/* Geometry of the calling thread's most recent convolution kernel launch (any mi355_conv_*forward call): workgroups in the grid,
+ * threads per workgroup, bytes of dynamic LDS, as the launcher chose them for the plan, batch and tile count.  Each pointer may be
+ * NULL.  Recorded host-side when the kernel is launched, so a call that was refused before any launch leaves the previous launch's
+ * values.  Returns MI355_EINVAL (and zeros) before the thread's first launch.  Tests assert with it which tiling branch a shape
+ * reaches. */
+int mi355_last_conv_launch(int *grid, int *threads, int *lds_bytes);
 
 /* ---- glue layers ---------------------------------------------------------------------------------------- */
 /* forward_maxpool_layer_quant (ref: src/maxpool_layer.c:109-172): window offset -pad/2, OOB taps = uint8 0 */

@@ -83,6 +83,10 @@ def shim():
         L.mi355_debug_flags.argtypes = [ci]
         L.mi355_last_conv_kernel.argtypes = []
         L.mi355_last_conv_kernel.restype = ci
+        if hasattr(L, "mi355_last_conv_launch"):  # (absent from older A/B builds under build_ab/)
+            L.mi355_last_conv_launch.argtypes = [C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+        L.mi355_conv_shortcut_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.POINTER(Tensor), C.POINTER(Tensor),
+                                                  C.c_int32, C.c_int32, C.c_uint8, C.c_uint8, vp]
         L.mi355_conv_yolo_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.POINTER(Tensor), vp, vp, ci, vp]
         L.mi355_conv_upsample_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.POINTER(Tensor), ci, vp]
         L.mi355_maxpool_forward.argtypes = [C.POINTER(Tensor), C.POINTER(Tensor), ci, ci, ci, vp]
@@ -211,12 +215,33 @@ def conv_pack(wq, zp_w, c, ksize, biases_int32, M_value, shift_value, activation
     return blob
 
 
+def last_conv_kernel():
+    """mi355_last_conv_kernel: the kernel family that served this thread's most recent conv call"""
+    return int(shim().mi355_last_conv_kernel())
+
+
+def last_conv_launch():
+    """mi355_last_conv_launch: (workgroups, threads per workgroup, dynamic LDS bytes) of this thread's most recent conv kernel launch"""
+    g, t, l = C.c_int(), C.c_int(), C.c_int()
+    shim().mi355_last_conv_launch(C.byref(g), C.byref(t), C.byref(l))
+    return g.value, t.value, l.value
+
+
+def _pack_blob(wq, zp_w, c, ksize, biases_int32, M_value, shift_value, activation, zp_act, epilogue):
+    """device blob; epilogue=True adds the epilogue table for (activation, zp_act), as the darknet host always does"""
+    ept = (activation, zp_act) if epilogue else ()
+    return DevBuf.from_numpy(conv_pack(wq, zp_w, c, ksize, biases_int32, M_value, shift_value, *ept))
+
+
 def conv_forward(x: DevTensor, wq, zp_w, ksize, biases_int32, M_value, shift_value, zp_in, zp_act, s_act,
-                 activation, store=STORE_WRAP, accum=ACC_EXACT, want_acc=True, want_f32=False, stride=1, pad=None):
-    """One quantized conv layer through the C-ABI. Returns dict(u8 NCHW, int32 [B,n,HW], f32).  pad=None: ksize // 2."""
+                 activation, store=STORE_WRAP, accum=ACC_EXACT, want_acc=True, want_f32=False, stride=1, pad=None,
+                 plan=0, epilogue=False):
+    """One quantized conv layer through the C-ABI. Returns dict(u8 NCHW, int32 [B,n,HW], f32).  pad=None: ksize // 2.
+    plan: mi355_conv_desc.plan (0 latency, 1 throughput).  epilogue: pack the blob's epilogue table for (activation, zp_act)
+    and set desc.epilogue_packed, as the darknet host does (host/layers.c)."""
     n = wq.shape[0]
     c = x.t.C
-    blob = DevBuf.from_numpy(conv_pack(wq, zp_w, c, ksize, biases_int32, M_value, shift_value))
+    blob = _pack_blob(wq, zp_w, c, ksize, biases_int32, M_value, shift_value, activation, zp_act, epilogue)
     wraw = DevBuf.from_numpy(np.ascontiguousarray(wq, np.uint8))
     zraw = DevBuf.from_numpy(np.ascontiguousarray(zp_w, np.uint8))
     if pad is None:
@@ -226,7 +251,7 @@ def conv_forward(x: DevTensor, wq, zp_w, ksize, biases_int32, M_value, shift_val
     cnt = x.t.B * n * OH * OW
     acc = DevBuf(cnt * 4) if want_acc else None
     f32 = DevBuf(cnt * 4) if want_f32 else None
-    d = ConvDesc(n, c, ksize, stride, pad, activation, store, accum, zp_in, zp_act, float(s_act))
+    d = ConvDesc(n, c, ksize, stride, pad, activation, store, accum, zp_in, zp_act, float(s_act), int(plan), int(bool(epilogue)))
     check(shim().mi355_conv_forward(C.byref(d), x.ref(), blob.ptr, wraw.ptr, zraw.ptr, y.ref(),
                                     acc.ptr if acc else None, f32.ptr if f32 else None, None), "conv_forward")
     check(shim().mi355_stream_sync(None), "sync")
@@ -235,6 +260,55 @@ def conv_forward(x: DevTensor, wq, zp_w, ksize, biases_int32, M_value, shift_val
         out["int32"] = acc.to_numpy(np.int32, cnt).reshape(x.t.B, n, OH * OW)
     if f32:
         out["f32"] = f32.to_numpy(np.float32, cnt).reshape(x.t.B, n, OH * OW)
+    return out
+
+
+FUSED = ("pool2", "pool1", "upsample", "yolo", "shortcut")
+
+
+def conv_fused_forward(x: DevTensor, wq, zp_w, ksize, biases_int32, M_value, shift_value, zp_in, zp_act, s_act, activation, fuse,
+                       store=STORE_WRAP, plan=0, epilogue=False, keep_y=False, classes=80, up=2, res=None, Ka=0, Kb=0,
+                       zp_from=0, zp_out=0):
+    """A conv fused with the layer after it, through the C-ABI entry point the darknet host uses for it (stride 1, pad ksize // 2):
+      pool2     2x2 / stride-2 maxpool (mi355_conv_pool_forward, pooled map)        -> out["u8"] = the pooled tensor
+      pool1     2x2 / stride-1 maxpool (mi355_conv_pool_forward, the conv's map)    -> out["u8"] = the pooled tensor
+      upsample  nearest x `up` (mi355_conv_upsample_forward)                        -> out["u8"] = the upsampled tensor
+      yolo      quant_stop head + yolo layer (mi355_conv_yolo_forward, `classes`)   -> out["u8"], out["f32"], out["yolo"]
+      shortcut  quantized residual add of DevTensor `res` (mi355_conv_shortcut_forward, Ka, Kb, zp_from, zp_out) -> out["u8"] = the sum
+    keep_y (pools): the conv's own tensor is stored as well, out["y"].  plan / epilogue as in conv_forward.  A refused call raises
+    MI355Error (code -22)."""
+    assert fuse in FUSED, fuse
+    n = wq.shape[0]
+    c = x.t.C
+    B, H, W = x.t.B, x.t.H, x.t.W
+    blob = _pack_blob(wq, zp_w, c, ksize, biases_int32, M_value, shift_value, activation, zp_act, epilogue)
+    d = ConvDesc(n, c, ksize, 1, ksize // 2, activation, store, ACC_EXACT, zp_in, zp_act, float(s_act), int(plan), int(bool(epilogue)))
+    S = shim()
+    out = {}
+    if fuse in ("pool2", "pool1"):
+        y = DevTensor(B, H, W, n, zp_act) if keep_y else None
+        yp = DevTensor(B, H // 2, W // 2, n, zp_act) if fuse == "pool2" else DevTensor(B, H, W, n, zp_act)
+        check(S.mi355_conv_pool_forward(C.byref(d), x.ref(), blob.ptr, y.ref() if y else None, yp.ref(), None), "conv_pool_forward")
+        res_t = yp
+        if y:
+            out["y"] = y.to_nchw()
+    elif fuse == "upsample":
+        res_t = DevTensor(B, H * up, W * up, n, zp_act)
+        check(S.mi355_conv_upsample_forward(C.byref(d), x.ref(), blob.ptr, res_t.ref(), up, None), "conv_upsample_forward")
+    elif fuse == "yolo":
+        res_t = DevTensor(B, H, W, n, zp_act)
+        cnt = B * n * H * W
+        f32, yo = DevBuf(cnt * 4), DevBuf(cnt * 4)
+        check(S.mi355_conv_yolo_forward(C.byref(d), x.ref(), blob.ptr, res_t.ref(), f32.ptr, yo.ptr, classes, None), "conv_yolo_forward")
+        out["f32"] = f32.to_numpy(np.float32, cnt).reshape(B, n, H * W)
+        out["yolo"] = yo.to_numpy(np.float32, cnt).reshape(B, n, H * W)
+    else:
+        res_t = DevTensor(B, H, W, n, zp_out)
+        check(S.mi355_conv_shortcut_forward(C.byref(d), x.ref(), blob.ptr, res.ref(), res_t.ref(), int(Ka), int(Kb), int(zp_from),
+                                            int(zp_out), None), "conv_shortcut_forward")
+    check(S.mi355_stream_sync(None), "sync")
+    out["u8"] = res_t.to_nchw()
+    out["tensor"] = res_t
     return out
 
 

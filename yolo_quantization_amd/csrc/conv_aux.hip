@@ -222,6 +222,7 @@ static int conv_first_pool_launch_act(AuxArgs &a, hipStream_t st)
     const int total = a.B * (a.H / 2) * (a.W / 2);
     const int grid = (total + bs - 1) / bs;
     const size_t lds = a.n * 11 * sizeof(uint32_t);
+    conv_launch_note(grid, bs, lds);
     if (a.store_mode == MI355_STORE_SATURATE)
         hipLaunchKernelGGL((conv_first_pool_u8_kernel<ACT, true, PI>), dim3(grid), dim3(bs), lds, st, a);
     else
@@ -247,6 +248,7 @@ int conv_first_launch(AuxArgs &a, hipStream_t st)
 {
     const int bs = 256;
     const int grid = (a.total_n + bs - 1) / bs;
+    conv_launch_note(grid, bs, a.n * 9 * sizeof(uint32_t));
     if (a.entry_of_image)
         hipLaunchKernelGGL(conv_first_u8_kernel<true>, dim3(grid), dim3(bs), a.n * 9 * sizeof(uint32_t), st, a);
     else
@@ -259,6 +261,7 @@ int conv_ref_f32_launch(AuxArgs &a, hipStream_t st)
     const int bs = 256;
     const long total = (long)a.B * a.n * a.H * a.W;
     const long grid = (total + bs - 1) / bs;
+    conv_launch_note(grid, bs, 0);
     if (a.entry_of_image)
         hipLaunchKernelGGL(conv_ref_f32_kernel<true>, dim3((unsigned)grid), dim3(bs), 0, st, a);
     else
@@ -1182,6 +1185,7 @@ __global__ __launch_bounds__(256, 4) void conv_first_mfma_kernel(const AuxArgs a
 template <int ACT, int NM, bool PI>
 static int first_mfma_launch_sat(AuxArgs &a, hipStream_t st, int grid)
 {
+    conv_launch_note(grid, 256, 0);
     if (a.planar) {
         if (a.store_mode == MI355_STORE_SATURATE)
             hipLaunchKernelGGL((conv_first_mfma_pool_kernel<ACT, true, NM, true, PI>), dim3(grid), dim3(256), 0, st, a);
@@ -1202,6 +1206,7 @@ static int first_mfma_launch_sat(AuxArgs &a, hipStream_t st, int grid)
 template <int ACT, int NM, bool PI>
 static int first_mfma_nopool_launch_sat(AuxArgs &a, hipStream_t st, int grid)
 {
+    conv_launch_note(grid, 256, 0);
     if (a.planar) {
         if (a.store_mode == MI355_STORE_SATURATE)
             hipLaunchKernelGGL((conv_first_mfma_kernel<ACT, true, NM, true, PI>), dim3(grid), dim3(256), 0, st, a);

@@ -596,6 +596,7 @@ static int launch_cfg(ConvArgs &a, hipStream_t st)
             return MI355_EHIP;
     }
     dim3 grid(a.ntiles_n * a.mtiles), block(NT);
+    conv_launch_note(grid.x, NT, lds);
     hipLaunchKernelGGL(kern, grid, block, lds, st, a);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }

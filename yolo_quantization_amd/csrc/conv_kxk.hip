@@ -290,6 +290,7 @@ int kxk_launch_one(const KxkArgs &a, int grid, size_t lds, hipStream_t st)
             h = lds;
         }
     }
+    conv_launch_note(grid, KXK_THREADS, lds);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(KXK_THREADS), lds, st, a);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }
@@ -347,6 +348,7 @@ int conv_ref_f32_general_launch(KxkArgs &a, hipStream_t st)
     const int bs = 256;
     const long total = (long)a.B * a.n * a.OH * a.OW;
     const long grid = (total + bs - 1) / bs;
+    conv_launch_note(grid, bs, 0);
     hipLaunchKernelGGL(conv_ref_f32_general_kernel, dim3((unsigned)grid), dim3(bs), 0, st, a);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }

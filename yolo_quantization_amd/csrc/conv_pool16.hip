@@ -334,6 +334,7 @@ bool conv_pool16_eligible(int n, int c, int ksize) { return ksize == 3 && c == 1
 template <int ACT>
 static int p16_launch_sat(ConvArgs &a, hipStream_t st, int grid)
 {
+    conv_launch_note(grid, 256, 0);
     if (a.store_mode == MI355_STORE_SATURATE) hipLaunchKernelGGL((conv_pool16_kernel<ACT, true>), dim3(grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((conv_pool16_kernel<ACT, false>), dim3(grid), dim3(256), 0, st, a);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;

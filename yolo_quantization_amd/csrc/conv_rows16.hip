@@ -734,6 +734,7 @@ static int rows16_launch_cfg(ConvArgs &a, hipStream_t st)
     a.fd_ntper = fastdiv_make((uint32_t)(a.xcd_mb * a.ntiles_n));
     a.fd_mb = fastdiv_make((uint32_t)a.xcd_mb);
     dim3 grid(a.ntiles_n * a.mtiles), block(NT);
+    conv_launch_note(grid.x, NT, lds);
     hipLaunchKernelGGL(kern, grid, block, lds, st, a);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }

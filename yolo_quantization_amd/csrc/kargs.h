@@ -205,6 +205,9 @@ bool conv1x1_ws_eligible(int n, int c, int ksize);
 int conv_ws3_launch(ConvArgs &a, hipStream_t st);
 bool conv_ws3_eligible(int n, int c, int ksize);
 int mi355_debug_flags_get();
+// Every convolution launch site records its geometry just before hipLaunchKernelGGL (shim.hip: read back by mi355_last_conv_launch):
+// workgroups, threads per workgroup, dynamic LDS bytes.  Host-side only, per calling thread.
+void conv_launch_note(long grid, int threads, size_t lds);
 // Throughput plan (mi355_conv_desc.plan): does this launch fit ONE round of whole-CU workgroups (128 x 384 output tiles, one
 // per CU)?  Only such launches are re-planned into half-CU workgroups that share a CU with another batch's layer; a launch of
 // several rounds keeps the whole-chip kernels, which are the more efficient ones and have their own tail to overlap
@@ -265,6 +268,7 @@ template <void (*kern)(const ConvArgs)>
 static inline int launch_big_lds(int grid, int threads, size_t lds, hipStream_t st, const ConvArgs &a)
 {
     if (!lds_limit_for<kern>(lds)) return MI355_EHIP;
+    conv_launch_note(grid, threads, lds);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, st, a);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }

@@ -318,6 +318,19 @@ static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 static thread_local int g_last_kernel = 0;
 extern "C" int mi355_last_conv_kernel(void) { return g_last_kernel; }
+static thread_local long g_last_grid = 0;
+static thread_local int g_last_threads = 0, g_last_lds = 0;
+extern "C++" void conv_launch_note(long grid, int threads, size_t lds)  // (kargs.h: C++ linkage, this file is one extern "C" block)
+{
+    g_last_grid = grid; g_last_threads = threads; g_last_lds = (int)lds;
+}
+extern "C" int mi355_last_conv_launch(int *grid, int *threads, int *lds_bytes)
+{
+    if (grid) *grid = (int)g_last_grid;
+    if (threads) *threads = g_last_threads;
+    if (lds_bytes) *lds_bytes = g_last_lds;
+    return g_last_grid ? MI355_OK : MI355_EINVAL;
+}
 
 // every shape the specialised kernels do not take (size 1..11, any channel count) gets conv_kxk.hip's packing (header.generic)
 static bool specialised_shape(int c, int ksize) { return (ksize == 1 || ksize == 3) && ((c == 3 && ksize == 3) || c % 16 == 0); }
