@@ -307,6 +307,11 @@ void network_bcast_packed(network *net, void *comm, int rank, int root);
 void network_save_packed(network *net, char *filename);
 void network_load_packed(network *net, char *filename);
 
+/* what the planner decided for layer i, as it stands now (after the launchers had their say at run time): out[0..7] = route_elided,
+ * out_view, byte offset of the layer's tensor inside the buffer that owns it, fuse_next_pool, fuse_next_upsample, fuse_next_shortcut,
+ * fuse_next_yolo, fuse_pool_keep.  Returns 0, or -1 for a bad index.  Read-only: tests and tools look at the plan through it. */
+int dnq_layer_plan(network *net, int i, int *out);
+
 /* misc */
 void error(const char *s);
 void file_error(const char *s);

@@ -61,3 +61,21 @@ def test_layer0_bank_entries_equal_oracle_constants_packed(tmp_path):
         assert len(zps) > 1  # the images really have different zero points
     finally:
         H.free_network(h)
+
+
+def test_per_image_refuses_a_three_filter_first_layer():
+    """A 3-filter layer stores 4-byte plain cells, which only the general kernel writes, and the general kernel is not served per image:
+    mi355_conv_forward_per_image answers MI355_EINVAL before anything is launched (arguments checked on the host: no device needed)."""
+    from yolo_quantization_amd import binding
+    S = binding.shim()
+    x, y = binding.Tensor(), binding.Tensor()
+    S.mi355_tensor_describe(C.byref(x), 2, 8, 8, 3)
+    S.mi355_tensor_describe(C.byref(y), 2, 8, 8, 3)
+    assert y.cs == 4
+    buf = np.zeros(1 << 16, np.uint8)  # never read: the call is refused on its arguments
+    x.data = y.data = buf.ctypes.data
+    d = binding.ConvDesc(n=3, c=3, ksize=3, stride=1, pad=1, activation=9)
+    eb = (int(S.mi355_conv_pack_size(3, 3, 3)) + 255) & ~255
+    rc = S.mi355_conv_forward_per_image(C.byref(d), C.byref(x), buf.ctypes.data, eb, buf.ctypes.data, buf.ctypes.data, None, None,
+                                        C.byref(y), None, None, None)
+    assert rc < 0 and b"not served per image" in S.mi355_last_error()

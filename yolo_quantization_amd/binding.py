@@ -370,6 +370,7 @@ def host():
         L.dnq_layer_is_fused.argtypes = [vp, ci]
         L.dnq_layer_fuses_next.argtypes = [vp, ci]
         L.dnq_layer_shortcut.argtypes = [vp, ci, vp]
+        L.dnq_layer_plan.argtypes = [vp, ci, vp]
         L.network_save_packed.argtypes = [vp, C.c_char_p]
         L.network_load_packed.argtypes = [vp, C.c_char_p]
         L.dnq_layer_conv_kernel.argtypes = [vp, ci]
@@ -390,6 +391,8 @@ def host():
 
 INFO_KEYS = ["type", "out_c", "out_h", "out_w", "c", "h", "w", "n", "size", "stride", "pad", "activation",
              "batch_normalize", "quantized", "quant_stop", "outputs"]
+PLAN_KEYS = ["route_elided", "out_view", "view_offset", "fuse_next_pool", "fuse_next_upsample", "fuse_next_shortcut", "fuse_next_yolo",
+             "fuse_pool_keep"]
 T_CONV, T_MAXPOOL, T_ROUTE, T_SHORTCUT, T_YOLO, T_UPSAMPLE = 0, 3, 8, 13, 23, 26
 
 
@@ -556,6 +559,13 @@ class Net:
     def fuses_next(self, i):
         """layer i + 1 runs inside conv i's kernel (conv i's own tensor may be stored too: a conv + pool whose output a route reads)."""
         return bool(self.H.dnq_layer_fuses_next(self.h, i))
+
+    def plan(self, i):
+        """The planner's decisions for layer i as they stand now (dnq_layer_plan): after a forward pass the fuse flags a launcher
+        refused are 0."""
+        a = (C.c_int * 8)()
+        assert self.H.dnq_layer_plan(self.h, i, a) == 0
+        return dict(zip(PLAN_KEYS, list(a)))
 
     def prep(self, i):
         n = max(self.info[i]["n"], 1)

@@ -401,7 +401,8 @@ static int blob_layout(int n, int c, int ksize, ConvBlobHeader *h)
         off = align16(off + sizeof(EptHeader) + (size_t)h->mpad * sizeof(EptEntry) + (size_t)LUTQ_N +
                       (h->first ? (size_t)((n + 15) / 16) * 64 * sizeof(L0Lane) : 0));
     }
-    if (ksize == 3) {  // the general kernel's fragments for the strides / paddings the 3x3 kernels refuse, behind everything they read
+    if (ksize == 3 || n == 3) {  // the general kernel's fragments for the strides / paddings the 3x3 kernels refuse and for every 3-filter
+                                 // layer (4-byte output cells: conv_forward_impl), behind everything the specialised kernels read
         h->off_gen = off;
         off = align16(off + gen_bytes);
     }
@@ -724,7 +725,11 @@ static int conv_forward_impl(const mi355_conv_desc *d, const mi355_tensor *x, co
     {  // the general kernels: shapes the specialised kernels do not take, and the strides / paddings they refuse
         const bool legacy_geom = d->stride == 1 && ((d->ksize == 3 && d->pad == 1) || (d->ksize == 1 && d->pad == 0));
         const bool legacy_exact = legacy_geom || (d->stride == 2 && d->ksize == 3 && d->pad == 1 && d->c % 16 == 0);
-        if (!specialised_shape(d->c, d->ksize) || !(d->accum_mode == MI355_ACC_REF_F32 ? legacy_geom : legacy_exact))
+        // a 3-filter layer's output cells are the image's: 4 bytes, plain (mi355_tensor_describe).  Only the general kernels store those;
+        // the specialised ones write biased bytes in 16-byte groups
+        const bool cell4_out = y && y->cs == 4;
+        if (bank && cell4_out) return einval("conv_forward_per_image: a 3-filter first layer runs on the general kernel, which is not served per image");
+        if (!specialised_shape(d->c, d->ksize) || !(d->accum_mode == MI355_ACC_REF_F32 ? legacy_geom : legacy_exact) || cell4_out)
             return conv_generic_forward(d, x, blob, w_u8, zp_w, y, acc_out, y_f32, (hipStream_t)stream,
                                         ypool || up != 1 || yolo_out || res);
     }

@@ -98,6 +98,33 @@ int dnq_layer_fuses_next(network *net, int i)
            net->accum_mode == MI355_ACC_EXACT;
 }
 
+/* The planner's decisions for layer i as they stand NOW (plan_views at allocation, plan_fusion at prep / network_set_plan, the flags
+ * the launchers cleared at run time): out[0] = route_elided, out[1] = out_view, out[2] = byte offset of the layer's tensor inside the
+ * buffer that owns it (0 for a tensor that owns its buffer; a one-input route that shares its input's tensor reports that input's),
+ * out[3..6] = fuse_next_pool, fuse_next_upsample, fuse_next_shortcut, fuse_next_yolo, out[7] = fuse_pool_keep.  The fuse flags are the
+ * raw ones: dnq_layer_fuses_next tells whether the run mode (fuse_maxpool, dump_int32, accum_mode) honours them. */
+int dnq_layer_plan(network *net, int i, int *out)
+{
+    if (i < 0 || i >= net->n || !out) return -1;
+    const layer *l = &net->layers[i];
+    out[0] = l->route_elided; out[1] = l->out_view; out[2] = 0;
+    out[3] = l->fuse_next_pool; out[4] = l->fuse_next_upsample; out[5] = l->fuse_next_shortcut; out[6] = l->fuse_next_yolo;
+    out[7] = l->fuse_pool_keep;
+    if (l->out_view && l->out_t.data) {
+        int j = i; /* a shared one-input route: the window (if any) is its input's */
+        while (net->layers[j].type == ROUTE && net->layers[j].n == 1 && net->layers[j].out_view) j = net->layers[j].input_layers[0];
+        const layer *p = &net->layers[j];
+        if (p->out_view)
+            for (int r = j + 1; r < net->n; ++r) { /* the concatenating route whose buffer layer j writes into */
+                const layer *q = &net->layers[r];
+                if (q->type != ROUTE || q->n < 2 || !q->route_elided) continue;
+                for (int k = 0; k < q->n; ++k)
+                    if (q->input_layers[k] == j) out[2] = (int)((const char *)p->out_t.data - (const char *)q->out_t.data);
+            }
+    }
+    return 0;
+}
+
 /* k[0..2] = Ka, Kb, `from` index of shortcut layer i */
 int dnq_layer_shortcut(network *net, int i, int32_t *k)
 {

@@ -351,7 +351,9 @@ static void plan_fusion(network *net)
     for (int i = 0; i < net->n; ++i) net->layers[i].fuse_next_upsample = 0;
     for (int i = 0; i + 1 < net->n; ++i) { /* conv + nearest upsample: the conv stores every pixel stride x stride times */
         layer *c = &net->layers[i], *u = &net->layers[i + 1];
-        if (c->type != CONVOLUTIONAL || u->type != UPSAMPLE || c->quant_stop_flag || c->c % 64 || u->stride > 4 || c->stride != 1) continue;
+        /* (an upsample with a quant_stop float tail runs on its own: the fused store skips the layer, and with it the tail) */
+        if (c->type != CONVOLUTIONAL || u->type != UPSAMPLE || c->quant_stop_flag || u->quant_stop_flag || c->c % 64 || u->stride > 4 ||
+            c->stride != 1) continue;
         if (!output_read_elsewhere(net, i)) c->fuse_next_upsample = 1;
     }
     for (int i = 0; i + 1 < net->n; ++i) { /* quant_stop head conv + yolo: one kernel writes both float tensors */

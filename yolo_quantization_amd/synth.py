@@ -134,13 +134,22 @@ def _quantize_per_channel(wf: np.ndarray) -> tuple[np.ndarray, np.ndarray, np.nd
     return q, scale, zp
 
 
-def synth_weights(cfg_path: str, out_path: str, seed: int = 1234, act_gain: float = 1.0, small_m_channels: int = 0) -> dict:
+def _glue_record(a, i: int, own_zp: bool):
+    """(scale, zero point) a glue layer writes: its input's, or -- own_zp -- the same scale with another zero point"""
+    return (a[0], (int(a[1]) + 16 + 7 * (i % 5)) % 256) if own_zp else a
+
+
+def synth_weights(cfg_path: str, out_path: str, seed: int = 1234, act_gain: float = 1.0, small_m_channels: int = 0,
+                  glue_own_zp: bool = False) -> dict:
     """Write a seeded synthetic `.weights` file for `cfg_path`. Returns {'sha256': ..., 'layers': [...]}.
     act_gain > 1 divides every activation scale by that factor so that requantised values overflow 0..255 and
     exercise the reference's wrap-on-store behaviour (src/convolutional_layer.c:737-749).
     small_m_channels > 0 shrinks the float weights of the first that many filters of every convolution by 64: their per-channel weight
     scale -- and with it the requantisation multiplier M = s_in * s_w / s_out (src/blas.c:313) -- falls to ~2e-5, below what the kernels'
-    integer requantisation accepts (common.h intrq_make): the 'unfriendly model' of bench.py --small-m-channels."""
+    integer requantisation accepts (common.h intrq_make): the 'unfriendly model' of bench.py --small-m-channels.
+    glue_own_zp (off: every byte of the file as before) gives the records of [maxpool], multi-input [route] and quantized [upsample] layers
+    a zero point that DIFFERS from their input's: the layer after such a glue layer takes its input zero point -- its pad value -- from
+    that record (src/blas.c:301-305), so a host that inherited it from the wrong layer no longer passes."""
     rng = np.random.default_rng(seed)
     _, layers = layer_shapes(read_cfg(cfg_path))
     act_q: list[tuple[np.float32, int]] = []
@@ -172,17 +181,19 @@ def synth_weights(cfg_path: str, out_path: str, seed: int = 1234, act_gain: floa
             act_q.append((a_s, a_zp))
             info.append({"i": i, "type": "conv", "K": K, "n": L.n})
         elif L.type == "maxpool":
-            a = act_q[i - 1]
+            a = _glue_record(act_q[i - 1], i, glue_own_zp)
             blob += struct.pack("<fB", float(a[0]), int(a[1]))
             act_q.append(a)
         elif L.type == "upsample":
             a = act_q[i - 1]
             if L.quantized:
+                a = _glue_record(a, i, glue_own_zp)
                 blob += struct.pack("<fB", float(a[0]), int(a[1]))
             act_q.append(a)
         elif L.type == "route":
             a = act_q[L.inputs[0]]
             if L.quantized and len(L.inputs) > 1:
+                a = _glue_record(a, i, glue_own_zp)
                 blob += struct.pack("<fB", float(a[0]), int(a[1]))
             act_q.append(a)
         elif L.type == "shortcut":
