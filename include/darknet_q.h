@@ -188,6 +188,14 @@ struct network {
     void *pi_idx_gpu, *pi_idx_host; /* [B] int32 entry | [B] float scale | [B] uint8 zero point */
     float *pi_mm_gpu, *pi_mm_host;  /* [B][2] max, min */
     int pi_packed;              /* bank entries packed by the last batch (the others came from the cache) */
+    /* 8-bit frame input (network_frames_u8_input_gpu): lazily allocated, sized by the batch, freed with the network and on re-batch.
+     * A replica owns its own. */
+    void *fr_arena_gpu;         /* staging of host frames: the bytes as they came, rows at their pitch, 256-byte aligned frames */
+    size_t fr_arena_bytes;
+    mi355_frame_u8 *fr_table_gpu, *fr_table_host; /* [fr_cap] frame table and its host mirror */
+    float *fr_mm_gpu, *fr_mm_host; /* [fr_cap][2] max, min */
+    void *fr_pair_gpu, *fr_pair_host; /* shared-scale mode: [fr_cap] float scale | [fr_cap] uint8 zero point, image 0's in every slot */
+    int fr_cap;
 };
 
 /* ---- construction / IO ------------------------------------------------------------------------------------ */
@@ -212,6 +220,19 @@ void quantization_weights_and_activations_gpu(network *net, const float *input_g
  * into batch slot `slot` of the network's float input, then the layer-0 quantiser over the whole batch. */
 void network_letterbox_input_gpu(network *net, int slot, const float *im_gpu, int imw, int imh);
 void network_quantize_input_gpu(network *net);
+/* The whole input step for a batch of 8-bit interleaved frames as a decoder delivers them, without a float image anywhere: frames[b] holds
+ * h[b] rows of w[b] pixels, three bytes each in `order` (MI355_FRAME_RGB / MI355_FRAME_BGR), rows pitch[b] bytes apart (pitch == NULL:
+ * 3 * w[b]); one entry per batch slot, sizes may differ.  frames_on_device == 0: host pointers, the bytes go up as they are into a
+ * staging arena the network owns (grown lazily, reused); != 0: device pointers, used in place (they must stay valid until the network's
+ * stream has run the call).  Then: frame table upload, letterbox + min / max of the batch in one launch
+ * (mi355_frames_u8_letterbox_minmax), the batch's one d2h + host sync, (scale, zero point) per image with the reference's expressions;
+ * with per-image quantisation on, the layer-0 bank is updated, otherwise image 0's pair serves every slot and layer 0 is re-derived when
+ * the pair changed (the branches, and errors, of quantization_weights_and_activations_gpu); last the quantiser launch
+ * (mi355_frames_u8_letterbox_quantize) into the network's uint8 input.  Bytes, scales and zero points equal
+ * network_letterbox_input_gpu on every frame's planes (byte / 255.f) + network_quantize_input_gpu, bit for bit.  3-channel networks only;
+ * a frame the letterbox cannot serve, a pitch below 3 * w or a null pointer die via error() before anything is launched. */
+void network_frames_u8_input_gpu(network *net, const uint8_t *const *frames, const int *w, const int *h, const int *pitch, int order,
+                                 int frames_on_device);
 /* Per-image input quantisation, opt-in (off: image 0 defines the scale of the whole batch, as before).  On: every image of a batch is
  * quantised with its own min / max, scale and zero point, and layer 0 runs with that image's constants (mi355_conv_forward_per_image):
  * slot b of every layer equals the batch-1 run on image b.  The quantisers above honour it.  Returns 0, or MI355_EINVAL with a message

@@ -301,6 +301,31 @@ int mi355_image_quantize(const float *x_f32, long count, float scale, int zero_p
 int mi355_image_minmax_batched(const float *x_f32, int B, long count_per_image, float *minmax, void *stream);
 int mi355_image_quantize_per_image(const float *x_f32, int B, long count_per_image, const float *scale_dev, const uint8_t *zp_dev,
                                    uint8_t *out_u8, void *stream);
+/* The same input step for a whole batch of 8-bit interleaved frames as a decoder delivers them (RGB or BGR, three bytes per pixel, rows
+ * `pitch` bytes apart), in two launches and without a float image in memory.  A source sample is (float)byte / 255.f -- load_image_color's
+ * planes (ref: src/image.c:1386) -- and every letterboxed float is the one mi355_letterbox_forward computes from those planes; min / max
+ * and the quantised bytes equal mi355_image_minmax_batched / mi355_image_quantize_per_image on that float image, bit for bit.
+ * One table entry per batch slot; frames may differ in size.  A new struct and new calls: MI355_ABI_VERSION is unchanged. */
+#define MI355_FRAME_RGB 0   /* plane k reads byte k of a pixel */
+#define MI355_FRAME_BGR 1   /* plane k reads byte 2 - k */
+typedef struct mi355_frame_u8 {
+    const uint8_t *data; /* DEVICE pointer to the first byte of row 0 */
+    int w, h;            /* pixels */
+    int pitch;           /* bytes from one row to the next, >= 3 * w */
+    int order;           /* MI355_FRAME_* */
+    int reserved[2];     /* explicit padding to 32 bytes, zero */
+} mi355_frame_u8;
+/* table_dev: B entries in device memory, read by the kernels.  table_host: the caller's host copy of the same B entries; the
+ * launcher validates THAT before anything is launched (the conditions of mi355_letterbox_forward per frame -- resized sides >= 2, every
+ * source row / column the resize touches inside the frame --, pitch >= 3 * w, non-null data, a known order) and returns MI355_EINVAL
+ * with a message when any frame fails; the two copies must agree.  (w, h): the network input size, B <= 65535.
+ * mi355_frames_u8_letterbox_minmax: minmax[2 b], minmax[2 b + 1] = max / min of frame b's letterboxed floats against the 0.0f seeds
+ * (device memory), nothing else is stored.  mi355_frames_u8_letterbox_quantize: the same floats quantised with scale_dev[b], zp_dev[b]
+ * (device memory) into out_u8[B][3][h][w] planar bytes, the layout of the network's uint8 input. */
+int mi355_frames_u8_letterbox_minmax(const mi355_frame_u8 *table_dev, const mi355_frame_u8 *table_host, int B, int w, int h,
+                                     float *minmax, void *stream);
+int mi355_frames_u8_letterbox_quantize(const mi355_frame_u8 *table_dev, const mi355_frame_u8 *table_host, int B, int w, int h,
+                                       const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
 /* *sum_dev += an order-independent 64-bit checksum of `dwords` 32-bit words at buf (device pointers; zero *sum_dev first).  The
  * host's determinism self-check compares it between passes over the same input (network_selfcheck, darknet_q.h). */
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream);

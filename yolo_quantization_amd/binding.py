@@ -35,6 +35,13 @@ class ConvDesc(C.Structure):
                 ("zp_in", C.c_uint8), ("zp_act", C.c_uint8), ("s_act", C.c_float), ("plan", C.c_int), ("epilogue_packed", C.c_int)]
 
 
+class FrameU8(C.Structure):
+    """mi355_frame_u8: one entry of the frame table of mi355_frames_u8_letterbox_minmax / _quantize (data: a DEVICE pointer)."""
+    _fields_ = [("data", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("pitch", C.c_int), ("order", C.c_int), ("reserved", C.c_int * 2)]
+
+
+FRAME_ORDER = {"rgb": 0, "bgr": 1}  # MI355_FRAME_RGB / MI355_FRAME_BGR
+
 _shim = None
 _host = None
 
@@ -106,6 +113,8 @@ def shim():
                                                    C.POINTER(Tensor), vp, vp, vp]
         L.mi355_conv_pool_forward_per_image.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.c_size_t, vp, vp,
                                                         C.POINTER(Tensor), C.POINTER(Tensor), vp]
+        L.mi355_frames_u8_letterbox_minmax.argtypes = [vp, C.POINTER(FrameU8), ci, ci, ci, vp, vp]
+        L.mi355_frames_u8_letterbox_quantize.argtypes = [vp, C.POINTER(FrameU8), ci, ci, ci, vp, vp, vp, vp]
         L.mi355_yolo_detections_sizes.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, C.c_float, ci, vp, ci, vp, vp]
         _shim = L
     return _shim
@@ -335,6 +344,7 @@ def host():
         L.quantization_weights_and_activations_gpu.argtypes = [vp, vp]
         L.network_letterbox_input_gpu.argtypes = [vp, ci, vp, ci, ci]
         L.network_quantize_input_gpu.argtypes = [vp]
+        L.network_frames_u8_input_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, ci]
         L.quantization_prep_host.argtypes = [vp, C.c_float, C.c_uint8]
         L.forward_network_gpu.argtypes = [vp]
         L.network_predict.restype = vp
@@ -515,6 +525,30 @@ class Net:
         check(shim().mi355_stream_sync(None), "sync")
         for b in bufs:
             b.free()
+        return self._prepared(out)
+
+    def prepare_from_frames_u8(self, frames, order="rgb"):
+        """8-bit frame input path (network_frames_u8_input_gpu): every frame (uint8 [h][w][3], any size, interleaved `order` = "rgb" |
+        "bgr") goes up as bytes; letterbox, min / max and the quantiser run on the device for the whole batch in two launches.  Rows
+        need not be contiguous: a frame whose pixels are 3 contiguous bytes and whose row stride is at least 3 * w is passed with that
+        stride as its pitch (anything else is copied first).  Returns what prepare_from_images_gpu returns."""
+        assert len(frames) == self.batch
+        B = self.batch
+        keep = []
+        ptrs, ws, hs, ps = (C.c_void_p * B)(), (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)()
+        for b, f in enumerate(frames):
+            a = np.asarray(f)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("prepare_from_frames_u8: every frame must be a uint8 [h][w][3] array")
+            if a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]:
+                a = np.ascontiguousarray(a)
+            keep.append(a)
+            ptrs[b], hs[b], ws[b], ps[b] = a.ctypes.data, a.shape[0], a.shape[1], a.strides[0]
+        self.H.network_frames_u8_input_gpu(self.h, ptrs, ws, hs, ps, FRAME_ORDER[order], 0)
+        self.sync()
+        out = np.empty(self.batch * self.inputs, np.uint8)
+        check(shim().mi355_d2h(out.ctypes.data, self.input_gpu_ptr(), out.nbytes, None), "d2h")
+        check(shim().mi355_stream_sync(None), "sync")
         return self._prepared(out)
 
     def push_input(self, x_u8):

@@ -473,6 +473,13 @@ __global__ __launch_bounds__(256) void image_quantize_per_image_kernel(const flo
     }
 }
 
+// the seeds alone, for reductions that live in another file (frames.hip)
+int image_minmax_seed_launch(uint32_t *mm, int B, hipStream_t st)
+{
+    hipLaunchKernelGGL(image_minmax_seed_kernel, dim3(nblk(2L * B)), dim3(256), 0, st, mm, B);
+    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
+}
+
 int image_minmax_batched_launch(const float *x, int B, long count, uint32_t *mm, hipStream_t st)
 {
     hipLaunchKernelGGL(image_minmax_seed_kernel, dim3(nblk(2L * B)), dim3(256), 0, st, mm, B);

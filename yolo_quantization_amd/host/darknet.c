@@ -21,6 +21,8 @@
  * model -- network_replica: own activations and stream, shared packed weights; the 4th on the default stream -- and their rate).
  * -list <file> (instead of <image>: one image path per line, dealt into batches of -batch, every image quantised with its own scale /
  * zero point -- set_input_quantization_per_image -- and reported with the block `detector test` prints for it alone).
+ * -frames u8 (the sources go to the device as the 8-bit interleaved bytes they are, the whole batch through one
+ * network_frames_u8_input_gpu call: no float conversion on the host, no float image on the device; same output).
  *
  * Image input: binary PPM (P6) of ANY size (letterboxed like the reference does), a raw `.u8` file holding [c][h][w] bytes at
  * network size, or `synthetic:<seed>`.  JPEG/PNG decoding is third-party code in the reference (stb_image, SURVEY.md 2
@@ -48,10 +50,9 @@ static const char *find_char_arg(int argc, char **argv, const char *arg, const c
 
 typedef struct { int w, h, c; float *data; } image; /* planar float [c][h][w] in 0..1, like the reference's `image` */
 
-/* load_image_color's contract (ref: src/image.c:1361-1395: bytes / 255., planar) for PPM / raw / synthetic sources */
-static image load_image_any(const char *path, int netc, int neth, int netw)
+/* the bytes of a PPM / raw / synthetic source: interleaved RGB [h][w][3] (PPM, *planar = 0) or planes [c][h][w] at network size */
+static uint8_t *load_bytes_any(const char *path, int netc, int neth, int netw, int *w, int *h, int *c, int *planar)
 {
-    image im = {0, 0, 0, NULL};
     if (0 == strncmp(path, "synthetic", 9) || (strlen(path) > 3 && 0 == strcmp(path + strlen(path) - 3, ".u8"))) {
         const size_t n = (size_t)netc * neth * netw;
         uint8_t *raw = malloc(n);
@@ -67,11 +68,8 @@ static image load_image_any(const char *path, int netc, int neth, int netw)
             if (fread(raw, 1, n, f) != n) error("raw .u8 image has the wrong size");
             fclose(f);
         }
-        im.w = netw; im.h = neth; im.c = netc;
-        im.data = malloc(n * sizeof(float));
-        for (size_t i = 0; i < n; ++i) im.data[i] = (float)raw[i] / 255.0f;
-        free(raw);
-        return im;
+        *w = netw; *h = neth; *c = netc; *planar = 1;
+        return raw;
     }
     FILE *f = fopen(path, "rb");
     if (!f) { fprintf(stderr, "Cannot load image \"%s\"\n", path); exit(0); }
@@ -84,12 +82,41 @@ static image load_image_any(const char *path, int netc, int neth, int netw)
     uint8_t *rgb = malloc((size_t)3 * iw * ih);
     if (fread(rgb, 1, (size_t)3 * iw * ih, f) != (size_t)3 * iw * ih) error("PPM truncated");
     fclose(f);
-    im.w = iw; im.h = ih; im.c = 3;
-    im.data = malloc((size_t)3 * iw * ih * sizeof(float));
-    for (int k = 0; k < 3; ++k)
-        for (int i = 0; i < iw * ih; ++i) im.data[(size_t)k * iw * ih + i] = (float)rgb[3 * i + k] / 255.f; /* ref :1386 */
-    free(rgb);
+    *w = iw; *h = ih; *c = 3; *planar = 0;
+    return rgb;
+}
+
+/* load_image_color's contract (ref: src/image.c:1361-1395: bytes / 255., planar) for PPM / raw / synthetic sources */
+static image load_image_any(const char *path, int netc, int neth, int netw)
+{
+    image im = {0, 0, 0, NULL};
+    int planar = 0;
+    uint8_t *raw = load_bytes_any(path, netc, neth, netw, &im.w, &im.h, &im.c, &planar);
+    const size_t hw = (size_t)im.w * im.h;
+    im.data = malloc(hw * im.c * sizeof(float));
+    if (planar) {
+        for (size_t i = 0; i < hw * im.c; ++i) im.data[i] = (float)raw[i] / 255.0f;
+    } else {
+        for (int k = 0; k < 3; ++k)
+            for (size_t i = 0; i < hw; ++i) im.data[(size_t)k * hw + i] = (float)raw[3 * i + k] / 255.f; /* ref :1386 */
+    }
+    free(raw);
     return im;
+}
+
+/* -frames u8: the same sources as interleaved RGB bytes [h][w][3], no float conversion (planar sources are interleaved) */
+static uint8_t *load_frame_u8(const char *path, int netc, int neth, int netw, int *w, int *h)
+{
+    int c = 0, planar = 0;
+    uint8_t *raw = load_bytes_any(path, netc, neth, netw, w, h, &c, &planar);
+    if (c != 3) error("-frames u8 needs a 3-channel network");
+    if (!planar) return raw;
+    const size_t hw = (size_t)*w * *h;
+    uint8_t *rgb = malloc(3 * hw);
+    for (int k = 0; k < 3; ++k)
+        for (size_t i = 0; i < hw; ++i) rgb[3 * i + k] = raw[(size_t)k * hw + i];
+    free(raw);
+    return rgb;
 }
 
 static void dump_layer(const char *dir, network *net, int i)
@@ -118,6 +145,7 @@ static void dump_layer(const char *dir, network *net, int i)
 typedef struct {
     const char *datacfg, *cfgfile, *weightfile, *filename, *dumpdir, *packed_in, *packed_out;
     const char *listfile;  /* -list: image paths, one per line, per-image input quantisation */
+    int frames_u8;         /* -frames u8: sources go up as interleaved bytes (network_frames_u8_input_gpu), no host float conversion */
     float thresh, hier_thresh;
     int batch, accum, store, use_graph, iters, gpu, boxes, quiet, inflight;
     int rank, nranks;      /* -gpus with -bcast: this replica's rank; rank 0 reads the weights file, the others receive blobs */
@@ -174,22 +202,30 @@ static void test_detector_list(detect_job *job, network *net, char **names, int 
     int *imw = calloc((size_t)B, sizeof(int)), *imh = calloc((size_t)B, sizeof(int));
     for (int first = 0; first < np; first += B) {
         const int cnt = np - first < B ? np - first : B;
-        for (int b = 0; b < B; ++b) {
-            const char *path = paths[first + (b < cnt ? b : cnt - 1)];
-            image im = load_image_any(path, net->c, net->h, net->w);
-            float *im_gpu = NULL;
-            const size_t imbytes = (size_t)im.c * im.h * im.w * sizeof(float);
-            if (mi355_alloc((void **)&im_gpu, imbytes) || mi355_h2d(im_gpu, im.data, imbytes, net->stream)) {
-                fprintf(stderr, "MI355: %s\n", mi355_last_error());
-                error("cannot stage the image on the device");
+        if (job->frames_u8) { /* the batch's frames as bytes, one call for the whole input step */
+            uint8_t **fr = calloc((size_t)B, sizeof(uint8_t *));
+            for (int b = 0; b < B; ++b) fr[b] = load_frame_u8(paths[first + (b < cnt ? b : cnt - 1)], net->c, net->h, net->w, &imw[b], &imh[b]);
+            network_frames_u8_input_gpu(net, (const uint8_t *const *)fr, imw, imh, NULL, MI355_FRAME_RGB, 0);
+            for (int b = 0; b < B; ++b) free(fr[b]);
+            free(fr);
+        } else {
+            for (int b = 0; b < B; ++b) {
+                const char *path = paths[first + (b < cnt ? b : cnt - 1)];
+                image im = load_image_any(path, net->c, net->h, net->w);
+                float *im_gpu = NULL;
+                const size_t imbytes = (size_t)im.c * im.h * im.w * sizeof(float);
+                if (mi355_alloc((void **)&im_gpu, imbytes) || mi355_h2d(im_gpu, im.data, imbytes, net->stream)) {
+                    fprintf(stderr, "MI355: %s\n", mi355_last_error());
+                    error("cannot stage the image on the device");
+                }
+                network_letterbox_input_gpu(net, b, im_gpu, im.w, im.h);
+                if (mi355_stream_sync(net->stream)) error("sync");
+                mi355_free(im_gpu);
+                imw[b] = im.w; imh[b] = im.h;
+                free(im.data);
             }
-            network_letterbox_input_gpu(net, b, im_gpu, im.w, im.h);
-            if (mi355_stream_sync(net->stream)) error("sync");
-            mi355_free(im_gpu);
-            imw[b] = im.w; imh[b] = im.h;
-            free(im.data);
+            network_quantize_input_gpu(net);
         }
-        network_quantize_input_gpu(net);
         const double t0 = what_time_is_it_now();
         network_predict(net, net->input);
         const double dt = what_time_is_it_now() - t0;
@@ -246,16 +282,27 @@ static void test_detector(detect_job *job)
         free_network(net);
         return;
     }
-    image im = load_image_any(job->filename, net->c, net->h, net->w);
-    /* input path on the device: the float image goes up once, letterbox_image + the layer-0 quantiser run in HBM */
+    image im = {0, 0, 0, NULL};
     float *im_gpu = NULL;
-    const size_t imbytes = (size_t)im.c * im.h * im.w * sizeof(float);
-    if (mi355_init(job->gpu) || mi355_alloc((void **)&im_gpu, imbytes) || mi355_h2d(im_gpu, im.data, imbytes, NULL) || mi355_stream_sync(NULL)) {
-        fprintf(stderr, "MI355: %s\n", mi355_last_error());
-        error("cannot stage the image on the device (this build has no CPU data path)");
+    if (job->frames_u8) { /* the source's bytes in every batch slot, one call for the whole input step */
+        if (mi355_init(job->gpu)) { fprintf(stderr, "MI355: %s\n", mi355_last_error()); error("mi355_init (this build has no CPU data path)"); }
+        uint8_t *rgb = load_frame_u8(job->filename, net->c, net->h, net->w, &im.w, &im.h);
+        const uint8_t **fr = calloc((size_t)job->batch, sizeof(uint8_t *));
+        int *fw = calloc((size_t)job->batch, sizeof(int)), *fh = calloc((size_t)job->batch, sizeof(int));
+        for (int b = 0; b < job->batch; ++b) { fr[b] = rgb; fw[b] = im.w; fh[b] = im.h; }
+        network_frames_u8_input_gpu(net, fr, fw, fh, NULL, MI355_FRAME_RGB, 0);
+        free(fr); free(fw); free(fh); free(rgb);
+    } else {
+        im = load_image_any(job->filename, net->c, net->h, net->w);
+        /* input path on the device: the float image goes up once, letterbox_image + the layer-0 quantiser run in HBM */
+        const size_t imbytes = (size_t)im.c * im.h * im.w * sizeof(float);
+        if (mi355_init(job->gpu) || mi355_alloc((void **)&im_gpu, imbytes) || mi355_h2d(im_gpu, im.data, imbytes, NULL) || mi355_stream_sync(NULL)) {
+            fprintf(stderr, "MI355: %s\n", mi355_last_error());
+            error("cannot stage the image on the device (this build has no CPU data path)");
+        }
+        for (int b = 0; b < job->batch; ++b) network_letterbox_input_gpu(net, b, im_gpu, im.w, im.h);
+        network_quantize_input_gpu(net); /* == quantization_weights_and_activations on the letterboxed floats (ref :918) */
     }
-    for (int b = 0; b < job->batch; ++b) network_letterbox_input_gpu(net, b, im_gpu, im.w, im.h);
-    network_quantize_input_gpu(net); /* == quantization_weights_and_activations on the letterboxed floats (ref :918) */
     if (job->packed_out) network_save_packed(net, (char *)job->packed_out);
 
     double t0 = what_time_is_it_now();
@@ -290,7 +337,7 @@ static void test_detector(detect_job *job)
 
     if (!job->quiet) print_detections(job, net, 0, im.w, im.h, names, nnames);
     if (job->dumpdir) for (int i = 0; i < net->n; ++i) dump_layer(job->dumpdir, net, i);
-    mi355_free(im_gpu);
+    if (im_gpu) mi355_free(im_gpu);
     free(im.data);
     for (int i = 0; i < nnames; ++i) free(names[i]);
     free(names);
@@ -308,7 +355,7 @@ int main(int argc, char **argv)
     if (argc < 2) {
         fprintf(stderr, "usage: %s detector test <data> <cfg> <weights> <image> [-thresh t] [-i gpu | -gpus a,b,..] [-batch B] "
                         "[-accum exact|ref-f32] [-parity wrap|saturate] [-dump dir] [-graph] [-n iters] [-boxes] "
-                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file]\n", argv[0]);
+                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8]\n", argv[0]);
         return 0;
     }
     detect_job job;
@@ -331,6 +378,9 @@ int main(int argc, char **argv)
     job.iters = atoi(find_char_arg(argc, argv, "-n", "1"));
     job.inflight = atoi(find_char_arg(argc, argv, "-inflight", "1"));
     job.listfile = find_char_arg(argc, argv, "-list", NULL);
+    const char *frames_s = find_char_arg(argc, argv, "-frames", NULL);
+    if (frames_s && strcmp(frames_s, "u8")) error("-frames: only `u8` (8-bit interleaved frames) is known");
+    job.frames_u8 = frames_s != NULL;
     if (job.iters < 1) job.iters = 1;
     if (job.batch < 1) job.batch = 1;
     job.accum = 0 == strcmp(accum_s, "ref-f32") ? MI355_ACC_REF_F32 : MI355_ACC_EXACT;

@@ -427,27 +427,11 @@ void quantization_weights_and_activations(network *net)
     push_network_input_uint8(net, net->input_uint8);
 }
 
-/* The same on the device (SURVEY 8(f) row 2, quantiser half): `input_gpu` holds batch x inputs floats in HBM.  Image 0
- * defines scale / zero point as in the reference (src/blas.c:279); min / max are reduced on the device, the two floats
- * come back to the host, which evaluates the reference's scale / zero-point expressions and -- only when they differ
- * from the ones layer 0 was prepared with -- re-derives and re-uploads layer 0's multipliers and blob in place (no other
- * layer depends on the input scale); the per-element quantiser then runs on the device straight into the network's uint8
- * input.  Byte-identical to quantization_weights_and_activations() on the same floats. */
-static void quantize_per_image_gpu(network *net, const float *input_gpu);
-
-void quantization_weights_and_activations_gpu(network *net, const float *input_gpu)
+/* One (scale, zero point) for the whole batch, as image 0 defines it: the first call prepares the network with it; a later call
+ * with another pair re-derives and re-uploads layer 0's multipliers and blob in place (no other layer depends on the input scale).
+ * Shared by the device input paths (float images, 8-bit frames). */
+static void input_pair_shared(network *net, float s, uint8_t zp)
 {
-    if (!input_gpu) error("quantization_weights_and_activations_gpu: null input");
-    check_mi355(mi355_init(net->gpu_index), "mi355_init");
-    if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
-    if (net->per_image) { quantize_per_image_gpu(net, input_gpu); return; }
-    if (!net->quant_mm_gpu) check_mi355(mi355_alloc((void **)&net->quant_mm_gpu, 2 * sizeof(float)), "alloc minmax");
-    float mm[2];
-    check_mi355(mi355_image_minmax(input_gpu, net->inputs, net->quant_mm_gpu, net->stream), "mi355_image_minmax");
-    check_mi355(mi355_d2h(mm, net->quant_mm_gpu, sizeof(mm), net->stream), "minmax d2h");
-    check_mi355(mi355_stream_sync(net->stream), "sync");
-    float s; uint8_t zp;
-    image_scale_zero_point(mm[1] + 0.0f, mm[0], &s, &zp);
     layer *l0 = &net->layers[0];
     if (!net->prepared) {
         quantization_weights_and_activations_fixed_input(net, s, zp);
@@ -471,6 +455,30 @@ void quantization_weights_and_activations_gpu(network *net, const float *input_g
          * (the input zero point) from there, not from pad cells in memory -> re-capture on the next forward */
         if (net->graph) { mi355_graph_destroy(net->graph); net->graph = NULL; }
     }
+}
+
+/* The same on the device (SURVEY 8(f) row 2, quantiser half): `input_gpu` holds batch x inputs floats in HBM.  Image 0
+ * defines scale / zero point as in the reference (src/blas.c:279); min / max are reduced on the device, the two floats
+ * come back to the host, which evaluates the reference's scale / zero-point expressions and -- only when they differ
+ * from the ones layer 0 was prepared with -- re-derives and re-uploads layer 0's multipliers and blob in place (no other
+ * layer depends on the input scale); the per-element quantiser then runs on the device straight into the network's uint8
+ * input.  Byte-identical to quantization_weights_and_activations() on the same floats. */
+static void quantize_per_image_gpu(network *net, const float *input_gpu);
+
+void quantization_weights_and_activations_gpu(network *net, const float *input_gpu)
+{
+    if (!input_gpu) error("quantization_weights_and_activations_gpu: null input");
+    check_mi355(mi355_init(net->gpu_index), "mi355_init");
+    if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
+    if (net->per_image) { quantize_per_image_gpu(net, input_gpu); return; }
+    if (!net->quant_mm_gpu) check_mi355(mi355_alloc((void **)&net->quant_mm_gpu, 2 * sizeof(float)), "alloc minmax");
+    float mm[2];
+    check_mi355(mi355_image_minmax(input_gpu, net->inputs, net->quant_mm_gpu, net->stream), "mi355_image_minmax");
+    check_mi355(mi355_d2h(mm, net->quant_mm_gpu, sizeof(mm), net->stream), "minmax d2h");
+    check_mi355(mi355_stream_sync(net->stream), "sync");
+    float s; uint8_t zp;
+    image_scale_zero_point(mm[1] + 0.0f, mm[0], &s, &zp);
+    input_pair_shared(net, s, zp);
     check_mi355(mi355_image_quantize(input_gpu, (long)net->batch * net->inputs, s, zp, net->input_uint8_gpu, net->stream),
                 "mi355_image_quantize");
 }
@@ -634,6 +642,20 @@ static void pi_bank_update(network *net, const float *scale, const uint8_t *zp)
     check_mi355(mi355_h2d(net->pi_idx_gpu, net->pi_idx_host, 9 * (size_t)B, net->stream), "upload bank index");
 }
 
+/* One (scale, zero point) per image from the batch's [B][2] max / min: the first call prepares the network with image 0's pair, then
+ * the bank and the index arrays (entry, scale, zero point per image) go up on the network's stream.  Shared by the device input
+ * paths (float images, 8-bit frames). */
+static void input_pairs_per_image(network *net, const float *mm)
+{
+    const int B = net->batch;
+    float *s = malloc(sizeof(float) * (size_t)B);
+    uint8_t *zp = malloc((size_t)B);
+    for (int b = 0; b < B; ++b) image_scale_zero_point(mm[2 * b + 1] + 0.0f, mm[2 * b], &s[b], &zp[b]);
+    if (!net->prepared) quantization_weights_and_activations_fixed_input(net, s[0], zp[0]);
+    pi_bank_update(net, s, zp);
+    free(s); free(zp);
+}
+
 static void quantize_per_image_gpu(network *net, const float *input_gpu)
 {
     const int B = net->batch;
@@ -641,12 +663,7 @@ static void quantize_per_image_gpu(network *net, const float *input_gpu)
     check_mi355(mi355_image_minmax_batched(input_gpu, B, net->inputs, net->pi_mm_gpu, net->stream), "mi355_image_minmax_batched");
     check_mi355(mi355_d2h(net->pi_mm_host, net->pi_mm_gpu, 2 * sizeof(float) * (size_t)B, net->stream), "minmax d2h");
     check_mi355(mi355_stream_sync(net->stream), "sync"); /* the batch's one host sync: every earlier upload of the bank is done too */
-    float *s = malloc(sizeof(float) * (size_t)B);
-    uint8_t *zp = malloc((size_t)B);
-    for (int b = 0; b < B; ++b) image_scale_zero_point(net->pi_mm_host[2 * b + 1] + 0.0f, net->pi_mm_host[2 * b], &s[b], &zp[b]);
-    if (!net->prepared) quantization_weights_and_activations_fixed_input(net, s[0], zp[0]);
-    pi_bank_update(net, s, zp);
-    free(s); free(zp);
+    input_pairs_per_image(net, net->pi_mm_host);
     const char *idx = (const char *)net->pi_idx_gpu;
     check_mi355(mi355_image_quantize_per_image(input_gpu, B, net->inputs, (const float *)(idx + 4 * (size_t)B),
                                                (const uint8_t *)(idx + 8 * (size_t)B), net->input_uint8_gpu, net->stream),
@@ -670,6 +687,104 @@ void network_quantize_input_gpu(network *net)
     quantization_weights_and_activations_gpu(net, net->input_gpu);
 }
 
+/* ------------------------------------------------------------------------------------------- 8-bit frame input
+ * Two launches for the whole batch (frames.hip): letterbox + min / max, then letterbox + quantise; the float image exists in registers
+ * only.  The (scale, zero point) branches are the float path's (input_pair_shared, input_pairs_per_image). */
+static void fr_free(network *net)
+{
+    if (net->fr_arena_gpu) mi355_free(net->fr_arena_gpu);
+    if (net->fr_table_gpu) mi355_free(net->fr_table_gpu);
+    if (net->fr_mm_gpu) mi355_free(net->fr_mm_gpu);
+    if (net->fr_pair_gpu) mi355_free(net->fr_pair_gpu);
+    free(net->fr_table_host); free(net->fr_mm_host); free(net->fr_pair_host);
+    net->fr_arena_gpu = NULL; net->fr_table_gpu = NULL; net->fr_table_host = NULL;
+    net->fr_mm_gpu = net->fr_mm_host = NULL;
+    net->fr_pair_gpu = net->fr_pair_host = NULL;
+    net->fr_arena_bytes = 0;
+    net->fr_cap = 0;
+}
+
+static void fr_alloc(network *net)
+{
+    const size_t B = (size_t)net->batch;
+    if (net->fr_cap == net->batch) return;
+    fr_free(net);
+    check_mi355(mi355_alloc((void **)&net->fr_table_gpu, sizeof(mi355_frame_u8) * B), "alloc frame table");
+    check_mi355(mi355_alloc((void **)&net->fr_mm_gpu, 2 * sizeof(float) * B), "alloc minmax");
+    check_mi355(mi355_alloc(&net->fr_pair_gpu, 5 * B), "alloc input pairs");
+    net->fr_table_host = calloc(B, sizeof(mi355_frame_u8));
+    net->fr_mm_host = calloc(2 * B, sizeof(float));
+    net->fr_pair_host = calloc(5, B);
+    net->fr_cap = net->batch;
+}
+
+void network_frames_u8_input_gpu(network *net, const uint8_t *const *frames, const int *w, const int *h, const int *pitch, int order,
+                                 int frames_on_device)
+{
+    const int B = net->batch;
+    if (!frames || !w || !h) error("network_frames_u8_input_gpu: null frames / sizes");
+    if (net->c != 3) error("network_frames_u8_input_gpu: 8-bit frames feed 3-channel networks only");
+    check_mi355(mi355_init(net->gpu_index), "mi355_init");
+    if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
+    fr_alloc(net);
+    mi355_frame_u8 *tab = net->fr_table_host;
+    size_t need = 0;
+    for (int b = 0; b < B; ++b) {
+        if (!frames[b]) error("network_frames_u8_input_gpu: null frame");
+        const int p = pitch ? pitch[b] : 3 * w[b];
+        if (w[b] < 1 || h[b] < 1 || p < 3 * w[b]) error("network_frames_u8_input_gpu: need w, h >= 1 and pitch >= 3 * w for every frame");
+        memset(&tab[b], 0, sizeof(tab[b]));
+        tab[b].data = frames[b];
+        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch = p; tab[b].order = order;
+        need += (((size_t)(h[b] - 1) * (size_t)p + 3 * (size_t)w[b]) + 255) & ~(size_t)255;
+    }
+    if (!frames_on_device) { /* the bytes as they are: rows keep their pitch, the last row ends with its last pixel */
+        if (need > net->fr_arena_bytes) {
+            check_mi355(mi355_stream_sync(net->stream), "sync"); /* nothing in flight reads the arena that is freed */
+            if (net->fr_arena_gpu) mi355_free(net->fr_arena_gpu);
+            net->fr_arena_gpu = NULL; net->fr_arena_bytes = 0;
+            check_mi355(mi355_alloc(&net->fr_arena_gpu, need), "alloc frame arena");
+            net->fr_arena_bytes = need;
+        }
+        size_t off = 0;
+        for (int b = 0; b < B; ++b) {
+            const size_t bytes = (size_t)(h[b] - 1) * (size_t)tab[b].pitch + 3 * (size_t)w[b];
+            int same = -1; /* one frame in several slots (`-batch B` of one image) goes up once */
+            for (int k = 0; k < b && same < 0; ++k)
+                if (frames[k] == frames[b] && w[k] == w[b] && h[k] == h[b] && tab[k].pitch == tab[b].pitch) same = k;
+            if (same >= 0) { tab[b].data = tab[same].data; continue; }
+            uint8_t *dst = (uint8_t *)net->fr_arena_gpu + off;
+            check_mi355(mi355_h2d(dst, frames[b], bytes, net->stream), "upload frame");
+            tab[b].data = dst;
+            off += (bytes + 255) & ~(size_t)255;
+        }
+    }
+    check_mi355(mi355_h2d(net->fr_table_gpu, tab, sizeof(mi355_frame_u8) * (size_t)B, net->stream), "upload frame table");
+    check_mi355(mi355_frames_u8_letterbox_minmax(net->fr_table_gpu, tab, B, net->w, net->h, net->fr_mm_gpu, net->stream),
+                "mi355_frames_u8_letterbox_minmax");
+    check_mi355(mi355_d2h(net->fr_mm_host, net->fr_mm_gpu, 2 * sizeof(float) * (size_t)B, net->stream), "minmax d2h");
+    check_mi355(mi355_stream_sync(net->stream), "sync"); /* the batch's one host sync: every earlier upload is done too */
+    const float *scale_dev;
+    const uint8_t *zp_dev;
+    if (net->per_image) {
+        input_pairs_per_image(net, net->fr_mm_host);
+        scale_dev = (const float *)((const char *)net->pi_idx_gpu + 4 * (size_t)B);
+        zp_dev = (const uint8_t *)net->pi_idx_gpu + 8 * (size_t)B;
+    } else { /* image 0 defines the pair of the whole batch */
+        float s; uint8_t zp;
+        image_scale_zero_point(net->fr_mm_host[1] + 0.0f, net->fr_mm_host[0], &s, &zp);
+        input_pair_shared(net, s, zp);
+        float *sc = (float *)net->fr_pair_host;
+        uint8_t *zq = (uint8_t *)net->fr_pair_host + 4 * (size_t)B;
+        for (int b = 0; b < B; ++b) { sc[b] = s; zq[b] = zp; }
+        check_mi355(mi355_h2d(net->fr_pair_gpu, net->fr_pair_host, 5 * (size_t)B, net->stream), "upload input pair");
+        scale_dev = (const float *)net->fr_pair_gpu;
+        zp_dev = (const uint8_t *)net->fr_pair_gpu + 4 * (size_t)B;
+    }
+    check_mi355(mi355_frames_u8_letterbox_quantize(net->fr_table_gpu, tab, B, net->w, net->h, scale_dev, zp_dev, net->input_uint8_gpu,
+                                                   net->stream), "mi355_frames_u8_letterbox_quantize");
+}
+
 void set_batch_network(network *net, int b)
 {
     if (b < 1) error("set_batch_network: batch < 1");
@@ -678,6 +793,7 @@ void set_batch_network(network *net, int b)
     if (net->n_replicas > 0) error("set_batch_network: free this network's replicas first (they borrow its packed weights on the device)");
     net->batch = b;
     pi_free(net); /* the per-image bank and index arrays are sized by the batch */
+    fr_free(net); /* so are the frame table, its min / max and the staging arena */
     free(net->input); free(net->input_uint8);
     net->input = calloc((size_t)net->inputs * b, sizeof(float));
     net->input_uint8 = calloc((size_t)net->inputs * b, sizeof(uint8_t));
@@ -1294,6 +1410,7 @@ void free_network(network *net)
     if (net->input_gpu) mi355_free(net->input_gpu);
     if (net->quant_mm_gpu) mi355_free(net->quant_mm_gpu);
     pi_free(net);
+    fr_free(net);
     if (net->selfcheck_gpu) mi355_free(net->selfcheck_gpu);
     if (net->stream) mi355_stream_release(net->stream);
     free(net->layers); free(net->input); free(net->input_uint8); free(net->seen); free(net->cfg_path);
