@@ -193,6 +193,7 @@ struct network {
     void *fr_arena_gpu;         /* staging of host frames: the bytes as they came, rows at their pitch, 256-byte aligned frames */
     size_t fr_arena_bytes;
     mi355_frame_u8 *fr_table_gpu, *fr_table_host; /* [fr_cap] frame table and its host mirror */
+    mi355_frame_yuv *fr_yuv_gpu, *fr_yuv_host;    /* the same for NV12 / NV21 frames (network_frames_nv12_input_gpu) */
     float *fr_mm_gpu, *fr_mm_host; /* [fr_cap][2] max, min */
     void *fr_pair_gpu, *fr_pair_host; /* shared-scale mode: [fr_cap] float scale | [fr_cap] uint8 zero point, image 0's in every slot */
     int fr_cap;
@@ -233,6 +234,15 @@ void network_quantize_input_gpu(network *net);
  * a frame the letterbox cannot serve, a pitch below 3 * w or a null pointer die via error() before anything is launched. */
 void network_frames_u8_input_gpu(network *net, const uint8_t *const *frames, const int *w, const int *h, const int *pitch, int order,
                                  int frames_on_device);
+/* The same step for NV12 / NV21 frames as video decoders and camera stacks deliver them (layout: MI355_YUV_NV12 / MI355_YUV_NV21):
+ * y[b] holds h[b] rows of w[b] luma bytes pitch_y[b] bytes apart, uv[b] (h[b] + 1) / 2 rows of (w[b] + 1) / 2 chroma pairs pitch_uv[b]
+ * bytes apart (a null pitch array: tightly packed planes).  Both planes go up as they are -- half the bytes of the RGB frame -- and are
+ * converted in registers with the integer formulas and the `matrix` (MI355_YUV_BT601 .. MI355_YUV_BT709_FULL) of mi355_frame_yuv
+ * (mi355_yolo_int8.h); no RGB frame exists anywhere.  The result is, bit for bit, network_frames_u8_input_gpu's on the RGB frame those
+ * formulas give; arena, min / max and pair buffers, the one host sync and both (scale, zero point) branches are that function's.
+ * frames_on_device != 0: the plane pointers are device pointers (a decoder's surfaces), used in place. */
+void network_frames_nv12_input_gpu(network *net, const uint8_t *const *y, const uint8_t *const *uv, const int *w, const int *h,
+                                   const int *pitch_y, const int *pitch_uv, int layout, int matrix, int frames_on_device);
 /* Per-image input quantisation, opt-in (off: image 0 defines the scale of the whole batch, as before).  On: every image of a batch is
  * quantised with its own min / max, scale and zero point, and layer 0 runs with that image's constants (mi355_conv_forward_per_image):
  * slot b of every layer equals the batch-1 run on image b.  The quantisers above honour it.  Returns 0, or MI355_EINVAL with a message

@@ -326,6 +326,44 @@ int mi355_frames_u8_letterbox_minmax(const mi355_frame_u8 *table_dev, const mi35
                                      float *minmax, void *stream);
 int mi355_frames_u8_letterbox_quantize(const mi355_frame_u8 *table_dev, const mi355_frame_u8 *table_host, int B, int w, int h,
                                        const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
+/* The same two calls for NV12 / NV21 frames as video decoders and camera stacks deliver them: a Y plane of h rows of w bytes, pitch_y
+ * bytes apart, and a chroma plane of (h + 1) / 2 rows of (w + 1) / 2 byte pairs, pitch_uv bytes apart; a pair is (U, V) in NV12 and
+ * (V, U) in NV21.  Odd w and h are legal.  Pixel (x, y) takes Y[y][x] and the pair at [y / 2][x / 2] (nearest sampling: no chroma
+ * interpolation, no siting offset).  Its 8-bit RGB is computed in int32 with an arithmetic (floor) right shift and a clamp to 0..255:
+ *     yy = cy * (Y - yoff)
+ *     R = clamp((yy + crv * (V - 128)                   + 32768) >> 16)
+ *     G = clamp((yy - cgu * (U - 128) - cgv * (V - 128) + 32768) >> 16)
+ *     B = clamp((yy + cbu * (U - 128)                   + 32768) >> 16)
+ * with (yoff, cy, crv, cgu, cgv, cbu), round(x * 65536) of the standards' real coefficients:
+ *     MI355_YUV_BT601       (limited range)  16, 76309, 104597, 25675, 53279, 132201
+ *     MI355_YUV_BT601_FULL                    0, 65536,  91881, 22553, 46802, 116130
+ *     MI355_YUV_BT709       (limited range)  16, 76309, 117489, 13975, 34925, 138438
+ *     MI355_YUV_BT709_FULL                    0, 65536, 103206, 12276, 30679, 121609
+ * The conversion happens in registers at every bilinear tap; from those bytes on nothing is new: min / max and the quantised bytes are,
+ * bit for bit, what the u8 calls above give for the interleaved RGB frame these formulas make.  A new struct and new calls:
+ * MI355_ABI_VERSION is unchanged. */
+#define MI355_YUV_NV12 0   /* chroma pair = (U, V) */
+#define MI355_YUV_NV21 1   /* chroma pair = (V, U) */
+#define MI355_YUV_BT601 0
+#define MI355_YUV_BT601_FULL 1
+#define MI355_YUV_BT709 2
+#define MI355_YUV_BT709_FULL 3
+typedef struct mi355_frame_yuv {
+    const uint8_t *y, *uv; /* DEVICE pointers to the first byte of row 0 of each plane */
+    int w, h;              /* pixels (of the Y plane) */
+    int pitch_y;           /* bytes from one Y row to the next, >= w */
+    int pitch_uv;          /* bytes from one chroma row to the next, >= 2 * ((w + 1) / 2) */
+    int layout;            /* MI355_YUV_NV12 / MI355_YUV_NV21 */
+    int matrix;            /* MI355_YUV_BT601 .. MI355_YUV_BT709_FULL */
+    int reserved[2];       /* explicit padding to 48 bytes, zero */
+} mi355_frame_yuv;
+/* The contract of the u8 calls: table_host is validated before anything is launched; a null plane, w or h outside 1..32768, a pitch
+ * below its minimum, an unknown layout or matrix, or a frame the letterbox geometry refuses return MI355_EINVAL with a message that
+ * starts "frames_yuv:", and nothing is written.  B <= 65535. */
+int mi355_frames_yuv_letterbox_minmax(const mi355_frame_yuv *table_dev, const mi355_frame_yuv *table_host, int B, int w, int h,
+                                      float *minmax, void *stream);
+int mi355_frames_yuv_letterbox_quantize(const mi355_frame_yuv *table_dev, const mi355_frame_yuv *table_host, int B, int w, int h,
+                                        const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
 /* *sum_dev += an order-independent 64-bit checksum of `dwords` 32-bit words at buf (device pointers; zero *sum_dev first).  The
  * host's determinism self-check compares it between passes over the same input (network_selfcheck, darknet_q.h). */
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream);

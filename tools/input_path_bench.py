@@ -1,13 +1,16 @@
 """Times the input step alone: from the batch's first upload to the network's uint8 input being ready on the device.
 
-yolov3-tiny @416, batch 64, 640 x 480 RGB frames (synthetic bytes, every frame its own range), two variants:
+yolov3-tiny @416, batch 64, 640 x 480 RGB frames (synthetic bytes, every frame its own range), three variants:
   float   the float entry points: per frame one upload of the planar float image (byte / 255, converted before the clock starts)
           and one network_letterbox_input_gpu, then network_quantize_input_gpu (min / max, host sync, quantise)
   frames  network_frames_u8_input_gpu: the bytes go up as they are, two launches for the whole batch
+  nv12    network_frames_nv12_input_gpu: the same frames as NV12 planes (made before the clock starts: BT.601 limited-range RGB -> YUV
+          in numpy, chroma of the top-left pixel of every 2 x 2 block), half the bytes go up, converted inside the two launches
 each in shared-scale and per-image mode.  A step is timed twice: HIP events on the network's stream around it, and the host clock
 from before the first upload to after a stream synchronise.  The variants alternate within a repeat; the same batch is fed every step
-(steady state: layer 0 is not re-derived, the per-image bank serves every key from its cache).  Before timing, the two variants' uint8
-inputs, scales and zero points are compared for equality.  `host_convert_ms` is the byte -> planar float conversion the float variant
+(steady state: layer 0 is not re-derived, the per-image bank serves every key from its cache).  Before timing, the float and frames
+variants' uint8 inputs, scales and zero points are compared for equality, and the nv12 variant's with those of the frames entry point
+fed the RGB frames a numpy restatement of the integer YUV -> RGB formulas makes of the NV12 planes.  `host_convert_ms` is the byte -> planar float conversion the float variant
 needs before its first upload, done with numpy here: an indication only, not part of either timed step.
 Prints one JSON line."""
 import argparse
@@ -29,6 +32,26 @@ CFG = os.path.join(ROOT, "cfg", "yolov3-tiny_quant.cfg")
 def make_frames(B, w, h):
     rng = np.random.default_rng(7)
     return [rng.integers(b % 40, 256 - (3 * b) % 90, (h, w, 3), dtype=np.uint8) for b in range(B)]
+
+
+def rgb_to_nv12(f):
+    """BT.601 limited-range RGB -> (y [h][w], uv [(h + 1) // 2][(w + 1) // 2][2]); any fixed formula serves: the planes are the input"""
+    r, g, b = (f[..., k].astype(np.float64) for k in range(3))
+    y = 16 + (65.481 * r + 128.553 * g + 24.966 * b) / 255
+    u = 128 + (-37.797 * r - 74.203 * g + 112.0 * b) / 255
+    v = 128 + (112.0 * r - 93.786 * g - 18.214 * b) / 255
+    q = [np.clip(np.rint(p), 0, 255).astype(np.uint8) for p in (y, u, v)]
+    return q[0], np.ascontiguousarray(np.stack([q[1][::2, ::2], q[2][::2, ::2]], axis=-1))
+
+
+def nv12_to_rgb(y, uv):
+    """the NV12 path's specification (MI355_YUV_BT601): int32, floor shift, clamp; nearest chroma"""
+    h, w = y.shape
+    c = uv[(np.arange(h) // 2)[:, None], (np.arange(w) // 2)[None, :]].astype(np.int32) - 128
+    yy = 76309 * (y.astype(np.int32) - 16)
+    rgb = [(yy + 104597 * c[..., 1] + 32768) >> 16, (yy - 25675 * c[..., 0] - 53279 * c[..., 1] + 32768) >> 16,
+           (yy + 132201 * c[..., 0] + 32768) >> 16]
+    return np.ascontiguousarray(np.stack([np.clip(p, 0, 255).astype(np.uint8) for p in rgb], axis=-1))
 
 
 class Events:
@@ -67,6 +90,24 @@ class FramesVariant:
 
     def step(self):
         self.net.H.network_frames_u8_input_gpu(self.net.h, self.ptrs, self.w, self.h, None, 0, 0)
+
+
+class NV12Variant:
+    def __init__(self, net, planes):
+        B = len(planes)
+        self.net, self.planes = net, planes
+        self.y, self.uv, self.w, self.h = (C.c_void_p * B)(), (C.c_void_p * B)(), (C.c_int * B)(), (C.c_int * B)()
+        for b, (y, uv) in enumerate(planes):
+            self.y[b], self.uv[b], self.h[b], self.w[b] = y.ctypes.data, uv.ctypes.data, y.shape[0], y.shape[1]
+
+    def step(self):
+        self.net.H.network_frames_nv12_input_gpu(self.net.h, self.y, self.uv, self.w, self.h, None, None, 0, 0, 0)
+
+
+def same_input(a, b):
+    same = np.array_equal(pull_input(a), pull_input(b))
+    qa, qb = a.input_quantization(), b.input_quantization()
+    return bool(same and np.array_equal(qa[0].view(np.uint32), qb[0].view(np.uint32)) and np.array_equal(qa[1], qb[1]))
 
 
 def timed(variant, ev, iters):
@@ -109,20 +150,25 @@ def main():
     for f in frames:
         np.ascontiguousarray(f.transpose(2, 0, 1)).astype(np.float32) / np.float32(255)
     convert_ms = (time.perf_counter() - t0) * 1e3
+    planes = [rgb_to_nv12(f) for f in frames]
+    converted = [nv12_to_rgb(y, uv) for y, uv in planes]
     ev = Events()
     res = {}
     for mode in ("shared", "per_image"):
-        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("float", "frames")}
+        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("float", "frames", "nv12")}
         if mode == "per_image":
             for n in nets.values():
                 n.set_input_per_image(True)
-        var = {"float": FloatVariant(nets["float"], frames), "frames": FramesVariant(nets["frames"], frames)}
+        var = {"float": FloatVariant(nets["float"], frames), "frames": FramesVariant(nets["frames"], frames),
+               "nv12": NV12Variant(nets["nv12"], planes)}
         for _ in range(a.warmup):
             for v in var.values():
                 v.step()
-        same = np.array_equal(pull_input(nets["float"]), pull_input(nets["frames"]))
-        qa, qb = nets["float"].input_quantization(), nets["frames"].input_quantization()
-        same = bool(same and np.array_equal(qa[0].view(np.uint32), qb[0].view(np.uint32)) and np.array_equal(qa[1], qb[1]))
+        same = same_input(nets["float"], nets["frames"])
+        FramesVariant(nets["frames"], converted).step()  # the frames entry point on the numpy conversion of the NV12 planes
+        same_nv12 = same_input(nets["nv12"], nets["frames"])
+        for _ in range(a.warmup):
+            var["frames"].step()
         runs = {k: {"device_ms": [], "wall_ms": []} for k in var}
         for _ in range(a.repeats):
             for k, v in var.items():  # alternating
@@ -130,14 +176,18 @@ def main():
                 runs[k]["device_ms"].append(round(d, 4))
                 runs[k]["wall_ms"].append(round(w, 4))
         med = {k: {m: float(np.median(r[m])) for m in r} for k, r in runs.items()}
-        res[mode] = {"identical_input": same, "float": runs["float"], "frames": runs["frames"],
+        res[mode] = {"identical_input": same, "nv12_identical_to_frames_on_converted_rgb": same_nv12, "float": runs["float"],
+                     "frames": runs["frames"], "nv12": runs["nv12"],
                      "speedup_device": round(med["float"]["device_ms"] / med["frames"]["device_ms"], 3),
-                     "speedup_wall": round(med["float"]["wall_ms"] / med["frames"]["wall_ms"], 3)}
+                     "speedup_wall": round(med["float"]["wall_ms"] / med["frames"]["wall_ms"], 3),
+                     "nv12_over_frames_device": round(med["frames"]["device_ms"] / med["nv12"]["device_ms"], 3),
+                     "nv12_over_frames_wall": round(med["frames"]["wall_ms"] / med["nv12"]["wall_ms"], 3)}
         for n in nets.values():
             n.close()
     res["host_convert_ms_numpy"] = round(convert_ms, 3)
     res["config"] = {"cfg": "yolov3-tiny_quant.cfg", "batch": a.batch, "src": a.src, "iters": a.iters, "warmup": a.warmup,
-                     "repeats": a.repeats, "values": "median of `iters` steps per repeat; speedup = median over repeats, float / frames"}
+                     "repeats": a.repeats, "values": "median of `iters` steps per repeat; speedup = median over repeats, float / frames; "
+                               "nv12_over_frames = frames / nv12"}
     print(json.dumps(res))
 
 

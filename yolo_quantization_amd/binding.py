@@ -42,6 +42,16 @@ class FrameU8(C.Structure):
 
 FRAME_ORDER = {"rgb": 0, "bgr": 1}  # MI355_FRAME_RGB / MI355_FRAME_BGR
 
+
+class FrameYUV(C.Structure):
+    """mi355_frame_yuv: one entry of the frame table of mi355_frames_yuv_letterbox_minmax / _quantize (y, uv: DEVICE pointers)."""
+    _fields_ = [("y", C.c_void_p), ("uv", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("pitch_y", C.c_int), ("pitch_uv", C.c_int),
+                ("layout", C.c_int), ("matrix", C.c_int), ("reserved", C.c_int * 2)]
+
+
+YUV_LAYOUT = {"nv12": 0, "nv21": 1}  # MI355_YUV_NV12 / MI355_YUV_NV21
+YUV_MATRIX = {"bt601": 0, "bt601f": 1, "bt709": 2, "bt709f": 3}  # MI355_YUV_BT601, _BT601_FULL, _BT709, _BT709_FULL
+
 _shim = None
 _host = None
 
@@ -115,6 +125,8 @@ def shim():
                                                         C.POINTER(Tensor), C.POINTER(Tensor), vp]
         L.mi355_frames_u8_letterbox_minmax.argtypes = [vp, C.POINTER(FrameU8), ci, ci, ci, vp, vp]
         L.mi355_frames_u8_letterbox_quantize.argtypes = [vp, C.POINTER(FrameU8), ci, ci, ci, vp, vp, vp, vp]
+        L.mi355_frames_yuv_letterbox_minmax.argtypes = [vp, C.POINTER(FrameYUV), ci, ci, ci, vp, vp]
+        L.mi355_frames_yuv_letterbox_quantize.argtypes = [vp, C.POINTER(FrameYUV), ci, ci, ci, vp, vp, vp, vp]
         L.mi355_yolo_detections_sizes.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, C.c_float, ci, vp, ci, vp, vp]
         _shim = L
     return _shim
@@ -345,6 +357,8 @@ def host():
         L.network_letterbox_input_gpu.argtypes = [vp, ci, vp, ci, ci]
         L.network_quantize_input_gpu.argtypes = [vp]
         L.network_frames_u8_input_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, ci]
+        L.network_frames_nv12_input_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci),
+                                                    C.POINTER(ci), ci, ci, ci]
         L.quantization_prep_host.argtypes = [vp, C.c_float, C.c_uint8]
         L.forward_network_gpu.argtypes = [vp]
         L.network_predict.restype = vp
@@ -545,11 +559,45 @@ class Net:
             keep.append(a)
             ptrs[b], hs[b], ws[b], ps[b] = a.ctypes.data, a.shape[0], a.shape[1], a.strides[0]
         self.H.network_frames_u8_input_gpu(self.h, ptrs, ws, hs, ps, FRAME_ORDER[order], 0)
+        return self._prepared(self._pull_input())
+
+    def _pull_input(self):
         self.sync()
         out = np.empty(self.batch * self.inputs, np.uint8)
         check(shim().mi355_d2h(out.ctypes.data, self.input_gpu_ptr(), out.nbytes, None), "d2h")
         check(shim().mi355_stream_sync(None), "sync")
-        return self._prepared(out)
+        return out
+
+    def prepare_from_frames_nv12(self, frames, layout="nv12", matrix="bt601", on_device=False):
+        """NV12 / NV21 frame input path (network_frames_nv12_input_gpu): frames[b] is a pair (y, uv) of uint8 arrays, [h][w] and
+        [(h + 1) // 2][(w + 1) // 2][2] (`layout` = "nv12": pairs are (U, V) | "nv21": (V, U)); both planes go up as they are and are
+        converted with `matrix` = "bt601" | "bt601f" | "bt709" | "bt709f" (f: full range) on the device, inside the letterbox.  Row
+        strides are passed through as pitches where the samples of a row are contiguous and the stride is at least the row
+        (anything else is copied first).  on_device: frames[b] is (y_ptr, uv_ptr, w, h, pitch_y, pitch_uv) with device addresses
+        instead, used in place.  Returns what prepare_from_frames_u8 returns."""
+        assert len(frames) == self.batch
+        B = self.batch
+        keep = []
+        ys, uvs = (C.c_void_p * B)(), (C.c_void_p * B)()
+        ws, hs, py, puv = (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)()
+        for b, f in enumerate(frames):
+            if on_device:
+                ys[b], uvs[b], ws[b], hs[b], py[b], puv[b] = f
+                continue
+            y, uv = np.asarray(f[0]), np.asarray(f[1])
+            if y.dtype != np.uint8 or y.ndim != 2 or uv.dtype != np.uint8 or uv.ndim != 3 or uv.shape[2] != 2:
+                raise ValueError("prepare_from_frames_nv12: every frame must be (uint8 [h][w], uint8 [(h + 1) // 2][(w + 1) // 2][2])")
+            h, w = y.shape
+            if uv.shape[:2] != ((h + 1) // 2, (w + 1) // 2):
+                raise ValueError("prepare_from_frames_nv12: the chroma plane must be [(h + 1) // 2][(w + 1) // 2][2]")
+            if y.strides[1] != 1 or y.strides[0] < w:
+                y = np.ascontiguousarray(y)
+            if uv.strides[2] != 1 or uv.strides[1] != 2 or uv.strides[0] < 2 * uv.shape[1]:
+                uv = np.ascontiguousarray(uv)
+            keep += [y, uv]
+            ys[b], uvs[b], hs[b], ws[b], py[b], puv[b] = y.ctypes.data, uv.ctypes.data, h, w, y.strides[0], uv.strides[0]
+        self.H.network_frames_nv12_input_gpu(self.h, ys, uvs, ws, hs, py, puv, YUV_LAYOUT[layout], YUV_MATRIX[matrix], int(on_device))
+        return self._prepared(self._pull_input())
 
     def push_input(self, x_u8):
         x = np.ascontiguousarray(x_u8, np.uint8).ravel()

@@ -7,6 +7,10 @@
 // the same expressions, each product and sum rounded on its own (-ffp-contract=off), the 0.5 fill, last column = the source's last
 // column, last row = first term only.  The quantiser is image_quantize_per_image_kernel's expression, min / max reduce with
 // image_minmax_batched_kernel's seeds, comparisons and atomics.
+//
+// NV12 / NV21 frames (mi355_frames_yuv_letterbox_minmax / _quantize) go through the same two kernel bodies with another source: the
+// bytes of a source pixel are converted from (Y, U, V) in registers at every bilinear tap, with the integer formulas of the header
+// (mi355_frame_yuv), and from there on every expression is the interleaved path's.  No RGB frame is written anywhere.
 #include "kargs.h"
 
 // letterbox_launch's geometry (glue.hip), shared by the host-side validation and the kernels: one function compiled for both sides, so
@@ -39,8 +43,100 @@ __device__ static inline void fill_byte_lut(float *lut)
     __syncthreads();
 }
 
+// A source gives the kernels the bytes of the up to four taps of one output pixel: taps(ix, iy, two_x, two_y, p) fills p[dy][dx][k]
+// with byte k (plane k) of source pixel (ix + dx, iy + dy); column 1 only when two_x, row 1 only when two_y (the launcher's geometry
+// check keeps ix + 1 and iy + 1 inside the frame then).
+struct SourceU8 {
+    const uint8_t *data;
+    int w, h, pitch, o0, o2;  // byte offsets of planes 0 and 2 inside a pixel (plane 1 is byte 1 in both orders)
+    __device__ explicit SourceU8(const mi355_frame_u8 &f)
+        : data(f.data), w(f.w), h(f.h), pitch(f.pitch), o0(f.order == MI355_FRAME_BGR ? 2 : 0), o2(f.order == MI355_FRAME_BGR ? 0 : 2) {}
+    __device__ void taps(int ix, int iy, bool two_x, bool two_y, uint8_t p[2][2][3]) const
+    {
+        const uint8_t *row = data + (size_t)iy * pitch + 3 * (size_t)ix;
+#pragma unroll
+        for (int r = 0; r < 2; ++r, row += pitch) {
+            if (r == 1 && !two_y) break;
+            p[r][0][0] = row[o0]; p[r][0][1] = row[1]; p[r][0][2] = row[o2];
+            if (two_x) { p[r][1][0] = row[3 + o0]; p[r][1][1] = row[4]; p[r][1][2] = row[3 + o2]; }
+        }
+    }
+};
+
+// (yoff, cy, crv, cgu, cgv, cbu) of MI355_YUV_BT601, _BT601_FULL, _BT709, _BT709_FULL: round(x * 65536) of the standards' coefficients
+static __constant__ int yuv_matrix[4][6] = {{16, 76309, 104597, 25675, 53279, 132201},
+                                            {0, 65536, 91881, 22553, 46802, 116130},
+                                            {16, 76309, 117489, 13975, 34925, 138438},
+                                            {0, 65536, 103206, 12276, 30679, 121609}};
+
+struct SourceYUV {
+    const uint8_t *y, *uv;
+    int w, h, pitch_y, pitch_uv;
+    int iu, iv;        // position of U and V inside a chroma pair: (0, 1) NV12, (1, 0) NV21
+    bool pair_aligned; // every chroma pair starts at an even address: one 2-byte load serves it
+    int yoff, cy, crv, cgu, cgv, cbu;  // the frame's matrix: uniform over the workgroup, read once from the constant table
+    __device__ explicit SourceYUV(const mi355_frame_yuv &f)
+        : y(f.y), uv(f.uv), w(f.w), h(f.h), pitch_y(f.pitch_y), pitch_uv(f.pitch_uv), iu(f.layout == MI355_YUV_NV21 ? 1 : 0),
+          iv(f.layout == MI355_YUV_NV21 ? 0 : 1), pair_aligned(((reinterpret_cast<size_t>(f.uv) | (size_t)f.pitch_uv) & 1) == 0)
+    {
+        const int *m = yuv_matrix[f.matrix];
+        yoff = m[0]; cy = m[1]; crv = m[2]; cgu = m[3]; cgv = m[4]; cbu = m[5];
+    }
+    // the three chroma terms of the pair at (cx, cy): what R, G and B add to the luma term, the rounding constant included
+    __device__ void chroma(int cx, int cyy, int t[3]) const
+    {
+        const uint8_t *p = uv + (size_t)cyy * pitch_uv + 2 * (size_t)cx;
+        int b[2];
+        if (pair_aligned) {
+            const uint32_t two = *reinterpret_cast<const uint16_t *>(p);
+            b[0] = (int)(two & 255); b[1] = (int)(two >> 8);
+        } else {
+            b[0] = p[0]; b[1] = p[1];
+        }
+        const int u = b[iu] - 128, v = b[iv] - 128;
+        t[0] = crv * v + 32768;
+        t[1] = 32768 - cgu * u - cgv * v;
+        t[2] = cbu * u + 32768;
+    }
+    __device__ static void copy3(int d[3], const int a[3]) { d[0] = a[0]; d[1] = a[1]; d[2] = a[2]; }
+    __device__ static uint8_t clamp8(int x) { return (uint8_t)(x < 0 ? 0 : (x > 255 ? 255 : x)); }
+    // int32 throughout, >> is the arithmetic shift; |luma term| < 2^25 and |chroma term| < 2^25: no overflow
+    __device__ void rgb(int luma, const int t[3], uint8_t out[3]) const
+    {
+        const int yy = cy * (luma - yoff);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[k] = clamp8((yy + t[k]) >> 16);
+    }
+    __device__ void taps(int ix, int iy, bool two_x, bool two_y, uint8_t p[2][2][3]) const
+    {
+        // columns ix, ix + 1 share a chroma pair when ix is even, rows iy, iy + 1 when iy is even: a pair is loaded once
+        const bool next_cx = two_x && (ix & 1), next_cy = two_y && (iy & 1);
+        const int cx = ix >> 1, cyy = iy >> 1;
+        int t[2][2][3];
+        chroma(cx, cyy, t[0][0]);
+        if (next_cx) chroma(cx + 1, cyy, t[0][1]);
+        else copy3(t[0][1], t[0][0]);
+        if (next_cy) {
+            chroma(cx, cyy + 1, t[1][0]);
+            if (next_cx) chroma(cx + 1, cyy + 1, t[1][1]);
+            else copy3(t[1][1], t[1][0]);
+        } else {
+            copy3(t[1][0], t[0][0]);
+            copy3(t[1][1], t[0][1]);
+        }
+        const uint8_t *row = y + (size_t)iy * pitch_y + ix;
+#pragma unroll
+        for (int r = 0; r < 2; ++r, row += pitch_y) {
+            if (r == 1 && !two_y) break;
+            rgb(row[0], t[r][0], p[r][0]);
+            if (two_x) rgb(row[1], t[r][1], p[r][1]);
+        }
+    }
+};
+
 // the three letterboxed floats (planes 0, 1, 2) of output pixel (x, y)
-__device__ static inline void letterbox_px3(const mi355_frame_u8 &f, const FrameGeo &g, const float *lut, int x, int y, float v[3])
+template <class Source>
+__device__ static inline void letterbox_px3(const Source &f, const FrameGeo &g, const float *lut, int x, int y, float v[3])
 {
     const int xx = x - g.ox, r = y - g.oy;
     if (xx < 0 || xx >= g.new_w || r < 0 || r >= g.new_h) {
@@ -58,27 +154,27 @@ __device__ static inline void letterbox_px3(const mi355_frame_u8 &f, const Frame
     const float sy = r * g.h_scale;
     const int iy = (int)sy;
     const float dy = sy - iy;
-    const uint8_t *row0 = f.data + (size_t)iy * f.pitch + 3 * (size_t)ix;
-    const uint8_t *row1 = row0 + f.pitch;  // only read when !last_y
+    uint8_t p[2][2][3];
+    f.taps(ix, iy, !last_x, !last_y, p);  // row 1 is only read when !last_y, column 1 when !last_x
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const int o = f.order == MI355_FRAME_BGR ? 2 - k : k;
-        const float a = last_x ? lut[row0[o]] : (1 - dx) * lut[row0[o]] + dx * lut[row0[3 + o]];
+        const float a = last_x ? lut[p[0][0][k]] : (1 - dx) * lut[p[0][0][k]] + dx * lut[p[0][1][k]];
         float val = (1 - dy) * a;
         if (!last_y) {
-            const float b = last_x ? lut[row1[o]] : (1 - dx) * lut[row1[o]] + dx * lut[row1[3 + o]];
+            const float b = last_x ? lut[p[1][0][k]] : (1 - dx) * lut[p[1][0][k]] + dx * lut[p[1][1][k]];
             val += dy * b;
         }
         v[k] = val;
     }
 }
 
-// grid: (workgroups per image, B).  mm[2 b] = max(x, +0), mm[2 b + 1] = min(x, -0) as in image_minmax_batched_kernel (seeded before)
-__global__ __launch_bounds__(256) void frames_u8_letterbox_minmax_kernel(const mi355_frame_u8 *table, int w, int h, uint32_t *mm)
+// grid: (workgroups per image, B).  mm[2 b] = max(x, +0), mm[2 b + 1] = min(x, -0) as in image_minmax_batched_kernel (seeded before).
+// One body for both sources; lut: the workgroup's 256-entry byte table.
+template <class Source, class Frame>
+__device__ static inline void letterbox_minmax_body(const Frame *table, int w, int h, uint32_t *mm, float *lut)
 {
-    __shared__ float lut[256];
     fill_byte_lut(lut);
-    const mi355_frame_u8 f = table[blockIdx.y];
+    const Source f(table[blockIdx.y]);
     uint32_t *mi = mm + 2 * (size_t)blockIdx.y;
     FrameGeo g;
     frame_geometry(f.w, f.h, w, h, g);  // checked by the launcher
@@ -105,17 +201,29 @@ __global__ __launch_bounds__(256) void frames_u8_letterbox_minmax_kernel(const m
     }
 }
 
-// grid: (workgroups per image, B); a thread serves four neighbouring x of one row in all three planes: one 4-byte store per plane
-// where the row position is 4-byte aligned, single bytes otherwise (w % 4 != 0: every other row, and the tail of each row)
-__global__ __launch_bounds__(256) void frames_u8_letterbox_quantize_kernel(const mi355_frame_u8 *table, int w, int h,
-                                                                           const float *scale_dev, const uint8_t *zp_dev, uint8_t *out)
+__global__ __launch_bounds__(256) void frames_u8_letterbox_minmax_kernel(const mi355_frame_u8 *table, int w, int h, uint32_t *mm)
 {
     __shared__ float lut[256];
+    letterbox_minmax_body<SourceU8>(table, w, h, mm, lut);
+}
+
+__global__ __launch_bounds__(256) void frames_yuv_letterbox_minmax_kernel(const mi355_frame_yuv *table, int w, int h, uint32_t *mm)
+{
+    __shared__ float lut[256];
+    letterbox_minmax_body<SourceYUV>(table, w, h, mm, lut);
+}
+
+// grid: (workgroups per image, B); a thread serves four neighbouring x of one row in all three planes: one 4-byte store per plane
+// where the row position is 4-byte aligned, single bytes otherwise (w % 4 != 0: every other row, and the tail of each row)
+template <class Source, class Frame>
+__device__ static inline void letterbox_quantize_body(const Frame *table, int w, int h, const float *scale_dev, const uint8_t *zp_dev,
+                                                      uint8_t *out, float *lut)
+{
     fill_byte_lut(lut);
     const int wq = (w + 3) / 4;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t < h * wq) {
-        const mi355_frame_u8 f = table[blockIdx.y];
+        const Source f(table[blockIdx.y]);
         FrameGeo g;
         frame_geometry(f.w, f.h, w, h, g);  // checked by the launcher
         const float scale = scale_dev[blockIdx.y];
@@ -146,6 +254,20 @@ __global__ __launch_bounds__(256) void frames_u8_letterbox_quantize_kernel(const
     }
 }
 
+__global__ __launch_bounds__(256) void frames_u8_letterbox_quantize_kernel(const mi355_frame_u8 *table, int w, int h,
+                                                                           const float *scale_dev, const uint8_t *zp_dev, uint8_t *out)
+{
+    __shared__ float lut[256];
+    letterbox_quantize_body<SourceU8>(table, w, h, scale_dev, zp_dev, out, lut);
+}
+
+__global__ __launch_bounds__(256) void frames_yuv_letterbox_quantize_kernel(const mi355_frame_yuv *table, int w, int h,
+                                                                            const float *scale_dev, const uint8_t *zp_dev, uint8_t *out)
+{
+    __shared__ float lut[256];
+    letterbox_quantize_body<SourceYUV>(table, w, h, scale_dev, zp_dev, out, lut);
+}
+
 // Host-side check of the table's host mirror, before anything is launched: NULL when every frame can be served, else what is wrong.
 const char *frames_u8_check(const mi355_frame_u8 *host, int B, int w, int h)
 {
@@ -163,22 +285,64 @@ const char *frames_u8_check(const mi355_frame_u8 *host, int B, int w, int h)
     return nullptr;
 }
 
+const char *frames_yuv_check(const mi355_frame_yuv *host, int B, int w, int h)
+{
+    if (!host || B <= 0 || B > 65535) return "frames_yuv: null table / need 1 <= B <= 65535";
+    if (w < 2 || h < 2 || w > 32768 || h > 32768) return "frames_yuv: need 2 <= w, h <= 32768 for the network input";
+    for (int b = 0; b < B; ++b) {
+        const mi355_frame_yuv &f = host[b];
+        if (!f.y || !f.uv) return "frames_yuv: null plane pointer";
+        if (f.w < 1 || f.h < 1 || f.w > 32768 || f.h > 32768) return "frames_yuv: need 1 <= w, h <= 32768 for every frame";
+        if (f.pitch_y < f.w) return "frames_yuv: pitch_y < w";
+        if (f.pitch_uv < 2 * ((f.w + 1) / 2)) return "frames_yuv: pitch_uv < 2 * ((w + 1) / 2)";
+        if (f.layout != MI355_YUV_NV12 && f.layout != MI355_YUV_NV21) return "frames_yuv: layout must be MI355_YUV_NV12 or MI355_YUV_NV21";
+        if (f.matrix < MI355_YUV_BT601 || f.matrix > MI355_YUV_BT709_FULL) return "frames_yuv: unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)";
+        FrameGeo g;
+        if (!frame_geometry(f.w, f.h, w, h, g)) return "frames_yuv: degenerate aspect (resized side < 2)";
+    }
+    return nullptr;
+}
+
+// about 2048 workgroups in all, at least one per image (image_minmax_batched_launch's sizing)
+static int minmax_grid_x(int B, int w, int h)
+{
+    const long want = ((long)h * w + 255) / 256;
+    const long cap = 2048 / B > 0 ? 2048 / B : 1;
+    return (int)(want < cap ? want : cap);
+}
+
+static unsigned quantize_grid_x(int w, int h)
+{
+    const long threads = (long)h * ((w + 3) / 4);
+    return (unsigned)((threads + 255) / 256);
+}
+
 int frames_u8_letterbox_minmax_launch(const mi355_frame_u8 *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st)
 {
     if (image_minmax_seed_launch(mm, B, st) != MI355_OK) return MI355_EHIP;
-    const long want = ((long)h * w + 255) / 256;
-    // about 2048 workgroups in all, at least one per image (image_minmax_batched_launch's sizing)
-    const long cap = 2048 / B > 0 ? 2048 / B : 1;
-    const int gx = (int)(want < cap ? want : cap);
-    hipLaunchKernelGGL(frames_u8_letterbox_minmax_kernel, dim3(gx, B), dim3(256), 0, st, table_dev, w, h, mm);
+    hipLaunchKernelGGL(frames_u8_letterbox_minmax_kernel, dim3(minmax_grid_x(B, w, h), B), dim3(256), 0, st, table_dev, w, h, mm);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }
 
 int frames_u8_letterbox_quantize_launch(const mi355_frame_u8 *table_dev, int B, int w, int h, const float *scale_dev,
                                         const uint8_t *zp_dev, uint8_t *out, hipStream_t st)
 {
-    const long threads = (long)h * ((w + 3) / 4);
-    hipLaunchKernelGGL(frames_u8_letterbox_quantize_kernel, dim3((unsigned)((threads + 255) / 256), B), dim3(256), 0, st, table_dev, w, h,
+    hipLaunchKernelGGL(frames_u8_letterbox_quantize_kernel, dim3(quantize_grid_x(w, h), B), dim3(256), 0, st, table_dev, w, h,
+                       scale_dev, zp_dev, out);
+    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
+}
+
+int frames_yuv_letterbox_minmax_launch(const mi355_frame_yuv *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st)
+{
+    if (image_minmax_seed_launch(mm, B, st) != MI355_OK) return MI355_EHIP;
+    hipLaunchKernelGGL(frames_yuv_letterbox_minmax_kernel, dim3(minmax_grid_x(B, w, h), B), dim3(256), 0, st, table_dev, w, h, mm);
+    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
+}
+
+int frames_yuv_letterbox_quantize_launch(const mi355_frame_yuv *table_dev, int B, int w, int h, const float *scale_dev,
+                                         const uint8_t *zp_dev, uint8_t *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(frames_yuv_letterbox_quantize_kernel, dim3(quantize_grid_x(w, h), B), dim3(256), 0, st, table_dev, w, h,
                        scale_dev, zp_dev, out);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }

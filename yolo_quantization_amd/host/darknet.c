@@ -23,6 +23,9 @@
  * zero point -- set_input_quantization_per_image -- and reported with the block `detector test` prints for it alone).
  * -frames u8 (the sources go to the device as the 8-bit interleaved bytes they are, the whole batch through one
  * network_frames_u8_input_gpu call: no float conversion on the host, no float image on the device; same output).
+ * -frames nv12 | nv21 [-matrix bt601|bt601f|bt709|bt709f] (every source is a raw video frame in a file named <anything>_<W>x<H>.nv12:
+ * W * H luma bytes, then the interleaved half-resolution chroma plane; both planes go up as they are and are converted inside the
+ * letterbox, network_frames_nv12_input_gpu; the output is that of -frames u8 on the converted RGB frame).
  *
  * Image input: binary PPM (P6) of ANY size (letterboxed like the reference does), a raw `.u8` file holding [c][h][w] bytes at
  * network size, or `synthetic:<seed>`.  JPEG/PNG decoding is third-party code in the reference (stb_image, SURVEY.md 2
@@ -34,6 +37,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "darknet_q.h"
+#include "nv12_file.h"
 
 static int find_arg(int argc, char **argv, const char *arg)
 {
@@ -119,6 +123,15 @@ static uint8_t *load_frame_u8(const char *path, int netc, int neth, int netw, in
     return rgb;
 }
 
+/* -frames nv12 / nv21: the file's two planes; the chroma plane starts at w * h */
+static uint8_t *load_frame_nv12(const char *path, int *w, int *h)
+{
+    char why[1024];
+    uint8_t *raw = load_nv12_file(path, w, h, why, sizeof(why));
+    if (!raw) error(why);
+    return raw;
+}
+
 static void dump_layer(const char *dir, network *net, int i)
 {
     layer *l = &net->layers[i];
@@ -146,6 +159,8 @@ typedef struct {
     const char *datacfg, *cfgfile, *weightfile, *filename, *dumpdir, *packed_in, *packed_out;
     const char *listfile;  /* -list: image paths, one per line, per-image input quantisation */
     int frames_u8;         /* -frames u8: sources go up as interleaved bytes (network_frames_u8_input_gpu), no host float conversion */
+    int frames_yuv;        /* -frames nv12 | nv21: sources are raw _<W>x<H>.nv12 files (network_frames_nv12_input_gpu) */
+    int yuv_layout, yuv_matrix; /* MI355_YUV_NV12 / _NV21, MI355_YUV_BT601 .. _BT709_FULL (-matrix) */
     float thresh, hier_thresh;
     int batch, accum, store, use_graph, iters, gpu, boxes, quiet, inflight;
     int rank, nranks;      /* -gpus with -bcast: this replica's rank; rank 0 reads the weights file, the others receive blobs */
@@ -202,7 +217,17 @@ static void test_detector_list(detect_job *job, network *net, char **names, int 
     int *imw = calloc((size_t)B, sizeof(int)), *imh = calloc((size_t)B, sizeof(int));
     for (int first = 0; first < np; first += B) {
         const int cnt = np - first < B ? np - first : B;
-        if (job->frames_u8) { /* the batch's frames as bytes, one call for the whole input step */
+        if (job->frames_yuv) { /* the batch's raw video frames, one call for the whole input step */
+            uint8_t **fr = calloc((size_t)B, sizeof(uint8_t *));
+            const uint8_t **uv = calloc((size_t)B, sizeof(uint8_t *));
+            for (int b = 0; b < B; ++b) {
+                fr[b] = load_frame_nv12(paths[first + (b < cnt ? b : cnt - 1)], &imw[b], &imh[b]);
+                uv[b] = fr[b] + (size_t)imw[b] * imh[b];
+            }
+            network_frames_nv12_input_gpu(net, (const uint8_t *const *)fr, uv, imw, imh, NULL, NULL, job->yuv_layout, job->yuv_matrix, 0);
+            for (int b = 0; b < B; ++b) free(fr[b]);
+            free(fr); free(uv);
+        } else if (job->frames_u8) { /* the batch's frames as bytes, one call for the whole input step */
             uint8_t **fr = calloc((size_t)B, sizeof(uint8_t *));
             for (int b = 0; b < B; ++b) fr[b] = load_frame_u8(paths[first + (b < cnt ? b : cnt - 1)], net->c, net->h, net->w, &imw[b], &imh[b]);
             network_frames_u8_input_gpu(net, (const uint8_t *const *)fr, imw, imh, NULL, MI355_FRAME_RGB, 0);
@@ -284,7 +309,15 @@ static void test_detector(detect_job *job)
     }
     image im = {0, 0, 0, NULL};
     float *im_gpu = NULL;
-    if (job->frames_u8) { /* the source's bytes in every batch slot, one call for the whole input step */
+    if (job->frames_yuv) { /* the raw video frame in every batch slot (it goes up once), one call for the whole input step */
+        if (mi355_init(job->gpu)) { fprintf(stderr, "MI355: %s\n", mi355_last_error()); error("mi355_init (this build has no CPU data path)"); }
+        uint8_t *raw = load_frame_nv12(job->filename, &im.w, &im.h);
+        const uint8_t **fy = calloc((size_t)job->batch, sizeof(uint8_t *)), **fuv = calloc((size_t)job->batch, sizeof(uint8_t *));
+        int *fw = calloc((size_t)job->batch, sizeof(int)), *fh = calloc((size_t)job->batch, sizeof(int));
+        for (int b = 0; b < job->batch; ++b) { fy[b] = raw; fuv[b] = raw + (size_t)im.w * im.h; fw[b] = im.w; fh[b] = im.h; }
+        network_frames_nv12_input_gpu(net, fy, fuv, fw, fh, NULL, NULL, job->yuv_layout, job->yuv_matrix, 0);
+        free(fy); free(fuv); free(fw); free(fh); free(raw);
+    } else if (job->frames_u8) { /* the source's bytes in every batch slot, one call for the whole input step */
         if (mi355_init(job->gpu)) { fprintf(stderr, "MI355: %s\n", mi355_last_error()); error("mi355_init (this build has no CPU data path)"); }
         uint8_t *rgb = load_frame_u8(job->filename, net->c, net->h, net->w, &im.w, &im.h);
         const uint8_t **fr = calloc((size_t)job->batch, sizeof(uint8_t *));
@@ -355,7 +388,7 @@ int main(int argc, char **argv)
     if (argc < 2) {
         fprintf(stderr, "usage: %s detector test <data> <cfg> <weights> <image> [-thresh t] [-i gpu | -gpus a,b,..] [-batch B] "
                         "[-accum exact|ref-f32] [-parity wrap|saturate] [-dump dir] [-graph] [-n iters] [-boxes] "
-                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8]\n", argv[0]);
+                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8|nv12|nv21] [-matrix bt601|bt601f|bt709|bt709f]\n", argv[0]);
         return 0;
     }
     detect_job job;
@@ -379,8 +412,21 @@ int main(int argc, char **argv)
     job.inflight = atoi(find_char_arg(argc, argv, "-inflight", "1"));
     job.listfile = find_char_arg(argc, argv, "-list", NULL);
     const char *frames_s = find_char_arg(argc, argv, "-frames", NULL);
-    if (frames_s && strcmp(frames_s, "u8")) error("-frames: only `u8` (8-bit interleaved frames) is known");
-    job.frames_u8 = frames_s != NULL;
+    const char *matrix_s = find_char_arg(argc, argv, "-matrix", NULL);
+    job.frames_u8 = frames_s && 0 == strcmp(frames_s, "u8");
+    job.frames_yuv = frames_s && (0 == strcmp(frames_s, "nv12") || 0 == strcmp(frames_s, "nv21"));
+    if (frames_s && !job.frames_u8 && !job.frames_yuv)
+        error("-frames: `u8` (8-bit interleaved frames), `nv12` and `nv21` (raw video frames, files named _<W>x<H>.nv12) are known");
+    job.yuv_layout = frames_s && 0 == strcmp(frames_s, "nv21") ? MI355_YUV_NV21 : MI355_YUV_NV12;
+    job.yuv_matrix = MI355_YUV_BT601;
+    if (matrix_s) {
+        static const char *const known[4] = {"bt601", "bt601f", "bt709", "bt709f"}; /* MI355_YUV_BT601 .. MI355_YUV_BT709_FULL */
+        int m = -1;
+        for (int k = 0; k < 4; ++k) if (0 == strcmp(matrix_s, known[k])) m = k;
+        if (m < 0) error("-matrix: bt601 (the default), bt601f, bt709 and bt709f are known");
+        if (!job.frames_yuv) error("-matrix goes with -frames nv12 | nv21");
+        job.yuv_matrix = m;
+    }
     if (job.iters < 1) job.iters = 1;
     if (job.batch < 1) job.batch = 1;
     job.accum = 0 == strcmp(accum_s, "ref-f32") ? MI355_ACC_REF_F32 : MI355_ACC_EXACT;

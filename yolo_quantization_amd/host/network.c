@@ -689,79 +689,90 @@ void network_quantize_input_gpu(network *net)
 
 /* ------------------------------------------------------------------------------------------- 8-bit frame input
  * Two launches for the whole batch (frames.hip): letterbox + min / max, then letterbox + quantise; the float image exists in registers
- * only.  The (scale, zero point) branches are the float path's (input_pair_shared, input_pairs_per_image). */
+ * only.  The (scale, zero point) branches are the float path's (input_pair_shared, input_pairs_per_image).  Interleaved RGB / BGR
+ * frames and NV12 / NV21 frames differ in their table, their staging and the pair of C-ABI calls; everything else is shared. */
 static void fr_free(network *net)
 {
     if (net->fr_arena_gpu) mi355_free(net->fr_arena_gpu);
     if (net->fr_table_gpu) mi355_free(net->fr_table_gpu);
+    if (net->fr_yuv_gpu) mi355_free(net->fr_yuv_gpu);
     if (net->fr_mm_gpu) mi355_free(net->fr_mm_gpu);
     if (net->fr_pair_gpu) mi355_free(net->fr_pair_gpu);
-    free(net->fr_table_host); free(net->fr_mm_host); free(net->fr_pair_host);
+    free(net->fr_table_host); free(net->fr_yuv_host); free(net->fr_mm_host); free(net->fr_pair_host);
     net->fr_arena_gpu = NULL; net->fr_table_gpu = NULL; net->fr_table_host = NULL;
+    net->fr_yuv_gpu = NULL; net->fr_yuv_host = NULL;
     net->fr_mm_gpu = net->fr_mm_host = NULL;
     net->fr_pair_gpu = net->fr_pair_host = NULL;
     net->fr_arena_bytes = 0;
     net->fr_cap = 0;
 }
 
-static void fr_alloc(network *net)
+/* The buffers both kinds of frames share, sized by the batch, and the table of the kind that is asked for: a network fed one kind
+ * never holds the other's table. */
+static void fr_alloc(network *net, int yuv)
 {
     const size_t B = (size_t)net->batch;
-    if (net->fr_cap == net->batch) return;
-    fr_free(net);
-    check_mi355(mi355_alloc((void **)&net->fr_table_gpu, sizeof(mi355_frame_u8) * B), "alloc frame table");
-    check_mi355(mi355_alloc((void **)&net->fr_mm_gpu, 2 * sizeof(float) * B), "alloc minmax");
-    check_mi355(mi355_alloc(&net->fr_pair_gpu, 5 * B), "alloc input pairs");
-    net->fr_table_host = calloc(B, sizeof(mi355_frame_u8));
-    net->fr_mm_host = calloc(2 * B, sizeof(float));
-    net->fr_pair_host = calloc(5, B);
-    net->fr_cap = net->batch;
+    if (net->fr_cap != net->batch) {
+        fr_free(net);
+        check_mi355(mi355_alloc((void **)&net->fr_mm_gpu, 2 * sizeof(float) * B), "alloc minmax");
+        check_mi355(mi355_alloc(&net->fr_pair_gpu, 5 * B), "alloc input pairs");
+        net->fr_mm_host = calloc(2 * B, sizeof(float));
+        net->fr_pair_host = calloc(5, B);
+        net->fr_cap = net->batch;
+    }
+    if (yuv && !net->fr_yuv_gpu) {
+        check_mi355(mi355_alloc((void **)&net->fr_yuv_gpu, sizeof(mi355_frame_yuv) * B), "alloc frame table");
+        net->fr_yuv_host = calloc(B, sizeof(mi355_frame_yuv));
+    } else if (!yuv && !net->fr_table_gpu) {
+        check_mi355(mi355_alloc((void **)&net->fr_table_gpu, sizeof(mi355_frame_u8) * B), "alloc frame table");
+        net->fr_table_host = calloc(B, sizeof(mi355_frame_u8));
+    }
 }
 
-void network_frames_u8_input_gpu(network *net, const uint8_t *const *frames, const int *w, const int *h, const int *pitch, int order,
-                                 int frames_on_device)
+static void fr_begin(network *net, int yuv, const char *not_3_channels)
 {
-    const int B = net->batch;
-    if (!frames || !w || !h) error("network_frames_u8_input_gpu: null frames / sizes");
-    if (net->c != 3) error("network_frames_u8_input_gpu: 8-bit frames feed 3-channel networks only");
+    if (net->c != 3) error(not_3_channels);
     check_mi355(mi355_init(net->gpu_index), "mi355_init");
     if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
-    fr_alloc(net);
-    mi355_frame_u8 *tab = net->fr_table_host;
-    size_t need = 0;
-    for (int b = 0; b < B; ++b) {
-        if (!frames[b]) error("network_frames_u8_input_gpu: null frame");
-        const int p = pitch ? pitch[b] : 3 * w[b];
-        if (w[b] < 1 || h[b] < 1 || p < 3 * w[b]) error("network_frames_u8_input_gpu: need w, h >= 1 and pitch >= 3 * w for every frame");
-        memset(&tab[b], 0, sizeof(tab[b]));
-        tab[b].data = frames[b];
-        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch = p; tab[b].order = order;
-        need += (((size_t)(h[b] - 1) * (size_t)p + 3 * (size_t)w[b]) + 255) & ~(size_t)255;
+    fr_alloc(net, yuv);
+}
+
+static size_t fr_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+/* the staging arena holds at least `need` bytes */
+static void fr_arena_reserve(network *net, size_t need)
+{
+    if (need <= net->fr_arena_bytes) return;
+    check_mi355(mi355_stream_sync(net->stream), "sync"); /* nothing in flight reads the arena that is freed */
+    if (net->fr_arena_gpu) mi355_free(net->fr_arena_gpu);
+    net->fr_arena_gpu = NULL; net->fr_arena_bytes = 0;
+    check_mi355(mi355_alloc(&net->fr_arena_gpu, need), "alloc frame arena");
+    net->fr_arena_bytes = need;
+}
+
+/* `bytes` host bytes go up as they are to the arena at *off, which moves on to the next 256-byte boundary */
+static const uint8_t *fr_stage(network *net, const uint8_t *src, size_t bytes, size_t *off)
+{
+    uint8_t *dst = (uint8_t *)net->fr_arena_gpu + *off;
+    check_mi355(mi355_h2d(dst, src, bytes, net->stream), "upload frame");
+    *off += fr_round(bytes);
+    return dst;
+}
+
+/* The common tail, the host mirror of the table filled with device pointers: table upload, min / max launch, the batch's one host
+ * sync, the (scale, zero point) branch, quantiser launch.  yuv: the NV12 / NV21 table and calls instead of the interleaved ones. */
+static void fr_finish(network *net, int yuv)
+{
+    const int B = net->batch;
+    if (yuv) {
+        check_mi355(mi355_h2d(net->fr_yuv_gpu, net->fr_yuv_host, sizeof(mi355_frame_yuv) * (size_t)B, net->stream), "upload frame table");
+        check_mi355(mi355_frames_yuv_letterbox_minmax(net->fr_yuv_gpu, net->fr_yuv_host, B, net->w, net->h, net->fr_mm_gpu, net->stream),
+                    "mi355_frames_yuv_letterbox_minmax");
+    } else {
+        check_mi355(mi355_h2d(net->fr_table_gpu, net->fr_table_host, sizeof(mi355_frame_u8) * (size_t)B, net->stream), "upload frame table");
+        check_mi355(mi355_frames_u8_letterbox_minmax(net->fr_table_gpu, net->fr_table_host, B, net->w, net->h, net->fr_mm_gpu, net->stream),
+                    "mi355_frames_u8_letterbox_minmax");
     }
-    if (!frames_on_device) { /* the bytes as they are: rows keep their pitch, the last row ends with its last pixel */
-        if (need > net->fr_arena_bytes) {
-            check_mi355(mi355_stream_sync(net->stream), "sync"); /* nothing in flight reads the arena that is freed */
-            if (net->fr_arena_gpu) mi355_free(net->fr_arena_gpu);
-            net->fr_arena_gpu = NULL; net->fr_arena_bytes = 0;
-            check_mi355(mi355_alloc(&net->fr_arena_gpu, need), "alloc frame arena");
-            net->fr_arena_bytes = need;
-        }
-        size_t off = 0;
-        for (int b = 0; b < B; ++b) {
-            const size_t bytes = (size_t)(h[b] - 1) * (size_t)tab[b].pitch + 3 * (size_t)w[b];
-            int same = -1; /* one frame in several slots (`-batch B` of one image) goes up once */
-            for (int k = 0; k < b && same < 0; ++k)
-                if (frames[k] == frames[b] && w[k] == w[b] && h[k] == h[b] && tab[k].pitch == tab[b].pitch) same = k;
-            if (same >= 0) { tab[b].data = tab[same].data; continue; }
-            uint8_t *dst = (uint8_t *)net->fr_arena_gpu + off;
-            check_mi355(mi355_h2d(dst, frames[b], bytes, net->stream), "upload frame");
-            tab[b].data = dst;
-            off += (bytes + 255) & ~(size_t)255;
-        }
-    }
-    check_mi355(mi355_h2d(net->fr_table_gpu, tab, sizeof(mi355_frame_u8) * (size_t)B, net->stream), "upload frame table");
-    check_mi355(mi355_frames_u8_letterbox_minmax(net->fr_table_gpu, tab, B, net->w, net->h, net->fr_mm_gpu, net->stream),
-                "mi355_frames_u8_letterbox_minmax");
     check_mi355(mi355_d2h(net->fr_mm_host, net->fr_mm_gpu, 2 * sizeof(float) * (size_t)B, net->stream), "minmax d2h");
     check_mi355(mi355_stream_sync(net->stream), "sync"); /* the batch's one host sync: every earlier upload is done too */
     const float *scale_dev;
@@ -781,8 +792,82 @@ void network_frames_u8_input_gpu(network *net, const uint8_t *const *frames, con
         scale_dev = (const float *)net->fr_pair_gpu;
         zp_dev = (const uint8_t *)net->fr_pair_gpu + 4 * (size_t)B;
     }
-    check_mi355(mi355_frames_u8_letterbox_quantize(net->fr_table_gpu, tab, B, net->w, net->h, scale_dev, zp_dev, net->input_uint8_gpu,
-                                                   net->stream), "mi355_frames_u8_letterbox_quantize");
+    if (yuv)
+        check_mi355(mi355_frames_yuv_letterbox_quantize(net->fr_yuv_gpu, net->fr_yuv_host, B, net->w, net->h, scale_dev, zp_dev,
+                                                        net->input_uint8_gpu, net->stream), "mi355_frames_yuv_letterbox_quantize");
+    else
+        check_mi355(mi355_frames_u8_letterbox_quantize(net->fr_table_gpu, net->fr_table_host, B, net->w, net->h, scale_dev, zp_dev,
+                                                       net->input_uint8_gpu, net->stream), "mi355_frames_u8_letterbox_quantize");
+}
+
+void network_frames_u8_input_gpu(network *net, const uint8_t *const *frames, const int *w, const int *h, const int *pitch, int order,
+                                 int frames_on_device)
+{
+    const int B = net->batch;
+    if (!frames || !w || !h) error("network_frames_u8_input_gpu: null frames / sizes");
+    fr_begin(net, 0, "network_frames_u8_input_gpu: 8-bit frames feed 3-channel networks only");
+    mi355_frame_u8 *tab = net->fr_table_host;
+    size_t need = 0;
+    for (int b = 0; b < B; ++b) {
+        if (!frames[b]) error("network_frames_u8_input_gpu: null frame");
+        const int p = pitch ? pitch[b] : 3 * w[b];
+        if (w[b] < 1 || h[b] < 1 || p < 3 * w[b]) error("network_frames_u8_input_gpu: need w, h >= 1 and pitch >= 3 * w for every frame");
+        memset(&tab[b], 0, sizeof(tab[b]));
+        tab[b].data = frames[b];
+        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch = p; tab[b].order = order;
+        need += fr_round((size_t)(h[b] - 1) * (size_t)p + 3 * (size_t)w[b]);
+    }
+    if (!frames_on_device) { /* the bytes as they are: rows keep their pitch, the last row ends with its last pixel */
+        fr_arena_reserve(net, need);
+        size_t off = 0;
+        for (int b = 0; b < B; ++b) {
+            const size_t bytes = (size_t)(h[b] - 1) * (size_t)tab[b].pitch + 3 * (size_t)w[b];
+            int same = -1; /* one frame in several slots (`-batch B` of one image) goes up once */
+            for (int k = 0; k < b && same < 0; ++k)
+                if (frames[k] == frames[b] && w[k] == w[b] && h[k] == h[b] && tab[k].pitch == tab[b].pitch) same = k;
+            if (same >= 0) { tab[b].data = tab[same].data; continue; }
+            tab[b].data = fr_stage(net, frames[b], bytes, &off);
+        }
+    }
+    fr_finish(net, 0);
+}
+
+void network_frames_nv12_input_gpu(network *net, const uint8_t *const *y, const uint8_t *const *uv, const int *w, const int *h,
+                                   const int *pitch_y, const int *pitch_uv, int layout, int matrix, int frames_on_device)
+{
+    const int B = net->batch;
+    if (!y || !uv || !w || !h) error("network_frames_nv12_input_gpu: null planes / sizes");
+    fr_begin(net, 1, "network_frames_nv12_input_gpu: NV12 / NV21 frames feed 3-channel networks only");
+    mi355_frame_yuv *tab = net->fr_yuv_host;
+    size_t need = 0;
+    for (int b = 0; b < B; ++b) {
+        if (!y[b] || !uv[b]) error("network_frames_nv12_input_gpu: null plane");
+        if (w[b] < 1 || h[b] < 1) error("network_frames_nv12_input_gpu: need w, h >= 1 for every frame");
+        const int cw2 = 2 * ((w[b] + 1) / 2), ch = (h[b] + 1) / 2;
+        const int py = pitch_y ? pitch_y[b] : w[b], puv = pitch_uv ? pitch_uv[b] : cw2;
+        if (py < w[b] || puv < cw2) error("network_frames_nv12_input_gpu: need pitch_y >= w and pitch_uv >= 2 * ((w + 1) / 2) for every frame");
+        memset(&tab[b], 0, sizeof(tab[b]));
+        tab[b].y = y[b]; tab[b].uv = uv[b];
+        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch_y = py; tab[b].pitch_uv = puv;
+        tab[b].layout = layout; tab[b].matrix = matrix;
+        need += fr_round((size_t)(h[b] - 1) * (size_t)py + (size_t)w[b]) + fr_round((size_t)(ch - 1) * (size_t)puv + (size_t)cw2);
+    }
+    if (!frames_on_device) { /* both planes as they are: rows keep their pitch, a plane's last row ends with its last sample */
+        fr_arena_reserve(net, need);
+        size_t off = 0;
+        for (int b = 0; b < B; ++b) {
+            const int cw2 = 2 * ((w[b] + 1) / 2), ch = (h[b] + 1) / 2;
+            int same = -1; /* one frame in several slots goes up once */
+            for (int k = 0; k < b && same < 0; ++k)
+                if (y[k] == y[b] && uv[k] == uv[b] && w[k] == w[b] && h[k] == h[b] && tab[k].pitch_y == tab[b].pitch_y &&
+                    tab[k].pitch_uv == tab[b].pitch_uv)
+                    same = k;
+            if (same >= 0) { tab[b].y = tab[same].y; tab[b].uv = tab[same].uv; continue; }
+            tab[b].y = fr_stage(net, y[b], (size_t)(h[b] - 1) * (size_t)tab[b].pitch_y + (size_t)w[b], &off);
+            tab[b].uv = fr_stage(net, uv[b], (size_t)(ch - 1) * (size_t)tab[b].pitch_uv + (size_t)cw2, &off);
+        }
+    }
+    fr_finish(net, 1);
 }
 
 void set_batch_network(network *net, int b)
