@@ -194,6 +194,7 @@ struct network {
     size_t fr_arena_bytes;
     mi355_frame_u8 *fr_table_gpu, *fr_table_host; /* [fr_cap] frame table and its host mirror */
     mi355_frame_yuv *fr_yuv_gpu, *fr_yuv_host;    /* the same for NV12 / NV21 frames (network_frames_nv12_input_gpu) */
+    mi355_frame_planar *fr_planar_gpu, *fr_planar_host; /* and for frames of three planes (network_frames_planar_input_gpu) */
     float *fr_mm_gpu, *fr_mm_host; /* [fr_cap][2] max, min */
     void *fr_pair_gpu, *fr_pair_host; /* shared-scale mode: [fr_cap] float scale | [fr_cap] uint8 zero point, image 0's in every slot */
     int fr_cap;
@@ -243,6 +244,18 @@ void network_frames_u8_input_gpu(network *net, const uint8_t *const *frames, con
  * frames_on_device != 0: the plane pointers are device pointers (a decoder's surfaces), used in place. */
 void network_frames_nv12_input_gpu(network *net, const uint8_t *const *y, const uint8_t *const *uv, const int *w, const int *h,
                                    const int *pitch_y, const int *pitch_uv, int layout, int matrix, int frames_on_device);
+/* The same step for frames of three separate planes, as software decoders (yuv420p), JPEG decoders and [3][h][w] tensors deliver them
+ * (format: MI355_PLANAR_I420, _YV12, _I422, _I444, _RGB, _BGR of mi355_frame_planar, mi355_yolo_int8.h).  p0[b], p1[b], p2[b] are
+ * frame b's planes in the order the format names them: p0 holds h[b] rows of w[b] bytes, p1 and p2 the format's chroma size
+ * ((w + 1) / 2 wide in I420 / YV12 / I422, (h + 1) / 2 high in I420 / YV12, else w and h), rows pitch0[b], pitch1[b], pitch2[b] bytes
+ * apart (a null pitch array: that plane is tightly packed).  The three planes go up as they are and the YUV formats are converted in
+ * registers with `matrix` (MI355_YUV_BT601 .. MI355_YUV_BT709_FULL; 0 with the RGB formats), chroma at [y >> sy][x >> sx]: I420 gives,
+ * bit for bit, network_frames_nv12_input_gpu's result on the interleaved chroma planes, every format network_frames_u8_input_gpu's
+ * on the interleaved RGB frame of the same pixels.  Arena, min / max and pair buffers, the one host sync and both (scale, zero point)
+ * branches are that function's.  frames_on_device != 0: the plane pointers are device pointers, used in place. */
+void network_frames_planar_input_gpu(network *net, const uint8_t *const *p0, const uint8_t *const *p1, const uint8_t *const *p2,
+                                     const int *w, const int *h, const int *pitch0, const int *pitch1, const int *pitch2,
+                                     int format, int matrix, int frames_on_device);
 /* Per-image input quantisation, opt-in (off: image 0 defines the scale of the whole batch, as before).  On: every image of a batch is
  * quantised with its own min / max, scale and zero point, and layer 0 runs with that image's constants (mi355_conv_forward_per_image):
  * slot b of every layer equals the batch-1 run on image b.  The quantisers above honour it.  Returns 0, or MI355_EINVAL with a message

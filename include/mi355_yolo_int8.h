@@ -364,6 +364,42 @@ int mi355_frames_yuv_letterbox_minmax(const mi355_frame_yuv *table_dev, const mi
                                       float *minmax, void *stream);
 int mi355_frames_yuv_letterbox_quantize(const mi355_frame_yuv *table_dev, const mi355_frame_yuv *table_host, int B, int w, int h,
                                         const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
+/* The same two calls for frames of three separate planes, as software decoders (libav's yuv420p), JPEG decoders and [3][h][w] tensors
+ * deliver them.  plane[0] always holds h rows of w bytes; the other two hold ch rows of cw bytes each, by format:
+ *     MI355_PLANAR_I420, _YV12   cw = (w + 1) / 2, ch = (h + 1) / 2     (4:2:0)
+ *     MI355_PLANAR_I422          cw = (w + 1) / 2, ch = h               (4:2:2)
+ *     MI355_PLANAR_I444          cw = w,           ch = h               (4:4:4)
+ *     MI355_PLANAR_RGB, _BGR     cw = w,           ch = h
+ * Rows of plane k lie pitch[k] bytes apart, pitch[0] >= w and pitch[1], pitch[2] >= cw; the three pitches are independent and odd
+ * w and h are legal.  In the YUV formats pixel (x, y) takes Y[y][x], U[y >> sy][x >> sx] and V[y >> sy][x >> sx], where sx = 1 when
+ * the chroma planes are half as wide and sy = 1 when they are half as high, else 0 (nearest sampling: no chroma interpolation, no
+ * siting offset -- the NV12 rule, generalised), and its RGB bytes come from the int32 formulas and the `matrix` rows of
+ * mi355_frame_yuv above, in registers at every bilinear tap.  In the two RGB formats byte k of a pixel is the byte of the plane that
+ * holds channel k (R, G, B); no formula is applied and `matrix` must be 0.  From those bytes on nothing is new: min / max and the
+ * quantised bytes are, bit for bit, what the u8 calls give for the interleaved RGB frame of the same pixels, and I420 gives what the
+ * _yuv_ calls give for the NV12 frame with the interleaved chroma planes.  A new struct and new calls: MI355_ABI_VERSION is unchanged. */
+#define MI355_PLANAR_I420 0  /* planes Y, U, V; chroma (w+1)/2 x (h+1)/2 */
+#define MI355_PLANAR_YV12 1  /* planes Y, V, U; same sizes */
+#define MI355_PLANAR_I422 2  /* planes Y, U, V; chroma (w+1)/2 x h */
+#define MI355_PLANAR_I444 3  /* planes Y, U, V; chroma w x h */
+#define MI355_PLANAR_RGB  4  /* planes R, G, B, all w x h; matrix must be 0 */
+#define MI355_PLANAR_BGR  5  /* planes B, G, R */
+typedef struct mi355_frame_planar {   /* 64 bytes */
+    const uint8_t *plane[3];          /* DEVICE pointers, in the order the format names */
+    int w, h;                         /* pixels (of plane 0) */
+    int pitch[3];                     /* bytes from one row of plane k to the next */
+    int format, matrix;               /* MI355_PLANAR_*; matrix: MI355_YUV_BT601 .. _BT709_FULL */
+    int reserved[3];                  /* zero */
+} mi355_frame_planar;
+/* The contract of the _yuv_ calls: table_host is validated before anything is launched; a null plane, w or h outside 1..32768,
+ * pitch[0] < w, a chroma pitch below that plane's width, an unknown format or matrix, a non-zero matrix with MI355_PLANAR_RGB / _BGR,
+ * or a frame the letterbox geometry refuses return MI355_EINVAL with a message that starts "frames_planar:", and nothing is written.
+ * B <= 65535. */
+int mi355_frames_planar_letterbox_minmax(const mi355_frame_planar *table_dev, const mi355_frame_planar *table_host,
+                                         int B, int w, int h, float *minmax, void *stream);
+int mi355_frames_planar_letterbox_quantize(const mi355_frame_planar *table_dev, const mi355_frame_planar *table_host,
+                                           int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev,
+                                           uint8_t *out_u8, void *stream);
 /* *sum_dev += an order-independent 64-bit checksum of `dwords` 32-bit words at buf (device pointers; zero *sum_dev first).  The
  * host's determinism self-check compares it between passes over the same input (network_selfcheck, darknet_q.h). */
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream);

@@ -1,16 +1,18 @@
 """Times the input step alone: from the batch's first upload to the network's uint8 input being ready on the device.
 
-yolov3-tiny @416, batch 64, 640 x 480 RGB frames (synthetic bytes, every frame its own range), three variants:
+yolov3-tiny @416, batch 64, 640 x 480 RGB frames (synthetic bytes, every frame its own range), four variants:
   float   the float entry points: per frame one upload of the planar float image (byte / 255, converted before the clock starts)
           and one network_letterbox_input_gpu, then network_quantize_input_gpu (min / max, host sync, quantise)
   frames  network_frames_u8_input_gpu: the bytes go up as they are, two launches for the whole batch
   nv12    network_frames_nv12_input_gpu: the same frames as NV12 planes (made before the clock starts: BT.601 limited-range RGB -> YUV
           in numpy, chroma of the top-left pixel of every 2 x 2 block), half the bytes go up, converted inside the two launches
+  i420    network_frames_planar_input_gpu: the same planes with the chroma de-interleaved into a U and a V plane (made before the
+          clock starts), the same number of bytes as nv12 in three host arrays per frame
 each in shared-scale and per-image mode.  A step is timed twice: HIP events on the network's stream around it, and the host clock
 from before the first upload to after a stream synchronise.  The variants alternate within a repeat; the same batch is fed every step
 (steady state: layer 0 is not re-derived, the per-image bank serves every key from its cache).  Before timing, the float and frames
 variants' uint8 inputs, scales and zero points are compared for equality, and the nv12 variant's with those of the frames entry point
-fed the RGB frames a numpy restatement of the integer YUV -> RGB formulas makes of the NV12 planes.  `host_convert_ms` is the byte -> planar float conversion the float variant
+fed the RGB frames a numpy restatement of the integer YUV -> RGB formulas makes of the NV12 planes; the i420 variant's are compared with the nv12 variant's.  `host_convert_ms` is the byte -> planar float conversion the float variant
 needs before its first upload, done with numpy here: an indication only, not part of either timed step.
 Prints one JSON line."""
 import argparse
@@ -104,6 +106,22 @@ class NV12Variant:
         self.net.H.network_frames_nv12_input_gpu(self.net.h, self.y, self.uv, self.w, self.h, None, None, 0, 0, 0)
 
 
+class I420Variant:
+    def __init__(self, net, planes):
+        B = len(planes)
+        self.net = net
+        self.planes = [(y, np.ascontiguousarray(uv[..., 0]), np.ascontiguousarray(uv[..., 1])) for y, uv in planes]
+        self.p = [(C.c_void_p * B)() for _ in range(3)]
+        self.w, self.h = (C.c_int * B)(), (C.c_int * B)()
+        for b, yuv in enumerate(self.planes):
+            for k in range(3):
+                self.p[k][b] = yuv[k].ctypes.data
+            self.h[b], self.w[b] = yuv[0].shape
+
+    def step(self):
+        self.net.H.network_frames_planar_input_gpu(self.net.h, self.p[0], self.p[1], self.p[2], self.w, self.h, None, None, None, 0, 0, 0)
+
+
 def same_input(a, b):
     same = np.array_equal(pull_input(a), pull_input(b))
     qa, qb = a.input_quantization(), b.input_quantization()
@@ -155,18 +173,19 @@ def main():
     ev = Events()
     res = {}
     for mode in ("shared", "per_image"):
-        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("float", "frames", "nv12")}
+        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("float", "frames", "nv12", "i420")}
         if mode == "per_image":
             for n in nets.values():
                 n.set_input_per_image(True)
         var = {"float": FloatVariant(nets["float"], frames), "frames": FramesVariant(nets["frames"], frames),
-               "nv12": NV12Variant(nets["nv12"], planes)}
+               "nv12": NV12Variant(nets["nv12"], planes), "i420": I420Variant(nets["i420"], planes)}
         for _ in range(a.warmup):
             for v in var.values():
                 v.step()
         same = same_input(nets["float"], nets["frames"])
         FramesVariant(nets["frames"], converted).step()  # the frames entry point on the numpy conversion of the NV12 planes
         same_nv12 = same_input(nets["nv12"], nets["frames"])
+        same_i420 = same_input(nets["i420"], nets["nv12"])
         for _ in range(a.warmup):
             var["frames"].step()
         runs = {k: {"device_ms": [], "wall_ms": []} for k in var}
@@ -176,18 +195,21 @@ def main():
                 runs[k]["device_ms"].append(round(d, 4))
                 runs[k]["wall_ms"].append(round(w, 4))
         med = {k: {m: float(np.median(r[m])) for m in r} for k, r in runs.items()}
-        res[mode] = {"identical_input": same, "nv12_identical_to_frames_on_converted_rgb": same_nv12, "float": runs["float"],
-                     "frames": runs["frames"], "nv12": runs["nv12"],
+        res[mode] = {"identical_input": same, "nv12_identical_to_frames_on_converted_rgb": same_nv12,
+                     "i420_identical_to_nv12": same_i420, "float": runs["float"], "frames": runs["frames"], "nv12": runs["nv12"],
+                     "i420": runs["i420"],
                      "speedup_device": round(med["float"]["device_ms"] / med["frames"]["device_ms"], 3),
                      "speedup_wall": round(med["float"]["wall_ms"] / med["frames"]["wall_ms"], 3),
                      "nv12_over_frames_device": round(med["frames"]["device_ms"] / med["nv12"]["device_ms"], 3),
-                     "nv12_over_frames_wall": round(med["frames"]["wall_ms"] / med["nv12"]["wall_ms"], 3)}
+                     "nv12_over_frames_wall": round(med["frames"]["wall_ms"] / med["nv12"]["wall_ms"], 3),
+                     "i420_over_nv12_device": round(med["nv12"]["device_ms"] / med["i420"]["device_ms"], 3),
+                     "i420_over_nv12_wall": round(med["nv12"]["wall_ms"] / med["i420"]["wall_ms"], 3)}
         for n in nets.values():
             n.close()
     res["host_convert_ms_numpy"] = round(convert_ms, 3)
     res["config"] = {"cfg": "yolov3-tiny_quant.cfg", "batch": a.batch, "src": a.src, "iters": a.iters, "warmup": a.warmup,
                      "repeats": a.repeats, "values": "median of `iters` steps per repeat; speedup = median over repeats, float / frames; "
-                               "nv12_over_frames = frames / nv12"}
+                               "nv12_over_frames = frames / nv12; i420_over_nv12 = nv12 / i420"}
     print(json.dumps(res))
 
 

@@ -52,6 +52,16 @@ class FrameYUV(C.Structure):
 YUV_LAYOUT = {"nv12": 0, "nv21": 1}  # MI355_YUV_NV12 / MI355_YUV_NV21
 YUV_MATRIX = {"bt601": 0, "bt601f": 1, "bt709": 2, "bt709f": 3}  # MI355_YUV_BT601, _BT601_FULL, _BT709, _BT709_FULL
 
+
+
+class FramePlanar(C.Structure):
+    """mi355_frame_planar: one entry of the frame table of mi355_frames_planar_letterbox_minmax / _quantize (plane: DEVICE pointers)."""
+    _fields_ = [("plane", C.c_void_p * 3), ("w", C.c_int), ("h", C.c_int), ("pitch", C.c_int * 3), ("format", C.c_int),
+                ("matrix", C.c_int), ("reserved", C.c_int * 3)]
+
+
+PLANAR_FORMAT = {"i420": 0, "yv12": 1, "i422": 2, "i444": 3, "rgb": 4, "bgr": 5}  # MI355_PLANAR_I420 .. MI355_PLANAR_BGR
+
 _shim = None
 _host = None
 
@@ -127,6 +137,8 @@ def shim():
         L.mi355_frames_u8_letterbox_quantize.argtypes = [vp, C.POINTER(FrameU8), ci, ci, ci, vp, vp, vp, vp]
         L.mi355_frames_yuv_letterbox_minmax.argtypes = [vp, C.POINTER(FrameYUV), ci, ci, ci, vp, vp]
         L.mi355_frames_yuv_letterbox_quantize.argtypes = [vp, C.POINTER(FrameYUV), ci, ci, ci, vp, vp, vp, vp]
+        L.mi355_frames_planar_letterbox_minmax.argtypes = [vp, C.POINTER(FramePlanar), ci, ci, ci, vp, vp]
+        L.mi355_frames_planar_letterbox_quantize.argtypes = [vp, C.POINTER(FramePlanar), ci, ci, ci, vp, vp, vp, vp]
         L.mi355_yolo_detections_sizes.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, C.c_float, ci, vp, ci, vp, vp]
         _shim = L
     return _shim
@@ -359,6 +371,8 @@ def host():
         L.network_frames_u8_input_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, ci]
         L.network_frames_nv12_input_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci),
                                                     C.POINTER(ci), ci, ci, ci]
+        L.network_frames_planar_input_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(ci), C.POINTER(ci),
+                                                      C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, ci, ci]
         L.quantization_prep_host.argtypes = [vp, C.c_float, C.c_uint8]
         L.forward_network_gpu.argtypes = [vp]
         L.network_predict.restype = vp
@@ -597,6 +611,53 @@ class Net:
             keep += [y, uv]
             ys[b], uvs[b], hs[b], ws[b], py[b], puv[b] = y.ctypes.data, uv.ctypes.data, h, w, y.strides[0], uv.strides[0]
         self.H.network_frames_nv12_input_gpu(self.h, ys, uvs, ws, hs, py, puv, YUV_LAYOUT[layout], YUV_MATRIX[matrix], int(on_device))
+        return self._prepared(self._pull_input())
+
+    def prepare_from_frames_planar(self, frames, format="i420", matrix="bt601", on_device=False):
+        """Planar frame input path (network_frames_planar_input_gpu): frames[b] is a tuple of three 2-D uint8 arrays in the order
+        `format` names them -- "i420": (Y, U, V), "yv12": (Y, V, U), chroma [(h + 1) // 2][(w + 1) // 2]; "i422": (Y, U, V), chroma
+        [h][(w + 1) // 2]; "i444": (Y, U, V), "rgb": (R, G, B), "bgr": (B, G, R), all [h][w].  For "rgb" / "bgr" a single [3][h][w]
+        array is accepted too and split along axis 0.  The planes go up as they are; the YUV formats are converted with `matrix` =
+        "bt601" | "bt601f" | "bt709" | "bt709f" on the device, inside the letterbox (leave it at its default with "rgb" / "bgr").
+        A plane's row stride is passed through as its pitch where the row's bytes are contiguous and the stride is at least the row
+        (anything else is copied first).  on_device: frames[b] is (ptr0, ptr1, ptr2, w, h, pitch0, pitch1, pitch2) with device
+        addresses instead, used in place -- or, for "rgb" / "bgr", a uint8 [3][h][w] device tensor (anything with data_ptr(), shape
+        and stride(), as a torch tensor has) whose rows are contiguous; the work that wrote it must have finished, and its memory
+        must belong to the HIP runtime this library is linked to.  Returns what prepare_from_frames_u8 returns."""
+        assert len(frames) == self.batch
+        B = self.batch
+        rgb = format in ("rgb", "bgr")
+        keep = []
+        ptr = [(C.c_void_p * B)() for _ in range(3)]
+        pitch = [(C.c_int * B)() for _ in range(3)]
+        ws, hs = (C.c_int * B)(), (C.c_int * B)()
+        for b, f in enumerate(frames):
+            if on_device:
+                if hasattr(f, "data_ptr"):
+                    if not rgb or tuple(f.shape[:1]) != (3,) or len(f.shape) != 3 or f.element_size() != 1 or f.stride(2) != 1 or f.stride(1) < f.shape[2]:
+                        raise ValueError("prepare_from_frames_planar: a device tensor must be uint8 [3][h][w] with contiguous rows, format rgb / bgr")
+                    f = tuple(f.data_ptr() + k * f.stride(0) for k in range(3)) + (f.shape[2], f.shape[1]) + (f.stride(1),) * 3
+                ptr[0][b], ptr[1][b], ptr[2][b], ws[b], hs[b], pitch[0][b], pitch[1][b], pitch[2][b] = f
+                continue
+            planes = [np.asarray(a) for a in f] if isinstance(f, (tuple, list)) else np.asarray(f)
+            if not isinstance(planes, list):
+                if not rgb or planes.ndim != 3 or planes.shape[0] != 3:
+                    raise ValueError("prepare_from_frames_planar: a single array must be [3][h][w], format rgb / bgr")
+                planes = [planes[k] for k in range(3)]
+            if len(planes) != 3 or any(a.dtype != np.uint8 or a.ndim != 2 for a in planes):
+                raise ValueError("prepare_from_frames_planar: every frame must be three 2-D uint8 arrays")
+            h, w = planes[0].shape
+            chroma = (h, w) if rgb or format == "i444" else ((h, (w + 1) // 2) if format == "i422" else ((h + 1) // 2, (w + 1) // 2))
+            if planes[1].shape != chroma or planes[2].shape != chroma:
+                raise ValueError(f"prepare_from_frames_planar: planes 1 and 2 of a {w} x {h} {format} frame must be {chroma[1]} x {chroma[0]}")
+            for k, a in enumerate(planes):
+                if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+                    a = np.ascontiguousarray(a)
+                keep.append(a)
+                ptr[k][b], pitch[k][b] = a.ctypes.data, a.strides[0]
+            hs[b], ws[b] = h, w
+        self.H.network_frames_planar_input_gpu(self.h, ptr[0], ptr[1], ptr[2], ws, hs, pitch[0], pitch[1], pitch[2],
+                                               PLANAR_FORMAT[format], YUV_MATRIX[matrix], int(on_device))
         return self._prepared(self._pull_input())
 
     def push_input(self, x_u8):

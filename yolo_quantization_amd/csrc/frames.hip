@@ -11,6 +11,10 @@
 // NV12 / NV21 frames (mi355_frames_yuv_letterbox_minmax / _quantize) go through the same two kernel bodies with another source: the
 // bytes of a source pixel are converted from (Y, U, V) in registers at every bilinear tap, with the integer formulas of the header
 // (mi355_frame_yuv), and from there on every expression is the interleaved path's.  No RGB frame is written anywhere.
+//
+// Frames of three separate planes (mi355_frames_planar_letterbox_minmax / _quantize: I420, YV12, I422, I444, planar RGB / BGR) are the
+// third source: the YUV formats share the NV12 source's tap walk and arithmetic with their own chroma shifts, the RGB formats take
+// their bytes as they are.
 #include "kargs.h"
 
 // letterbox_launch's geometry (glue.hip), shared by the host-side validation and the kernels: one function compiled for both sides, so
@@ -69,20 +73,76 @@ static __constant__ int yuv_matrix[4][6] = {{16, 76309, 104597, 25675, 53279, 13
                                             {16, 76309, 117489, 13975, 34925, 138438},
                                             {0, 65536, 103206, 12276, 30679, 121609}};
 
+// The frame's matrix: uniform over the workgroup, read once from the constant table
+struct YuvMatrix {
+    int yoff, cy, crv, cgu, cgv, cbu;
+    __device__ explicit YuvMatrix(int id)
+    {
+        const int *m = yuv_matrix[id];
+        yoff = m[0]; cy = m[1]; crv = m[2]; cgu = m[3]; cgv = m[4]; cbu = m[5];
+    }
+};
+
+__device__ static inline void copy3(int d[3], const int a[3]) { d[0] = a[0]; d[1] = a[1]; d[2] = a[2]; }
+__device__ static inline uint8_t clamp8(int x) { return (uint8_t)(x < 0 ? 0 : (x > 255 ? 255 : x)); }
+
+// the three chroma terms of one (U, V) sample: what R, G and B add to the luma term, the rounding constant included
+__device__ static inline void yuv_chroma_terms(const YuvMatrix &m, int ub, int vb, int t[3])
+{
+    const int u = ub - 128, v = vb - 128;
+    t[0] = m.crv * v + 32768;
+    t[1] = 32768 - m.cgu * u - m.cgv * v;
+    t[2] = m.cbu * u + 32768;
+}
+
+// int32 throughout, >> is the arithmetic shift; |luma term| < 2^25 and |chroma term| < 2^25: no overflow
+__device__ static inline void yuv_rgb(const YuvMatrix &m, int luma, const int t[3], uint8_t out[3])
+{
+    const int yy = m.cy * (luma - m.yoff);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = clamp8((yy + t[k]) >> 16);
+}
+
+// The taps of a YUV source whose chroma sample of pixel (x, y) lies at (x >> sx, y >> sy), sx, sy in {0, 1}.  Columns ix, ix + 1 share
+// a sample when sx = 1 and ix is even, rows iy, iy + 1 when sy = 1 and iy is even: a sample is loaded once; with a shift of 0 the
+// neighbouring tap always has its own.  Src: y, pitch_y, m and chroma(cx, cy, t), the terms of the sample at (cx, cy).
+template <class Src>
+__device__ static inline void yuv_taps(const Src &s, int sx, int sy, int ix, int iy, bool two_x, bool two_y, uint8_t p[2][2][3])
+{
+    const bool next_cx = two_x && (ix & sx) == sx, next_cy = two_y && (iy & sy) == sy;
+    const int cx = ix >> sx, cyy = iy >> sy;
+    int t[2][2][3];
+    s.chroma(cx, cyy, t[0][0]);
+    if (next_cx) s.chroma(cx + 1, cyy, t[0][1]);
+    else copy3(t[0][1], t[0][0]);
+    if (next_cy) {
+        s.chroma(cx, cyy + 1, t[1][0]);
+        if (next_cx) s.chroma(cx + 1, cyy + 1, t[1][1]);
+        else copy3(t[1][1], t[1][0]);
+    } else {
+        copy3(t[1][0], t[0][0]);
+        copy3(t[1][1], t[0][1]);
+    }
+    const uint8_t *row = s.y + (size_t)iy * s.pitch_y + ix;
+#pragma unroll
+    for (int r = 0; r < 2; ++r, row += s.pitch_y) {
+        if (r == 1 && !two_y) break;
+        yuv_rgb(s.m, row[0], t[r][0], p[r][0]);
+        if (two_x) yuv_rgb(s.m, row[1], t[r][1], p[r][1]);
+    }
+}
+
 struct SourceYUV {
     const uint8_t *y, *uv;
     int w, h, pitch_y, pitch_uv;
     int iu, iv;        // position of U and V inside a chroma pair: (0, 1) NV12, (1, 0) NV21
     bool pair_aligned; // every chroma pair starts at an even address: one 2-byte load serves it
-    int yoff, cy, crv, cgu, cgv, cbu;  // the frame's matrix: uniform over the workgroup, read once from the constant table
+    YuvMatrix m;
     __device__ explicit SourceYUV(const mi355_frame_yuv &f)
         : y(f.y), uv(f.uv), w(f.w), h(f.h), pitch_y(f.pitch_y), pitch_uv(f.pitch_uv), iu(f.layout == MI355_YUV_NV21 ? 1 : 0),
-          iv(f.layout == MI355_YUV_NV21 ? 0 : 1), pair_aligned(((reinterpret_cast<size_t>(f.uv) | (size_t)f.pitch_uv) & 1) == 0)
-    {
-        const int *m = yuv_matrix[f.matrix];
-        yoff = m[0]; cy = m[1]; crv = m[2]; cgu = m[3]; cgv = m[4]; cbu = m[5];
-    }
-    // the three chroma terms of the pair at (cx, cy): what R, G and B add to the luma term, the rounding constant included
+          iv(f.layout == MI355_YUV_NV21 ? 0 : 1), pair_aligned(((reinterpret_cast<size_t>(f.uv) | (size_t)f.pitch_uv) & 1) == 0),
+          m(f.matrix) {}
+    // the chroma terms of the pair at (cx, cy)
     __device__ void chroma(int cx, int cyy, int t[3]) const
     {
         const uint8_t *p = uv + (size_t)cyy * pitch_uv + 2 * (size_t)cx;
@@ -93,43 +153,53 @@ struct SourceYUV {
         } else {
             b[0] = p[0]; b[1] = p[1];
         }
-        const int u = b[iu] - 128, v = b[iv] - 128;
-        t[0] = crv * v + 32768;
-        t[1] = 32768 - cgu * u - cgv * v;
-        t[2] = cbu * u + 32768;
+        yuv_chroma_terms(m, b[iu], b[iv], t);
     }
-    __device__ static void copy3(int d[3], const int a[3]) { d[0] = a[0]; d[1] = a[1]; d[2] = a[2]; }
-    __device__ static uint8_t clamp8(int x) { return (uint8_t)(x < 0 ? 0 : (x > 255 ? 255 : x)); }
-    // int32 throughout, >> is the arithmetic shift; |luma term| < 2^25 and |chroma term| < 2^25: no overflow
-    __device__ void rgb(int luma, const int t[3], uint8_t out[3]) const
+    __device__ void taps(int ix, int iy, bool two_x, bool two_y, uint8_t p[2][2][3]) const { yuv_taps(*this, 1, 1, ix, iy, two_x, two_y, p); }
+};
+
+// Three separate planes (mi355_frame_planar).  YUV formats: y = plane Y, u / v the chroma planes whichever order the format names
+// them in, sampled at (x >> sx, y >> sy).  RGB formats: y, u, v hold the planes of R, G, B and their bytes are the pixel's.  The
+// format is uniform over the workgroup, so its branches do not diverge.
+struct SourcePlanar {
+    const uint8_t *y, *u, *v;
+    int w, h, pitch_y, pitch_u, pitch_v;
+    int sx, sy;
+    bool rgb;
+    YuvMatrix m;
+    __device__ explicit SourcePlanar(const mi355_frame_planar &f)
+        : w(f.w), h(f.h), sx(f.format == MI355_PLANAR_I420 || f.format == MI355_PLANAR_YV12 || f.format == MI355_PLANAR_I422 ? 1 : 0),
+          sy(f.format == MI355_PLANAR_I420 || f.format == MI355_PLANAR_YV12 ? 1 : 0),
+          rgb(f.format == MI355_PLANAR_RGB || f.format == MI355_PLANAR_BGR), m(f.matrix)
     {
-        const int yy = cy * (luma - yoff);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) out[k] = clamp8((yy + t[k]) >> 16);
+        // the plane that serves (y | R), (u | G), (v | B): YV12 names V before U, BGR names B first
+        const int iy = f.format == MI355_PLANAR_BGR ? 2 : 0, iv = f.format == MI355_PLANAR_YV12 ? 1 : (f.format == MI355_PLANAR_BGR ? 0 : 2);
+        const int iu = 3 - iy - iv;
+        y = f.plane[iy]; pitch_y = f.pitch[iy];
+        u = f.plane[iu]; pitch_u = f.pitch[iu];
+        v = f.plane[iv]; pitch_v = f.pitch[iv];
+    }
+    // the chroma terms of the sample at (cx, cy): one byte from each chroma plane
+    __device__ void chroma(int cx, int cyy, int t[3]) const
+    {
+        yuv_chroma_terms(m, u[(size_t)cyy * pitch_u + cx], v[(size_t)cyy * pitch_v + cx], t);
     }
     __device__ void taps(int ix, int iy, bool two_x, bool two_y, uint8_t p[2][2][3]) const
     {
-        // columns ix, ix + 1 share a chroma pair when ix is even, rows iy, iy + 1 when iy is even: a pair is loaded once
-        const bool next_cx = two_x && (ix & 1), next_cy = two_y && (iy & 1);
-        const int cx = ix >> 1, cyy = iy >> 1;
-        int t[2][2][3];
-        chroma(cx, cyy, t[0][0]);
-        if (next_cx) chroma(cx + 1, cyy, t[0][1]);
-        else copy3(t[0][1], t[0][0]);
-        if (next_cy) {
-            chroma(cx, cyy + 1, t[1][0]);
-            if (next_cx) chroma(cx + 1, cyy + 1, t[1][1]);
-            else copy3(t[1][1], t[1][0]);
-        } else {
-            copy3(t[1][0], t[0][0]);
-            copy3(t[1][1], t[0][1]);
+        if (!rgb) {
+            yuv_taps(*this, sx, sy, ix, iy, two_x, two_y, p);
+            return;
         }
-        const uint8_t *row = y + (size_t)iy * pitch_y + ix;
+        const uint8_t *row[3] = {y + (size_t)iy * pitch_y + ix, u + (size_t)iy * pitch_u + ix, v + (size_t)iy * pitch_v + ix};
+        const int pitch[3] = {pitch_y, pitch_u, pitch_v};
 #pragma unroll
-        for (int r = 0; r < 2; ++r, row += pitch_y) {
-            if (r == 1 && !two_y) break;
-            rgb(row[0], t[r][0], p[r][0]);
-            if (two_x) rgb(row[1], t[r][1], p[r][1]);
+        for (int k = 0; k < 3; ++k) {
+            p[0][0][k] = row[k][0];
+            if (two_x) p[0][1][k] = row[k][1];
+            if (two_y) {
+                p[1][0][k] = row[k][pitch[k]];
+                if (two_x) p[1][1][k] = row[k][pitch[k] + 1];
+            }
         }
     }
 };
@@ -169,7 +239,7 @@ __device__ static inline void letterbox_px3(const Source &f, const FrameGeo &g, 
 }
 
 // grid: (workgroups per image, B).  mm[2 b] = max(x, +0), mm[2 b + 1] = min(x, -0) as in image_minmax_batched_kernel (seeded before).
-// One body for both sources; lut: the workgroup's 256-entry byte table.
+// One body for every source; lut: the workgroup's 256-entry byte table.
 template <class Source, class Frame>
 __device__ static inline void letterbox_minmax_body(const Frame *table, int w, int h, uint32_t *mm, float *lut)
 {
@@ -211,6 +281,12 @@ __global__ __launch_bounds__(256) void frames_yuv_letterbox_minmax_kernel(const 
 {
     __shared__ float lut[256];
     letterbox_minmax_body<SourceYUV>(table, w, h, mm, lut);
+}
+
+__global__ __launch_bounds__(256) void frames_planar_letterbox_minmax_kernel(const mi355_frame_planar *table, int w, int h, uint32_t *mm)
+{
+    __shared__ float lut[256];
+    letterbox_minmax_body<SourcePlanar>(table, w, h, mm, lut);
 }
 
 // grid: (workgroups per image, B); a thread serves four neighbouring x of one row in all three planes: one 4-byte store per plane
@@ -268,6 +344,13 @@ __global__ __launch_bounds__(256) void frames_yuv_letterbox_quantize_kernel(cons
     letterbox_quantize_body<SourceYUV>(table, w, h, scale_dev, zp_dev, out, lut);
 }
 
+__global__ __launch_bounds__(256) void frames_planar_letterbox_quantize_kernel(const mi355_frame_planar *table, int w, int h,
+                                                                               const float *scale_dev, const uint8_t *zp_dev, uint8_t *out)
+{
+    __shared__ float lut[256];
+    letterbox_quantize_body<SourcePlanar>(table, w, h, scale_dev, zp_dev, out, lut);
+}
+
 // Host-side check of the table's host mirror, before anything is launched: NULL when every frame can be served, else what is wrong.
 const char *frames_u8_check(const mi355_frame_u8 *host, int B, int w, int h)
 {
@@ -299,6 +382,27 @@ const char *frames_yuv_check(const mi355_frame_yuv *host, int B, int w, int h)
         if (f.matrix < MI355_YUV_BT601 || f.matrix > MI355_YUV_BT709_FULL) return "frames_yuv: unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)";
         FrameGeo g;
         if (!frame_geometry(f.w, f.h, w, h, g)) return "frames_yuv: degenerate aspect (resized side < 2)";
+    }
+    return nullptr;
+}
+
+const char *frames_planar_check(const mi355_frame_planar *host, int B, int w, int h)
+{
+    if (!host || B <= 0 || B > 65535) return "frames_planar: null table / need 1 <= B <= 65535";
+    if (w < 2 || h < 2 || w > 32768 || h > 32768) return "frames_planar: need 2 <= w, h <= 32768 for the network input";
+    for (int b = 0; b < B; ++b) {
+        const mi355_frame_planar &f = host[b];
+        if (!f.plane[0] || !f.plane[1] || !f.plane[2]) return "frames_planar: null plane pointer";
+        if (f.w < 1 || f.h < 1 || f.w > 32768 || f.h > 32768) return "frames_planar: need 1 <= w, h <= 32768 for every frame";
+        if (f.format < MI355_PLANAR_I420 || f.format > MI355_PLANAR_BGR) return "frames_planar: unknown format (MI355_PLANAR_I420 .. _BGR)";
+        if (f.matrix < MI355_YUV_BT601 || f.matrix > MI355_YUV_BT709_FULL) return "frames_planar: unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)";
+        const bool rgb = f.format == MI355_PLANAR_RGB || f.format == MI355_PLANAR_BGR;
+        if (rgb && f.matrix != 0) return "frames_planar: matrix must be 0 with MI355_PLANAR_RGB / _BGR";
+        const int cw = rgb || f.format == MI355_PLANAR_I444 ? f.w : (f.w + 1) / 2;  // the width of planes 1 and 2
+        if (f.pitch[0] < f.w) return "frames_planar: pitch[0] < w";
+        if (f.pitch[1] < cw || f.pitch[2] < cw) return "frames_planar: pitch[1] or pitch[2] below the width of its plane";
+        FrameGeo g;
+        if (!frame_geometry(f.w, f.h, w, h, g)) return "frames_planar: degenerate aspect (resized side < 2)";
     }
     return nullptr;
 }
@@ -343,6 +447,21 @@ int frames_yuv_letterbox_quantize_launch(const mi355_frame_yuv *table_dev, int B
                                          const uint8_t *zp_dev, uint8_t *out, hipStream_t st)
 {
     hipLaunchKernelGGL(frames_yuv_letterbox_quantize_kernel, dim3(quantize_grid_x(w, h), B), dim3(256), 0, st, table_dev, w, h,
+                       scale_dev, zp_dev, out);
+    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
+}
+
+int frames_planar_letterbox_minmax_launch(const mi355_frame_planar *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st)
+{
+    if (image_minmax_seed_launch(mm, B, st) != MI355_OK) return MI355_EHIP;
+    hipLaunchKernelGGL(frames_planar_letterbox_minmax_kernel, dim3(minmax_grid_x(B, w, h), B), dim3(256), 0, st, table_dev, w, h, mm);
+    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
+}
+
+int frames_planar_letterbox_quantize_launch(const mi355_frame_planar *table_dev, int B, int w, int h, const float *scale_dev,
+                                            const uint8_t *zp_dev, uint8_t *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(frames_planar_letterbox_quantize_kernel, dim3(quantize_grid_x(w, h), B), dim3(256), 0, st, table_dev, w, h,
                        scale_dev, zp_dev, out);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }

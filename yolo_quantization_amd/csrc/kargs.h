@@ -247,6 +247,10 @@ const char *frames_yuv_check(const mi355_frame_yuv *host, int B, int w, int h);
 int frames_yuv_letterbox_minmax_launch(const mi355_frame_yuv *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st);
 int frames_yuv_letterbox_quantize_launch(const mi355_frame_yuv *table_dev, int B, int w, int h, const float *scale_dev,
                                          const uint8_t *zp_dev, uint8_t *out, hipStream_t st);
+const char *frames_planar_check(const mi355_frame_planar *host, int B, int w, int h);
+int frames_planar_letterbox_minmax_launch(const mi355_frame_planar *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st);
+int frames_planar_letterbox_quantize_launch(const mi355_frame_planar *table_dev, int B, int w, int h, const float *scale_dev,
+                                            const uint8_t *zp_dev, uint8_t *out, hipStream_t st);
 int yolo_detections_sizes_launch(const float *out, int B, int n, int classes, int h, int w, const float *biases, const int *mask,
                                  int netw, int neth, const int *imw_dev, const int *imh_dev, float thresh, int relative, float *recs,
                                  int max_recs, int *counts, hipStream_t st);

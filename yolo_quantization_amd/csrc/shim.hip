@@ -1081,6 +1081,24 @@ int mi355_frames_yuv_letterbox_quantize(const mi355_frame_yuv *table_dev, const 
     return frames_yuv_letterbox_quantize_launch(table_dev, B, w, h, scale_dev, zp_dev, out_u8, (hipStream_t)stream);
 }
 
+int mi355_frames_planar_letterbox_minmax(const mi355_frame_planar *table_dev, const mi355_frame_planar *table_host, int B, int w, int h,
+                                         float *minmax, void *stream)
+{
+    if (!table_dev || !minmax) return einval("frames_planar: letterbox_minmax: null");
+    const char *why = frames_planar_check(table_host, B, w, h);
+    if (why) return einval(why);
+    return frames_planar_letterbox_minmax_launch(table_dev, B, w, h, reinterpret_cast<uint32_t *>(minmax), (hipStream_t)stream);
+}
+
+int mi355_frames_planar_letterbox_quantize(const mi355_frame_planar *table_dev, const mi355_frame_planar *table_host, int B, int w, int h,
+                                           const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream)
+{
+    if (!table_dev || !scale_dev || !zp_dev || !out_u8) return einval("frames_planar: letterbox_quantize: null");
+    const char *why = frames_planar_check(table_host, B, w, h);
+    if (why) return einval(why);
+    return frames_planar_letterbox_quantize_launch(table_dev, B, w, h, scale_dev, zp_dev, out_u8, (hipStream_t)stream);
+}
+
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream)
 {
     if (!buf || !sum_dev || dwords < 0) return einval("checksum: null");

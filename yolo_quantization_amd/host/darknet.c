@@ -26,6 +26,8 @@
  * -frames nv12 | nv21 [-matrix bt601|bt601f|bt709|bt709f] (every source is a raw video frame in a file named <anything>_<W>x<H>.nv12:
  * W * H luma bytes, then the interleaved half-resolution chroma plane; both planes go up as they are and are converted inside the
  * letterbox, network_frames_nv12_input_gpu; the output is that of -frames u8 on the converted RGB frame).
+ * -frames i420 | yv12 | i422 | i444 [-matrix ...] (the same for raw frames of three tightly packed planes, as software decoders write
+ * them, in files named <anything>_<W>x<H>.<format>; network_frames_planar_input_gpu).
  *
  * Image input: binary PPM (P6) of ANY size (letterboxed like the reference does), a raw `.u8` file holding [c][h][w] bytes at
  * network size, or `synthetic:<seed>`.  JPEG/PNG decoding is third-party code in the reference (stb_image, SURVEY.md 2
@@ -38,6 +40,7 @@
 #include <string.h>
 #include "darknet_q.h"
 #include "nv12_file.h"
+#include "planar_file.h"
 
 static int find_arg(int argc, char **argv, const char *arg)
 {
@@ -132,6 +135,17 @@ static uint8_t *load_frame_nv12(const char *path, int *w, int *h)
     return raw;
 }
 
+/* -frames i420 / yv12 / i422 / i444: the file's three planes, p[k] pointing into the returned bytes */
+static uint8_t *load_frame_planar(const char *path, int format, int *w, int *h, const uint8_t *p[3])
+{
+    char why[1024];
+    size_t bytes[2];
+    uint8_t *raw = load_planar_file(path, format, w, h, bytes, why, sizeof(why));
+    if (!raw) error(why);
+    p[0] = raw; p[1] = raw + bytes[0]; p[2] = p[1] + bytes[1];
+    return raw;
+}
+
 static void dump_layer(const char *dir, network *net, int i)
 {
     layer *l = &net->layers[i];
@@ -161,6 +175,8 @@ typedef struct {
     int frames_u8;         /* -frames u8: sources go up as interleaved bytes (network_frames_u8_input_gpu), no host float conversion */
     int frames_yuv;        /* -frames nv12 | nv21: sources are raw _<W>x<H>.nv12 files (network_frames_nv12_input_gpu) */
     int yuv_layout, yuv_matrix; /* MI355_YUV_NV12 / _NV21, MI355_YUV_BT601 .. _BT709_FULL (-matrix) */
+    int frames_planar;     /* -frames i420 | yv12 | i422 | i444: raw _<W>x<H>.<format> files (network_frames_planar_input_gpu) */
+    int planar_format;     /* MI355_PLANAR_I420 .. MI355_PLANAR_I444 */
     float thresh, hier_thresh;
     int batch, accum, store, use_graph, iters, gpu, boxes, quiet, inflight;
     int rank, nranks;      /* -gpus with -bcast: this replica's rank; rank 0 reads the weights file, the others receive blobs */
@@ -217,7 +233,20 @@ static void test_detector_list(detect_job *job, network *net, char **names, int 
     int *imw = calloc((size_t)B, sizeof(int)), *imh = calloc((size_t)B, sizeof(int));
     for (int first = 0; first < np; first += B) {
         const int cnt = np - first < B ? np - first : B;
-        if (job->frames_yuv) { /* the batch's raw video frames, one call for the whole input step */
+        if (job->frames_planar) { /* the batch's raw planar frames, one call for the whole input step */
+            uint8_t **fr = calloc((size_t)B, sizeof(uint8_t *));
+            const uint8_t **pl[3];
+            for (int k = 0; k < 3; ++k) pl[k] = calloc((size_t)B, sizeof(uint8_t *));
+            for (int b = 0; b < B; ++b) {
+                const uint8_t *p[3];
+                fr[b] = load_frame_planar(paths[first + (b < cnt ? b : cnt - 1)], job->planar_format, &imw[b], &imh[b], p);
+                for (int k = 0; k < 3; ++k) pl[k][b] = p[k];
+            }
+            network_frames_planar_input_gpu(net, pl[0], pl[1], pl[2], imw, imh, NULL, NULL, NULL, job->planar_format, job->yuv_matrix, 0);
+            for (int b = 0; b < B; ++b) free(fr[b]);
+            for (int k = 0; k < 3; ++k) free(pl[k]);
+            free(fr);
+        } else if (job->frames_yuv) { /* the batch's raw video frames, one call for the whole input step */
             uint8_t **fr = calloc((size_t)B, sizeof(uint8_t *));
             const uint8_t **uv = calloc((size_t)B, sizeof(uint8_t *));
             for (int b = 0; b < B; ++b) {
@@ -309,7 +338,17 @@ static void test_detector(detect_job *job)
     }
     image im = {0, 0, 0, NULL};
     float *im_gpu = NULL;
-    if (job->frames_yuv) { /* the raw video frame in every batch slot (it goes up once), one call for the whole input step */
+    if (job->frames_planar) { /* the raw planar frame in every batch slot (it goes up once), one call for the whole input step */
+        if (mi355_init(job->gpu)) { fprintf(stderr, "MI355: %s\n", mi355_last_error()); error("mi355_init (this build has no CPU data path)"); }
+        const uint8_t *p[3], **pl[3];
+        uint8_t *raw = load_frame_planar(job->filename, job->planar_format, &im.w, &im.h, p);
+        int *fw = calloc((size_t)job->batch, sizeof(int)), *fh = calloc((size_t)job->batch, sizeof(int));
+        for (int k = 0; k < 3; ++k) pl[k] = calloc((size_t)job->batch, sizeof(uint8_t *));
+        for (int b = 0; b < job->batch; ++b) { for (int k = 0; k < 3; ++k) pl[k][b] = p[k]; fw[b] = im.w; fh[b] = im.h; }
+        network_frames_planar_input_gpu(net, pl[0], pl[1], pl[2], fw, fh, NULL, NULL, NULL, job->planar_format, job->yuv_matrix, 0);
+        for (int k = 0; k < 3; ++k) free(pl[k]);
+        free(fw); free(fh); free(raw);
+    } else if (job->frames_yuv) { /* the raw video frame in every batch slot (it goes up once), one call for the whole input step */
         if (mi355_init(job->gpu)) { fprintf(stderr, "MI355: %s\n", mi355_last_error()); error("mi355_init (this build has no CPU data path)"); }
         uint8_t *raw = load_frame_nv12(job->filename, &im.w, &im.h);
         const uint8_t **fy = calloc((size_t)job->batch, sizeof(uint8_t *)), **fuv = calloc((size_t)job->batch, sizeof(uint8_t *));
@@ -388,7 +427,7 @@ int main(int argc, char **argv)
     if (argc < 2) {
         fprintf(stderr, "usage: %s detector test <data> <cfg> <weights> <image> [-thresh t] [-i gpu | -gpus a,b,..] [-batch B] "
                         "[-accum exact|ref-f32] [-parity wrap|saturate] [-dump dir] [-graph] [-n iters] [-boxes] "
-                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8|nv12|nv21] [-matrix bt601|bt601f|bt709|bt709f]\n", argv[0]);
+                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8|nv12|nv21|i420|yv12|i422|i444] [-matrix bt601|bt601f|bt709|bt709f]\n", argv[0]);
         return 0;
     }
     detect_job job;
@@ -415,8 +454,14 @@ int main(int argc, char **argv)
     const char *matrix_s = find_char_arg(argc, argv, "-matrix", NULL);
     job.frames_u8 = frames_s && 0 == strcmp(frames_s, "u8");
     job.frames_yuv = frames_s && (0 == strcmp(frames_s, "nv12") || 0 == strcmp(frames_s, "nv21"));
-    if (frames_s && !job.frames_u8 && !job.frames_yuv)
-        error("-frames: `u8` (8-bit interleaved frames), `nv12` and `nv21` (raw video frames, files named _<W>x<H>.nv12) are known");
+    static const char *const planar_known[4] = {"i420", "yv12", "i422", "i444"}; /* MI355_PLANAR_I420 .. MI355_PLANAR_I444 */
+    job.frames_planar = 0;
+    job.planar_format = MI355_PLANAR_I420;
+    for (int k = 0; k < 4; ++k)
+        if (frames_s && 0 == strcmp(frames_s, planar_known[k])) { job.frames_planar = 1; job.planar_format = k; }
+    if (frames_s && !job.frames_u8 && !job.frames_yuv && !job.frames_planar)
+        error("-frames: `u8` (8-bit interleaved frames), `nv12` and `nv21` (raw video frames, files named _<W>x<H>.nv12), `i420`, `yv12`, "
+              "`i422` and `i444` (raw planar frames, files named _<W>x<H>.<format>) are known");
     job.yuv_layout = frames_s && 0 == strcmp(frames_s, "nv21") ? MI355_YUV_NV21 : MI355_YUV_NV12;
     job.yuv_matrix = MI355_YUV_BT601;
     if (matrix_s) {
@@ -424,7 +469,7 @@ int main(int argc, char **argv)
         int m = -1;
         for (int k = 0; k < 4; ++k) if (0 == strcmp(matrix_s, known[k])) m = k;
         if (m < 0) error("-matrix: bt601 (the default), bt601f, bt709 and bt709f are known");
-        if (!job.frames_yuv) error("-matrix goes with -frames nv12 | nv21");
+        if (!job.frames_yuv && !job.frames_planar) error("-matrix goes with -frames nv12 | nv21 | i420 | yv12 | i422 | i444");
         job.yuv_matrix = m;
     }
     if (job.iters < 1) job.iters = 1;

@@ -690,26 +690,30 @@ void network_quantize_input_gpu(network *net)
 /* ------------------------------------------------------------------------------------------- 8-bit frame input
  * Two launches for the whole batch (frames.hip): letterbox + min / max, then letterbox + quantise; the float image exists in registers
  * only.  The (scale, zero point) branches are the float path's (input_pair_shared, input_pairs_per_image).  Interleaved RGB / BGR
- * frames and NV12 / NV21 frames differ in their table, their staging and the pair of C-ABI calls; everything else is shared. */
+ * frames, NV12 / NV21 frames and frames of three separate planes differ in their table, their staging and the pair of C-ABI calls;
+ * everything else is shared. */
+enum { FR_U8, FR_YUV, FR_PLANAR }; /* the kind of frames an entry point feeds */
 static void fr_free(network *net)
 {
     if (net->fr_arena_gpu) mi355_free(net->fr_arena_gpu);
     if (net->fr_table_gpu) mi355_free(net->fr_table_gpu);
     if (net->fr_yuv_gpu) mi355_free(net->fr_yuv_gpu);
+    if (net->fr_planar_gpu) mi355_free(net->fr_planar_gpu);
     if (net->fr_mm_gpu) mi355_free(net->fr_mm_gpu);
     if (net->fr_pair_gpu) mi355_free(net->fr_pair_gpu);
-    free(net->fr_table_host); free(net->fr_yuv_host); free(net->fr_mm_host); free(net->fr_pair_host);
+    free(net->fr_table_host); free(net->fr_yuv_host); free(net->fr_planar_host); free(net->fr_mm_host); free(net->fr_pair_host);
     net->fr_arena_gpu = NULL; net->fr_table_gpu = NULL; net->fr_table_host = NULL;
     net->fr_yuv_gpu = NULL; net->fr_yuv_host = NULL;
+    net->fr_planar_gpu = NULL; net->fr_planar_host = NULL;
     net->fr_mm_gpu = net->fr_mm_host = NULL;
     net->fr_pair_gpu = net->fr_pair_host = NULL;
     net->fr_arena_bytes = 0;
     net->fr_cap = 0;
 }
 
-/* The buffers both kinds of frames share, sized by the batch, and the table of the kind that is asked for: a network fed one kind
- * never holds the other's table. */
-static void fr_alloc(network *net, int yuv)
+/* The buffers every kind of frames shares, sized by the batch, and the table of the kind that is asked for: a network fed one kind
+ * never holds another's table. */
+static void fr_alloc(network *net, int kind)
 {
     const size_t B = (size_t)net->batch;
     if (net->fr_cap != net->batch) {
@@ -720,21 +724,24 @@ static void fr_alloc(network *net, int yuv)
         net->fr_pair_host = calloc(5, B);
         net->fr_cap = net->batch;
     }
-    if (yuv && !net->fr_yuv_gpu) {
+    if (kind == FR_PLANAR && !net->fr_planar_gpu) {
+        check_mi355(mi355_alloc((void **)&net->fr_planar_gpu, sizeof(mi355_frame_planar) * B), "alloc frame table");
+        net->fr_planar_host = calloc(B, sizeof(mi355_frame_planar));
+    } else if (kind == FR_YUV && !net->fr_yuv_gpu) {
         check_mi355(mi355_alloc((void **)&net->fr_yuv_gpu, sizeof(mi355_frame_yuv) * B), "alloc frame table");
         net->fr_yuv_host = calloc(B, sizeof(mi355_frame_yuv));
-    } else if (!yuv && !net->fr_table_gpu) {
+    } else if (kind == FR_U8 && !net->fr_table_gpu) {
         check_mi355(mi355_alloc((void **)&net->fr_table_gpu, sizeof(mi355_frame_u8) * B), "alloc frame table");
         net->fr_table_host = calloc(B, sizeof(mi355_frame_u8));
     }
 }
 
-static void fr_begin(network *net, int yuv, const char *not_3_channels)
+static void fr_begin(network *net, int kind, const char *not_3_channels)
 {
     if (net->c != 3) error(not_3_channels);
     check_mi355(mi355_init(net->gpu_index), "mi355_init");
     if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
-    fr_alloc(net, yuv);
+    fr_alloc(net, kind);
 }
 
 static size_t fr_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
@@ -760,11 +767,15 @@ static const uint8_t *fr_stage(network *net, const uint8_t *src, size_t bytes, s
 }
 
 /* The common tail, the host mirror of the table filled with device pointers: table upload, min / max launch, the batch's one host
- * sync, the (scale, zero point) branch, quantiser launch.  yuv: the NV12 / NV21 table and calls instead of the interleaved ones. */
-static void fr_finish(network *net, int yuv)
+ * sync, the (scale, zero point) branch, quantiser launch, with the table and the calls of the frames' kind. */
+static void fr_finish(network *net, int kind)
 {
     const int B = net->batch;
-    if (yuv) {
+    if (kind == FR_PLANAR) {
+        check_mi355(mi355_h2d(net->fr_planar_gpu, net->fr_planar_host, sizeof(mi355_frame_planar) * (size_t)B, net->stream), "upload frame table");
+        check_mi355(mi355_frames_planar_letterbox_minmax(net->fr_planar_gpu, net->fr_planar_host, B, net->w, net->h, net->fr_mm_gpu, net->stream),
+                    "mi355_frames_planar_letterbox_minmax");
+    } else if (kind == FR_YUV) {
         check_mi355(mi355_h2d(net->fr_yuv_gpu, net->fr_yuv_host, sizeof(mi355_frame_yuv) * (size_t)B, net->stream), "upload frame table");
         check_mi355(mi355_frames_yuv_letterbox_minmax(net->fr_yuv_gpu, net->fr_yuv_host, B, net->w, net->h, net->fr_mm_gpu, net->stream),
                     "mi355_frames_yuv_letterbox_minmax");
@@ -792,7 +803,10 @@ static void fr_finish(network *net, int yuv)
         scale_dev = (const float *)net->fr_pair_gpu;
         zp_dev = (const uint8_t *)net->fr_pair_gpu + 4 * (size_t)B;
     }
-    if (yuv)
+    if (kind == FR_PLANAR)
+        check_mi355(mi355_frames_planar_letterbox_quantize(net->fr_planar_gpu, net->fr_planar_host, B, net->w, net->h, scale_dev, zp_dev,
+                                                           net->input_uint8_gpu, net->stream), "mi355_frames_planar_letterbox_quantize");
+    else if (kind == FR_YUV)
         check_mi355(mi355_frames_yuv_letterbox_quantize(net->fr_yuv_gpu, net->fr_yuv_host, B, net->w, net->h, scale_dev, zp_dev,
                                                         net->input_uint8_gpu, net->stream), "mi355_frames_yuv_letterbox_quantize");
     else
@@ -805,7 +819,7 @@ void network_frames_u8_input_gpu(network *net, const uint8_t *const *frames, con
 {
     const int B = net->batch;
     if (!frames || !w || !h) error("network_frames_u8_input_gpu: null frames / sizes");
-    fr_begin(net, 0, "network_frames_u8_input_gpu: 8-bit frames feed 3-channel networks only");
+    fr_begin(net, FR_U8, "network_frames_u8_input_gpu: 8-bit frames feed 3-channel networks only");
     mi355_frame_u8 *tab = net->fr_table_host;
     size_t need = 0;
     for (int b = 0; b < B; ++b) {
@@ -829,7 +843,7 @@ void network_frames_u8_input_gpu(network *net, const uint8_t *const *frames, con
             tab[b].data = fr_stage(net, frames[b], bytes, &off);
         }
     }
-    fr_finish(net, 0);
+    fr_finish(net, FR_U8);
 }
 
 void network_frames_nv12_input_gpu(network *net, const uint8_t *const *y, const uint8_t *const *uv, const int *w, const int *h,
@@ -837,7 +851,7 @@ void network_frames_nv12_input_gpu(network *net, const uint8_t *const *y, const 
 {
     const int B = net->batch;
     if (!y || !uv || !w || !h) error("network_frames_nv12_input_gpu: null planes / sizes");
-    fr_begin(net, 1, "network_frames_nv12_input_gpu: NV12 / NV21 frames feed 3-channel networks only");
+    fr_begin(net, FR_YUV, "network_frames_nv12_input_gpu: NV12 / NV21 frames feed 3-channel networks only");
     mi355_frame_yuv *tab = net->fr_yuv_host;
     size_t need = 0;
     for (int b = 0; b < B; ++b) {
@@ -867,7 +881,60 @@ void network_frames_nv12_input_gpu(network *net, const uint8_t *const *y, const 
             tab[b].uv = fr_stage(net, uv[b], (size_t)(ch - 1) * (size_t)tab[b].pitch_uv + (size_t)cw2, &off);
         }
     }
-    fr_finish(net, 1);
+    fr_finish(net, FR_YUV);
+}
+
+void network_frames_planar_input_gpu(network *net, const uint8_t *const *p0, const uint8_t *const *p1, const uint8_t *const *p2,
+                                     const int *w, const int *h, const int *pitch0, const int *pitch1, const int *pitch2,
+                                     int format, int matrix, int frames_on_device)
+{
+    const int B = net->batch;
+    const uint8_t *const *const planes[3] = {p0, p1, p2};
+    const int *const pitches[3] = {pitch0, pitch1, pitch2};
+    if (!p0 || !p1 || !p2 || !w || !h) error("network_frames_planar_input_gpu: null planes / sizes");
+    if (format < MI355_PLANAR_I420 || format > MI355_PLANAR_BGR) error("network_frames_planar_input_gpu: unknown format (MI355_PLANAR_I420 .. _BGR)");
+    if (matrix < MI355_YUV_BT601 || matrix > MI355_YUV_BT709_FULL) error("network_frames_planar_input_gpu: unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)");
+    const int rgb = format == MI355_PLANAR_RGB || format == MI355_PLANAR_BGR;
+    if (rgb && matrix != 0) error("network_frames_planar_input_gpu: matrix must be 0 with MI355_PLANAR_RGB / _BGR");
+    const int half_w = !rgb && format != MI355_PLANAR_I444, half_h = format == MI355_PLANAR_I420 || format == MI355_PLANAR_YV12;
+    if (net->c != 3) error("network_frames_planar_input_gpu: planar frames feed 3-channel networks only");
+    for (int b = 0; b < B; ++b) { /* every refusal comes before the device is touched */
+        if (!p0[b] || !p1[b] || !p2[b]) error("network_frames_planar_input_gpu: null plane");
+        if (w[b] < 1 || h[b] < 1 || w[b] > 32768 || h[b] > 32768) error("network_frames_planar_input_gpu: need 1 <= w, h <= 32768 for every frame");
+        for (int k = 0; k < 3; ++k)
+            if (pitches[k] && pitches[k][b] < (k && half_w ? (w[b] + 1) / 2 : w[b]))
+                error("network_frames_planar_input_gpu: need pitch >= the width of its plane for every plane");
+    }
+    fr_begin(net, FR_PLANAR, "network_frames_planar_input_gpu: planar frames feed 3-channel networks only");
+    mi355_frame_planar *tab = net->fr_planar_host;
+    size_t need = 0;
+    for (int b = 0; b < B; ++b) {
+        memset(&tab[b], 0, sizeof(tab[b]));
+        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].format = format; tab[b].matrix = matrix;
+        for (int k = 0; k < 3; ++k) { /* plane 0 is w x h, planes 1 and 2 the format's chroma size */
+            const int pw = k && half_w ? (w[b] + 1) / 2 : w[b], ph = k && half_h ? (h[b] + 1) / 2 : h[b];
+            const int p = pitches[k] ? pitches[k][b] : pw;
+            tab[b].plane[k] = planes[k][b]; tab[b].pitch[k] = p;
+            need += fr_round((size_t)(ph - 1) * (size_t)p + (size_t)pw);
+        }
+    }
+    if (!frames_on_device) { /* three planes as they are: rows keep their pitch, a plane's last row ends with its last sample */
+        fr_arena_reserve(net, need);
+        size_t off = 0;
+        for (int b = 0; b < B; ++b) {
+            int same = -1; /* one frame in several slots goes up once */
+            for (int k = 0; k < b && same < 0; ++k)
+                if (p0[k] == p0[b] && p1[k] == p1[b] && p2[k] == p2[b] && w[k] == w[b] && h[k] == h[b] &&
+                    0 == memcmp(tab[k].pitch, tab[b].pitch, sizeof(tab[b].pitch)))
+                    same = k;
+            if (same >= 0) { memcpy(tab[b].plane, tab[same].plane, sizeof(tab[b].plane)); continue; }
+            for (int k = 0; k < 3; ++k) {
+                const int pw = k && half_w ? (w[b] + 1) / 2 : w[b], ph = k && half_h ? (h[b] + 1) / 2 : h[b];
+                tab[b].plane[k] = fr_stage(net, planes[k][b], (size_t)(ph - 1) * (size_t)tab[b].pitch[k] + (size_t)pw, &off);
+            }
+        }
+    }
+    fr_finish(net, FR_PLANAR);
 }
 
 void set_batch_network(network *net, int b)
