@@ -188,13 +188,13 @@ struct network {
     void *pi_idx_gpu, *pi_idx_host; /* [B] int32 entry | [B] float scale | [B] uint8 zero point */
     float *pi_mm_gpu, *pi_mm_host;  /* [B][2] max, min */
     int pi_packed;              /* bank entries packed by the last batch (the others came from the cache) */
-    /* 8-bit frame input (network_frames_u8_input_gpu): lazily allocated, sized by the batch, freed with the network and on re-batch.
-     * A replica owns its own. */
-    void *fr_arena_gpu;         /* staging of host frames: the bytes as they came, rows at their pitch, 256-byte aligned frames */
+    /* Frame input (network_frames_u8 / _nv12 / _planar_input_gpu): lazily allocated, sized by the batch, freed with the network and on
+     * re-batch.  A replica owns its own. */
+    void *fr_arena_gpu;         /* staging of host frames: the bytes as they came, rows at their pitch, 256-byte aligned planes */
     size_t fr_arena_bytes;
-    mi355_frame_u8 *fr_table_gpu, *fr_table_host; /* [fr_cap] frame table and its host mirror */
-    mi355_frame_yuv *fr_yuv_gpu, *fr_yuv_host;    /* the same for NV12 / NV21 frames (network_frames_nv12_input_gpu) */
-    mi355_frame_planar *fr_planar_gpu, *fr_planar_host; /* and for frames of three planes (network_frames_planar_input_gpu) */
+    void *fr_table_gpu, *fr_table_host; /* [fr_cap] entries of the kind last fed (mi355_frame_u8 | _yuv | _planar) and their host mirror:
+                                           one table for every kind, sized for the largest entry */
+    int fr_kind;                /* the kind of frames in the table */
     float *fr_mm_gpu, *fr_mm_host; /* [fr_cap][2] max, min */
     void *fr_pair_gpu, *fr_pair_host; /* shared-scale mode: [fr_cap] float scale | [fr_cap] uint8 zero point, image 0's in every slot */
     int fr_cap;

@@ -8,26 +8,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from frames_util import COEF, ROOT, yuv_to_rgb
 from yolo_quantization_amd import binding
 
-ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-
-# (yoff, cy, crv, cgu, cgv, cbu): round(x * 65536) of the standards' coefficients, by matrix id
-COEF = {0: (16, 76309, 104597, 25675, 53279, 132201), 1: (0, 65536, 91881, 22553, 46802, 116130),
-        2: (16, 76309, 117489, 13975, 34925, 138438), 3: (0, 65536, 103206, 12276, 30679, 121609)}
 # the standards themselves: (Kr, Kb, limited range)
 REAL = {0: (0.299, 0.114, True), 1: (0.299, 0.114, False), 2: (0.2126, 0.0722, True), 3: (0.2126, 0.0722, False)}
-
-
-def yuv_to_rgb(Y, U, V, matrix):
-    """the specified integer conversion: int32, floor shift, clamp"""
-    yoff, cy, crv, cgu, cgv, cbu = COEF[matrix]
-    Y, U, V = (np.asarray(a).astype(np.int32) for a in (Y, U, V))
-    yy = cy * (Y - yoff)
-    r = (yy + crv * (V - 128) + 32768) >> 16
-    g = (yy - cgu * (U - 128) - cgv * (V - 128) + 32768) >> 16
-    b = (yy + cbu * (U - 128) + 32768) >> 16
-    return np.stack([np.clip(c, 0, 255).astype(np.uint8) for c in (r, g, b)], axis=-1)
 
 
 def test_yuv_struct_mirror_matches_the_c_header(tmp_path):
@@ -90,12 +75,13 @@ def test_integer_formulas_agree_with_the_real_valued_standard(matrix):
 READER_MAIN = r"""
 #include <stdio.h>
 #include <stdlib.h>
-#include "nv12_file.h"
+#include "raw_frame_file.h"
 int main(int argc, char **argv)
 {
     int w = -1, h = -1;
+    size_t bytes[2] = {0, 0};
     char why[1024] = "";
-    uint8_t *raw = load_nv12_file(argv[1], &w, &h, why, sizeof(why));
+    uint8_t *raw = load_raw_frame_file(argv[1], RAW_FRAME_NV12, &w, &h, bytes, why, sizeof(why));
     if (!raw) { fprintf(stderr, "%s", why); return 1; }
     printf("%d %d\n", w, h);
     fwrite(raw, 1, (size_t)w * h + (size_t)((h + 1) / 2) * 2 * ((w + 1) / 2), stdout);
@@ -107,12 +93,12 @@ int main(int argc, char **argv)
 
 @pytest.fixture(scope="module")
 def reader(tmp_path_factory):
-    """the CLI's raw-file reader (host/nv12_file.c, linked into ./darknet only) behind a main of the test's: no device, no library"""
+    """the CLI's raw-file reader (host/raw_frame_file.c, linked into ./darknet only) behind a main of the test's: no device, no library"""
     d = tmp_path_factory.mktemp("nv12_reader")
     host = os.path.join(ROOT, "yolo_quantization_amd", "host")
     (d / "main.c").write_text(READER_MAIN)
     exe = d / "reader"
-    subprocess.run(["gcc", "-O1", "-Wall", "-I", host, str(d / "main.c"), os.path.join(host, "nv12_file.c"), "-o", str(exe)], check=True)
+    subprocess.run(["gcc", "-O1", "-Wall", "-I", host, str(d / "main.c"), os.path.join(host, "raw_frame_file.c"), "-o", str(exe)], check=True)
 
     def load(path):
         r = subprocess.run([str(exe), str(path)], capture_output=True)

@@ -9,9 +9,9 @@ import sys
 import numpy as np
 import pytest
 
+from frames_util import ROOT
 from yolo_quantization_amd import binding
 
-ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 FORMATS = ["i420", "yv12", "i422", "i444", "rgb", "bgr"]
 
 
@@ -55,14 +55,14 @@ def test_new_entry_points_are_exported():
 READER_MAIN = r"""
 #include <stdio.h>
 #include <stdlib.h>
-#include "planar_file.h"
+#include "raw_frame_file.h"
 int main(int argc, char **argv)
 {
     int w = -1, h = -1;
     size_t bytes[2] = {0, 0};
     char why[1024] = "";
     if (argc != 3) return 2;
-    uint8_t *raw = load_planar_file(argv[1], atoi(argv[2]), &w, &h, bytes, why, sizeof(why));
+    uint8_t *raw = load_raw_frame_file(argv[1], atoi(argv[2]), &w, &h, bytes, why, sizeof(why));
     if (!raw) { fprintf(stderr, "%s", why); return 1; }
     printf("%d %d %zu %zu\n", w, h, bytes[0], bytes[1]);
     fwrite(raw, 1, bytes[0] + 2 * bytes[1], stdout);
@@ -74,12 +74,12 @@ int main(int argc, char **argv)
 
 @pytest.fixture(scope="module")
 def reader(tmp_path_factory):
-    """the CLI's raw-file reader (host/planar_file.c, linked into ./darknet only) behind a main of the test's: no device, no library"""
+    """the CLI's raw-file reader (host/raw_frame_file.c, linked into ./darknet only) behind a main of the test's: no device, no library"""
     d = tmp_path_factory.mktemp("planar_reader")
     host = os.path.join(ROOT, "yolo_quantization_amd", "host")
     (d / "main.c").write_text(READER_MAIN)
     exe = d / "reader"
-    subprocess.run(["gcc", "-O1", "-Wall", "-Wextra", "-Werror", "-I", host, str(d / "main.c"), os.path.join(host, "planar_file.c"), "-o",
+    subprocess.run(["gcc", "-O1", "-Wall", "-Wextra", "-Werror", "-I", host, str(d / "main.c"), os.path.join(host, "raw_frame_file.c"), "-o",
                     str(exe)], check=True)
 
     def load(path, fmt):

@@ -2,23 +2,25 @@
 network_frames_nv12_input_gpu (host), Net.prepare_from_frames_nv12 (Python) and `detector test -frames nv12` (CLI).
 
 Every comparison is exact: bytes and float bits, no tolerance.  The expected result of a frame never comes from the code under test:
-this file's numpy conversion (nv12_to_rgb, the specified integer formulas with the coefficient table of test_frames_nv12_cpu written
+this file's numpy conversion (nv12_to_rgb, the specified integer formulas with the coefficient table of frames_util written
 out as numbers) makes the interleaved RGB frame, and that goes where the u8 tests' frames go: the oracle's letterbox + layer-0
 quantiser on its planes (byte / 255), and at host level Net.prepare_from_frames_u8 of a second Net."""
-import ctypes as C
+import functools
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import frames_util
+from frames_util import (CFG, EINVAL, ROOT, _assert_frame, _assert_same_run, _bits, _blocks, _expected, _layers_and_dets, _padded, _write_ppm,
+                         _wts, yuv_to_rgb)
 from yolo_quantization_amd import binding
-from test_frames_nv12_cpu import yuv_to_rgb
-from test_gpu_frames_u8 import (CFG, CLASSES, EINVAL, ROOT, _assert_frame, _assert_same_run, _bits, _blocks, _expected, _layers_and_dets,
-                                _pair_from_minmax, _write_ppm, _wts)
 
 pytestmark = pytest.mark.gpu
 
+# pitch[b] = (pitch_y, pitch_uv) pads every row with 0xEE bytes; layout / matrix: one name for the batch or one per frame
+_Launch = functools.partial(frames_util._Launch, "yuv")
 MATRICES = ["bt601", "bt601f", "bt709", "bt709f"]
 
 
@@ -39,72 +41,6 @@ def _yuv(w, h, seed, lo=0, hi=256, clo=0, chi=256):
     """(y [h][w], uv [(h + 1) // 2][(w + 1) // 2][2]) with luma in lo..hi-1 and chroma in clo..chi-1"""
     rng = np.random.default_rng(seed)
     return (rng.integers(lo, hi, (h, w), dtype=np.uint8), rng.integers(clo, chi, ((h + 1) // 2, (w + 1) // 2, 2), dtype=np.uint8))
-
-
-def _padded(plane2d, pitch):
-    rows = np.full((plane2d.shape[0], pitch), 0xEE, np.uint8)
-    rows[:, :plane2d.shape[1]] = plane2d
-    return rows
-
-
-class _Launch:
-    """One batch through the two C-ABI calls.  frames: (y, uv) pairs; pitch[b] = (pitch_y, pitch_uv) pads every row with 0xEE bytes;
-    layout / matrix: one name for the batch or one per frame."""
-
-    def __init__(self, frames, netw, neth, layout="nv12", matrix="bt601", pitch=None):
-        B = len(frames)
-        self.B, self.netw, self.neth = B, netw, neth
-        self.bufs = []
-        self.table = (binding.FrameYUV * B)()
-        for b, (y, uv) in enumerate(frames):
-            h, w = y.shape
-            cw2 = 2 * ((w + 1) // 2)
-            py, puv = pitch[b] if pitch else (w, cw2)
-            by = binding.DevBuf.from_numpy(_padded(y, py))
-            buv = binding.DevBuf.from_numpy(_padded(uv.reshape(uv.shape[0], cw2), puv))
-            self.bufs += [by, buv]
-            lay = layout if isinstance(layout, str) else layout[b]
-            mat = matrix if isinstance(matrix, str) else matrix[b]
-            self.table[b] = binding.FrameYUV(by.ptr.value, buv.ptr.value, w, h, py, puv, binding.YUV_LAYOUT[lay], binding.YUV_MATRIX[mat],
-                                             (C.c_int * 2)(0, 0))
-        self.out = binding.DevBuf.from_numpy(np.full(B * 3 * neth * netw, 0xA5, np.uint8))
-        self.mm = binding.DevBuf.from_numpy(np.full(2 * B, 7.0, np.float32))
-        self.pairs = None
-
-    def upload_table(self):
-        self.table_dev = binding.DevBuf(C.sizeof(self.table))
-        binding.check(binding.shim().mi355_h2d(self.table_dev.ptr, C.addressof(self.table), C.sizeof(self.table), None), "h2d")
-        binding.check(binding.shim().mi355_stream_sync(None), "sync")
-
-    def minmax_rc(self):
-        return binding.shim().mi355_frames_yuv_letterbox_minmax(self.table_dev.ptr, self.table, self.B, self.netw, self.neth, self.mm.ptr,
-                                                                None)
-
-    def quantize_rc(self, scales, zps):
-        self.pairs = (binding.DevBuf.from_numpy(np.asarray(scales, np.float32)), binding.DevBuf.from_numpy(np.asarray(zps, np.uint8)))
-        return binding.shim().mi355_frames_yuv_letterbox_quantize(self.table_dev.ptr, self.table, self.B, self.netw, self.neth,
-                                                                  self.pairs[0].ptr, self.pairs[1].ptr, self.out.ptr, None)
-
-    def run(self):
-        """(minmax [B][2], scale [B], zero point [B], bytes [B][3][h][w])"""
-        self.upload_table()
-        binding.check(self.minmax_rc(), "minmax")
-        mm = self.mm.to_numpy(np.float32, 2 * self.B).reshape(self.B, 2)
-        pairs = [_pair_from_minmax(mm[b, 0], mm[b, 1]) for b in range(self.B)]
-        s = np.array([p[0] for p in pairs], np.float32)
-        z = np.array([p[1] for p in pairs], np.uint8)
-        binding.check(self.quantize_rc(s, z), "quantize")
-        q = self.out.to_numpy(np.uint8, self.B * 3 * self.neth * self.netw).reshape(self.B, 3, self.neth, self.netw)
-        return mm, s, z, q
-
-    def out_bytes(self):
-        return self.out.to_numpy(np.uint8, self.B * 3 * self.neth * self.netw)
-
-    def free(self):
-        for b in self.bufs + [self.out, self.mm] + list(self.pairs or ()):
-            b.free()
-        if hasattr(self, "table_dev"):
-            self.table_dev.free()
 
 
 def _same(ga, gb):

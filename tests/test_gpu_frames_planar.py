@@ -5,25 +5,27 @@ mi355_frames_planar_letterbox_minmax / _quantize (C-ABI), network_frames_planar_
 Every comparison is exact: bytes and float bits, no tolerance.  The expected result of a frame never comes from the code under test:
 it is what the NV12 calls give for the same Y plane and the interleaved chroma planes (I420), and what the u8 calls give for the
 interleaved RGB frame that this file's numpy restatement of the sampling rule -- U[y >> sy][x >> sx] -- and the header's integer
-formulas (yuv_to_rgb of test_frames_nv12_cpu) make of the planes.  Both of those paths are pinned to the oracle by their own tests."""
-import ctypes as C
+formulas (yuv_to_rgb of frames_util) make of the planes.  Both of those paths are pinned to the oracle by their own tests."""
+import functools
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import frames_util
+from frames_util import (CFG, EINVAL, ROOT, SHIFTS, _assert_same_run, _bits, _blocks, _layers_and_dets, _padded, _write_ppm, _wts, plane_shapes,
+                         yuv_to_rgb)
 from yolo_quantization_amd import binding
-from test_frames_nv12_cpu import yuv_to_rgb
-from test_gpu_frames_nv12 import _Launch as _LaunchNV12
-from test_gpu_frames_u8 import _Launch as _LaunchU8
-from test_gpu_frames_u8 import (CFG, EINVAL, ROOT, _assert_same_run, _bits, _blocks, _layers_and_dets, _pair_from_minmax, _write_ppm, _wts)
 
 pytestmark = pytest.mark.gpu
 
+# fmt / matrix: one name for the batch or one per frame; pitch[b] = three pitches, rows padded with 0xEE bytes
+_Launch = functools.partial(frames_util._Launch, "planar")
+_LaunchNV12 = functools.partial(frames_util._Launch, "yuv")
+_LaunchU8 = functools.partial(frames_util._Launch, "u8")
 MATRICES = ["bt601", "bt601f", "bt709", "bt709f"]
 FORMATS = ["i420", "yv12", "i422", "i444", "rgb", "bgr"]
-SHIFTS = {"i420": (1, 1), "yv12": (1, 1), "i422": (1, 0), "i444": (0, 0)}  # (sx, sy)
 # net size <- source sizes: odd widths and heights, so the last chroma column and row serve one luma column and row; up- and
 # downscaling in one batch; letterbox bars on either axis; a width that is no multiple of 4; several workgroups per image
 SHAPES = [(13, 11, [(9, 17)]), (52, 36, [(40, 30), (17, 50)]), (416, 416, [(640, 480)])]
@@ -33,15 +35,6 @@ SHAPE_IDS = ["w_not_multiple_of_4_odd_h", "letterbox_bars_up_and_down", "several
 @pytest.fixture(scope="module", autouse=True)
 def _dev():
     binding.init(0)
-
-
-def plane_shapes(fmt, w, h):
-    """[(rows, columns)] of the three planes"""
-    if fmt in ("rgb", "bgr"):
-        return [(h, w)] * 3
-    sx, sy = SHIFTS[fmt]
-    c = ((h + sy) >> sy, (w + sx) >> sx)
-    return [(h, w), c, c]
 
 
 def planar_to_rgb(planes, fmt, matrix="bt601", shifts=None):
@@ -64,75 +57,6 @@ def _frame(fmt, w, h, seed, lo=0, hi=256, clo=0, chi=256):
     if fmt in ("rgb", "bgr"):
         clo, chi = lo, hi
     return tuple(rng.integers(a, b, s, dtype=np.uint8) for s, (a, b) in zip(shp, [(lo, hi), (clo, chi), (clo, chi)]))
-
-
-def _padded(plane2d, pitch):
-    rows = np.full((plane2d.shape[0], pitch), 0xEE, np.uint8)
-    rows[:, :plane2d.shape[1]] = plane2d
-    return rows
-
-
-def _per_frame(x, b):
-    return x if isinstance(x, str) else x[b]
-
-
-class _Launch:
-    """One batch through the two C-ABI calls.  frames: tuples of three planes; fmt / matrix: one name for the batch or one per frame
-    (matrix is passed as 0 for rgb / bgr frames); pitch[b] = three pitches, rows padded with 0xEE bytes."""
-
-    def __init__(self, frames, netw, neth, fmt="i420", matrix="bt601", pitch=None):
-        B = len(frames)
-        self.B, self.netw, self.neth = B, netw, neth
-        self.bufs = []
-        self.table = (binding.FramePlanar * B)()
-        for b, planes in enumerate(frames):
-            h, w = planes[0].shape
-            f = _per_frame(fmt, b)
-            assert [p.shape for p in planes] == plane_shapes(f, w, h)
-            ps = pitch[b] if pitch else [p.shape[1] for p in planes]
-            bufs = [binding.DevBuf.from_numpy(_padded(p, q)) for p, q in zip(planes, ps)]
-            self.bufs += bufs
-            m = 0 if f in ("rgb", "bgr") else binding.YUV_MATRIX[_per_frame(matrix, b)]
-            self.table[b] = binding.FramePlanar((C.c_void_p * 3)(*[x.ptr.value for x in bufs]), w, h, (C.c_int * 3)(*ps),
-                                                binding.PLANAR_FORMAT[f], m, (C.c_int * 3)(0, 0, 0))
-        self.out = binding.DevBuf.from_numpy(np.full(B * 3 * neth * netw, 0xA5, np.uint8))
-        self.mm = binding.DevBuf.from_numpy(np.full(2 * B, 7.0, np.float32))
-        self.pairs = None
-
-    def upload_table(self):
-        self.table_dev = binding.DevBuf(C.sizeof(self.table))
-        binding.check(binding.shim().mi355_h2d(self.table_dev.ptr, C.addressof(self.table), C.sizeof(self.table), None), "h2d")
-        binding.check(binding.shim().mi355_stream_sync(None), "sync")
-
-    def minmax_rc(self):
-        return binding.shim().mi355_frames_planar_letterbox_minmax(self.table_dev.ptr, self.table, self.B, self.netw, self.neth,
-                                                                   self.mm.ptr, None)
-
-    def quantize_rc(self, scales, zps):
-        self.pairs = (binding.DevBuf.from_numpy(np.asarray(scales, np.float32)), binding.DevBuf.from_numpy(np.asarray(zps, np.uint8)))
-        return binding.shim().mi355_frames_planar_letterbox_quantize(self.table_dev.ptr, self.table, self.B, self.netw, self.neth,
-                                                                     self.pairs[0].ptr, self.pairs[1].ptr, self.out.ptr, None)
-
-    def run(self):
-        """(minmax [B][2], scale [B], zero point [B], bytes [B][3][h][w])"""
-        self.upload_table()
-        binding.check(self.minmax_rc(), "minmax")
-        mm = self.mm.to_numpy(np.float32, 2 * self.B).reshape(self.B, 2)
-        pairs = [_pair_from_minmax(mm[b, 0], mm[b, 1]) for b in range(self.B)]
-        s = np.array([p[0] for p in pairs], np.float32)
-        z = np.array([p[1] for p in pairs], np.uint8)
-        binding.check(self.quantize_rc(s, z), "quantize")
-        q = self.out.to_numpy(np.uint8, self.B * 3 * self.neth * self.netw).reshape(self.B, 3, self.neth, self.netw)
-        return mm, s, z, q
-
-    def out_bytes(self):
-        return self.out.to_numpy(np.uint8, self.B * 3 * self.neth * self.netw)
-
-    def free(self):
-        for b in self.bufs + [self.out, self.mm] + list(self.pairs or ()):
-            b.free()
-        if hasattr(self, "table_dev"):
-            self.table_dev.free()
 
 
 def _run(cls, *a, **kw):

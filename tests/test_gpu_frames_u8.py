@@ -3,20 +3,21 @@ network_frames_u8_input_gpu (host), Net.prepare_from_frames_u8 (Python) and `det
 
 Every comparison is exact: bytes and float bits, no tolerance.  The expected result of a frame is the oracle's letterbox + layer-0
 quantiser on the planes load_image_color makes of it (byte / 255), and the float path of this library on the same planes."""
-import ctypes as C
+import functools
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-import oracle
-from yolo_quantization_amd import binding, synth
+import frames_util
+from frames_util import (CFG, EINVAL, ROOT, _assert_frame, _assert_same_run, _bits, _blocks, _expected, _layers_and_dets, _planes, _write_ppm,
+                         _wts)
+from yolo_quantization_amd import binding
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EINVAL = -22
+_Launch = functools.partial(frames_util._Launch, "u8")  # order="rgb" | "bgr"; pitch[b] > 3 w pads every row with 0xEE bytes
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -26,96 +27,6 @@ def _dev():
 
 def _frame(w, h, seed, lo=0, hi=256):
     return np.random.default_rng(seed).integers(lo, hi, (h, w, 3), dtype=np.uint8)
-
-
-def _planes(frame):
-    """load_image_color's planar floats of an RGB frame (ref: src/image.c:1386)"""
-    return np.ascontiguousarray(frame.transpose(2, 0, 1)).astype(np.float32) / np.float32(255)
-
-
-def _expected(frame, netw, neth):
-    lb = oracle.letterbox_image(_planes(frame), neth, netw)
-    q, s, z = oracle.quantize_image(lb)
-    return lb, q, s, z
-
-
-def _pair_from_minmax(mx, mn):
-    """the host's own scale / zero-point expressions (quant_image_with_min_max) on a two-element image with that max / min"""
-    x = np.array([mx, mn + np.float32(0)], np.float32)
-    out = np.zeros(2, np.uint8)
-    s, z = C.c_float(), C.c_uint8()
-    binding.host().quant_image_with_min_max(2, x.ctypes.data, out.ctypes.data, C.byref(s), C.byref(z))
-    return np.float32(s.value), z.value
-
-
-class _Launch:
-    """One batch through the two C-ABI calls.  frames: uint8 [h][w][3] arrays; pitch[b] > 3 w pads every row with 0xEE bytes."""
-
-    def __init__(self, frames, netw, neth, order="rgb", pitch=None):
-        B = len(frames)
-        self.B, self.netw, self.neth = B, netw, neth
-        self.bufs = []
-        self.table = (binding.FrameU8 * B)()
-        for b, f in enumerate(frames):
-            h, w, _ = f.shape
-            p = pitch[b] if pitch else 3 * w
-            rows = np.full((h, p), 0xEE, np.uint8)
-            rows[:, :3 * w] = f.reshape(h, 3 * w)
-            buf = binding.DevBuf.from_numpy(rows)
-            self.bufs.append(buf)
-            self.table[b] = binding.FrameU8(buf.ptr.value, w, h, p, binding.FRAME_ORDER[order], (C.c_int * 2)(0, 0))
-        self.out = binding.DevBuf.from_numpy(np.full(B * 3 * neth * netw, 0xA5, np.uint8))
-        self.mm = binding.DevBuf.from_numpy(np.full(2 * B, 7.0, np.float32))
-        self.pairs = None
-
-    def upload_table(self):
-        self.table_dev = binding.DevBuf(C.sizeof(self.table))
-        binding.check(binding.shim().mi355_h2d(self.table_dev.ptr, C.addressof(self.table), C.sizeof(self.table), None), "h2d")
-        binding.check(binding.shim().mi355_stream_sync(None), "sync")
-
-    def minmax_rc(self):
-        return binding.shim().mi355_frames_u8_letterbox_minmax(self.table_dev.ptr, self.table, self.B, self.netw, self.neth, self.mm.ptr,
-                                                               None)
-
-    def quantize_rc(self, scales, zps):
-        self.pairs = (binding.DevBuf.from_numpy(np.asarray(scales, np.float32)), binding.DevBuf.from_numpy(np.asarray(zps, np.uint8)))
-        return binding.shim().mi355_frames_u8_letterbox_quantize(self.table_dev.ptr, self.table, self.B, self.netw, self.neth,
-                                                                 self.pairs[0].ptr, self.pairs[1].ptr, self.out.ptr, None)
-
-    def run(self):
-        """(minmax [B][2], scale [B], zero point [B], bytes [B][3][h][w])"""
-        self.upload_table()
-        binding.check(self.minmax_rc(), "minmax")
-        mm = self.mm.to_numpy(np.float32, 2 * self.B).reshape(self.B, 2)
-        pairs = [_pair_from_minmax(mm[b, 0], mm[b, 1]) for b in range(self.B)]
-        s = np.array([p[0] for p in pairs], np.float32)
-        z = np.array([p[1] for p in pairs], np.uint8)
-        binding.check(self.quantize_rc(s, z), "quantize")
-        q = self.out.to_numpy(np.uint8, self.B * 3 * self.neth * self.netw).reshape(self.B, 3, self.neth, self.netw)
-        return mm, s, z, q
-
-    def out_bytes(self):
-        return self.out.to_numpy(np.uint8, self.B * 3 * self.neth * self.netw)
-
-    def free(self):
-        for b in self.bufs + [self.out, self.mm] + list(self.pairs or ()):
-            b.free()
-        if hasattr(self, "table_dev"):
-            self.table_dev.free()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _assert_frame(got, b, frame, netw, neth, what):
-    mm, s, z, q = got
-    lb, want_q, want_s, want_z = _expected(frame, netw, neth)
-    want_max, want_min = max(lb.max(), np.float32(0)), min(lb.min(), np.float32(0))
-    assert _bits(mm[b, 0]) == _bits(want_max), f"{what}: max"
-    assert mm[b, 1] == want_min, f"{what}: min"  # -0.0f (the seed) == 0.0f
-    assert _bits(s[b]) == _bits(want_s) and z[b] == want_z, f"{what}: scale / zero point"
-    assert np.array_equal(q[b], want_q), f"{what}: bytes"
 
 
 def _all_bytes_frame():
@@ -209,41 +120,10 @@ def test_refusals_launch_nothing(what):
 
 
 # ------------------------------------------------------------------------------------------------------------ host level
-CFG = os.path.join(ROOT, "cfg", "tiny_unit.cfg")
-CLASSES = 5
-
-
-def _wts(tmp_path, seed=3):
-    p = str(tmp_path / f"tiny_unit_{seed}.weights")
-    synth.synth_weights(CFG, p, seed=seed)
-    return p
-
-
 def _host_frames(seed):
     """three frames of different sizes and byte ranges (w x h: wide, tall, network size)"""
     specs = [((53, 37), 0, 256), ((12, 20), 40, 140), ((12, 12), 100, 230)]
     return [_frame(w, h, seed + k, lo, hi) for k, ((w, h), lo, hi) in enumerate(specs)]
-
-
-def _layers_and_dets(net, frames):
-    net.forward()
-    net.sync()
-    outs = [net.pull(i) for i in range(net.n)]
-    heads = [i for i, inf in enumerate(net.info) if inf["type"] == binding.T_YOLO]
-    dets = [net.detections_sizes(i, CLASSES, [f.shape[1] for f in frames], [f.shape[0] for f in frames], 0.005, 1, 512) for i in heads]
-    return outs, dets
-
-
-def _assert_same_run(got, want, what):
-    (outs_a, dets_a), (outs_b, dets_b) = got, want
-    for i, (a, b) in enumerate(zip(outs_a, outs_b)):
-        assert a.keys() == b.keys()
-        for k in a:
-            assert np.array_equal(a[k], b[k]), f"{what}: layer {i} {k}"
-    assert len(dets_a) == len(dets_b) > 0
-    for (ca, ra), (cb, rb) in zip(dets_a, dets_b):
-        assert np.array_equal(ca, cb) and np.array_equal(ra, rb), f"{what}: detections"
-        assert ca.sum() > 0
 
 
 def test_host_shared_scale_equals_float_path_and_rederives_layer0(tmp_path):
@@ -369,24 +249,6 @@ def test_host_replica_beside_its_parent(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------------------------- CLI
-def _write_ppm(path, rgb_hwc):
-    with open(path, "wb") as f:
-        f.write(f"P6\n{rgb_hwc.shape[1]} {rgb_hwc.shape[0]}\n255\n".encode())
-        f.write(np.ascontiguousarray(rgb_hwc, np.uint8).tobytes())
-
-
-def _blocks(stdout):
-    """per-image blocks of `detector test` output, the timing line reduced to the file name"""
-    out, cur = [], None
-    for line in stdout.splitlines():
-        if ": Predicted in " in line:
-            cur = [line.split(": Predicted in ")[0]]
-            out.append(cur)
-        elif cur is not None:
-            cur.append(line)
-    return out
-
-
 def test_cli_frames_u8_blocks_equal_the_float_path(tmp_path):
     exe = os.path.join(ROOT, "yolo_quantization_amd", "bin", "darknet")
     wts = _wts(tmp_path, seed=1)

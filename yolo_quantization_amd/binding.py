@@ -438,6 +438,15 @@ def _as(ptr, n, dt):
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(dt)), shape=(n,))
 
 
+def _byte_rows(a, keep):
+    """(address, pitch) of a uint8 array [rows][...]: its row stride serves as the pitch where a row's bytes are contiguous and the stride
+    is at least the row, anything else is copied first.  `keep` keeps what the address points into alive over the call."""
+    if not a[:1].flags["C_CONTIGUOUS"] or a.strides[0] < a[:1].size:
+        a = np.ascontiguousarray(a)
+    keep.append(a)
+    return a.ctypes.data, a.strides[0]
+
+
 class Net:
     """The darknet host network (libdarknet_q.so): load_network -> prep -> forward_network_gpu."""
 
@@ -568,10 +577,8 @@ class Net:
             a = np.asarray(f)
             if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
                 raise ValueError("prepare_from_frames_u8: every frame must be a uint8 [h][w][3] array")
-            if a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < 3 * a.shape[1]:
-                a = np.ascontiguousarray(a)
-            keep.append(a)
-            ptrs[b], hs[b], ws[b], ps[b] = a.ctypes.data, a.shape[0], a.shape[1], a.strides[0]
+            ptrs[b], ps[b] = _byte_rows(a, keep)
+            hs[b], ws[b] = a.shape[:2]
         self.H.network_frames_u8_input_gpu(self.h, ptrs, ws, hs, ps, FRAME_ORDER[order], 0)
         return self._prepared(self._pull_input())
 
@@ -604,12 +611,7 @@ class Net:
             h, w = y.shape
             if uv.shape[:2] != ((h + 1) // 2, (w + 1) // 2):
                 raise ValueError("prepare_from_frames_nv12: the chroma plane must be [(h + 1) // 2][(w + 1) // 2][2]")
-            if y.strides[1] != 1 or y.strides[0] < w:
-                y = np.ascontiguousarray(y)
-            if uv.strides[2] != 1 or uv.strides[1] != 2 or uv.strides[0] < 2 * uv.shape[1]:
-                uv = np.ascontiguousarray(uv)
-            keep += [y, uv]
-            ys[b], uvs[b], hs[b], ws[b], py[b], puv[b] = y.ctypes.data, uv.ctypes.data, h, w, y.strides[0], uv.strides[0]
+            (ys[b], py[b]), (uvs[b], puv[b]), hs[b], ws[b] = _byte_rows(y, keep), _byte_rows(uv, keep), h, w
         self.H.network_frames_nv12_input_gpu(self.h, ys, uvs, ws, hs, py, puv, YUV_LAYOUT[layout], YUV_MATRIX[matrix], int(on_device))
         return self._prepared(self._pull_input())
 
@@ -651,10 +653,7 @@ class Net:
             if planes[1].shape != chroma or planes[2].shape != chroma:
                 raise ValueError(f"prepare_from_frames_planar: planes 1 and 2 of a {w} x {h} {format} frame must be {chroma[1]} x {chroma[0]}")
             for k, a in enumerate(planes):
-                if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
-                    a = np.ascontiguousarray(a)
-                keep.append(a)
-                ptr[k][b], pitch[k][b] = a.ctypes.data, a.strides[0]
+                ptr[k][b], pitch[k][b] = _byte_rows(a, keep)
             hs[b], ws[b] = h, w
         self.H.network_frames_planar_input_gpu(self.h, ptr[0], ptr[1], ptr[2], ws, hs, pitch[0], pitch[1], pitch[2],
                                                PLANAR_FORMAT[format], YUV_MATRIX[matrix], int(on_device))

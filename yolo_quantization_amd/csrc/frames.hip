@@ -1,20 +1,21 @@
-// frames.hip -- the batched input path for 8-bit interleaved frames (mi355_frames_u8_letterbox_minmax / _quantize): letterbox_image
-// (ref: src/image.c:812-831) + the layer-0 quantiser (ref: src/blas.c:108-168) straight from the decoder's bytes, one launch per pass
-// for the whole batch, no float image in memory.  Pass 1 reduces min / max of the letterboxed floats per image, the host derives
-// (scale, zero point), pass 2 recomputes the same floats and stores the quantised planar bytes.
+// frames.hip -- the batched input path for 8-bit frames: letterbox_image (ref: src/image.c:812-831) + the layer-0 quantiser (ref:
+// src/blas.c:108-168) straight from the decoder's bytes, one launch per pass for the whole batch, no float image in memory.  Pass 1
+// reduces min / max of the letterboxed floats per image, the host derives (scale, zero point), pass 2 recomputes the same floats and
+// stores the quantised planar bytes.
 //
 // Every float is the one letterbox_kernel (glue.hip) computes from load_image_color's planes (ref: src/image.c:1386, byte / 255.):
 // the same expressions, each product and sum rounded on its own (-ffp-contract=off), the 0.5 fill, last column = the source's last
 // column, last row = first term only.  The quantiser is image_quantize_per_image_kernel's expression, min / max reduce with
 // image_minmax_batched_kernel's seeds, comparisons and atomics.
 //
-// NV12 / NV21 frames (mi355_frames_yuv_letterbox_minmax / _quantize) go through the same two kernel bodies with another source: the
-// bytes of a source pixel are converted from (Y, U, V) in registers at every bilinear tap, with the integer formulas of the header
-// (mi355_frame_yuv), and from there on every expression is the interleaved path's.  No RGB frame is written anywhere.
-//
-// Frames of three separate planes (mi355_frames_planar_letterbox_minmax / _quantize: I420, YV12, I422, I444, planar RGB / BGR) are the
-// third source: the YUV formats share the NV12 source's tap walk and arithmetic with their own chroma shifts, the RGB formats take
-// their bytes as they are.
+// One path for every kind of frames.  A kind is a Source: it names its table entry of the C-ABI (Frame), its prefix in refusals (name),
+// the refusals that are its own (check_pointers, check), and hands the kernels the bytes of a pixel's taps (taps).  The two kernels,
+// the host-side check and the two launchers are templates over the Source, instantiated at the end of the file for
+//   SourceU8      interleaved RGB / BGR (mi355_frames_u8_*): the bytes as they are;
+//   SourceYUV     NV12 / NV21 (mi355_frames_yuv_*): the bytes of a source pixel are converted from (Y, U, V) in registers at every
+//                 bilinear tap, with the integer formulas of the header (mi355_frame_yuv); no RGB frame is written anywhere;
+//   SourcePlanar  three separate planes (mi355_frames_planar_*: I420, YV12, I422, I444, planar RGB / BGR): the YUV formats share the
+//                 NV12 source's tap walk and arithmetic with their own chroma shifts, the RGB formats take their bytes as they are.
 #include "kargs.h"
 
 // letterbox_launch's geometry (glue.hip), shared by the host-side validation and the kernels: one function compiled for both sides, so
@@ -51,6 +52,15 @@ __device__ static inline void fill_byte_lut(float *lut)
 // with byte k (plane k) of source pixel (ix + dx, iy + dy); column 1 only when two_x, row 1 only when two_y (the launcher's geometry
 // check keeps ix + 1 and iy + 1 inside the frame then).
 struct SourceU8 {
+    using Frame = mi355_frame_u8;
+    static constexpr const char *name = "frames_u8";
+    static const char *check_pointers(const Frame &f) { return f.data ? nullptr : "null frame pointer"; }
+    static const char *check(const Frame &f)
+    {
+        if (f.pitch < 3 * f.w) return "pitch < 3 * w";
+        if (f.order != MI355_FRAME_RGB && f.order != MI355_FRAME_BGR) return "channel order must be MI355_FRAME_RGB or MI355_FRAME_BGR";
+        return nullptr;
+    }
     const uint8_t *data;
     int w, h, pitch, o0, o2;  // byte offsets of planes 0 and 2 inside a pixel (plane 1 is byte 1 in both orders)
     __device__ explicit SourceU8(const mi355_frame_u8 &f)
@@ -133,6 +143,17 @@ __device__ static inline void yuv_taps(const Src &s, int sx, int sy, int ix, int
 }
 
 struct SourceYUV {
+    using Frame = mi355_frame_yuv;
+    static constexpr const char *name = "frames_yuv";
+    static const char *check_pointers(const Frame &f) { return f.y && f.uv ? nullptr : "null plane pointer"; }
+    static const char *check(const Frame &f)
+    {
+        if (f.pitch_y < f.w) return "pitch_y < w";
+        if (f.pitch_uv < 2 * ((f.w + 1) / 2)) return "pitch_uv < 2 * ((w + 1) / 2)";
+        if (f.layout != MI355_YUV_NV12 && f.layout != MI355_YUV_NV21) return "layout must be MI355_YUV_NV12 or MI355_YUV_NV21";
+        if (f.matrix < MI355_YUV_BT601 || f.matrix > MI355_YUV_BT709_FULL) return "unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)";
+        return nullptr;
+    }
     const uint8_t *y, *uv;
     int w, h, pitch_y, pitch_uv;
     int iu, iv;        // position of U and V inside a chroma pair: (0, 1) NV12, (1, 0) NV21
@@ -162,6 +183,20 @@ struct SourceYUV {
 // them in, sampled at (x >> sx, y >> sy).  RGB formats: y, u, v hold the planes of R, G, B and their bytes are the pixel's.  The
 // format is uniform over the workgroup, so its branches do not diverge.
 struct SourcePlanar {
+    using Frame = mi355_frame_planar;
+    static constexpr const char *name = "frames_planar";
+    static const char *check_pointers(const Frame &f) { return f.plane[0] && f.plane[1] && f.plane[2] ? nullptr : "null plane pointer"; }
+    static const char *check(const Frame &f)
+    {
+        if (f.format < MI355_PLANAR_I420 || f.format > MI355_PLANAR_BGR) return "unknown format (MI355_PLANAR_I420 .. _BGR)";
+        if (f.matrix < MI355_YUV_BT601 || f.matrix > MI355_YUV_BT709_FULL) return "unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)";
+        const bool rgb = f.format == MI355_PLANAR_RGB || f.format == MI355_PLANAR_BGR;
+        if (rgb && f.matrix != 0) return "matrix must be 0 with MI355_PLANAR_RGB / _BGR";
+        const int cw = rgb || f.format == MI355_PLANAR_I444 ? f.w : (f.w + 1) / 2;  // the width of planes 1 and 2
+        if (f.pitch[0] < f.w) return "pitch[0] < w";
+        if (f.pitch[1] < cw || f.pitch[2] < cw) return "pitch[1] or pitch[2] below the width of its plane";
+        return nullptr;
+    }
     const uint8_t *y, *u, *v;
     int w, h, pitch_y, pitch_u, pitch_v;
     int sx, sy;
@@ -247,7 +282,7 @@ __device__ static inline void letterbox_minmax_body(const Frame *table, int w, i
     const Source f(table[blockIdx.y]);
     uint32_t *mi = mm + 2 * (size_t)blockIdx.y;
     FrameGeo g;
-    frame_geometry(f.w, f.h, w, h, g);  // checked by the launcher
+    frame_geometry(f.w, f.h, w, h, g);  // checked by frames_check
     float mx = 0.0f, mn = 0.0f;
     const int hw = h * w;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) {
@@ -271,22 +306,11 @@ __device__ static inline void letterbox_minmax_body(const Frame *table, int w, i
     }
 }
 
-__global__ __launch_bounds__(256) void frames_u8_letterbox_minmax_kernel(const mi355_frame_u8 *table, int w, int h, uint32_t *mm)
+template <class Source>
+__global__ __launch_bounds__(256) void frames_letterbox_minmax_kernel(const typename Source::Frame *table, int w, int h, uint32_t *mm)
 {
     __shared__ float lut[256];
-    letterbox_minmax_body<SourceU8>(table, w, h, mm, lut);
-}
-
-__global__ __launch_bounds__(256) void frames_yuv_letterbox_minmax_kernel(const mi355_frame_yuv *table, int w, int h, uint32_t *mm)
-{
-    __shared__ float lut[256];
-    letterbox_minmax_body<SourceYUV>(table, w, h, mm, lut);
-}
-
-__global__ __launch_bounds__(256) void frames_planar_letterbox_minmax_kernel(const mi355_frame_planar *table, int w, int h, uint32_t *mm)
-{
-    __shared__ float lut[256];
-    letterbox_minmax_body<SourcePlanar>(table, w, h, mm, lut);
+    letterbox_minmax_body<Source>(table, w, h, mm, lut);
 }
 
 // grid: (workgroups per image, B); a thread serves four neighbouring x of one row in all three planes: one 4-byte store per plane
@@ -301,7 +325,7 @@ __device__ static inline void letterbox_quantize_body(const Frame *table, int w,
     if (t < h * wq) {
         const Source f(table[blockIdx.y]);
         FrameGeo g;
-        frame_geometry(f.w, f.h, w, h, g);  // checked by the launcher
+        frame_geometry(f.w, f.h, w, h, g);  // checked by frames_check
         const float scale = scale_dev[blockIdx.y];
         const int zp = zp_dev[blockIdx.y];
         const int y = t / wq, x0 = (t % wq) * 4;
@@ -330,81 +354,35 @@ __device__ static inline void letterbox_quantize_body(const Frame *table, int w,
     }
 }
 
-__global__ __launch_bounds__(256) void frames_u8_letterbox_quantize_kernel(const mi355_frame_u8 *table, int w, int h,
-                                                                           const float *scale_dev, const uint8_t *zp_dev, uint8_t *out)
+template <class Source>
+__global__ __launch_bounds__(256) void frames_letterbox_quantize_kernel(const typename Source::Frame *table, int w, int h,
+                                                                        const float *scale_dev, const uint8_t *zp_dev, uint8_t *out)
 {
     __shared__ float lut[256];
-    letterbox_quantize_body<SourceU8>(table, w, h, scale_dev, zp_dev, out, lut);
+    letterbox_quantize_body<Source>(table, w, h, scale_dev, zp_dev, out, lut);
 }
 
-__global__ __launch_bounds__(256) void frames_yuv_letterbox_quantize_kernel(const mi355_frame_yuv *table, int w, int h,
-                                                                            const float *scale_dev, const uint8_t *zp_dev, uint8_t *out)
+// Host-side check of the table's host mirror, before anything is launched: NULL when every frame can be served, else what is wrong
+// ("<Source::name>: <reason>", in a buffer of the calling thread).  The conditions every kind shares are here, a kind's own in its
+// Source::check_pointers and Source::check.
+template <class Source, class Frame>
+const char *frames_check(const Frame *host, int B, int w, int h)
 {
-    __shared__ float lut[256];
-    letterbox_quantize_body<SourceYUV>(table, w, h, scale_dev, zp_dev, out, lut);
-}
-
-__global__ __launch_bounds__(256) void frames_planar_letterbox_quantize_kernel(const mi355_frame_planar *table, int w, int h,
-                                                                               const float *scale_dev, const uint8_t *zp_dev, uint8_t *out)
-{
-    __shared__ float lut[256];
-    letterbox_quantize_body<SourcePlanar>(table, w, h, scale_dev, zp_dev, out, lut);
-}
-
-// Host-side check of the table's host mirror, before anything is launched: NULL when every frame can be served, else what is wrong.
-const char *frames_u8_check(const mi355_frame_u8 *host, int B, int w, int h)
-{
-    if (!host || B <= 0 || B > 65535) return "frames_u8: null table / need 1 <= B <= 65535";
-    if (w < 2 || h < 2 || w > 32768 || h > 32768) return "frames_u8: need 2 <= w, h <= 32768 for the network input";
-    for (int b = 0; b < B; ++b) {
-        const mi355_frame_u8 &f = host[b];
-        if (!f.data) return "frames_u8: null frame pointer";
-        if (f.w < 1 || f.h < 1 || f.w > 32768 || f.h > 32768) return "frames_u8: need 1 <= w, h <= 32768 for every frame";
-        if (f.pitch < 3 * f.w) return "frames_u8: pitch < 3 * w";
-        if (f.order != MI355_FRAME_RGB && f.order != MI355_FRAME_BGR) return "frames_u8: channel order must be MI355_FRAME_RGB or MI355_FRAME_BGR";
+    static thread_local char why[160];
+    const char *bad = nullptr;
+    if (!host || B <= 0 || B > 65535) bad = "null table / need 1 <= B <= 65535";
+    else if (w < 2 || h < 2 || w > 32768 || h > 32768) bad = "need 2 <= w, h <= 32768 for the network input";
+    for (int b = 0; b < B && !bad; ++b) {
+        const Frame &f = host[b];
         FrameGeo g;
-        if (!frame_geometry(f.w, f.h, w, h, g)) return "frames_u8: degenerate aspect (resized side < 2)";
+        bad = Source::check_pointers(f);  // in the order the refusals have always had
+        if (!bad && (f.w < 1 || f.h < 1 || f.w > 32768 || f.h > 32768)) bad = "need 1 <= w, h <= 32768 for every frame";
+        if (!bad) bad = Source::check(f);
+        if (!bad && !frame_geometry(f.w, f.h, w, h, g)) bad = "degenerate aspect (resized side < 2)";
     }
-    return nullptr;
-}
-
-const char *frames_yuv_check(const mi355_frame_yuv *host, int B, int w, int h)
-{
-    if (!host || B <= 0 || B > 65535) return "frames_yuv: null table / need 1 <= B <= 65535";
-    if (w < 2 || h < 2 || w > 32768 || h > 32768) return "frames_yuv: need 2 <= w, h <= 32768 for the network input";
-    for (int b = 0; b < B; ++b) {
-        const mi355_frame_yuv &f = host[b];
-        if (!f.y || !f.uv) return "frames_yuv: null plane pointer";
-        if (f.w < 1 || f.h < 1 || f.w > 32768 || f.h > 32768) return "frames_yuv: need 1 <= w, h <= 32768 for every frame";
-        if (f.pitch_y < f.w) return "frames_yuv: pitch_y < w";
-        if (f.pitch_uv < 2 * ((f.w + 1) / 2)) return "frames_yuv: pitch_uv < 2 * ((w + 1) / 2)";
-        if (f.layout != MI355_YUV_NV12 && f.layout != MI355_YUV_NV21) return "frames_yuv: layout must be MI355_YUV_NV12 or MI355_YUV_NV21";
-        if (f.matrix < MI355_YUV_BT601 || f.matrix > MI355_YUV_BT709_FULL) return "frames_yuv: unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)";
-        FrameGeo g;
-        if (!frame_geometry(f.w, f.h, w, h, g)) return "frames_yuv: degenerate aspect (resized side < 2)";
-    }
-    return nullptr;
-}
-
-const char *frames_planar_check(const mi355_frame_planar *host, int B, int w, int h)
-{
-    if (!host || B <= 0 || B > 65535) return "frames_planar: null table / need 1 <= B <= 65535";
-    if (w < 2 || h < 2 || w > 32768 || h > 32768) return "frames_planar: need 2 <= w, h <= 32768 for the network input";
-    for (int b = 0; b < B; ++b) {
-        const mi355_frame_planar &f = host[b];
-        if (!f.plane[0] || !f.plane[1] || !f.plane[2]) return "frames_planar: null plane pointer";
-        if (f.w < 1 || f.h < 1 || f.w > 32768 || f.h > 32768) return "frames_planar: need 1 <= w, h <= 32768 for every frame";
-        if (f.format < MI355_PLANAR_I420 || f.format > MI355_PLANAR_BGR) return "frames_planar: unknown format (MI355_PLANAR_I420 .. _BGR)";
-        if (f.matrix < MI355_YUV_BT601 || f.matrix > MI355_YUV_BT709_FULL) return "frames_planar: unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)";
-        const bool rgb = f.format == MI355_PLANAR_RGB || f.format == MI355_PLANAR_BGR;
-        if (rgb && f.matrix != 0) return "frames_planar: matrix must be 0 with MI355_PLANAR_RGB / _BGR";
-        const int cw = rgb || f.format == MI355_PLANAR_I444 ? f.w : (f.w + 1) / 2;  // the width of planes 1 and 2
-        if (f.pitch[0] < f.w) return "frames_planar: pitch[0] < w";
-        if (f.pitch[1] < cw || f.pitch[2] < cw) return "frames_planar: pitch[1] or pitch[2] below the width of its plane";
-        FrameGeo g;
-        if (!frame_geometry(f.w, f.h, w, h, g)) return "frames_planar: degenerate aspect (resized side < 2)";
-    }
-    return nullptr;
+    if (!bad) return nullptr;
+    snprintf(why, sizeof(why), "%s: %s", Source::name, bad);
+    return why;
 }
 
 // about 2048 workgroups in all, at least one per image (image_minmax_batched_launch's sizing)
@@ -421,47 +399,29 @@ static unsigned quantize_grid_x(int w, int h)
     return (unsigned)((threads + 255) / 256);
 }
 
-int frames_u8_letterbox_minmax_launch(const mi355_frame_u8 *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st)
+template <class Source, class Frame>
+int frames_letterbox_minmax_launch(const Frame *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st)
 {
     if (image_minmax_seed_launch(mm, B, st) != MI355_OK) return MI355_EHIP;
-    hipLaunchKernelGGL(frames_u8_letterbox_minmax_kernel, dim3(minmax_grid_x(B, w, h), B), dim3(256), 0, st, table_dev, w, h, mm);
+    hipLaunchKernelGGL(frames_letterbox_minmax_kernel<Source>, dim3(minmax_grid_x(B, w, h), B), dim3(256), 0, st, table_dev, w, h, mm);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }
 
-int frames_u8_letterbox_quantize_launch(const mi355_frame_u8 *table_dev, int B, int w, int h, const float *scale_dev,
-                                        const uint8_t *zp_dev, uint8_t *out, hipStream_t st)
+template <class Source, class Frame>
+int frames_letterbox_quantize_launch(const Frame *table_dev, int B, int w, int h, const float *scale_dev,
+                                     const uint8_t *zp_dev, uint8_t *out, hipStream_t st)
 {
-    hipLaunchKernelGGL(frames_u8_letterbox_quantize_kernel, dim3(quantize_grid_x(w, h), B), dim3(256), 0, st, table_dev, w, h,
+    hipLaunchKernelGGL(frames_letterbox_quantize_kernel<Source>, dim3(quantize_grid_x(w, h), B), dim3(256), 0, st, table_dev, w, h,
                        scale_dev, zp_dev, out);
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }
 
-int frames_yuv_letterbox_minmax_launch(const mi355_frame_yuv *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st)
-{
-    if (image_minmax_seed_launch(mm, B, st) != MI355_OK) return MI355_EHIP;
-    hipLaunchKernelGGL(frames_yuv_letterbox_minmax_kernel, dim3(minmax_grid_x(B, w, h), B), dim3(256), 0, st, table_dev, w, h, mm);
-    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
-}
-
-int frames_yuv_letterbox_quantize_launch(const mi355_frame_yuv *table_dev, int B, int w, int h, const float *scale_dev,
-                                         const uint8_t *zp_dev, uint8_t *out, hipStream_t st)
-{
-    hipLaunchKernelGGL(frames_yuv_letterbox_quantize_kernel, dim3(quantize_grid_x(w, h), B), dim3(256), 0, st, table_dev, w, h,
-                       scale_dev, zp_dev, out);
-    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
-}
-
-int frames_planar_letterbox_minmax_launch(const mi355_frame_planar *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st)
-{
-    if (image_minmax_seed_launch(mm, B, st) != MI355_OK) return MI355_EHIP;
-    hipLaunchKernelGGL(frames_planar_letterbox_minmax_kernel, dim3(minmax_grid_x(B, w, h), B), dim3(256), 0, st, table_dev, w, h, mm);
-    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
-}
-
-int frames_planar_letterbox_quantize_launch(const mi355_frame_planar *table_dev, int B, int w, int h, const float *scale_dev,
-                                            const uint8_t *zp_dev, uint8_t *out, hipStream_t st)
-{
-    hipLaunchKernelGGL(frames_planar_letterbox_quantize_kernel, dim3(quantize_grid_x(w, h), B), dim3(256), 0, st, table_dev, w, h,
-                       scale_dev, zp_dev, out);
-    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
-}
+// the three kinds behind the C-ABI (shim.hip)
+#define FRAMES_KIND(S)                                                                                                                \
+    template const char *frames_check<S, S::Frame>(const S::Frame *, int, int, int);                                                            \
+    template int frames_letterbox_minmax_launch<S, S::Frame>(const S::Frame *, int, int, int, uint32_t *, hipStream_t);                         \
+    template int frames_letterbox_quantize_launch<S, S::Frame>(const S::Frame *, int, int, int, const float *, const uint8_t *, uint8_t *, \
+                                                               hipStream_t);
+FRAMES_KIND(SourceU8)
+FRAMES_KIND(SourceYUV)
+FRAMES_KIND(SourcePlanar)

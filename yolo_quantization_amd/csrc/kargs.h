@@ -239,18 +239,15 @@ int image_minmax_batched_launch(const float *x, int B, long count, uint32_t *mm,
 int image_quantize_per_image_launch(const float *x, int B, long count, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out,
                                     hipStream_t st);
 int image_minmax_seed_launch(uint32_t *mm, int B, hipStream_t st);
-const char *frames_u8_check(const mi355_frame_u8 *host, int B, int w, int h);
-int frames_u8_letterbox_minmax_launch(const mi355_frame_u8 *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st);
-int frames_u8_letterbox_quantize_launch(const mi355_frame_u8 *table_dev, int B, int w, int h, const float *scale_dev,
-                                        const uint8_t *zp_dev, uint8_t *out, hipStream_t st);
-const char *frames_yuv_check(const mi355_frame_yuv *host, int B, int w, int h);
-int frames_yuv_letterbox_minmax_launch(const mi355_frame_yuv *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st);
-int frames_yuv_letterbox_quantize_launch(const mi355_frame_yuv *table_dev, int B, int w, int h, const float *scale_dev,
-                                         const uint8_t *zp_dev, uint8_t *out, hipStream_t st);
-const char *frames_planar_check(const mi355_frame_planar *host, int B, int w, int h);
-int frames_planar_letterbox_minmax_launch(const mi355_frame_planar *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st);
-int frames_planar_letterbox_quantize_launch(const mi355_frame_planar *table_dev, int B, int w, int h, const float *scale_dev,
-                                            const uint8_t *zp_dev, uint8_t *out, hipStream_t st);
+// frames.hip: a kind of frames is a Source (Frame = its table entry in the C-ABI), instantiated there for these three
+struct SourceU8;      // mi355_frame_u8
+struct SourceYUV;     // mi355_frame_yuv
+struct SourcePlanar;  // mi355_frame_planar
+template <class Source, class Frame> const char *frames_check(const Frame *host, int B, int w, int h);  // NULL, or why the batch is refused
+template <class Source, class Frame> int frames_letterbox_minmax_launch(const Frame *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st);
+template <class Source, class Frame>
+int frames_letterbox_quantize_launch(const Frame *table_dev, int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out,
+                                     hipStream_t st);
 int yolo_detections_sizes_launch(const float *out, int B, int n, int classes, int h, int w, const float *biases, const int *mask,
                                  int netw, int neth, const int *imw_dev, const int *imh_dev, float thresh, int relative, float *recs,
                                  int max_recs, int *counts, hipStream_t st);

@@ -27,6 +27,28 @@ static int einval(const char *msg)
     return MI355_EINVAL;
 }
 
+// The two calls of every kind of frames (frames.hip): refuse a null argument with the call's own message, then what frames_check
+// refuses, else launch.
+template <class Source, class Frame>
+static int frames_minmax(const char *null_msg, const Frame *table_dev, const Frame *table_host, int B, int w, int h, float *minmax,
+                         void *stream)
+{
+    if (!table_dev || !minmax) return einval(null_msg);
+    const char *why = frames_check<Source>(table_host, B, w, h);
+    if (why) return einval(why);
+    return frames_letterbox_minmax_launch<Source>(table_dev, B, w, h, reinterpret_cast<uint32_t *>(minmax), (hipStream_t)stream);
+}
+
+template <class Source, class Frame>
+static int frames_quantize(const char *null_msg, const Frame *table_dev, const Frame *table_host, int B, int w, int h,
+                           const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream)
+{
+    if (!table_dev || !scale_dev || !zp_dev || !out_u8) return einval(null_msg);
+    const char *why = frames_check<Source>(table_host, B, w, h);
+    if (why) return einval(why);
+    return frames_letterbox_quantize_launch<Source>(table_dev, B, w, h, scale_dev, zp_dev, out_u8, (hipStream_t)stream);
+}
+
 extern "C" {
 
 const char *mi355_last_error(void) { return g_err; }
@@ -1048,55 +1070,38 @@ int mi355_image_quantize_per_image(const float *x_f32, int B, long count_per_ima
 int mi355_frames_u8_letterbox_minmax(const mi355_frame_u8 *table_dev, const mi355_frame_u8 *table_host, int B, int w, int h,
                                      float *minmax, void *stream)
 {
-    if (!table_dev || !minmax) return einval("frames_u8_letterbox_minmax: null");
-    const char *why = frames_u8_check(table_host, B, w, h);
-    if (why) return einval(why);
-    return frames_u8_letterbox_minmax_launch(table_dev, B, w, h, reinterpret_cast<uint32_t *>(minmax), (hipStream_t)stream);
+    return frames_minmax<SourceU8>("frames_u8_letterbox_minmax: null", table_dev, table_host, B, w, h, minmax, stream);
 }
 
 int mi355_frames_u8_letterbox_quantize(const mi355_frame_u8 *table_dev, const mi355_frame_u8 *table_host, int B, int w, int h,
                                        const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream)
 {
-    if (!table_dev || !scale_dev || !zp_dev || !out_u8) return einval("frames_u8_letterbox_quantize: null");
-    const char *why = frames_u8_check(table_host, B, w, h);
-    if (why) return einval(why);
-    return frames_u8_letterbox_quantize_launch(table_dev, B, w, h, scale_dev, zp_dev, out_u8, (hipStream_t)stream);
+    return frames_quantize<SourceU8>("frames_u8_letterbox_quantize: null", table_dev, table_host, B, w, h, scale_dev, zp_dev, out_u8, stream);
 }
 
 int mi355_frames_yuv_letterbox_minmax(const mi355_frame_yuv *table_dev, const mi355_frame_yuv *table_host, int B, int w, int h,
                                       float *minmax, void *stream)
 {
-    if (!table_dev || !minmax) return einval("frames_yuv: letterbox_minmax: null");
-    const char *why = frames_yuv_check(table_host, B, w, h);
-    if (why) return einval(why);
-    return frames_yuv_letterbox_minmax_launch(table_dev, B, w, h, reinterpret_cast<uint32_t *>(minmax), (hipStream_t)stream);
+    return frames_minmax<SourceYUV>("frames_yuv: letterbox_minmax: null", table_dev, table_host, B, w, h, minmax, stream);
 }
 
 int mi355_frames_yuv_letterbox_quantize(const mi355_frame_yuv *table_dev, const mi355_frame_yuv *table_host, int B, int w, int h,
                                         const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream)
 {
-    if (!table_dev || !scale_dev || !zp_dev || !out_u8) return einval("frames_yuv: letterbox_quantize: null");
-    const char *why = frames_yuv_check(table_host, B, w, h);
-    if (why) return einval(why);
-    return frames_yuv_letterbox_quantize_launch(table_dev, B, w, h, scale_dev, zp_dev, out_u8, (hipStream_t)stream);
+    return frames_quantize<SourceYUV>("frames_yuv: letterbox_quantize: null", table_dev, table_host, B, w, h, scale_dev, zp_dev, out_u8, stream);
 }
 
 int mi355_frames_planar_letterbox_minmax(const mi355_frame_planar *table_dev, const mi355_frame_planar *table_host, int B, int w, int h,
                                          float *minmax, void *stream)
 {
-    if (!table_dev || !minmax) return einval("frames_planar: letterbox_minmax: null");
-    const char *why = frames_planar_check(table_host, B, w, h);
-    if (why) return einval(why);
-    return frames_planar_letterbox_minmax_launch(table_dev, B, w, h, reinterpret_cast<uint32_t *>(minmax), (hipStream_t)stream);
+    return frames_minmax<SourcePlanar>("frames_planar: letterbox_minmax: null", table_dev, table_host, B, w, h, minmax, stream);
 }
 
 int mi355_frames_planar_letterbox_quantize(const mi355_frame_planar *table_dev, const mi355_frame_planar *table_host, int B, int w, int h,
                                            const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream)
 {
-    if (!table_dev || !scale_dev || !zp_dev || !out_u8) return einval("frames_planar: letterbox_quantize: null");
-    const char *why = frames_planar_check(table_host, B, w, h);
-    if (why) return einval(why);
-    return frames_planar_letterbox_quantize_launch(table_dev, B, w, h, scale_dev, zp_dev, out_u8, (hipStream_t)stream);
+    return frames_quantize<SourcePlanar>("frames_planar: letterbox_quantize: null", table_dev, table_host, B, w, h, scale_dev, zp_dev, out_u8,
+                                         stream);
 }
 
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream)

@@ -39,8 +39,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "darknet_q.h"
-#include "nv12_file.h"
-#include "planar_file.h"
+#include "raw_frame_file.h"
 
 static int find_arg(int argc, char **argv, const char *arg)
 {
@@ -126,26 +125,6 @@ static uint8_t *load_frame_u8(const char *path, int netc, int neth, int netw, in
     return rgb;
 }
 
-/* -frames nv12 / nv21: the file's two planes; the chroma plane starts at w * h */
-static uint8_t *load_frame_nv12(const char *path, int *w, int *h)
-{
-    char why[1024];
-    uint8_t *raw = load_nv12_file(path, w, h, why, sizeof(why));
-    if (!raw) error(why);
-    return raw;
-}
-
-/* -frames i420 / yv12 / i422 / i444: the file's three planes, p[k] pointing into the returned bytes */
-static uint8_t *load_frame_planar(const char *path, int format, int *w, int *h, const uint8_t *p[3])
-{
-    char why[1024];
-    size_t bytes[2];
-    uint8_t *raw = load_planar_file(path, format, w, h, bytes, why, sizeof(why));
-    if (!raw) error(why);
-    p[0] = raw; p[1] = raw + bytes[0]; p[2] = p[1] + bytes[1];
-    return raw;
-}
-
 static void dump_layer(const char *dir, network *net, int i)
 {
     layer *l = &net->layers[i];
@@ -169,13 +148,16 @@ static void dump_layer(const char *dir, network *net, int i)
     }
 }
 
+/* -frames u8: the sources go up as interleaved bytes (network_frames_u8_input_gpu), no host float conversion; nv12 | nv21: they are raw
+ * _<W>x<H>.nv12 files (network_frames_nv12_input_gpu); i420 | yv12 | i422 | i444: raw _<W>x<H>.<format> files
+ * (network_frames_planar_input_gpu) */
+enum { FRAMES_NONE, FRAMES_U8, FRAMES_NV12, FRAMES_PLANAR };
+
 typedef struct {
     const char *datacfg, *cfgfile, *weightfile, *filename, *dumpdir, *packed_in, *packed_out;
     const char *listfile;  /* -list: image paths, one per line, per-image input quantisation */
-    int frames_u8;         /* -frames u8: sources go up as interleaved bytes (network_frames_u8_input_gpu), no host float conversion */
-    int frames_yuv;        /* -frames nv12 | nv21: sources are raw _<W>x<H>.nv12 files (network_frames_nv12_input_gpu) */
+    int frames;            /* -frames: FRAMES_NONE, or how the sources go to the device (feed_frames) */
     int yuv_layout, yuv_matrix; /* MI355_YUV_NV12 / _NV21, MI355_YUV_BT601 .. _BT709_FULL (-matrix) */
-    int frames_planar;     /* -frames i420 | yv12 | i422 | i444: raw _<W>x<H>.<format> files (network_frames_planar_input_gpu) */
     int planar_format;     /* MI355_PLANAR_I420 .. MI355_PLANAR_I444 */
     float thresh, hier_thresh;
     int batch, accum, store, use_graph, iters, gpu, boxes, quiet, inflight;
@@ -209,6 +191,41 @@ static void print_detections(const detect_job *job, network *net, int b, int imw
     free_detections(dets, nboxes);
 }
 
+/* -frames: the batch's sources, one path per slot, through the entry point of the kind that is set: one call for the whole input step.
+ * A slot whose path is the slot's before it (one image in every slot, the free slots of a short last batch) shares its bytes, which
+ * then go up once.  imw, imh: the sources' sizes. */
+static void feed_frames(const detect_job *job, network *net, char *const *paths, int *imw, int *imh)
+{
+    const int B = net->batch;
+    uint8_t **raw = calloc((size_t)B, sizeof(uint8_t *));
+    const uint8_t **pl[3];
+    for (int k = 0; k < 3; ++k) pl[k] = calloc((size_t)B, sizeof(uint8_t *));
+    for (int b = 0; b < B; ++b) {
+        if (b && paths[b] == paths[b - 1]) {
+            for (int k = 0; k < 3; ++k) pl[k][b] = pl[k][b - 1];
+            imw[b] = imw[b - 1]; imh[b] = imh[b - 1];
+        } else if (job->frames == FRAMES_U8) {
+            pl[0][b] = raw[b] = load_frame_u8(paths[b], net->c, net->h, net->w, &imw[b], &imh[b]);
+        } else { /* the file's planes one after the other */
+            char why[1024];
+            size_t bytes[2];
+            raw[b] = load_raw_frame_file(paths[b], job->frames == FRAMES_NV12 ? RAW_FRAME_NV12 : job->planar_format, &imw[b], &imh[b], bytes,
+                                         why, sizeof(why));
+            if (!raw[b]) error(why);
+            pl[0][b] = raw[b]; pl[1][b] = raw[b] + bytes[0]; pl[2][b] = pl[1][b] + bytes[1];
+        }
+    }
+    if (job->frames == FRAMES_PLANAR)
+        network_frames_planar_input_gpu(net, pl[0], pl[1], pl[2], imw, imh, NULL, NULL, NULL, job->planar_format, job->yuv_matrix, 0);
+    else if (job->frames == FRAMES_NV12)
+        network_frames_nv12_input_gpu(net, pl[0], pl[1], imw, imh, NULL, NULL, job->yuv_layout, job->yuv_matrix, 0);
+    else
+        network_frames_u8_input_gpu(net, pl[0], imw, imh, NULL, MI355_FRAME_RGB, 0);
+    for (int b = 0; b < B; ++b) free(raw[b]);
+    for (int k = 0; k < 3; ++k) free(pl[k]);
+    free(raw);
+}
+
 /* -list <file>: one image path per line (the reference's valid= lists), dealt into batches of -batch with every image quantised on
  * its own (set_input_quantization_per_image).  Each image prints the block `detector test` prints for it alone.  The slots a short
  * last batch leaves free repeat its last image (they are not printed). */
@@ -233,35 +250,11 @@ static void test_detector_list(detect_job *job, network *net, char **names, int 
     int *imw = calloc((size_t)B, sizeof(int)), *imh = calloc((size_t)B, sizeof(int));
     for (int first = 0; first < np; first += B) {
         const int cnt = np - first < B ? np - first : B;
-        if (job->frames_planar) { /* the batch's raw planar frames, one call for the whole input step */
-            uint8_t **fr = calloc((size_t)B, sizeof(uint8_t *));
-            const uint8_t **pl[3];
-            for (int k = 0; k < 3; ++k) pl[k] = calloc((size_t)B, sizeof(uint8_t *));
-            for (int b = 0; b < B; ++b) {
-                const uint8_t *p[3];
-                fr[b] = load_frame_planar(paths[first + (b < cnt ? b : cnt - 1)], job->planar_format, &imw[b], &imh[b], p);
-                for (int k = 0; k < 3; ++k) pl[k][b] = p[k];
-            }
-            network_frames_planar_input_gpu(net, pl[0], pl[1], pl[2], imw, imh, NULL, NULL, NULL, job->planar_format, job->yuv_matrix, 0);
-            for (int b = 0; b < B; ++b) free(fr[b]);
-            for (int k = 0; k < 3; ++k) free(pl[k]);
-            free(fr);
-        } else if (job->frames_yuv) { /* the batch's raw video frames, one call for the whole input step */
-            uint8_t **fr = calloc((size_t)B, sizeof(uint8_t *));
-            const uint8_t **uv = calloc((size_t)B, sizeof(uint8_t *));
-            for (int b = 0; b < B; ++b) {
-                fr[b] = load_frame_nv12(paths[first + (b < cnt ? b : cnt - 1)], &imw[b], &imh[b]);
-                uv[b] = fr[b] + (size_t)imw[b] * imh[b];
-            }
-            network_frames_nv12_input_gpu(net, (const uint8_t *const *)fr, uv, imw, imh, NULL, NULL, job->yuv_layout, job->yuv_matrix, 0);
-            for (int b = 0; b < B; ++b) free(fr[b]);
-            free(fr); free(uv);
-        } else if (job->frames_u8) { /* the batch's frames as bytes, one call for the whole input step */
-            uint8_t **fr = calloc((size_t)B, sizeof(uint8_t *));
-            for (int b = 0; b < B; ++b) fr[b] = load_frame_u8(paths[first + (b < cnt ? b : cnt - 1)], net->c, net->h, net->w, &imw[b], &imh[b]);
-            network_frames_u8_input_gpu(net, (const uint8_t *const *)fr, imw, imh, NULL, MI355_FRAME_RGB, 0);
-            for (int b = 0; b < B; ++b) free(fr[b]);
-            free(fr);
+        if (job->frames) {
+            char **slot = calloc((size_t)B, sizeof(char *));
+            for (int b = 0; b < B; ++b) slot[b] = paths[first + (b < cnt ? b : cnt - 1)];
+            feed_frames(job, net, slot, imw, imh);
+            free(slot);
         } else {
             for (int b = 0; b < B; ++b) {
                 const char *path = paths[first + (b < cnt ? b : cnt - 1)];
@@ -338,32 +331,14 @@ static void test_detector(detect_job *job)
     }
     image im = {0, 0, 0, NULL};
     float *im_gpu = NULL;
-    if (job->frames_planar) { /* the raw planar frame in every batch slot (it goes up once), one call for the whole input step */
+    if (job->frames) { /* the source in every batch slot (it goes up once) */
         if (mi355_init(job->gpu)) { fprintf(stderr, "MI355: %s\n", mi355_last_error()); error("mi355_init (this build has no CPU data path)"); }
-        const uint8_t *p[3], **pl[3];
-        uint8_t *raw = load_frame_planar(job->filename, job->planar_format, &im.w, &im.h, p);
+        char **slot = calloc((size_t)job->batch, sizeof(char *));
         int *fw = calloc((size_t)job->batch, sizeof(int)), *fh = calloc((size_t)job->batch, sizeof(int));
-        for (int k = 0; k < 3; ++k) pl[k] = calloc((size_t)job->batch, sizeof(uint8_t *));
-        for (int b = 0; b < job->batch; ++b) { for (int k = 0; k < 3; ++k) pl[k][b] = p[k]; fw[b] = im.w; fh[b] = im.h; }
-        network_frames_planar_input_gpu(net, pl[0], pl[1], pl[2], fw, fh, NULL, NULL, NULL, job->planar_format, job->yuv_matrix, 0);
-        for (int k = 0; k < 3; ++k) free(pl[k]);
-        free(fw); free(fh); free(raw);
-    } else if (job->frames_yuv) { /* the raw video frame in every batch slot (it goes up once), one call for the whole input step */
-        if (mi355_init(job->gpu)) { fprintf(stderr, "MI355: %s\n", mi355_last_error()); error("mi355_init (this build has no CPU data path)"); }
-        uint8_t *raw = load_frame_nv12(job->filename, &im.w, &im.h);
-        const uint8_t **fy = calloc((size_t)job->batch, sizeof(uint8_t *)), **fuv = calloc((size_t)job->batch, sizeof(uint8_t *));
-        int *fw = calloc((size_t)job->batch, sizeof(int)), *fh = calloc((size_t)job->batch, sizeof(int));
-        for (int b = 0; b < job->batch; ++b) { fy[b] = raw; fuv[b] = raw + (size_t)im.w * im.h; fw[b] = im.w; fh[b] = im.h; }
-        network_frames_nv12_input_gpu(net, fy, fuv, fw, fh, NULL, NULL, job->yuv_layout, job->yuv_matrix, 0);
-        free(fy); free(fuv); free(fw); free(fh); free(raw);
-    } else if (job->frames_u8) { /* the source's bytes in every batch slot, one call for the whole input step */
-        if (mi355_init(job->gpu)) { fprintf(stderr, "MI355: %s\n", mi355_last_error()); error("mi355_init (this build has no CPU data path)"); }
-        uint8_t *rgb = load_frame_u8(job->filename, net->c, net->h, net->w, &im.w, &im.h);
-        const uint8_t **fr = calloc((size_t)job->batch, sizeof(uint8_t *));
-        int *fw = calloc((size_t)job->batch, sizeof(int)), *fh = calloc((size_t)job->batch, sizeof(int));
-        for (int b = 0; b < job->batch; ++b) { fr[b] = rgb; fw[b] = im.w; fh[b] = im.h; }
-        network_frames_u8_input_gpu(net, fr, fw, fh, NULL, MI355_FRAME_RGB, 0);
-        free(fr); free(fw); free(fh); free(rgb);
+        for (int b = 0; b < job->batch; ++b) slot[b] = (char *)job->filename;
+        feed_frames(job, net, slot, fw, fh);
+        im.w = fw[0]; im.h = fh[0];
+        free(slot); free(fw); free(fh);
     } else {
         im = load_image_any(job->filename, net->c, net->h, net->w);
         /* input path on the device: the float image goes up once, letterbox_image + the layer-0 quantiser run in HBM */
@@ -452,14 +427,14 @@ int main(int argc, char **argv)
     job.listfile = find_char_arg(argc, argv, "-list", NULL);
     const char *frames_s = find_char_arg(argc, argv, "-frames", NULL);
     const char *matrix_s = find_char_arg(argc, argv, "-matrix", NULL);
-    job.frames_u8 = frames_s && 0 == strcmp(frames_s, "u8");
-    job.frames_yuv = frames_s && (0 == strcmp(frames_s, "nv12") || 0 == strcmp(frames_s, "nv21"));
     static const char *const planar_known[4] = {"i420", "yv12", "i422", "i444"}; /* MI355_PLANAR_I420 .. MI355_PLANAR_I444 */
-    job.frames_planar = 0;
+    job.frames = FRAMES_NONE;
     job.planar_format = MI355_PLANAR_I420;
+    if (frames_s && 0 == strcmp(frames_s, "u8")) job.frames = FRAMES_U8;
+    if (frames_s && (0 == strcmp(frames_s, "nv12") || 0 == strcmp(frames_s, "nv21"))) job.frames = FRAMES_NV12;
     for (int k = 0; k < 4; ++k)
-        if (frames_s && 0 == strcmp(frames_s, planar_known[k])) { job.frames_planar = 1; job.planar_format = k; }
-    if (frames_s && !job.frames_u8 && !job.frames_yuv && !job.frames_planar)
+        if (frames_s && 0 == strcmp(frames_s, planar_known[k])) { job.frames = FRAMES_PLANAR; job.planar_format = k; }
+    if (frames_s && !job.frames)
         error("-frames: `u8` (8-bit interleaved frames), `nv12` and `nv21` (raw video frames, files named _<W>x<H>.nv12), `i420`, `yv12`, "
               "`i422` and `i444` (raw planar frames, files named _<W>x<H>.<format>) are known");
     job.yuv_layout = frames_s && 0 == strcmp(frames_s, "nv21") ? MI355_YUV_NV21 : MI355_YUV_NV12;
@@ -469,7 +444,7 @@ int main(int argc, char **argv)
         int m = -1;
         for (int k = 0; k < 4; ++k) if (0 == strcmp(matrix_s, known[k])) m = k;
         if (m < 0) error("-matrix: bt601 (the default), bt601f, bt709 and bt709f are known");
-        if (!job.frames_yuv && !job.frames_planar) error("-matrix goes with -frames nv12 | nv21 | i420 | yv12 | i422 | i444");
+        if (job.frames != FRAMES_NV12 && job.frames != FRAMES_PLANAR) error("-matrix goes with -frames nv12 | nv21 | i420 | yv12 | i422 | i444");
         job.yuv_matrix = m;
     }
     if (job.iters < 1) job.iters = 1;

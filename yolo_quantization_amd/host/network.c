@@ -687,61 +687,52 @@ void network_quantize_input_gpu(network *net)
     quantization_weights_and_activations_gpu(net, net->input_gpu);
 }
 
-/* ------------------------------------------------------------------------------------------- 8-bit frame input
+/* ------------------------------------------------------------------------------------------------- frame input
  * Two launches for the whole batch (frames.hip): letterbox + min / max, then letterbox + quantise; the float image exists in registers
  * only.  The (scale, zero point) branches are the float path's (input_pair_shared, input_pairs_per_image).  Interleaved RGB / BGR
- * frames, NV12 / NV21 frames and frames of three separate planes differ in their table, their staging and the pair of C-ABI calls;
- * everything else is shared. */
-enum { FR_U8, FR_YUV, FR_PLANAR }; /* the kind of frames an entry point feeds */
+ * frames, NV12 / NV21 frames and frames of three separate planes differ in their table entries, the planes they describe and the pair
+ * of C-ABI calls; the table, the staging arena and everything else are shared. */
+enum { FR_U8, FR_YUV, FR_PLANAR }; /* the kind of frames an entry point feeds (net->fr_kind) */
+static const size_t fr_entry_bytes[3] = {sizeof(mi355_frame_u8), sizeof(mi355_frame_yuv), sizeof(mi355_frame_planar)};
+
 static void fr_free(network *net)
 {
     if (net->fr_arena_gpu) mi355_free(net->fr_arena_gpu);
     if (net->fr_table_gpu) mi355_free(net->fr_table_gpu);
-    if (net->fr_yuv_gpu) mi355_free(net->fr_yuv_gpu);
-    if (net->fr_planar_gpu) mi355_free(net->fr_planar_gpu);
     if (net->fr_mm_gpu) mi355_free(net->fr_mm_gpu);
     if (net->fr_pair_gpu) mi355_free(net->fr_pair_gpu);
-    free(net->fr_table_host); free(net->fr_yuv_host); free(net->fr_planar_host); free(net->fr_mm_host); free(net->fr_pair_host);
+    free(net->fr_table_host); free(net->fr_mm_host); free(net->fr_pair_host);
     net->fr_arena_gpu = NULL; net->fr_table_gpu = NULL; net->fr_table_host = NULL;
-    net->fr_yuv_gpu = NULL; net->fr_yuv_host = NULL;
-    net->fr_planar_gpu = NULL; net->fr_planar_host = NULL;
     net->fr_mm_gpu = net->fr_mm_host = NULL;
     net->fr_pair_gpu = net->fr_pair_host = NULL;
     net->fr_arena_bytes = 0;
     net->fr_cap = 0;
 }
 
-/* The buffers every kind of frames shares, sized by the batch, and the table of the kind that is asked for: a network fed one kind
- * never holds another's table. */
-static void fr_alloc(network *net, int kind)
+/* Everything but the arena, sized by the batch; the one table holds entries of any kind (the planar entry is the largest). */
+static void fr_alloc(network *net)
 {
     const size_t B = (size_t)net->batch;
-    if (net->fr_cap != net->batch) {
-        fr_free(net);
-        check_mi355(mi355_alloc((void **)&net->fr_mm_gpu, 2 * sizeof(float) * B), "alloc minmax");
-        check_mi355(mi355_alloc(&net->fr_pair_gpu, 5 * B), "alloc input pairs");
-        net->fr_mm_host = calloc(2 * B, sizeof(float));
-        net->fr_pair_host = calloc(5, B);
-        net->fr_cap = net->batch;
-    }
-    if (kind == FR_PLANAR && !net->fr_planar_gpu) {
-        check_mi355(mi355_alloc((void **)&net->fr_planar_gpu, sizeof(mi355_frame_planar) * B), "alloc frame table");
-        net->fr_planar_host = calloc(B, sizeof(mi355_frame_planar));
-    } else if (kind == FR_YUV && !net->fr_yuv_gpu) {
-        check_mi355(mi355_alloc((void **)&net->fr_yuv_gpu, sizeof(mi355_frame_yuv) * B), "alloc frame table");
-        net->fr_yuv_host = calloc(B, sizeof(mi355_frame_yuv));
-    } else if (kind == FR_U8 && !net->fr_table_gpu) {
-        check_mi355(mi355_alloc((void **)&net->fr_table_gpu, sizeof(mi355_frame_u8) * B), "alloc frame table");
-        net->fr_table_host = calloc(B, sizeof(mi355_frame_u8));
-    }
+    if (net->fr_cap == net->batch) return;
+    fr_free(net);
+    check_mi355(mi355_alloc((void **)&net->fr_mm_gpu, 2 * sizeof(float) * B), "alloc minmax");
+    check_mi355(mi355_alloc(&net->fr_pair_gpu, 5 * B), "alloc input pairs");
+    check_mi355(mi355_alloc(&net->fr_table_gpu, sizeof(mi355_frame_planar) * B), "alloc frame table");
+    net->fr_mm_host = calloc(2 * B, sizeof(float));
+    net->fr_pair_host = calloc(5, B);
+    net->fr_table_host = calloc(B, sizeof(mi355_frame_planar));
+    net->fr_cap = net->batch;
 }
 
-static void fr_begin(network *net, int kind, const char *not_3_channels)
+/* The first touch of the device, after every refusal of an entry point.  Returns the host mirror of the table, [batch] entries of `kind`
+ * for the entry point to fill. */
+static void *fr_begin(network *net, int kind)
 {
-    if (net->c != 3) error(not_3_channels);
     check_mi355(mi355_init(net->gpu_index), "mi355_init");
     if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
-    fr_alloc(net, kind);
+    fr_alloc(net);
+    net->fr_kind = kind;
+    return net->fr_table_host;
 }
 
 static size_t fr_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
@@ -766,24 +757,46 @@ static const uint8_t *fr_stage(network *net, const uint8_t *src, size_t bytes, s
     return dst;
 }
 
-/* The common tail, the host mirror of the table filled with device pointers: table upload, min / max launch, the batch's one host
- * sync, the (scale, zero point) branch, quantiser launch, with the table and the calls of the frames' kind. */
-static void fr_finish(network *net, int kind)
+/* One plane of a frame in host memory, as it is: rows keep their pitch, the last row ends with its last sample. */
+typedef struct {
+    const uint8_t *host;
+    size_t row_bytes, rows, pitch;
+    const uint8_t **dev; /* the table entry's pointer to this plane: set to where the bytes went */
+} fr_plane;
+
+static size_t fr_plane_bytes(const fr_plane *p) { return (p->rows - 1) * p->pitch + p->row_bytes; }
+
+/* Host frames go up to the arena: planes[b * np + k] is plane k of the frame in slot b.  Frame by frame, plane by plane, each at a
+ * 256-byte boundary; one frame in several slots (`-batch B` of one image: the same pointers and geometry) goes up once. */
+static void fr_stage_frames(network *net, const fr_plane *planes, int np)
 {
     const int B = net->batch;
-    if (kind == FR_PLANAR) {
-        check_mi355(mi355_h2d(net->fr_planar_gpu, net->fr_planar_host, sizeof(mi355_frame_planar) * (size_t)B, net->stream), "upload frame table");
-        check_mi355(mi355_frames_planar_letterbox_minmax(net->fr_planar_gpu, net->fr_planar_host, B, net->w, net->h, net->fr_mm_gpu, net->stream),
-                    "mi355_frames_planar_letterbox_minmax");
-    } else if (kind == FR_YUV) {
-        check_mi355(mi355_h2d(net->fr_yuv_gpu, net->fr_yuv_host, sizeof(mi355_frame_yuv) * (size_t)B, net->stream), "upload frame table");
-        check_mi355(mi355_frames_yuv_letterbox_minmax(net->fr_yuv_gpu, net->fr_yuv_host, B, net->w, net->h, net->fr_mm_gpu, net->stream),
-                    "mi355_frames_yuv_letterbox_minmax");
-    } else {
-        check_mi355(mi355_h2d(net->fr_table_gpu, net->fr_table_host, sizeof(mi355_frame_u8) * (size_t)B, net->stream), "upload frame table");
-        check_mi355(mi355_frames_u8_letterbox_minmax(net->fr_table_gpu, net->fr_table_host, B, net->w, net->h, net->fr_mm_gpu, net->stream),
-                    "mi355_frames_u8_letterbox_minmax");
+    size_t need = 0, off = 0;
+    for (int i = 0; i < B * np; ++i) need += fr_round(fr_plane_bytes(&planes[i]));
+    fr_arena_reserve(net, need);
+    for (int b = 0; b < B; ++b) {
+        const fr_plane *f = planes + (size_t)b * np, *same = NULL;
+        for (int k = 0; k < b && !same; ++k) {
+            const fr_plane *g = planes + (size_t)k * np;
+            int eq = 1;
+            for (int i = 0; i < np; ++i)
+                eq &= g[i].host == f[i].host && g[i].row_bytes == f[i].row_bytes && g[i].rows == f[i].rows && g[i].pitch == f[i].pitch;
+            if (eq) same = g;
+        }
+        for (int i = 0; i < np; ++i) *f[i].dev = same ? *same[i].dev : fr_stage(net, f[i].host, fr_plane_bytes(&f[i]), &off);
     }
+}
+
+/* The common tail, the host mirror of the table filled with device pointers: table upload, min / max launch, the batch's one host
+ * sync, the (scale, zero point) branch, quantiser launch, with the calls of the frames' kind. */
+static void fr_finish(network *net)
+{
+    const int B = net->batch, kind = net->fr_kind, w = net->w, h = net->h;
+    const void *tg = net->fr_table_gpu, *th = net->fr_table_host;
+    check_mi355(mi355_h2d(net->fr_table_gpu, th, fr_entry_bytes[kind] * (size_t)B, net->stream), "upload frame table");
+    if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_planar_letterbox_minmax");
+    else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_yuv_letterbox_minmax");
+    else check_mi355(mi355_frames_u8_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_u8_letterbox_minmax");
     check_mi355(mi355_d2h(net->fr_mm_host, net->fr_mm_gpu, 2 * sizeof(float) * (size_t)B, net->stream), "minmax d2h");
     check_mi355(mi355_stream_sync(net->stream), "sync"); /* the batch's one host sync: every earlier upload is done too */
     const float *scale_dev;
@@ -803,47 +816,35 @@ static void fr_finish(network *net, int kind)
         scale_dev = (const float *)net->fr_pair_gpu;
         zp_dev = (const uint8_t *)net->fr_pair_gpu + 4 * (size_t)B;
     }
-    if (kind == FR_PLANAR)
-        check_mi355(mi355_frames_planar_letterbox_quantize(net->fr_planar_gpu, net->fr_planar_host, B, net->w, net->h, scale_dev, zp_dev,
-                                                           net->input_uint8_gpu, net->stream), "mi355_frames_planar_letterbox_quantize");
-    else if (kind == FR_YUV)
-        check_mi355(mi355_frames_yuv_letterbox_quantize(net->fr_yuv_gpu, net->fr_yuv_host, B, net->w, net->h, scale_dev, zp_dev,
-                                                        net->input_uint8_gpu, net->stream), "mi355_frames_yuv_letterbox_quantize");
-    else
-        check_mi355(mi355_frames_u8_letterbox_quantize(net->fr_table_gpu, net->fr_table_host, B, net->w, net->h, scale_dev, zp_dev,
-                                                       net->input_uint8_gpu, net->stream), "mi355_frames_u8_letterbox_quantize");
+    uint8_t *out = net->input_uint8_gpu;
+    if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_planar_letterbox_quantize");
+    else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_yuv_letterbox_quantize");
+    else check_mi355(mi355_frames_u8_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_u8_letterbox_quantize");
 }
 
+/* Every entry point: refuse what it must before the device is touched, fill its table entries with the caller's pointers, describe the
+ * planes, stage them unless they are on the device already, fr_finish. */
 void network_frames_u8_input_gpu(network *net, const uint8_t *const *frames, const int *w, const int *h, const int *pitch, int order,
                                  int frames_on_device)
 {
     const int B = net->batch;
     if (!frames || !w || !h) error("network_frames_u8_input_gpu: null frames / sizes");
-    fr_begin(net, FR_U8, "network_frames_u8_input_gpu: 8-bit frames feed 3-channel networks only");
-    mi355_frame_u8 *tab = net->fr_table_host;
-    size_t need = 0;
+    if (net->c != 3) error("network_frames_u8_input_gpu: 8-bit frames feed 3-channel networks only");
     for (int b = 0; b < B; ++b) {
         if (!frames[b]) error("network_frames_u8_input_gpu: null frame");
-        const int p = pitch ? pitch[b] : 3 * w[b];
-        if (w[b] < 1 || h[b] < 1 || p < 3 * w[b]) error("network_frames_u8_input_gpu: need w, h >= 1 and pitch >= 3 * w for every frame");
+        if (w[b] < 1 || h[b] < 1 || (pitch && pitch[b] < 3 * w[b])) error("network_frames_u8_input_gpu: need w, h >= 1 and pitch >= 3 * w for every frame");
+    }
+    mi355_frame_u8 *tab = fr_begin(net, FR_U8);
+    fr_plane *planes = calloc((size_t)B, sizeof(fr_plane));
+    for (int b = 0; b < B; ++b) {
         memset(&tab[b], 0, sizeof(tab[b]));
         tab[b].data = frames[b];
-        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch = p; tab[b].order = order;
-        need += fr_round((size_t)(h[b] - 1) * (size_t)p + 3 * (size_t)w[b]);
+        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch = pitch ? pitch[b] : 3 * w[b]; tab[b].order = order;
+        planes[b] = (fr_plane){frames[b], 3 * (size_t)w[b], (size_t)h[b], (size_t)tab[b].pitch, &tab[b].data};
     }
-    if (!frames_on_device) { /* the bytes as they are: rows keep their pitch, the last row ends with its last pixel */
-        fr_arena_reserve(net, need);
-        size_t off = 0;
-        for (int b = 0; b < B; ++b) {
-            const size_t bytes = (size_t)(h[b] - 1) * (size_t)tab[b].pitch + 3 * (size_t)w[b];
-            int same = -1; /* one frame in several slots (`-batch B` of one image) goes up once */
-            for (int k = 0; k < b && same < 0; ++k)
-                if (frames[k] == frames[b] && w[k] == w[b] && h[k] == h[b] && tab[k].pitch == tab[b].pitch) same = k;
-            if (same >= 0) { tab[b].data = tab[same].data; continue; }
-            tab[b].data = fr_stage(net, frames[b], bytes, &off);
-        }
-    }
-    fr_finish(net, FR_U8);
+    if (!frames_on_device) fr_stage_frames(net, planes, 1);
+    free(planes);
+    fr_finish(net);
 }
 
 void network_frames_nv12_input_gpu(network *net, const uint8_t *const *y, const uint8_t *const *uv, const int *w, const int *h,
@@ -851,37 +852,27 @@ void network_frames_nv12_input_gpu(network *net, const uint8_t *const *y, const 
 {
     const int B = net->batch;
     if (!y || !uv || !w || !h) error("network_frames_nv12_input_gpu: null planes / sizes");
-    fr_begin(net, FR_YUV, "network_frames_nv12_input_gpu: NV12 / NV21 frames feed 3-channel networks only");
-    mi355_frame_yuv *tab = net->fr_yuv_host;
-    size_t need = 0;
+    if (net->c != 3) error("network_frames_nv12_input_gpu: NV12 / NV21 frames feed 3-channel networks only");
     for (int b = 0; b < B; ++b) {
         if (!y[b] || !uv[b]) error("network_frames_nv12_input_gpu: null plane");
         if (w[b] < 1 || h[b] < 1) error("network_frames_nv12_input_gpu: need w, h >= 1 for every frame");
+        if ((pitch_y && pitch_y[b] < w[b]) || (pitch_uv && pitch_uv[b] < 2 * ((w[b] + 1) / 2)))
+            error("network_frames_nv12_input_gpu: need pitch_y >= w and pitch_uv >= 2 * ((w + 1) / 2) for every frame");
+    }
+    mi355_frame_yuv *tab = fr_begin(net, FR_YUV);
+    fr_plane *planes = calloc(2 * (size_t)B, sizeof(fr_plane));
+    for (int b = 0; b < B; ++b) {
         const int cw2 = 2 * ((w[b] + 1) / 2), ch = (h[b] + 1) / 2;
-        const int py = pitch_y ? pitch_y[b] : w[b], puv = pitch_uv ? pitch_uv[b] : cw2;
-        if (py < w[b] || puv < cw2) error("network_frames_nv12_input_gpu: need pitch_y >= w and pitch_uv >= 2 * ((w + 1) / 2) for every frame");
         memset(&tab[b], 0, sizeof(tab[b]));
         tab[b].y = y[b]; tab[b].uv = uv[b];
-        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch_y = py; tab[b].pitch_uv = puv;
+        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch_y = pitch_y ? pitch_y[b] : w[b]; tab[b].pitch_uv = pitch_uv ? pitch_uv[b] : cw2;
         tab[b].layout = layout; tab[b].matrix = matrix;
-        need += fr_round((size_t)(h[b] - 1) * (size_t)py + (size_t)w[b]) + fr_round((size_t)(ch - 1) * (size_t)puv + (size_t)cw2);
+        planes[2 * b] = (fr_plane){y[b], (size_t)w[b], (size_t)h[b], (size_t)tab[b].pitch_y, &tab[b].y};
+        planes[2 * b + 1] = (fr_plane){uv[b], (size_t)cw2, (size_t)ch, (size_t)tab[b].pitch_uv, &tab[b].uv};
     }
-    if (!frames_on_device) { /* both planes as they are: rows keep their pitch, a plane's last row ends with its last sample */
-        fr_arena_reserve(net, need);
-        size_t off = 0;
-        for (int b = 0; b < B; ++b) {
-            const int cw2 = 2 * ((w[b] + 1) / 2), ch = (h[b] + 1) / 2;
-            int same = -1; /* one frame in several slots goes up once */
-            for (int k = 0; k < b && same < 0; ++k)
-                if (y[k] == y[b] && uv[k] == uv[b] && w[k] == w[b] && h[k] == h[b] && tab[k].pitch_y == tab[b].pitch_y &&
-                    tab[k].pitch_uv == tab[b].pitch_uv)
-                    same = k;
-            if (same >= 0) { tab[b].y = tab[same].y; tab[b].uv = tab[same].uv; continue; }
-            tab[b].y = fr_stage(net, y[b], (size_t)(h[b] - 1) * (size_t)tab[b].pitch_y + (size_t)w[b], &off);
-            tab[b].uv = fr_stage(net, uv[b], (size_t)(ch - 1) * (size_t)tab[b].pitch_uv + (size_t)cw2, &off);
-        }
-    }
-    fr_finish(net, FR_YUV);
+    if (!frames_on_device) fr_stage_frames(net, planes, 2);
+    free(planes);
+    fr_finish(net);
 }
 
 void network_frames_planar_input_gpu(network *net, const uint8_t *const *p0, const uint8_t *const *p1, const uint8_t *const *p2,
@@ -889,7 +880,7 @@ void network_frames_planar_input_gpu(network *net, const uint8_t *const *p0, con
                                      int format, int matrix, int frames_on_device)
 {
     const int B = net->batch;
-    const uint8_t *const *const planes[3] = {p0, p1, p2};
+    const uint8_t *const *const src[3] = {p0, p1, p2};
     const int *const pitches[3] = {pitch0, pitch1, pitch2};
     if (!p0 || !p1 || !p2 || !w || !h) error("network_frames_planar_input_gpu: null planes / sizes");
     if (format < MI355_PLANAR_I420 || format > MI355_PLANAR_BGR) error("network_frames_planar_input_gpu: unknown format (MI355_PLANAR_I420 .. _BGR)");
@@ -898,43 +889,27 @@ void network_frames_planar_input_gpu(network *net, const uint8_t *const *p0, con
     if (rgb && matrix != 0) error("network_frames_planar_input_gpu: matrix must be 0 with MI355_PLANAR_RGB / _BGR");
     const int half_w = !rgb && format != MI355_PLANAR_I444, half_h = format == MI355_PLANAR_I420 || format == MI355_PLANAR_YV12;
     if (net->c != 3) error("network_frames_planar_input_gpu: planar frames feed 3-channel networks only");
-    for (int b = 0; b < B; ++b) { /* every refusal comes before the device is touched */
+    for (int b = 0; b < B; ++b) {
         if (!p0[b] || !p1[b] || !p2[b]) error("network_frames_planar_input_gpu: null plane");
         if (w[b] < 1 || h[b] < 1 || w[b] > 32768 || h[b] > 32768) error("network_frames_planar_input_gpu: need 1 <= w, h <= 32768 for every frame");
         for (int k = 0; k < 3; ++k)
             if (pitches[k] && pitches[k][b] < (k && half_w ? (w[b] + 1) / 2 : w[b]))
                 error("network_frames_planar_input_gpu: need pitch >= the width of its plane for every plane");
     }
-    fr_begin(net, FR_PLANAR, "network_frames_planar_input_gpu: planar frames feed 3-channel networks only");
-    mi355_frame_planar *tab = net->fr_planar_host;
-    size_t need = 0;
+    mi355_frame_planar *tab = fr_begin(net, FR_PLANAR);
+    fr_plane *planes = calloc(3 * (size_t)B, sizeof(fr_plane));
     for (int b = 0; b < B; ++b) {
         memset(&tab[b], 0, sizeof(tab[b]));
         tab[b].w = w[b]; tab[b].h = h[b]; tab[b].format = format; tab[b].matrix = matrix;
         for (int k = 0; k < 3; ++k) { /* plane 0 is w x h, planes 1 and 2 the format's chroma size */
             const int pw = k && half_w ? (w[b] + 1) / 2 : w[b], ph = k && half_h ? (h[b] + 1) / 2 : h[b];
-            const int p = pitches[k] ? pitches[k][b] : pw;
-            tab[b].plane[k] = planes[k][b]; tab[b].pitch[k] = p;
-            need += fr_round((size_t)(ph - 1) * (size_t)p + (size_t)pw);
+            tab[b].plane[k] = src[k][b]; tab[b].pitch[k] = pitches[k] ? pitches[k][b] : pw;
+            planes[3 * b + k] = (fr_plane){src[k][b], (size_t)pw, (size_t)ph, (size_t)tab[b].pitch[k], &tab[b].plane[k]};
         }
     }
-    if (!frames_on_device) { /* three planes as they are: rows keep their pitch, a plane's last row ends with its last sample */
-        fr_arena_reserve(net, need);
-        size_t off = 0;
-        for (int b = 0; b < B; ++b) {
-            int same = -1; /* one frame in several slots goes up once */
-            for (int k = 0; k < b && same < 0; ++k)
-                if (p0[k] == p0[b] && p1[k] == p1[b] && p2[k] == p2[b] && w[k] == w[b] && h[k] == h[b] &&
-                    0 == memcmp(tab[k].pitch, tab[b].pitch, sizeof(tab[b].pitch)))
-                    same = k;
-            if (same >= 0) { memcpy(tab[b].plane, tab[same].plane, sizeof(tab[b].plane)); continue; }
-            for (int k = 0; k < 3; ++k) {
-                const int pw = k && half_w ? (w[b] + 1) / 2 : w[b], ph = k && half_h ? (h[b] + 1) / 2 : h[b];
-                tab[b].plane[k] = fr_stage(net, planes[k][b], (size_t)(ph - 1) * (size_t)tab[b].pitch[k] + (size_t)pw, &off);
-            }
-        }
-    }
-    fr_finish(net, FR_PLANAR);
+    if (!frames_on_device) fr_stage_frames(net, planes, 3);
+    free(planes);
+    fr_finish(net);
 }
 
 void set_batch_network(network *net, int b)
