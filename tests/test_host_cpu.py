@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import oracle
+from epilogue_points import read_ept
 from yolo_quantization_amd import binding, synth
 
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -404,14 +405,11 @@ def test_pack_epilogue_table(n, c, act):
     sv = 2.0 ** -s.astype(np.float64)
     zp_act = 23 if act != "linear" else 128
     blob = binding.conv_pack(wq, zp_w, c, 3, bias, mv, sv, binding.ACT[act], zp_act)
-    off_ept = int(np.frombuffer(blob, np.uint64, 1, 144)[0])
-    total = int(np.frombuffer(blob, np.uint64, 1, 96)[0])
+    t = read_ept(blob)   # (tests/epilogue_points.py: the reader shared with the epilogue-point tests)
+    off_ept, total, mpad, key, flags, ent = t["off"], t["total"], t["mpad"], t["key"], t["flags"], t["ent"]
     assert off_ept and total == blob.size
-    mpad = int(np.frombuffer(blob, np.int32, 1, 16)[0])
-    key, flags = [int(v) for v in np.frombuffer(blob, np.uint32, 2, off_ept)]
     kact = binding.ACT["linear"] if act == "relu" else binding.ACT[act]
     assert key == (0x45500000 | (kact << 8) | zp_act)
-    ent = np.frombuffer(blob, np.int32, mpad * 8, off_ept + 16).reshape(mpad, 8)
     oact = oracle.ACT[act]
     accepted = 0
     for ch in range(n):
@@ -443,7 +441,7 @@ def test_pack_epilogue_table(n, c, act):
                 assert q == (f + 1 if (a < 0 and (a * m0) % (1 << (32 + sh))) else f), (ch, a)
     assert bool(flags & 2) == (accepted < n)
     if c == 3 and act == "leaky":  # the first layer's byte table: entry i <-> f (all channels integer) or q = i - 3072
-        lut = np.frombuffer(blob, np.uint8, 4096, off_ept + 16 + 32 * mpad)
+        lut = np.frombuffer(blob, np.uint8, 4096, t["lut_off"])
         for i in (0, 1, 3000, 3071, 3072, 3073, 3300, 4095):
             v = i - 3072
             q = v + 1 if (v < 0 and not (flags & 2)) else v
