@@ -198,6 +198,14 @@ struct network {
     float *fr_mm_gpu, *fr_mm_host; /* [fr_cap][2] max, min */
     void *fr_pair_gpu, *fr_pair_host; /* shared-scale mode: [fr_cap] float scale | [fr_cap] uint8 zero point, image 0's in every slot */
     int fr_cap;
+    /* Batched box decode (network_yolo_detections_batch_gpu): lazily allocated, grown when needed, freed with the network and on
+     * re-batch.  A replica owns its own. */
+    int *detb_ints_gpu, *detb_ints_host; /* [2][batch] source sizes | counts [batch][nheads] | offsets [batch + 1] */
+    int *detb_work_gpu;                  /* mi355_yolo_detections_batch's scratch */
+    float *detb_recs_gpu;                /* packed records of the batch */
+    int detb_batch, detb_nheads;         /* what detb_ints_* are sized for */
+    long detb_work_ints;
+    size_t detb_recs_cap;                /* records detb_recs_gpu holds */
 };
 
 /* ---- construction / IO ------------------------------------------------------------------------------------ */
@@ -303,6 +311,25 @@ void network_yolo_detections_gpu(network *net, int i, int imw, int imh, float th
 void network_yolo_detections_gpu_sizes(network *net, int i, const int *imw, const int *imh, float thresh, int relative, float *recs,
                                        int max_recs, int *counts);
 
+/* The same decode for ALL yolo layers and the whole batch in one call (mi355_yolo_detections_batch): image b's records, packed back to
+ * back, are recs[offsets[b] .. offsets[b + 1]) -- records of 6 + classes floats as above, in the reference's order without a host sort:
+ * yolo layers in network order, rank ascending inside a layer (rank = cell * n + anchor within the record's own layer).
+ *   imw, imh        [batch] source sizes (host)
+ *   max_per_image   an image keeps its FIRST max_per_image records of that order; <= 0: every candidate, which never truncates
+ *   recs            host, room for batch * min(max_per_image, candidates) records, candidates = sum of n * h * w over the yolo layers
+ *                   (network_detections_batch_shape) -- with max_per_image <= 0 that is batch * candidates * (6 + classes) floats,
+ *                   56 MB for yolov3-tiny at 416, batch 64, 80 classes; the device buffer kept on the network has the same size
+ *   counts          host [batch][nheads]: detections FOUND per image and yolo layer (found may exceed kept)
+ *   offsets         host [batch + 1]
+ * Per call: one upload (the sizes), three launches, one download of counts + offsets, one download of offsets[batch] records, two
+ * synchronisations of net->stream (one when nothing was found), whatever the batch and the number of yolo layers.
+ * Returns 0, or MI355_EINVAL with a message on stderr and nothing launched: no yolo layer, more than MI355_YOLO_MAX_HEADS of them, yolo
+ * layers with differing `classes`, a size < 1. */
+int network_yolo_detections_batch_gpu(network *net, const int *imw, const int *imh, float thresh, int relative, int max_per_image,
+                                      float *recs, int *counts, int *offsets);
+/* number of yolo layers, their common `classes`, candidates per image; 0 or MI355_EINVAL as above.  Host only. */
+int network_detections_batch_shape(network *net, int *nheads, int *classes, int *candidates);
+
 /* ---- detections (what `detector test` does after network_predict; ref: include/darknet.h:658-669) -------------------- */
 typedef struct { float x, y, w, h; } box;
 typedef struct detection {
@@ -317,6 +344,17 @@ typedef struct detection {
 detection *get_network_boxes(network *net, int w, int h, float thresh, float hier, int *map, int relative, int *num);
 detection *get_network_boxes_batch(network *net, int b, int w, int h, float thresh, float hier, int *map, int relative, int *num);
 void free_detections(detection *dets, int n);
+/* get_network_boxes_batch for every image of the batch from ONE decode: dets[b] (num[b] entries; dets, num: [batch], the caller's) is
+ * the array get_network_boxes_batch(net, b, imw[b], imh[b], thresh, ., ., relative, .) returns, with do_nms_sort(dets[b], num[b], classes,
+ * nms) applied when nms > 0.  max_per_image as in network_yolo_detections_batch_gpu (<= 0: every candidate; the host copy holds only the
+ * records that exist).  Returns 0 or MI355_EINVAL like that call (dets[b] = NULL, num[b] = 0 then). */
+int network_detections_batch(network *net, const int *imw, const int *imh, float thresh, int relative, float nms, int max_per_image,
+                             detection **dets, int *num);
+void free_detections_batch(detection **dets, int *num, int batch); /* frees every dets[b], not the two arrays */
+/* The device-free half of it: packed records (B images, offsets [B + 1]) -> detection arrays -> NMS. */
+void detections_from_records(const float *recs, const int *offsets, int B, int classes, float nms, detection **dets, int *num);
+/* flat copies of a detection array for FFI callers: boxes [n][4], objectness [n], probs [n][classes], in the array's order */
+void detections_to_arrays(const detection *dets, int n, int classes, float *boxes, float *objectness, float *probs);
 void do_nms_sort(detection *dets, int total, int classes, float thresh); /* ref: src/box.c:58-89 */
 void do_nms_sort_arrays(const float *boxes, float *probs, const float *objectness, int n, int classes, float thresh);
 float box_iou(box a, box b);

@@ -422,6 +422,36 @@ int mi355_yolo_detections_sizes(const float *yolo_out, int B, int n, int classes
                                 const int *mask, int netw, int neth, const int *imw_dev, const int *imh_dev, float thresh,
                                 int relative, float *recs, int max_recs, int *counts, void *stream);
 
+/* The same decode for EVERY yolo layer ("head") of a network and every image of the batch in one call, records in the reference's order
+ * straight from the device: no atomic counter decides a slot, no host sort is needed.
+ *   heads[nheads]   HOST array, 1 <= nheads <= MI355_YOLO_MAX_HEADS, in network order (it travels to the kernels by value, like every
+ *                   argument struct of this library); the pointers in it are device pointers as in mi355_yolo_detections
+ *   imw_dev, imh_dev  [B] letterbox source sizes, device memory
+ *   recs            device, records of 6 + classes floats in the format above; rank = cell * n + anchor within the record's OWN head
+ *   counts          device [B][nheads]: detections FOUND per image and head (may exceed what is kept)
+ *   offsets         device [B + 1]: image b's kept records are recs[offsets[b] .. offsets[b + 1]), packed back to back over the batch
+ *   work            device scratch of at least mi355_yolo_detections_batch_work_ints(heads, nheads, B) ints (work_ints: what is there)
+ * Order inside an image: heads as given, rank ascending inside a head -- the order of the reference's loops (ref: src/network.c:615-638).
+ * An image keeps the FIRST max_per_image records of that order (deterministic); nothing is written at or beyond recs[offsets[B]], and
+ * offsets[B] <= B * min(max_per_image, sum over heads of n * H * W), which is the capacity recs must have.  Every field of a record
+ * carries the bits mi355_yolo_detections_sizes writes for it.  Three launches, whatever B and nheads: count per block of 256 cells,
+ * one scan over (image, head, block), one write pass that places every record.
+ * MI355_EINVAL before any launch: nheads outside 1..MI355_YOLO_MAX_HEADS, a head with n * H * W >= 2^24 (rank is a float) or n, H,
+ * W < 1, classes < 1, max_per_image < 1, B outside 1..65535, B * candidates per image >= 2^31, a null pointer, work_ints too small.
+ * A new struct and new calls: MI355_ABI_VERSION is unchanged. */
+#define MI355_YOLO_MAX_HEADS 8
+typedef struct mi355_yolo_head {
+    const float *yolo_out;  /* DEVICE: the yolo layer's output [B][n * (classes + 5)][H * W] */
+    const float *anchors;   /* DEVICE: [2 * num] */
+    const int *mask;        /* DEVICE: [n] */
+    int n, H, W;
+    int reserved;           /* zero */
+} mi355_yolo_head;
+long mi355_yolo_detections_batch_work_ints(const mi355_yolo_head *heads, int nheads, int B); /* 0 on bad arguments */
+int mi355_yolo_detections_batch(const mi355_yolo_head *heads, int nheads, int B, int classes, int netw, int neth, const int *imw_dev,
+                                const int *imh_dev, float thresh, int relative, int max_per_image, float *recs, int *counts,
+                                int *offsets, int *work, long work_ints, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,15 @@ class FramePlanar(C.Structure):
 
 PLANAR_FORMAT = {"i420": 0, "yv12": 1, "i422": 2, "i444": 3, "rgb": 4, "bgr": 5}  # MI355_PLANAR_I420 .. MI355_PLANAR_BGR
 
+
+class YoloHead(C.Structure):
+    """mi355_yolo_head: one yolo layer of mi355_yolo_detections_batch (yolo_out, anchors, mask: DEVICE pointers)."""
+    _fields_ = [("yolo_out", C.c_void_p), ("anchors", C.c_void_p), ("mask", C.c_void_p), ("n", C.c_int), ("H", C.c_int), ("W", C.c_int),
+                ("reserved", C.c_int)]
+
+
+YOLO_MAX_HEADS = 8  # MI355_YOLO_MAX_HEADS
+
 _shim = None
 _host = None
 
@@ -140,6 +149,10 @@ def shim():
         L.mi355_frames_planar_letterbox_minmax.argtypes = [vp, C.POINTER(FramePlanar), ci, ci, ci, vp, vp]
         L.mi355_frames_planar_letterbox_quantize.argtypes = [vp, C.POINTER(FramePlanar), ci, ci, ci, vp, vp, vp, vp]
         L.mi355_yolo_detections_sizes.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, C.c_float, ci, vp, ci, vp, vp]
+        L.mi355_yolo_detections_batch_work_ints.restype = C.c_long
+        L.mi355_yolo_detections_batch_work_ints.argtypes = [C.POINTER(YoloHead), ci, ci]
+        L.mi355_yolo_detections_batch.argtypes = [C.POINTER(YoloHead), ci, ci, ci, ci, ci, vp, vp, C.c_float, ci, ci, vp, vp, vp, vp,
+                                                  C.c_long, vp]
         _shim = L
     return _shim
 
@@ -423,6 +436,15 @@ def host():
         L.network_layer0_entry.argtypes = [vp, C.c_float, C.c_uint8, vp]
         L.dnq_net_graph.argtypes = [vp]
         L.dnq_net_graph.restype = vp
+        L.dnq_net_detb_counts.argtypes = [vp]
+        L.dnq_net_detb_counts.restype = vp
+        L.network_detections_batch_shape.argtypes = [vp, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+        L.network_yolo_detections_batch_gpu.argtypes = [vp, vp, vp, C.c_float, ci, ci, vp, vp, vp]
+        L.network_detections_batch.argtypes = [vp, vp, vp, C.c_float, ci, C.c_float, ci, C.POINTER(vp), C.POINTER(ci)]
+        L.free_detections_batch.argtypes = [C.POINTER(vp), C.POINTER(ci), ci]
+        L.detections_from_records.argtypes = [vp, vp, ci, ci, C.c_float, C.POINTER(vp), C.POINTER(ci)]
+        L.detections_to_arrays.argtypes = [vp, ci, ci, vp, vp, vp]
+        L.do_nms_sort_arrays.argtypes = [vp, vp, vp, ci, ci, C.c_float]
         _host = L
     return _host
 
@@ -736,6 +758,67 @@ class Net:
         self.H.network_yolo_detections_gpu_sizes(self.h, i, w.ctypes.data, h.ctypes.data, C.c_float(thresh), int(relative),
                                                  recs.ctypes.data, max_recs, counts.ctypes.data)
         return counts, recs
+
+    def detections_shape(self):
+        """(number of yolo layers, their common class count, candidates per image) of the batched decode; raises MI355Error for a
+        network it refuses (no yolo layer, more than YOLO_MAX_HEADS, differing class counts)."""
+        nh, cl, ca = C.c_int(), C.c_int(), C.c_int()
+        rc = self.H.network_detections_batch_shape(self.h, C.byref(nh), C.byref(cl), C.byref(ca))
+        if rc != 0:
+            raise MI355Error(f"network_detections_batch_shape: code {rc} (the yolo layers of this network cannot be decoded together)")
+        return nh.value, cl.value, ca.value
+
+    def _sizes(self, imw, imh):
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(imw, np.int32), (self.batch,)))
+        h = np.ascontiguousarray(np.broadcast_to(np.asarray(imh, np.int32), (self.batch,)))
+        return w, h
+
+    def detections_batch(self, imw, imh, thresh, relative=1, max_per_image=None):
+        """Box decode of every yolo layer and every image in one call (network_yolo_detections_batch_gpu): (counts [B, nheads] found per
+        image and layer, offsets [B + 1], records [total, 6 + classes]); image b's records are recs[offsets[b]:offsets[b + 1]], yolo
+        layers in network order, rank ascending inside a layer.  imw / imh: scalars or length-B sequences.  max_per_image: an image
+        keeps its first max_per_image records (None: all)."""
+        nh, classes, cand = self.detections_shape()
+        w, h = self._sizes(imw, imh)
+        cap = cand if max_per_image is None or max_per_image <= 0 else min(int(max_per_image), cand)
+        recs = np.zeros((self.batch * cap, 6 + classes), np.float32)
+        counts = np.zeros((self.batch, nh), np.int32)
+        offsets = np.zeros(self.batch + 1, np.int32)
+        rc = self.H.network_yolo_detections_batch_gpu(self.h, w.ctypes.data, h.ctypes.data, C.c_float(thresh), int(relative), cap,
+                                                      recs.ctypes.data, counts.ctypes.data, offsets.ctypes.data)
+        if rc != 0:
+            raise MI355Error(f"network_yolo_detections_batch_gpu: code {rc} (refused: see stderr)")
+        return counts, offsets, recs[:offsets[-1]].copy()
+
+    def detect(self, imw, imh, thresh=.5, nms=.45, relative=True, max_per_image=None):
+        """Final boxes of every image of the batch (network_detections_batch, then the host's do_nms_sort on each image): a list of
+        dicts, one per image: boxes [k, 4] (x, y, w, h), objectness [k], probs [k, classes] with the scores NMS suppressed set to 0,
+        rows in the reference's order (yolo layers in network order, rank ascending); found = candidates above thresh, kept = k."""
+        nh, classes, cand = self.detections_shape()
+        w, h = self._sizes(imw, imh)
+        B = self.batch
+        dets, num = (C.c_void_p * B)(), (C.c_int * B)()
+        rc = self.H.network_detections_batch(self.h, w.ctypes.data, h.ctypes.data, C.c_float(thresh), int(bool(relative)), C.c_float(0.0),
+                                             0 if max_per_image is None else int(max_per_image), dets, num)
+        if rc != 0:
+            raise MI355Error(f"network_detections_batch: code {rc} (refused: see stderr)")
+        counts = self._last_counts()
+        out = []
+        for b in range(B):
+            k = num[b]
+            boxes, obj, probs = np.zeros((k, 4), np.float32), np.zeros(k, np.float32), np.zeros((k, classes), np.float32)
+            self.H.detections_to_arrays(dets[b], k, classes, boxes.ctypes.data, obj.ctypes.data, probs.ctypes.data)
+            if nms and nms > 0:  # rows keep their place, suppressed scores become 0
+                self.H.do_nms_sort_arrays(boxes.ctypes.data, probs.ctypes.data, obj.ctypes.data, k, classes, C.c_float(nms))
+            out.append(dict(boxes=boxes, objectness=obj, probs=probs, found=int(counts[b].sum()), kept=int(k)))
+        self.H.free_detections_batch(dets, num, B)
+        return out
+
+    def _last_counts(self):
+        """counts [B, nheads] of the last batched decode (the host's staging copy)"""
+        nh = self.detections_shape()[0]
+        p = self.H.dnq_net_detb_counts(self.h)
+        return _as(p, self.batch * nh, C.c_int).copy().reshape(self.batch, nh)
 
     def layer0_entry(self, scale, zp):
         """Host-side bank entry of layer 0 for one (input scale, zero point): the bytes the per-image path uploads for it."""

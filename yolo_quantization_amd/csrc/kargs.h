@@ -252,6 +252,24 @@ int yolo_detections_sizes_launch(const float *out, int B, int n, int classes, in
                                  int netw, int neth, const int *imw_dev, const int *imh_dev, float thresh, int relative, float *recs,
                                  int max_recs, int *counts, hipStream_t st);
 int yolo_logistic_launch(const float *in, float *out, int B, int n, int classes, int hw, hipStream_t st);
+// detect.hip: every head of a network, every image of the batch, records in reference order (mi355_yolo_detections_batch)
+struct DetHead {
+    const float *out, *biases;  // yolo output [B][n * (classes + 5)][h * w], anchors
+    const int *mask;
+    int n, h, w;
+    int blk0;                   // first block (of 256 cells) of this head inside an image's row of blocks
+};
+struct DetBatchArgs {
+    DetHead head[MI355_YOLO_MAX_HEADS];
+    int nheads, B, classes, netw, neth, relative, max_per_image;
+    int nblk;                   // blocks per image over all heads
+    float thresh;
+    const int *imw, *imh;       // [B], device
+    float *recs;
+    int *counts, *offsets;      // [B][nheads], [B + 1]
+    int *work;                  // [B][nblk]: count of a block, then its exclusive offset inside the image
+};
+int yolo_detections_batch_launch(const DetBatchArgs &a, hipStream_t st);
 int checksum_u32_launch(const uint32_t *p, long n, unsigned long long *out, hipStream_t st);
 
 // Kernels with more than 64 KB of dynamic LDS need their limit raised: per kernel instantiation (the template argument) and per device --

@@ -1137,4 +1137,58 @@ int mi355_yolo_detections_sizes(const float *yolo_out, int B, int n, int classes
                                         recs, max_recs, counts, (hipStream_t)stream);
 }
 
+// blocks of 256 cells per image over all heads, or 0 when a head or the head count is refused
+static long det_batch_blocks(const mi355_yolo_head *heads, int nheads, long *cand)
+{
+    if (!heads || nheads < 1 || nheads > MI355_YOLO_MAX_HEADS) return 0;
+    long nblk = 0;
+    *cand = 0;
+    for (int k = 0; k < nheads; ++k) {
+        const mi355_yolo_head &h = heads[k];
+        if (h.n < 1 || h.H < 1 || h.W < 1 || (long)h.n * h.H * h.W >= (1L << 24) || (long)h.H * h.W >= (1L << 24)) return 0;
+        nblk += ((long)h.H * h.W + 255) / 256;
+        *cand += (long)h.n * h.H * h.W;
+    }
+    return nblk;
+}
+
+long mi355_yolo_detections_batch_work_ints(const mi355_yolo_head *heads, int nheads, int B)
+{
+    long cand;
+    const long nblk = det_batch_blocks(heads, nheads, &cand);
+    return B < 1 || B > 65535 ? 0 : nblk * B;
+}
+
+int mi355_yolo_detections_batch(const mi355_yolo_head *heads, int nheads, int B, int classes, int netw, int neth, const int *imw_dev,
+                                const int *imh_dev, float thresh, int relative, int max_per_image, float *recs, int *counts,
+                                int *offsets, int *work, long work_ints, void *stream)
+{
+    if (!heads) return einval("yolo_detections_batch: null");
+    if (nheads < 1 || nheads > MI355_YOLO_MAX_HEADS) return einval("yolo_detections_batch: 1 to 8 heads");
+    long cand;
+    const long nblk = det_batch_blocks(heads, nheads, &cand);
+    if (!nblk) return einval("yolo_detections_batch: a head needs n, H, W >= 1 and n * H * W < 2^24 (the rank of a record is a float)");
+    if (classes < 1) return einval("yolo_detections_batch: classes < 1");
+    if (max_per_image < 1) return einval("yolo_detections_batch: max_per_image < 1");
+    if (B < 1 || B > 65535) return einval("yolo_detections_batch: batch outside 1..65535");
+    if (cand * B >= (1L << 31) || nblk > 0x7fffffffL) return einval("yolo_detections_batch: batch * candidates per image >= 2^31");
+    if (netw < 1 || neth < 1) return einval("yolo_detections_batch: network size < 1");
+    if (!imw_dev || !imh_dev || !recs || !counts || !offsets || !work) return einval("yolo_detections_batch: null");
+    if (work_ints < nblk * B) return einval("yolo_detections_batch: work buffer below mi355_yolo_detections_batch_work_ints");
+    DetBatchArgs a;
+    memset(&a, 0, sizeof(a));
+    int blk0 = 0;
+    for (int k = 0; k < nheads; ++k) {
+        if (!heads[k].yolo_out || !heads[k].anchors || !heads[k].mask) return einval("yolo_detections_batch: null in a head");
+        a.head[k].out = heads[k].yolo_out; a.head[k].biases = heads[k].anchors; a.head[k].mask = heads[k].mask;
+        a.head[k].n = heads[k].n; a.head[k].h = heads[k].H; a.head[k].w = heads[k].W;
+        a.head[k].blk0 = blk0;
+        blk0 += (heads[k].H * heads[k].W + 255) / 256;
+    }
+    a.nheads = nheads; a.B = B; a.classes = classes; a.netw = netw; a.neth = neth; a.relative = relative;
+    a.max_per_image = max_per_image; a.nblk = (int)nblk; a.thresh = thresh;
+    a.imw = imw_dev; a.imh = imh_dev; a.recs = recs; a.counts = counts; a.offsets = offsets; a.work = work;
+    return yolo_detections_batch_launch(a, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -138,3 +138,5 @@ int dnq_net_pi_packed(network *net) { return net->pi_packed; }
 long dnq_net_pi_entry_bytes(network *net) { return (long)net->pi_entry_bytes; }
 /* the captured graph of the layer loop (NULL: none yet); tests compare it across batches to see that no re-capture happened */
 void *dnq_net_graph(network *net) { return net->graph; }
+/* counts [batch][nheads] of the last batched box decode (the host staging copy), or NULL before the first */
+int *dnq_net_detb_counts(network *net) { return net->detb_ints_host ? net->detb_ints_host + 2 * net->batch : NULL; }

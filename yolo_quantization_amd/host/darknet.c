@@ -166,19 +166,26 @@ typedef struct {
     double seconds; /* out: per forward pass */
 } detect_job;
 
-/* boxes of batch slot b (source image imw x imh), NMS, and draw_detections' console output */
-static void print_detections(const detect_job *job, network *net, int b, int imw, int imh, char **names, int nnames)
+/* Boxes of the whole batch (slot b's source image is imw[b] x imh[b]) from one decode, NMS applied (ref :892, :927): dets[b], num[b].
+ * Returns the class count, 0 for a network without a yolo layer (nothing to print). */
+static int batch_detections(const detect_job *job, network *net, const int *imw, const int *imh, detection **dets, int *num)
 {
     int classes = 0;
     for (int i = 0; i < net->n; ++i)
         if (net->layers[i].type == YOLO) classes = net->layers[i].classes; /* ref: `l = net->layers[net->n-1]` (:910) */
-    if (!classes) return;
+    for (int b = 0; b < net->batch; ++b) { dets[b] = NULL; num[b] = 0; }
+    if (!classes) return 0;
     const float nms = .45f; /* ref :892 */
-    int nboxes = 0;
-    detection *dets = get_network_boxes_batch(net, b, imw, imh, job->thresh, job->hier_thresh, 0, 1, &nboxes);
+    if (network_detections_batch(net, imw, imh, job->thresh, 1, nms, 0, dets, num)) error("detector: the network's yolo layers cannot be decoded together");
+    return classes;
+}
+
+/* draw_detections' console output for one slot of batch_detections' result */
+static void print_detections(const detect_job *job, int classes, const detection *dets, int nboxes, char **names, int nnames)
+{
+    if (!classes) return;
     printf("%d\n", nboxes);
     printf("-----------------------\n");
-    if (nms) do_nms_sort(dets, nboxes, classes, nms);
     for (int i = 0; i < nboxes; ++i) /* draw_detections' console output (src/image.c:246-257) */
         for (int j = 0; j < classes; ++j)
             if (dets[i].prob[j] > job->thresh) {
@@ -188,7 +195,6 @@ static void print_detections(const detect_job *job, network *net, int b, int imw
                     printf("box: class %d prob %.9g x %.9g y %.9g w %.9g h %.9g\n", j, dets[i].prob[j], dets[i].bbox.x,
                            dets[i].bbox.y, dets[i].bbox.w, dets[i].bbox.h);
             }
-    free_detections(dets, nboxes);
 }
 
 /* -frames: the batch's sources, one path per slot, through the entry point of the kind that is set: one call for the whole input step.
@@ -248,6 +254,8 @@ static void test_detector_list(detect_job *job, network *net, char **names, int 
     if (set_input_quantization_per_image(net, 1)) error("-list: layer 0 cannot quantise every image on its own");
     const int B = net->batch;
     int *imw = calloc((size_t)B, sizeof(int)), *imh = calloc((size_t)B, sizeof(int));
+    detection **dets = calloc((size_t)B, sizeof(detection *));
+    int *num = calloc((size_t)B, sizeof(int));
     for (int first = 0; first < np; first += B) {
         const int cnt = np - first < B ? np - first : B;
         if (job->frames) {
@@ -276,13 +284,15 @@ static void test_detector_list(detect_job *job, network *net, char **names, int 
         const double t0 = what_time_is_it_now();
         network_predict(net, net->input);
         const double dt = what_time_is_it_now() - t0;
+        const int classes = batch_detections(job, net, imw, imh, dets, num); /* one decode per forward pass, every slot's block from it */
         for (int b = 0; b < cnt; ++b) {
             printf("%s: Predicted in %f seconds. (batch %d, %.1f images/s, gpu %d, accum=%s, parity=%s)\n", paths[first + b], dt, B,
                    B / dt, job->gpu, job->accum == MI355_ACC_EXACT ? "exact" : "ref-f32", job->store == MI355_STORE_WRAP ? "wrap" : "saturate");
-            print_detections(job, net, b, imw[b], imh[b], names, nnames);
+            print_detections(job, classes, dets[b], num[b], names, nnames);
         }
+        free_detections_batch(dets, num, B);
     }
-    free(imw); free(imh);
+    free(imw); free(imh); free(dets); free(num);
     for (int i = 0; i < np; ++i) free(paths[i]);
     free(paths);
 }
@@ -382,7 +392,16 @@ static void test_detector(detect_job *job)
         for (int k = n - 1; k >= 1; --k) free_network(ex[k]);
     }
 
-    if (!job->quiet) print_detections(job, net, 0, im.w, im.h, names, nnames);
+    if (!job->quiet) { /* every slot holds the one image */
+        const int B = net->batch;
+        int *imw = calloc((size_t)B, sizeof(int)), *imh = calloc((size_t)B, sizeof(int)), *num = calloc((size_t)B, sizeof(int));
+        detection **dets = calloc((size_t)B, sizeof(detection *));
+        for (int b = 0; b < B; ++b) { imw[b] = im.w; imh[b] = im.h; }
+        const int classes = batch_detections(job, net, imw, imh, dets, num);
+        print_detections(job, classes, dets[0], num[0], names, nnames);
+        free_detections_batch(dets, num, B);
+        free(imw); free(imh); free(num); free(dets);
+    }
     if (job->dumpdir) for (int i = 0; i < net->n; ++i) dump_layer(job->dumpdir, net, i);
     if (im_gpu) mi355_free(im_gpu);
     free(im.data);

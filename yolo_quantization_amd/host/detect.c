@@ -60,6 +60,65 @@ void free_detections(detection *dets, int n)
     free(dets);
 }
 
+/* packed records -> the arrays get_network_boxes_batch builds from them, image by image; the NMS call `detector test` makes (ref:
+ * examples/detector.c:927).  No device. */
+void detections_from_records(const float *recs, const int *offsets, int B, int classes, float nms, detection **dets, int *num)
+{
+    const int rl = 6 + classes;
+    for (int b = 0; b < B; ++b) {
+        const int cnt = offsets[b + 1] - offsets[b];
+        detection *d = calloc((size_t)cnt + 1, sizeof(detection));
+        for (int k = 0; k < cnt; ++k) {
+            const float *r = recs + ((size_t)offsets[b] + k) * rl;
+            d[k].bbox.x = r[1]; d[k].bbox.y = r[2]; d[k].bbox.w = r[3]; d[k].bbox.h = r[4];
+            d[k].objectness = r[5];
+            d[k].classes = classes;
+            d[k].prob = calloc((size_t)classes, sizeof(float));
+            memcpy(d[k].prob, r + 6, sizeof(float) * (size_t)classes);
+        }
+        if (nms > 0) do_nms_sort(d, cnt, classes, nms);
+        dets[b] = d;
+        num[b] = cnt;
+    }
+}
+
+void detections_to_arrays(const detection *dets, int n, int classes, float *boxes, float *objectness, float *probs)
+{
+    for (int i = 0; i < n; ++i) {
+        boxes[4 * i] = dets[i].bbox.x; boxes[4 * i + 1] = dets[i].bbox.y; boxes[4 * i + 2] = dets[i].bbox.w; boxes[4 * i + 3] = dets[i].bbox.h;
+        objectness[i] = dets[i].objectness;
+        memcpy(probs + (size_t)i * classes, dets[i].prob, sizeof(float) * (size_t)classes);
+    }
+}
+
+int network_detections_batch(network *net, const int *imw, const int *imh, float thresh, int relative, float nms, int max_per_image,
+                             detection **dets, int *num)
+{
+    const int B = net->batch;
+    int nheads = 0, classes = 0;
+    for (int b = 0; b < B; ++b) { dets[b] = NULL; num[b] = 0; }
+    const int rc = network_detections_batch_shape(net, &nheads, &classes, NULL);
+    if (rc) return rc;
+    int *counts = calloc((size_t)B * nheads, sizeof(int)), *offsets = calloc((size_t)B + 1, sizeof(int));
+    const int total = network_detb_run(net, imw, imh, thresh, relative, max_per_image, counts, offsets);
+    if (total >= 0) {
+        float *recs = malloc(sizeof(float) * ((size_t)total + 1) * (6 + classes));
+        network_detb_pull(net, recs, total);
+        detections_from_records(recs, offsets, B, classes, nms, dets, num);
+        free(recs);
+    }
+    free(counts); free(offsets);
+    return total < 0 ? total : 0;
+}
+
+void free_detections_batch(detection **dets, int *num, int batch)
+{
+    for (int b = 0; b < batch; ++b) {
+        if (dets[b]) free_detections(dets[b], num[b]);
+        dets[b] = NULL; num[b] = 0;
+    }
+}
+
 /* ref: src/box.c:151-182 */
 static float overlap(float x1, float w1, float x2, float w2)
 {

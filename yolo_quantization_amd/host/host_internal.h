@@ -19,4 +19,8 @@ layer make_shortcut_layer(int batch, int index, int w, int h, int c, int w2, int
 layer make_yolo_layer(int batch, int w, int h, int n, int total, int *mask, int classes, int count);
 
 void free_layer_device(layer *l);
+/* network_yolo_detections_batch_gpu in its two halves (detect.c sizes its host copy by what was found): launch + counts / offsets back,
+ * first sync -> records kept in the batch (or MI355_EINVAL); then the records, second sync */
+int network_detb_run(network *net, const int *imw, const int *imh, float thresh, int relative, int max_per_image, int *counts, int *offsets);
+void network_detb_pull(network *net, float *recs, int total);
 #endif

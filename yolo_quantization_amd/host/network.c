@@ -695,6 +695,19 @@ void network_quantize_input_gpu(network *net)
 enum { FR_U8, FR_YUV, FR_PLANAR }; /* the kind of frames an entry point feeds (net->fr_kind) */
 static const size_t fr_entry_bytes[3] = {sizeof(mi355_frame_u8), sizeof(mi355_frame_yuv), sizeof(mi355_frame_planar)};
 
+static void detb_free(network *net)
+{
+    if (net->detb_ints_gpu) mi355_free(net->detb_ints_gpu);
+    if (net->detb_work_gpu) mi355_free(net->detb_work_gpu);
+    if (net->detb_recs_gpu) mi355_free(net->detb_recs_gpu);
+    free(net->detb_ints_host);
+    net->detb_ints_gpu = net->detb_ints_host = net->detb_work_gpu = NULL;
+    net->detb_recs_gpu = NULL;
+    net->detb_batch = net->detb_nheads = 0;
+    net->detb_work_ints = 0;
+    net->detb_recs_cap = 0;
+}
+
 static void fr_free(network *net)
 {
     if (net->fr_arena_gpu) mi355_free(net->fr_arena_gpu);
@@ -921,6 +934,7 @@ void set_batch_network(network *net, int b)
     net->batch = b;
     pi_free(net); /* the per-image bank and index arrays are sized by the batch */
     fr_free(net); /* so are the frame table, its min / max and the staging arena */
+    detb_free(net); /* and the batched box decode's buffers */
     free(net->input); free(net->input_uint8);
     net->input = calloc((size_t)net->inputs * b, sizeof(float));
     net->input_uint8 = calloc((size_t)net->inputs * b, sizeof(uint8_t));
@@ -1165,15 +1179,20 @@ static int cmp_rec_rank(const void *a, const void *b)
 }
 
 /* anchors, masks and room for max_recs records per image of yolo layer l on the device (kept on the layer) */
-static void det_buffers(network *net, layer *l, int max_recs)
+static void det_anchors(network *net, layer *l)
 {
-    const int B = net->batch, rl = 6 + l->classes;
     if (!l->anchors_gpu) {
         check_mi355(mi355_alloc((void **)&l->anchors_gpu, sizeof(float) * 2 * (size_t)l->total), "alloc anchors");
         check_mi355(mi355_h2d(l->anchors_gpu, l->anchors, sizeof(float) * 2 * (size_t)l->total, net->stream), "anchors");
         check_mi355(mi355_alloc((void **)&l->mask_gpu, sizeof(int) * (size_t)l->n), "alloc mask");
         check_mi355(mi355_h2d(l->mask_gpu, l->mask, sizeof(int) * (size_t)l->n, net->stream), "mask");
     }
+}
+
+static void det_buffers(network *net, layer *l, int max_recs)
+{
+    const int B = net->batch, rl = 6 + l->classes;
+    det_anchors(net, l);
     if (l->det_cap < max_recs) {
         if (l->det_recs_gpu) { mi355_free(l->det_recs_gpu); mi355_free(l->det_counts_gpu); }
         check_mi355(mi355_alloc((void **)&l->det_recs_gpu, sizeof(float) * (size_t)B * max_recs * rl), "alloc records");
@@ -1228,6 +1247,117 @@ void network_yolo_detections_gpu_sizes(network *net, int i, const int *imw, cons
                                             l->det_counts_gpu, net->stream),
                 "mi355_yolo_detections_sizes");
     det_pull(net, l, recs, max_recs, counts); /* (its first sync also retires the size uploads from the caller's arrays) */
+}
+
+/* ------------------------------------------------------------------------------------ batched box decode
+ * Every yolo layer, every image, one call (detect.hip).  The records leave the device in the reference's order, so nothing is sorted
+ * here and the number of copies and synchronisations does not depend on the batch. */
+static int detb_refuse(const char *why)
+{
+    fprintf(stderr, "darknet_q: batched detections: %s\n", why);
+    return MI355_EINVAL;
+}
+
+/* the yolo layers in network order -> idx[], or MI355_EINVAL */
+static int detb_heads(network *net, int *idx, int *nheads, int *classes, int *candidates)
+{
+    int nh = 0, cls = 0;
+    long cand = 0;
+    for (int i = 0; i < net->n; ++i) {
+        const layer *l = &net->layers[i];
+        if (l->type != YOLO) continue;
+        if (nh == MI355_YOLO_MAX_HEADS) return detb_refuse("more yolo layers than MI355_YOLO_MAX_HEADS");
+        if (nh && l->classes != cls) return detb_refuse("the yolo layers differ in `classes`: decode them one by one (network_yolo_detections_gpu)");
+        cls = l->classes;
+        cand += (long)l->n * l->h * l->w;
+        idx[nh++] = i;
+    }
+    if (!nh) return detb_refuse("the network has no yolo layer");
+    if (cand * net->batch >= (1L << 31)) return detb_refuse("batch * candidates per image >= 2^31");
+    *nheads = nh; *classes = cls; *candidates = (int)cand;
+    return 0;
+}
+
+int network_detections_batch_shape(network *net, int *nheads, int *classes, int *candidates)
+{
+    int idx[MI355_YOLO_MAX_HEADS], nh, cls, cand;
+    const int rc = detb_heads(net, idx, &nh, &cls, &cand);
+    if (rc) return rc;
+    if (nheads) *nheads = nh;
+    if (classes) *classes = cls;
+    if (candidates) *candidates = cand;
+    return 0;
+}
+
+int network_detb_run(network *net, const int *imw, const int *imh, float thresh, int relative, int max_per_image, int *counts, int *offsets)
+{
+    int idx[MI355_YOLO_MAX_HEADS], nh, classes, cand;
+    const int rc = detb_heads(net, idx, &nh, &classes, &cand);
+    if (rc) return rc;
+    const int B = net->batch;
+    for (int b = 0; b < B; ++b)
+        if (imw[b] < 1 || imh[b] < 1) return detb_refuse("image sizes must be positive");
+    if (!net->prepared) error("network_yolo_detections_batch_gpu before quantization_weights_and_activations");
+    const int cap = max_per_image <= 0 || max_per_image > cand ? cand : max_per_image; /* records an image can keep */
+    mi355_yolo_head heads[MI355_YOLO_MAX_HEADS];
+    memset(heads, 0, sizeof(heads));
+    for (int k = 0; k < nh; ++k) {
+        layer *l = &net->layers[idx[k]];
+        det_anchors(net, l);
+        heads[k].yolo_out = l->output_gpu; heads[k].anchors = l->anchors_gpu; heads[k].mask = l->mask_gpu;
+        heads[k].n = l->n; heads[k].H = l->h; heads[k].W = l->w;
+    }
+    const size_t nints = 2 * (size_t)B + (size_t)B * nh + B + 1;
+    if (net->detb_batch != B || net->detb_nheads != nh) {
+        if (net->detb_ints_gpu) mi355_free(net->detb_ints_gpu);
+        free(net->detb_ints_host);
+        check_mi355(mi355_alloc((void **)&net->detb_ints_gpu, sizeof(int) * nints), "alloc detection counts");
+        net->detb_ints_host = calloc(nints, sizeof(int));
+        net->detb_batch = B; net->detb_nheads = nh;
+    }
+    const long work = mi355_yolo_detections_batch_work_ints(heads, nh, B);
+    if (!work) { fprintf(stderr, "MI355: %s\n", mi355_last_error()); return detb_refuse("a yolo layer the device decode does not serve"); }
+    if (net->detb_work_ints < work) {
+        if (net->detb_work_gpu) mi355_free(net->detb_work_gpu);
+        check_mi355(mi355_alloc((void **)&net->detb_work_gpu, sizeof(int) * (size_t)work), "alloc detection scratch");
+        net->detb_work_ints = work;
+    }
+    if (net->detb_recs_cap < (size_t)B * cap) {
+        if (net->detb_recs_gpu) mi355_free(net->detb_recs_gpu);
+        check_mi355(mi355_alloc((void **)&net->detb_recs_gpu, sizeof(float) * (size_t)B * cap * (6 + classes)), "alloc records");
+        net->detb_recs_cap = (size_t)B * cap;
+    }
+    int *hs = net->detb_ints_host, *ds = net->detb_ints_gpu;
+    memcpy(hs, imw, sizeof(int) * (size_t)B);
+    memcpy(hs + B, imh, sizeof(int) * (size_t)B);
+    check_mi355(mi355_h2d(ds, hs, 2 * sizeof(int) * (size_t)B, net->stream), "sizes");
+    int *counts_gpu = ds + 2 * B, *offsets_gpu = counts_gpu + (size_t)B * nh;
+    check_mi355(mi355_yolo_detections_batch(heads, nh, B, classes, net->w, net->h, ds, ds + B, thresh, relative, cap, net->detb_recs_gpu,
+                                            counts_gpu, offsets_gpu, net->detb_work_gpu, net->detb_work_ints, net->stream),
+                "mi355_yolo_detections_batch");
+    check_mi355(mi355_d2h(hs + 2 * B, counts_gpu, sizeof(int) * ((size_t)B * nh + B + 1), net->stream), "pull counts + offsets");
+    check_mi355(mi355_stream_sync(net->stream), "sync");
+    memcpy(counts, hs + 2 * B, sizeof(int) * (size_t)B * nh);
+    memcpy(offsets, hs + 2 * B + (size_t)B * nh, sizeof(int) * ((size_t)B + 1));
+    return offsets[B];
+}
+
+void network_detb_pull(network *net, float *recs, int total)
+{
+    if (total <= 0) return;
+    int classes = 0;
+    network_detections_batch_shape(net, NULL, &classes, NULL);
+    check_mi355(mi355_d2h(recs, net->detb_recs_gpu, sizeof(float) * (size_t)total * (6 + classes), net->stream), "pull records");
+    check_mi355(mi355_stream_sync(net->stream), "sync");
+}
+
+int network_yolo_detections_batch_gpu(network *net, const int *imw, const int *imh, float thresh, int relative, int max_per_image,
+                                      float *recs, int *counts, int *offsets)
+{
+    const int total = network_detb_run(net, imw, imh, thresh, relative, max_per_image, counts, offsets);
+    if (total < 0) return total;
+    network_detb_pull(net, recs, total);
+    return 0;
 }
 
 /* ------------------------------------------------------------------------------------ packed-weight exchange */
@@ -1538,6 +1668,7 @@ void free_network(network *net)
     if (net->quant_mm_gpu) mi355_free(net->quant_mm_gpu);
     pi_free(net);
     fr_free(net);
+    detb_free(net);
     if (net->selfcheck_gpu) mi355_free(net->selfcheck_gpu);
     if (net->stream) mi355_stream_release(net->stream);
     free(net->layers); free(net->input); free(net->input_uint8); free(net->seen); free(net->cfg_path);
