@@ -35,6 +35,9 @@ extern "C" {
 typedef enum { LOGISTIC = 0, RELU = 1, LINEAR = 3, RELU6 = 8, LEAKY = 9 } ACTIVATION;
 typedef enum { CONVOLUTIONAL = 0, MAXPOOL = 3, ROUTE = 8, SHORTCUT = 13, YOLO = 23, UPSAMPLE = 26 } LAYER_TYPE;
 
+/* layer.fuse_next: the layer after a conv that runs inside the conv's kernel.  The type of that layer decides the kind */
+enum { FUSE_NONE = 0, FUSE_POOL, FUSE_UPSAMPLE, FUSE_SHORTCUT, FUSE_YOLO };
+
 #define QUANT_POSITIVE_LIMIT 255
 #define QUANT_NEGATIVE_LIMIT 0
 
@@ -100,12 +103,15 @@ struct layer {
     int32_t *output_int32_gpu;     /* reference layout; allocated only when net->dump_int32 */
     float *output_gpu;             /* reference layout float (quant_stop convs, yolo) */
     uint8_t *output_uint8_nchw_gpu; /* scratch for pull_layer_output */
-    int fuse_next_pool; /* this conv and the 2x2 maxpool (stride 2, or stride 1 behind a 128 / 256-channel conv) after it run as one kernel (set by the prep) */
-    int fuse_pool_keep; /* ... which also stores the conv's own tensor: a route reads it */
-    int fuse_next_upsample; /* this conv stores its pixels straight into the upsample layer's tensor after it */
+    int input_direct;   /* layer 0 only.  1: it is fed the network's input_nchw_t, no conversion pass; its forward_gpu clears it on the
+                           first MI355_EINVAL */
+    int fuse_next;      /* FUSE_*: the planner's candidate (plan_fusion); a launcher's refusal sets it back to FUSE_NONE.
+                           POOL: this conv and the 2x2 maxpool (stride 2, or stride 1 behind a 128 / 256-channel conv) after it run as
+                           one kernel.  UPSAMPLE: it stores its pixels straight into the upsample layer's tensor.  SHORTCUT: its epilogue
+                           also does the quantized residual add of the [shortcut].  YOLO: this quant_stop head conv also writes the yolo
+                           layer's activations */
+    int fuse_pool_keep; /* FUSE_POOL which also stores the conv's own tensor: a route reads it */
     int conv_kernel;    /* kernel family that served this conv's last forward (mi355_last_conv_kernel) */
-    int fuse_next_yolo; /* this quant_stop head conv also writes the activations of the yolo layer after it */
-    int fuse_next_shortcut; /* this conv's epilogue also does the quantized residual add of the [shortcut] after it */
     int prepared;
 };
 
@@ -128,8 +134,6 @@ struct network {
     float *input_gpu;         /* batch x inputs floats on the device: the letterboxed images of the device input path */
     mi355_tensor input_t;     /* cs==4 image tensor */
     mi355_tensor input_nchw_t; /* input_uint8_gpu described as it is (planar): layer 0 reads it in place where its kernel can */
-    int *input_direct_p;      /* executor -> layer 0: where to clear input_direct (the network travels by value) */
-    int input_direct;         /* 1: layer 0 is fed input_nchw_t, no conversion pass; cleared by the first MI355_EINVAL */
     int input_direct_off;     /* user knob (dnq_net_set "input_direct" 0): never feed the planes directly, whatever is re-allocated */
     const mi355_tensor *cur_t; /* uint8 hand-off: the reference's `net.input_uint8 = l.output_uint8_final` */
     const float *cur_f32_gpu;  /* float hand-off: `net.input = l.output` */
@@ -139,14 +143,9 @@ struct network {
     int dump_int32; /* keep int32 accumulators of every conv (parity runs) */
     int keep_head_float; /* 0 (default): a head conv fused with its yolo layer does not store its own float tensor (l.output: an
                             intermediate only the yolo layer reads); 1: it does (per-layer parity dumps) */
-    int fuse_maxpool; /* 1 (default): conv + following 2x2/2 maxpool fused, the pre-pool tensor is not stored.
-                         0: every layer writes its own tensor like the reference (per-layer parity dumps) */
-    const mi355_tensor *fused_up_t;   /* run-time: upsampled tensor the conv being run has to fill, or NULL */
-    int fused_up_stride;
-    float *fused_yolo_out;            /* run-time: yolo output buffer the conv being run has to fill, or NULL */
-    int fused_yolo_classes;
-    const mi355_tensor *fused_pool_t; /* executor -> conv forward_gpu: pooled output tensor of the fused pair */
-    const struct layer *fused_shortcut; /* executor -> conv forward_gpu: the [shortcut] layer whose add this conv performs, or NULL */
+    int fuse_maxpool; /* 1 (default): all four fused forms are on: a conv runs the maxpool / upsample / [shortcut] / yolo layer after it
+                         in its own kernel where plan_fusion marks it (layer.fuse_next); a fused conv's own tensor is not stored unless
+                         something else reads it.  0: every layer writes its own tensor like the reference (per-layer parity dumps) */
     int verbose;
     int prepared;
     int range_lo, range_hi; /* diagnostic (tools/layer_flood.py): forward_network_gpu runs layers [range_lo, range_hi) only, on the tensors the

@@ -1,6 +1,17 @@
 """CPU suite for the network generator of the whole-network sweep (tests/netgen.py): determinism, acceptance by the shape inference and by
-the host parser, an oracle run of every net, liveness of the oracle's data and static coverage of the sweep.  No device."""
+the host parser, an oracle run of every net, liveness of the oracle's data and static coverage of the sweep; and the host planner's fusion
+candidates (plan_fusion), which the host-only prep leaves readable.  No device.
+
+Mutation check of the planner tests (scratch copies of host/network.c):
+  * plan_fusion sets the upsample kind where it should set pool: test_planner_invariants and test_fusion_candidates_are_the_recorded_ones
+    are red for every net with a pool candidate (pool_keep_view, refused_pool_padding0, pool_64_to_96, pool_16_to_32 in both, rand135 in
+    the first, yolov3-tiny in the second).
+  * plan_fusion's shortcut case without `index != i`: nothing goes red, and nothing can.  output_read_elsewhere already answers 1 for a
+    conv that is the `from` of any shortcut, the one after it included, so the condition is implied by the one beside it and the plans of
+    all nets are the same without it.  With that reader not counted either, conv 4 of shortcut_neighbours becomes a candidate and
+    test_fusion_candidates_are_the_recorded_ones[shortcut_neighbours] is red."""
 import hashlib
+import os
 
 import numpy as np
 import pytest
@@ -38,7 +49,6 @@ def test_generator_is_deterministic(tmp_path):
 def test_glue_own_zp_is_opt_in(cfg_dir, tmp_path):
     """synth_weights writes the bytes it always wrote unless glue_own_zp is asked for; with it, every glue record keeps its input's scale
     and carries another zero point."""
-    import os
     cfg = os.path.join(cfg_dir, "yolov3-tiny_quant.cfg")
     a = synth.synth_weights(cfg, str(tmp_path / "a.weights"), seed=5)
     b = synth.synth_weights(cfg, str(tmp_path / "b.weights"), seed=5, glue_own_zp=False)
@@ -119,3 +129,84 @@ def test_static_coverage_of_the_sweep(tmp_path):
     assert not missing, missing
     assert any(s % 16 == 0 for s in sums) and any(s % 16 for s in sums)  # concatenations that are and are not multiples of 16
     assert len(netgen.AIMED) >= 12 and all(a["clause"] for a in netgen.AIMED.values())
+
+
+KINDS = {"fuse_next_pool": "pool", "fuse_next_upsample": "upsample", "fuse_next_shortcut": "shortcut", "fuse_next_yolo": "yolo"}
+NEXT_TYPE = {"pool": binding.T_MAXPOOL, "upsample": binding.T_UPSAMPLE, "shortcut": binding.T_SHORTCUT, "yolo": binding.T_YOLO}
+
+
+def _candidates(cfg, wts):
+    """(layer index -> kind, "pool+keep" for a pool with fuse_pool_keep) as Net.plan shows it after the host-only prep, with the
+    invariants every plan keeps checked on the way."""
+    net = binding.Net(cfg, wts)
+    net.prepare_host_only(1.0 / 255.0, 0)
+    got = {}
+    for i in range(net.n):
+        p = net.plan(i)
+        kinds = [kind for key, kind in KINDS.items() if p[key]]
+        assert len(kinds) <= 1, (i, p)
+        assert not p["fuse_pool_keep"] or p["fuse_next_pool"], (i, p)
+        if kinds:
+            assert net.info[i]["type"] == binding.T_CONV and i + 1 < net.n and net.info[i + 1]["type"] == NEXT_TYPE[kinds[0]], (i, p)
+            got[i] = kinds[0] + ("+keep" if p["fuse_pool_keep"] else "")
+    net.close()
+    return got
+
+
+@pytest.mark.parametrize("name", list(NETS))
+def test_planner_invariants(tmp_path, name):
+    """Every net of the sweep after the host-only prep: a layer carries at most one fusion kind, a kind sits on a conv whose successor has
+    the matching type, and fuse_pool_keep comes only with the pool kind."""
+    cfg, wts, _ = _files(tmp_path, name)
+    _candidates(cfg, wts)
+
+
+# The planner's candidates as the commit before the single fuse_next field gave them (recorded from a build of that commit, with only
+# plan_fusion's call moved into the host prep): layer index -> kind.
+CANDIDATES = {
+    "view_same_zp": {5: "yolo"},
+    "view_zp_differs": {5: "yolo"},
+    "shared_route_same_zp": {7: "yolo"},
+    "shared_route_zp_differs": {7: "yolo"},
+    "view_maxpool_upsample": {7: "yolo"},
+    "glue_own_zp": {9: "yolo"},
+    "fused_upsample_window_s3": {3: "upsample", 7: "yolo"},
+    "fused_upsample_window_s4": {3: "upsample", 7: "yolo"},
+    "pool_keep_view": {1: "pool+keep", 7: "yolo"},
+    "fused_shortcut_from_view": {2: "shortcut", 6: "yolo"},
+    "producer_in_two_routes": {6: "yolo"},
+    "route_same_layer_twice": {4: "yolo"},
+    "route_byte_copy": {5: "yolo"},
+    "shortcut_neighbours": {2: "shortcut", 6: "yolo"},
+    "refused_upsample_5x5": {1: "upsample", 3: "yolo"},
+    "refused_shortcut_5x5": {1: "shortcut", 3: "yolo"},
+    "refused_yolo_5x5": {1: "yolo"},
+    "refused_pool_padding0": {1: "pool", 3: "yolo"},
+    "pool_64_to_96": {1: "pool", 3: "yolo"},
+    "pool_16_to_32": {1: "pool", 3: "yolo"},
+    "pool_non_candidates": {5: "yolo"},
+    "kxk_reads_window": {},
+    "cell4_conv_feeds_conv": {5: "yolo"},
+    "fused_upsample_quant_stop": {3: "yolo"},
+    "cfg/yolov3-tiny_quant.cfg": {0: "pool", 2: "pool", 4: "pool", 6: "pool", 8: "pool+keep", 10: "pool", 15: "yolo", 18: "upsample", 22: "yolo"},
+    "cfg/yolov3_quant.cfg": {**{i: "shortcut" for i in (3, 7, 10, 14, 17, 20, 23, 26, 29, 32, 35, 39, 42, 45, 48, 51, 54, 57, 60, 64, 67, 70, 73)},
+                             81: "yolo", 84: "upsample", 93: "yolo", 96: "upsample", 105: "yolo"},
+    "cfg/res_unit.cfg": {2: "shortcut", 6: "shortcut", 8: "upsample", 13: "yolo"},
+}
+
+
+def test_candidate_table_covers_every_aimed_net():
+    assert set(netgen.AIMED) <= set(CANDIDATES)
+
+
+@pytest.mark.parametrize("name", list(CANDIDATES))
+def test_fusion_candidates_are_the_recorded_ones(cfg_dir, tmp_path, name):
+    """plan_fusion marks exactly the recorded (layer, kind) pairs in every aimed net of the sweep and in the shipped yolov3-tiny, yolov3
+    and residual-unit nets."""
+    if name.startswith("cfg/"):
+        cfg = os.path.join(cfg_dir, name[4:])
+        wts = str(tmp_path / "shipped.weights")
+        synth.synth_weights(cfg, wts, seed=1)
+    else:
+        cfg, wts, _ = _files(tmp_path, name)
+    assert _candidates(cfg, wts) == CANDIDATES[name]

@@ -27,7 +27,7 @@ int dnq_net_set(network *net, const char *key, int val)
     else if (!strcmp(key, "plan")) network_set_plan(net, val); /* MI355_PLAN_LATENCY / MI355_PLAN_THROUGHPUT: syncs, drops the graph, re-plans fusion */
     else if (!strcmp(key, "input_direct")) { /* 0: always convert the input to 4-byte cells (A/B runs); survives re-allocation */
         net->input_direct_off = !val;
-        net->input_direct = val && net->c == 3 && !net->dump_int32;
+        net->layers[0].input_direct = val && net->c == 3 && !net->dump_int32;
     }
     else return -1;
     return 0;
@@ -71,8 +71,6 @@ int dnq_layer_prep(network *net, int i, int32_t *biases_int32, double *M_value, 
     return 0;
 }
 
-/* 1 when layer i (a conv) runs fused with the maxpool / upsample after it in the current configuration: its own uint8
- * tensor is then not stored (only the pooled / upsampled one is) */
 /* kernel family (mi355_last_conv_kernel codes) that served conv layer i in the last forward pass, 0 for other layers */
 int dnq_layer_conv_kernel(network *net, int i)
 {
@@ -85,30 +83,27 @@ int dnq_layer_is_fused(network *net, int i)
 {
     if (i < 0 || i >= net->n) return 0;
     const layer *l = &net->layers[i];
-    return ((l->fuse_next_pool && !l->fuse_pool_keep) || l->fuse_next_upsample || l->fuse_next_shortcut) && net->fuse_maxpool && !net->dump_int32 &&
-           net->accum_mode == MI355_ACC_EXACT;
+    return fusion_on(net) && ((l->fuse_next == FUSE_POOL && !l->fuse_pool_keep) || l->fuse_next == FUSE_UPSAMPLE || l->fuse_next == FUSE_SHORTCUT);
 }
 
 /* layer i + 1 runs inside layer i's kernel (whether or not layer i's own tensor is stored as well) */
 int dnq_layer_fuses_next(network *net, int i)
 {
     if (i < 0 || i >= net->n) return 0;
-    const layer *l = &net->layers[i];
-    return (l->fuse_next_pool || l->fuse_next_upsample || l->fuse_next_shortcut || l->fuse_next_yolo) && net->fuse_maxpool && !net->dump_int32 &&
-           net->accum_mode == MI355_ACC_EXACT;
+    return fusion_on(net) && net->layers[i].fuse_next != FUSE_NONE;
 }
 
 /* The planner's decisions for layer i as they stand NOW (plan_views at allocation, plan_fusion at prep / network_set_plan, the flags
  * the launchers cleared at run time): out[0] = route_elided, out[1] = out_view, out[2] = byte offset of the layer's tensor inside the
  * buffer that owns it (0 for a tensor that owns its buffer; a one-input route that shares its input's tensor reports that input's),
- * out[3..6] = fuse_next_pool, fuse_next_upsample, fuse_next_shortcut, fuse_next_yolo, out[7] = fuse_pool_keep.  The fuse flags are the
+ * out[3..6] = fuse_next is FUSE_POOL, FUSE_UPSAMPLE, FUSE_SHORTCUT, FUSE_YOLO, out[7] = fuse_pool_keep.  The fuse flags are the
  * raw ones: dnq_layer_fuses_next tells whether the run mode (fuse_maxpool, dump_int32, accum_mode) honours them. */
 int dnq_layer_plan(network *net, int i, int *out)
 {
     if (i < 0 || i >= net->n || !out) return -1;
     const layer *l = &net->layers[i];
     out[0] = l->route_elided; out[1] = l->out_view; out[2] = 0;
-    out[3] = l->fuse_next_pool; out[4] = l->fuse_next_upsample; out[5] = l->fuse_next_shortcut; out[6] = l->fuse_next_yolo;
+    out[3] = l->fuse_next == FUSE_POOL; out[4] = l->fuse_next == FUSE_UPSAMPLE; out[5] = l->fuse_next == FUSE_SHORTCUT; out[6] = l->fuse_next == FUSE_YOLO;
     out[7] = l->fuse_pool_keep;
     if (l->out_view && l->out_t.data) {
         int j = i; /* a shared one-input route: the window (if any) is its input's */

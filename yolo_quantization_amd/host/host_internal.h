@@ -5,6 +5,10 @@
 
 void check_mi355(int rc, const char *what); /* maps shim error codes to error(), like the reference's check_error */
 
+/* Does this run mode honour the planner's fused forms (layer.fuse_next)?  Parity dumps (fuse_maxpool = 0, dump_int32) and the ref-f32
+ * twin run every layer on its own. */
+static inline int fusion_on(const network *net) { return net->fuse_maxpool && !net->dump_int32 && net->accum_mode == MI355_ACC_EXACT; }
+
 layer make_convolutional_layer(int batch, int h, int w, int c, int n, int groups, int size, int stride, int padding,
                                ACTIVATION activation, int batch_normalize, int quant_stop_flag,
                                int close_quantization, int layer_quantization, int count);

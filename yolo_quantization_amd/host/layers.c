@@ -29,42 +29,31 @@ static void alloc_act_record(layer *l)
     l->activ_data_uint8_zero_point = calloc(1, sizeof(uint8_t));
 }
 
-/* Layer 0 under per-image input quantisation (set_input_quantization_per_image): the same launches on the network's bank of
- * layer-0 blobs, one entry per image (mi355_conv_forward_per_image); fusion as in the shared-scale path below */
-static void forward_first_layer_per_image(layer l, network net, const mi355_conv_desc *d)
+/* The plain convolution and the conv + maxpool pair on the layer's own blob, or (pi: layer 0 under per-image input quantisation,
+ * set_input_quantization_per_image) the same launches on the network's bank of layer-0 blobs, one entry per image.  full = 0 is the
+ * bare exact-mode launch of the planar-input attempt: no raw weights, no int32 or float copy of the output. */
+static int conv_plain(const layer *l, const network *net, const mi355_conv_desc *d, int pi, int full)
 {
-    const size_t eb = net.pi_entry_bytes;
-    const int32_t *entry = (const int32_t *)net.pi_idx_gpu;
-    const uint8_t *zp = (const uint8_t *)net.pi_idx_gpu + 8 * (size_t)net.batch;
-    layer *self = &net.layers[net.index];
-    mi355_tensor converted;
-    if (!net.pi_bank_gpu) error("per-image input: layer 0 runs before the batch was quantised (no bank)");
-    if (net.cur_t->cs == 1) { /* planar network input: in place where the kernel can, else converted once and for all */
-        int rc = MI355_EINVAL;
-        if (net.fused_pool_t) rc = mi355_conv_pool_forward_per_image(d, net.cur_t, net.pi_bank_gpu, eb, entry, zp, NULL, net.fused_pool_t, net.stream);
-        else if (!l.quant_stop_flag)
-            rc = mi355_conv_forward_per_image(d, net.cur_t, net.pi_bank_gpu, eb, entry, zp, NULL, NULL, &l.out_t, NULL, NULL, net.stream);
-        if (rc != MI355_EINVAL) { check_mi355(rc, "mi355_conv_forward_per_image (planar input)"); return; }
-        if (net.input_direct_p) *net.input_direct_p = 0;
-        converted = net.input_t;
-        check_mi355(mi355_nchw_to_tensor((const uint8_t *)net.cur_t->data, &converted, net.stream), "input layout");
-        net.cur_t = &converted;
-    }
-    if (net.fused_pool_t) {
-        const int rc = mi355_conv_pool_forward_per_image(d, net.cur_t, net.pi_bank_gpu, eb, entry, zp, l.fuse_pool_keep ? &l.out_t : NULL,
-                                                         net.fused_pool_t, net.stream);
-        if (rc != MI355_EINVAL) { check_mi355(rc, "mi355_conv_pool_forward_per_image"); return; }
-        self->fuse_next_pool = 0;
-    }
-    check_mi355(mi355_conv_forward_per_image(d, net.cur_t, net.pi_bank_gpu, eb, entry, zp, l.weights_uint8_gpu, l.weight_zero_point_gpu,
-                                             &l.out_t, net.dump_int32 ? l.output_int32_gpu : NULL, l.quant_stop_flag ? l.output_gpu : NULL,
-                                             net.stream),
-                "mi355_conv_forward_per_image");
+    const uint8_t *w = full ? l->weights_uint8_gpu : NULL, *zp_w = full ? l->weight_zero_point_gpu : NULL;
+    int32_t *acc = full && net->dump_int32 ? l->output_int32_gpu : NULL;
+    float *f32 = full && l->quant_stop_flag ? l->output_gpu : NULL;
+    if (!pi) return mi355_conv_forward(d, net->cur_t, l->blob_gpu, w, zp_w, &l->out_t, acc, f32, net->stream);
+    return mi355_conv_forward_per_image(d, net->cur_t, net->pi_bank_gpu, net->pi_entry_bytes, (const int32_t *)net->pi_idx_gpu,
+                                        (const uint8_t *)net->pi_idx_gpu + 8 * (size_t)net->batch, w, zp_w, &l->out_t, acc, f32, net->stream);
+}
+
+static int conv_pool(const layer *l, const network *net, const mi355_conv_desc *d, int pi, const mi355_tensor *keep, const mi355_tensor *pooled)
+{
+    if (!pi) return mi355_conv_pool_forward(d, net->cur_t, l->blob_gpu, keep, pooled, net->stream);
+    return mi355_conv_pool_forward_per_image(d, net->cur_t, net->pi_bank_gpu, net->pi_entry_bytes, (const int32_t *)net->pi_idx_gpu,
+                                             (const uint8_t *)net->pi_idx_gpu + 8 * (size_t)net->batch, keep, pooled, net->stream);
 }
 
 /* ref: forward_convolutional_layer_quant_inputi_outputi, src/convolutional_layer.c:694-761 */
 static void forward_convolutional_layer_quant_gpu(layer l, network net)
 {
+    static const char *const fused_name[] = { "mi355_conv_forward", "mi355_conv_pool_forward", "mi355_conv_upsample_forward",
+                                              "mi355_conv_shortcut_forward", "mi355_conv_yolo_forward" };
     if (!l.prepared) error("forward_gpu before quantization_weights_and_activations");
     mi355_conv_desc d;
     memset(&d, 0, sizeof(d));
@@ -77,54 +66,53 @@ static void forward_convolutional_layer_quant_gpu(layer l, network net)
     d.zp_in = l.input_data_uint8_zero_point[0];
     d.zp_act = l.activ_data_uint8_zero_point[0];
     d.s_act = l.activ_data_uint8_scales[0];
+    /* per-image layer 0 is a 3-channel conv (l0_per_image_shape_ok): of the fused forms plan_fusion only offers it the pool */
+    const int pi = net.per_image && net.index == 0;
+    if (pi && !net.pi_bank_gpu) error("per-image input: layer 0 runs before the batch was quantised (no bank)");
     /* Fused forms: the executor's plan marks candidates by shape, the launchers decide.  MI355_EINVAL from a fused entry
-     * point means "no kernel fuses this shape" (nothing was launched): the flag is cleared in the network's layer array
+     * point means "no kernel fuses this shape" (nothing was launched): fuse_next is cleared in the network's layer array
      * (net.layers points at it; `l` is a by-value copy) and the convolution runs unfused below, the layer after it on its
      * own. */
-    if (net.per_image && net.index == 0) { forward_first_layer_per_image(l, net, &d); return; }
     layer *self = &net.layers[net.index];
+    const layer *next = self + 1; /* read only when the planner named it */
+    const int kind = fusion_on(&net) ? l.fuse_next : FUSE_NONE;
     mi355_tensor converted;
     if (net.cur_t->cs == 1) { /* planar network input: try the in-place read; MI355_EINVAL -> convert, once and for all */
         int rc = MI355_EINVAL;
-        if (net.fused_pool_t) rc = mi355_conv_pool_forward(&d, net.cur_t, l.blob_gpu, NULL, net.fused_pool_t, net.stream);
-        else if (!net.fused_up_t && !net.fused_yolo_out && !net.fused_shortcut && !l.quant_stop_flag)
-            rc = mi355_conv_forward(&d, net.cur_t, l.blob_gpu, NULL, NULL, &l.out_t, NULL, NULL, net.stream);
+        if (kind == FUSE_POOL) rc = conv_pool(&l, &net, &d, pi, NULL, &next->out_t);
+        else if (kind == FUSE_NONE && !l.quant_stop_flag) rc = conv_plain(&l, &net, &d, pi, 0);
         if (rc != MI355_EINVAL) { check_mi355(rc, "mi355_conv_forward (planar input)"); return; }
-        if (net.input_direct_p) *net.input_direct_p = 0;
+        self->input_direct = 0;
         converted = net.input_t;
         check_mi355(mi355_nchw_to_tensor((const uint8_t *)net.cur_t->data, &converted, net.stream), "input layout");
         net.cur_t = &converted;
     }
-    if (net.fused_pool_t) { /* this conv + the 2x2 maxpool after it as one kernel; the pre-pool tensor is stored only if a route reads it */
-        const int rc = mi355_conv_pool_forward(&d, net.cur_t, l.blob_gpu, l.fuse_pool_keep ? &l.out_t : NULL, net.fused_pool_t, net.stream);
-        if (rc != MI355_EINVAL) { check_mi355(rc, "mi355_conv_pool_forward"); return; }
-        self->fuse_next_pool = 0;
+    int rc = MI355_EINVAL;
+    switch (kind) {
+    case FUSE_POOL: /* one kernel for the conv and the 2x2 maxpool; the pre-pool tensor is stored only if a route reads it */
+        rc = conv_pool(&l, &net, &d, pi, l.fuse_pool_keep ? &l.out_t : NULL, &next->out_t);
+        break;
+    case FUSE_UPSAMPLE: /* the conv stores into the nearest-neighbour upsample's tensor; its own is not stored */
+        rc = mi355_conv_upsample_forward(&d, net.cur_t, l.blob_gpu, &next->out_t, next->stride, net.stream);
+        break;
+    case FUSE_SHORTCUT: { /* the conv's epilogue does the quantized residual add; its own tensor is not stored */
+        const layer *from = &net.layers[next->index];
+        rc = mi355_conv_shortcut_forward(&d, net.cur_t, l.blob_gpu, &from->out_t, &next->out_t, next->shortcut_Ka, next->shortcut_Kb,
+                                         from->activ_data_uint8_zero_point[0], next->activ_data_uint8_zero_point[0], net.stream);
+        break;
     }
-    if (net.fused_up_t) { /* this conv + the nearest-neighbour upsample after it; the conv's own tensor is not stored */
-        const int rc = mi355_conv_upsample_forward(&d, net.cur_t, l.blob_gpu, net.fused_up_t, net.fused_up_stride, net.stream);
-        if (rc != MI355_EINVAL) { check_mi355(rc, "mi355_conv_upsample_forward"); return; }
-        self->fuse_next_upsample = 0;
-    }
-    if (net.fused_shortcut) { /* this conv + the quantized residual add after it; the conv's own tensor is not stored */
-        const layer *sc = net.fused_shortcut, *from = &net.layers[sc->index];
-        const int rc = mi355_conv_shortcut_forward(&d, net.cur_t, l.blob_gpu, &from->out_t, &sc->out_t, sc->shortcut_Ka, sc->shortcut_Kb,
-                                                   from->activ_data_uint8_zero_point[0], sc->activ_data_uint8_zero_point[0], net.stream);
-        if (rc != MI355_EINVAL) { check_mi355(rc, "mi355_conv_shortcut_forward"); return; }
-        self->fuse_next_shortcut = 0;
-    }
-    if (net.fused_yolo_out) { /* quant_stop head + the yolo layer after it (ref: src/yolo_layer.c:132-146) in one kernel */
-        int rc = MI355_EINVAL;
-        if (!net.keep_head_float && !net.dump_int32) /* the head's own float tensor is not stored; MI355_EINVAL: this kernel needs it */
-            rc = mi355_conv_yolo_forward(&d, net.cur_t, l.blob_gpu, &l.out_t, NULL, net.fused_yolo_out, net.fused_yolo_classes, net.stream);
+    case FUSE_YOLO: /* quant_stop head + the yolo layer after it (ref: src/yolo_layer.c:132-146) in one kernel */
+        if (!net.keep_head_float) /* the head's own float tensor is not stored; MI355_EINVAL: this kernel needs it */
+            rc = mi355_conv_yolo_forward(&d, net.cur_t, l.blob_gpu, &l.out_t, NULL, next->output_gpu, next->classes, net.stream);
         if (rc == MI355_EINVAL)
-            rc = mi355_conv_yolo_forward(&d, net.cur_t, l.blob_gpu, &l.out_t, l.output_gpu, net.fused_yolo_out, net.fused_yolo_classes, net.stream);
-        if (rc != MI355_EINVAL) { check_mi355(rc, "mi355_conv_yolo_forward"); return; }
-        self->fuse_next_yolo = 0;
+            rc = mi355_conv_yolo_forward(&d, net.cur_t, l.blob_gpu, &l.out_t, l.output_gpu, next->output_gpu, next->classes, net.stream);
+        break;
     }
-    check_mi355(mi355_conv_forward(&d, net.cur_t, l.blob_gpu, l.weights_uint8_gpu, l.weight_zero_point_gpu, &l.out_t,
-                                   net.dump_int32 ? l.output_int32_gpu : NULL,
-                                   l.quant_stop_flag ? l.output_gpu : NULL, net.stream),
-                "mi355_conv_forward");
+    if (kind != FUSE_NONE) {
+        if (rc != MI355_EINVAL) { check_mi355(rc, fused_name[kind]); return; }
+        self->fuse_next = FUSE_NONE;
+    }
+    check_mi355(conv_plain(&l, &net, &d, pi, 1), fused_name[FUSE_NONE]);
 }
 
 /* quant_stop tail shared by the glue layers: l.output = (u8 - zp) * scale (ref: src/maxpool_layer.c:163-171,

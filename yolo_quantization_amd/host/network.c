@@ -196,8 +196,8 @@ static int view_producer_ok(network *net, int j, int r)
     layer *p = &net->layers[j];
     if (j >= r || p->out_view || p->out_c % 16) return 0;
     if (p->type != CONVOLUTIONAL && p->type != UPSAMPLE && p->type != MAXPOOL) return 0;
-    if (p->type == CONVOLUTIONAL && (p->fuse_next_pool && !p->fuse_pool_keep && net->fuse_maxpool)) return 0;
-    if (j > 0 && net->layers[j - 1].fuse_next_pool && net->fuse_maxpool && p->type == MAXPOOL) return 0; /* written by the fused conv */
+    if (p->type == CONVOLUTIONAL && p->fuse_next == FUSE_POOL && !p->fuse_pool_keep && net->fuse_maxpool) return 0;
+    if (j > 0 && net->layers[j - 1].fuse_next == FUSE_POOL && net->fuse_maxpool && p->type == MAXPOOL) return 0; /* written by the fused conv */
     const int zp_differs = p->activ_data_uint8_zero_point[0] != net->layers[r].activ_data_uint8_zero_point[0];
     if (j + 1 < net->n) {
         layer *c = &net->layers[j + 1];
@@ -243,7 +243,7 @@ static void plan_views(network *net)
         if (l->type != ROUTE || l->n != 1) continue;
         layer *p = &net->layers[l->input_layers[0]];
         if (l->input_layers[0] >= r || p->type == YOLO || !p->out_t.data) continue;
-        if (p->type == CONVOLUTIONAL && p->fuse_next_pool && !p->fuse_pool_keep && net->fuse_maxpool) continue;
+        if (p->type == CONVOLUTIONAL && p->fuse_next == FUSE_POOL && !p->fuse_pool_keep && net->fuse_maxpool) continue;
         mi355_free(l->out_t.data);
         l->out_t = p->out_t;
         l->out_view = 1;
@@ -267,7 +267,7 @@ static void alloc_network_device(network *net)
     check_mi355(mi355_tensor_fill(&net->input_t, net->layers[0].input_data_uint8_zero_point[0], net->stream), "fill input");
     mi355_tensor_describe_nchw(&net->input_nchw_t, net->batch, net->h, net->w, net->c);
     net->input_nchw_t.data = net->input_uint8_gpu;
-    net->input_direct = net->c == 3 && !net->dump_int32 && !net->input_direct_off;
+    net->layers[0].input_direct = net->c == 3 && !net->dump_int32 && !net->input_direct_off;
     for (int i = 0; i < net->n; ++i) alloc_layer_device(net, i);
     plan_views(net);
     if (net->graph) { mi355_graph_destroy(net->graph); net->graph = NULL; }
@@ -334,54 +334,56 @@ void quantization_prep_host(network *net, float in_scale, uint8_t in_zp)
         check_mi355(mi355_conv_pack_epilogue(l->n, l->c, l->size, l->activation, l->activ_data_uint8_zero_point[0], l->blob_host),
                     "mi355_conv_pack_epilogue");
     }
+    plan_fusion(net); /* pure host logic: the candidates are readable (dnq_layer_plan) without a device */
 }
 
-/* conv i + maxpool i+1 can run as one kernel when the pool is the reference's size-2 / stride-2 / offset-0 window on an
- * even map, the conv is 3x3 and nothing else (a route) reads the conv's own output */
+/* The fusion candidates: conv i can run the layer after it in its own kernel, in the one way that layer's type allows
+ * (layer.fuse_next).  The planner judges by shape; the launchers have the last word at run time (layers.c).
+ *   maxpool:  the reference's size-2 window, stride 2 on an even map (or stride 1 behind a 128 / 256-channel conv), behind a 3x3
+ *             stride-1 conv; the conv's own tensor has no other reader, or (128 / 256 channels) is stored as well (fuse_pool_keep)
+ *   upsample: the conv stores every pixel stride x stride times; its own tensor has no other reader
+ *   shortcut: the conv's epilogue does the quantized residual add; its own tensor has no other reader and is not the `from`
+ *   yolo:     a quant_stop head conv whose kernel writes both float tensors */
 static void plan_fusion(network *net)
 {
-    for (int i = 0; i < net->n; ++i)
-        net->layers[i].fuse_next_pool = net->layers[i].fuse_pool_keep = net->layers[i].fuse_next_yolo = net->layers[i].fuse_next_shortcut = 0;
-    for (int i = 0; i + 1 < net->n; ++i) { /* conv + quantized residual add: the conv's own tensor has no other reader */
-        layer *c = &net->layers[i], *sc = &net->layers[i + 1];
-        if (c->type == CONVOLUTIONAL && sc->type == SHORTCUT && c->stride == 1 && !c->quant_stop_flag && !sc->quant_stop_flag &&
-            c->c % 16 == 0 && sc->index != i && !output_read_elsewhere(net, i))
-            c->fuse_next_shortcut = 1;
-    }
-    for (int i = 0; i < net->n; ++i) net->layers[i].fuse_next_upsample = 0;
-    for (int i = 0; i + 1 < net->n; ++i) { /* conv + nearest upsample: the conv stores every pixel stride x stride times */
-        layer *c = &net->layers[i], *u = &net->layers[i + 1];
-        /* (an upsample with a quant_stop float tail runs on its own: the fused store skips the layer, and with it the tail) */
-        if (c->type != CONVOLUTIONAL || u->type != UPSAMPLE || c->quant_stop_flag || u->quant_stop_flag || c->c % 64 || u->stride > 4 ||
-            c->stride != 1) continue;
-        if (!output_read_elsewhere(net, i)) c->fuse_next_upsample = 1;
-    }
-    for (int i = 0; i + 1 < net->n; ++i) { /* quant_stop head conv + yolo: one kernel writes both float tensors */
-        layer *c = &net->layers[i], *y = &net->layers[i + 1];
-        if (c->type == CONVOLUTIONAL && c->quant_stop_flag && y->type == YOLO && c->c % 16 == 0 && c->stride == 1 &&
-            c->n == y->n * (y->classes + 5))
-            c->fuse_next_yolo = 1;
-    }
+    for (int i = 0; i < net->n; ++i) net->layers[i].fuse_next = net->layers[i].fuse_pool_keep = 0;
     for (int i = 0; i + 1 < net->n; ++i) {
         layer *c = &net->layers[i], *p = &net->layers[i + 1];
-        if (c->type != CONVOLUTIONAL || p->type != MAXPOOL) continue;
-        if (c->size != 3 || c->stride != 1 || c->quant_stop_flag || p->quant_stop_flag || p->size != 2 || p->pad / 2 != 0) continue;
-        if (c->c == 128 || c->c == 256) {
-            /* the weights-stationary kernel of the middle layers (conv_ws3.hip) pools the bytes of its tile in LDS: the stride-2
-             * window on even maps, and the reference's stride-1 window (pad = 1: same size as the conv's map; yolov3-tiny's
-             * layer 11); it stores the conv's own tensor as well when a route reads it (layer 8) */
-            const int s2 = p->stride == 2 && !(c->out_h & 1) && !(c->out_w & 1);
-            const int s1 = p->stride == 1 && p->pad == 1 && p->out_h == c->out_h && p->out_w == c->out_w && c->out_h > 1;
-            if (!s2 && !s1) continue;
-            c->fuse_next_pool = 1;
-            c->fuse_pool_keep = output_read_elsewhere(net, i);
-            continue;
+        if (c->type != CONVOLUTIONAL) continue;
+        switch (p->type) {
+        case SHORTCUT:
+            if (c->stride == 1 && !c->quant_stop_flag && !p->quant_stop_flag && c->c % 16 == 0 && p->index != i && !output_read_elsewhere(net, i))
+                c->fuse_next = FUSE_SHORTCUT;
+            break;
+        case UPSAMPLE:
+            /* (an upsample with a quant_stop float tail runs on its own: the fused store skips the layer, and with it the tail) */
+            if (!c->quant_stop_flag && !p->quant_stop_flag && c->c % 64 == 0 && p->stride <= 4 && c->stride == 1 && !output_read_elsewhere(net, i))
+                c->fuse_next = FUSE_UPSAMPLE;
+            break;
+        case YOLO:
+            if (c->quant_stop_flag && c->c % 16 == 0 && c->stride == 1 && c->n == p->n * (p->classes + 5)) c->fuse_next = FUSE_YOLO;
+            break;
+        case MAXPOOL:
+            if (c->size != 3 || c->stride != 1 || c->quant_stop_flag || p->quant_stop_flag || p->size != 2 || p->pad / 2 != 0) break;
+            if (c->c == 128 || c->c == 256) {
+                /* the weights-stationary kernel of the middle layers (conv_ws3.hip) pools the bytes of its tile in LDS: the stride-2
+                 * window on even maps, and the reference's stride-1 window (pad = 1: same size as the conv's map; yolov3-tiny's
+                 * layer 11); it stores the conv's own tensor as well when a route reads it (layer 8) */
+                const int s2 = p->stride == 2 && !(c->out_h & 1) && !(c->out_w & 1);
+                const int s1 = p->stride == 1 && p->pad == 1 && p->out_h == c->out_h && p->out_w == c->out_w && c->out_h > 1;
+                if (!s2 && !s1) break;
+                c->fuse_next = FUSE_POOL;
+                c->fuse_pool_keep = output_read_elsewhere(net, i);
+                break;
+            }
+            if (p->stride != 2 || (c->out_h & 1) || (c->out_w & 1) || (c->c != 3 && c->c % 16)) break;
+            /* 64-byte-chunk layers use the row-image kernel, which has no fused form; 64 -> 64..128 has its own fused kernel */
+            if (c->c % 64 == 0 && !(c->c == 64 && c->n % 32 == 0 && c->n >= 64 && c->n <= 128)) break;
+            if (!output_read_elsewhere(net, i)) c->fuse_next = FUSE_POOL;
+            break;
+        default:
+            break;
         }
-        if (p->stride != 2) continue;
-        if ((c->out_h & 1) || (c->out_w & 1) || (c->c != 3 && c->c % 16)) continue;
-        /* 64-byte-chunk layers use the row-image kernel, which has no fused form; 64 -> 64..128 has its own fused kernel */
-        if (c->c % 64 == 0 && !(c->c == 64 && c->n % 32 == 0 && c->n >= 64 && c->n <= 128)) continue;
-        if (!output_read_elsewhere(net, i)) c->fuse_next_pool = 1;
     }
 }
 
@@ -389,7 +391,6 @@ void quantization_weights_and_activations_fixed_input(network *net, float in_sca
 {
     if (net->n_replicas > 0 || net->replica_of) error("quantization_weights_and_activations: not while replicas share this network's packed weights");
     quantization_prep_host(net, in_scale, in_zp);
-    plan_fusion(net);
     alloc_network_device(net);
     for (int i = 0; i < net->n; ++i)
         if (net->layers[i].type == CONVOLUTIONAL) upload_conv(net, i, net->has_host_weights);
@@ -1002,8 +1003,8 @@ static void run_layers(network *netp)
         if (netp->prof_ev && netp->prof_used < netp->prof_cap) error("forward_network_gpu: a layer range cannot be combined with armed per-layer events");
         if (netp->range_lo > 0) {
             const layer *pl = &netp->layers[netp->range_lo - 1];
-            const int stored = !(pl->type == CONVOLUTIONAL && netp->fuse_maxpool && !netp->dump_int32 && netp->accum_mode == MI355_ACC_EXACT &&
-                                 ((pl->fuse_next_pool && !pl->fuse_pool_keep) || pl->fuse_next_upsample || pl->fuse_next_shortcut || pl->fuse_next_yolo));
+            /* (a head conv fused with its yolo layer counts as not stored here, unlike in dnq_layer_is_fused) */
+            const int stored = !(fusion_on(netp) && pl->fuse_next != FUSE_NONE && !(pl->fuse_next == FUSE_POOL && pl->fuse_pool_keep));
             if (!stored) error("forward_network_gpu: layer range starts behind a conv whose own tensor is not stored (fused with the layer after it)");
         }
     }
@@ -1012,64 +1013,29 @@ static void run_layers(network *netp)
     if (ev) check_mi355(mi355_event_record(ev[0], net.stream), "event");
     /* The first layer reads the reference's [B][3][H][W] planes in place where its kernel can (no conversion pass); else the
      * input goes through the 4-byte-cell tensor.  The conv's forward_gpu falls back itself on MI355_EINVAL and clears the flag. */
-    const int direct = netp->input_direct && net.accum_mode == MI355_ACC_EXACT && !net.dump_int32;
+    const int direct = netp->layers[0].input_direct && net.accum_mode == MI355_ACC_EXACT && !net.dump_int32;
     const int lo = (netp->range_hi > netp->range_lo) ? netp->range_lo : 0, hi = (netp->range_hi > netp->range_lo) ? netp->range_hi : net.n;
     if (lo < 0 || hi > net.n) error("forward_network_gpu: bad layer range");
     if (!direct && lo == 0) check_mi355(mi355_nchw_to_tensor(netp->input_uint8_gpu, &netp->input_t, net.stream), "input layout");
     if (ev) check_mi355(mi355_event_record(ev[1], net.stream), "event");
     net.cur_t = direct ? &netp->input_nchw_t : &netp->input_t;
-    net.input_direct_p = &netp->input_direct;
     net.cur_f32_gpu = NULL;
     if (lo > 0) net.cur_t = &netp->layers[lo - 1].out_t;
     for (int i = lo; i < hi; ++i) {
         net.index = i;
         layer l = net.layers[i];
-        const int fuse0 = l.fuse_next_pool && net.fuse_maxpool && !net.dump_int32 && net.accum_mode == MI355_ACC_EXACT;
-        const int fuse_yolo0 = l.fuse_next_yolo && net.fuse_maxpool && !net.dump_int32 && net.accum_mode == MI355_ACC_EXACT;
-        net.fused_pool_t = fuse0 ? &netp->layers[i + 1].out_t : NULL;
-        net.fused_yolo_out = fuse_yolo0 ? netp->layers[i + 1].output_gpu : NULL;
-        net.fused_yolo_classes = fuse_yolo0 ? netp->layers[i + 1].classes : 0;
-        const int fuse_sc0 = l.fuse_next_shortcut && net.fuse_maxpool && !net.dump_int32 && net.accum_mode == MI355_ACC_EXACT;
-        net.fused_shortcut = fuse_sc0 ? &netp->layers[i + 1] : NULL;
-        const int fuse_up0 = l.fuse_next_upsample && net.fuse_maxpool && !net.dump_int32 && net.accum_mode == MI355_ACC_EXACT;
-        net.fused_up_t = fuse_up0 ? &netp->layers[i + 1].out_t : NULL;
-        net.fused_up_stride = fuse_up0 ? netp->layers[i + 1].stride : 1;
+        const int asked = fusion_on(&net) ? l.fuse_next : FUSE_NONE;
         l.forward_gpu(l, net);
         if (l.type == CONVOLUTIONAL) netp->layers[i].conv_kernel = mi355_last_conv_kernel();
-        /* plan_fusion marks candidates by shape; the launchers have the last word.  A fused call they refuse
-         * (MI355_EINVAL) was re-run unfused by the conv's forward_gpu, which also cleared the flag for good: the layer
-         * after it then runs on its own like any other. */
-        const int fuse = fuse0 && netp->layers[i].fuse_next_pool;
-        const int fuse_yolo = fuse_yolo0 && netp->layers[i].fuse_next_yolo;
-        const int fuse_up = fuse_up0 && netp->layers[i].fuse_next_upsample;
-        const int fuse_sc = fuse_sc0 && netp->layers[i].fuse_next_shortcut;
-        if (fuse_sc) { /* the shortcut layer's tensor was written by the conv kernel: hand it on and skip the layer */
-            if (ev) check_mi355(mi355_event_record(ev[i + 2], net.stream), "event");
-            ++i;
-            net.cur_t = &netp->layers[i].out_t;
-            net.cur_f32_gpu = NULL;
-            if (ev) check_mi355(mi355_event_record(ev[i + 2], net.stream), "event");
-            continue;
-        }
         if (ev) check_mi355(mi355_event_record(ev[i + 2], net.stream), "event");
-        if (fuse_up) { /* the upsample layer's tensor was written by the conv kernel: hand it on and skip the layer */
+        /* plan_fusion marks candidates by shape; the launchers have the last word.  A fused call they refuse
+         * (MI355_EINVAL) was re-run unfused by the conv's forward_gpu, which also cleared fuse_next for good: the layer
+         * after it then runs on its own like any other.  Taken: that layer's tensor was written by the conv kernel, it is
+         * handed on and the layer skipped.  A yolo layer hands on the head conv's uint8 tensor and its own activations. */
+        if (asked != FUSE_NONE && netp->layers[i].fuse_next == asked) {
             ++i;
-            net.cur_t = &netp->layers[i].out_t;
-            net.cur_f32_gpu = NULL;
-            if (ev) check_mi355(mi355_event_record(ev[i + 2], net.stream), "event");
-            continue;
-        }
-        if (fuse_yolo) { /* the yolo layer's activations were written by the conv kernel: skip it */
-            net.cur_t = &netp->layers[i].out_t;
-            ++i;
-            net.cur_f32_gpu = netp->layers[i].output_gpu;
-            if (ev) check_mi355(mi355_event_record(ev[i + 2], net.stream), "event");
-            continue;
-        }
-        if (fuse) { /* the maxpool layer already ran inside the conv kernel: hand its tensor on and skip it */
-            ++i;
-            net.cur_t = &netp->layers[i].out_t;
-            net.cur_f32_gpu = NULL;
+            net.cur_t = &netp->layers[asked == FUSE_YOLO ? i - 1 : i].out_t;
+            net.cur_f32_gpu = asked == FUSE_YOLO ? netp->layers[i].output_gpu : NULL;
             if (ev) check_mi355(mi355_event_record(ev[i + 2], net.stream), "event");
             continue;
         }
