@@ -154,6 +154,41 @@ def test_kernel_vs_oracle(si):
         assert (buf[offsets[-1]:] == SENTINEL).all(), f"{pattern}: a float at or beyond recs[offsets[B]] was written"
 
 
+MANY = [(B, names, pattern, mpi) for B in (257, 600) for names in (("n3_1x1",), ("n3_5x7",), ("n3_1x1", "n3_5x7"))
+        for pattern, mpi in (("all", None), ("rand50", None), ("empty_mid", None))]
+MANY.append((600, ("n3_5x7",), "rand50", 52))  # about half of 105 candidates are found: 52 kept truncates some images and not others
+
+
+@pytest.mark.parametrize("B,names,pattern,mpi", MANY, ids=[f"B{B}-{'+'.join(n)}-{p}" + (f"-max{m}" if m else "") for B, n, p, m in MANY])
+def test_kernel_vs_oracle_many_images(B, names, pattern, mpi):
+    """det_scan_kernel scans the images 256 at a time and carries the sum from one chunk to the next: batches of 257 (one image into the second
+    chunk) and 600 (two full chunks and a partial third), with and without a max_per_image that cuts some images short"""
+    classes, relative = 5, B % 2
+    imw, imh = [SIZES[b % len(SIZES)][0] + b % 7 for b in range(B)], [SIZES[b % len(SIZES)][1] + b % 3 for b in range(B)]
+    outs, thresh = _tensors(names, B, classes, pattern, seed=B + len(pattern))
+    cand = sum(HEADS[nm][0] * HEADS[nm][1] * HEADS[nm][2] for nm in names)
+    rc, counts, offsets, buf = _abi_decode(names, outs, B, classes, imw, imh, thresh, relative, mpi or cand)
+    assert rc == 0, binding.shim().mi355_last_error()
+    recs = buf.view(np.float32)
+    found = np.zeros(B, np.int64)
+    assert offsets[0] == 0
+    for b in range(B):
+        want = _oracle_image(names, outs, b, classes, imw[b], imh[b], thresh, relative)
+        assert counts[b].tolist() == [c for c, _ in want], (pattern, b)
+        found[b] = sum(c for c, _ in want)
+        kept = min(found[b], mpi or cand)
+        assert offsets[b + 1] - offsets[b] == kept, (pattern, b)
+        allw = np.concatenate([w for _, w in want]) if found[b] else np.zeros((0, recs.shape[1]), np.float32)
+        _assert_vs_oracle(recs[offsets[b]:offsets[b] + kept], allw[:kept])  # the heads one after the other, the first `kept` of them
+    if pattern == "all":
+        assert (found == cand).all()
+    if pattern == "empty_mid":
+        assert found[1] == 0 and offsets[1] == offsets[2] == cand and offsets[-1] == (B - 1) * cand
+    if mpi:
+        assert (found > mpi).any() and (found < mpi).any(), "the limit must cut some images short and leave others whole"
+    assert (buf[offsets[-1]:] == SENTINEL).all(), f"{pattern}: a float at or beyond recs[offsets[B]] was written"
+
+
 def test_truncation_keeps_the_first_records_and_writes_nothing_behind_them():
     names, B, classes = ("n3_5x7", "n5_19x19"), 3, 5
     imw, imh = [s[0] for s in SIZES[:B]], [s[1] for s in SIZES[:B]]

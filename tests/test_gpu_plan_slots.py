@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import oracle
+from launch_geometry import geom_conv1x1, geom_small64
 from yolo_quantization_amd import binding, synth
 
 pytestmark = pytest.mark.gpu
@@ -98,39 +99,7 @@ class Case:
         return self.name
 
 
-# ---- launch geometry the launchers must choose (restated from conv1x1.hip / conv_small.hip; a changed threshold shows up here)
-def geom_conv1x1(c, n, total, plan):
-    gmax = 32 if c <= 64 else (16 if c == 128 else 8)
-    n32 = (n + 31) & ~31
-    mtiles = ceil_div(n32, 256) if n32 > 256 else 1
-    want = 256 // mtiles
-    rounds = ceil_div(total, want * gmax * 32)
-    tp = max(ceil_div(total, want * rounds), 16)
-    if plan == 1:
-        tp = (tp + 31) & ~31
-        if rounds == 1:
-            ab = min(n32, 256) * c
-            while ab > 2 * tp * c and (c // 64) * 2 * ((tp + 32) // 32) * 1024 <= 128 * 1024:
-                tp += 32
-    G = ceil_div(tp, 32)
-    nfw = min(n32, 256)
-    nq = nfw // 32
-    lds = (c // 64) * 2 * G * 1024 + nfw * 16 + 1024 + 2 * G * 256
-    return dict(grid=ceil_div(total, tp) * mtiles, threads=max(8 // nq, 1) * nq * 64, lds=lds, tp=tp, mtiles=mtiles, rounds=rounds)
-
-
-def geom_small64(n, B, H, W, plan):
-    """conv_small.hip, 64 channels, flat tiles (pooled / 2x2-block width < 64)"""
-    OH, OW = H // 2, W // 2
-    assert OW < 64
-    total = B * OH * OW
-    rounds = ceil_div(total, 256 * 8 * 32)
-    tp = max(ceil_div(total, 256 * rounds), 32)
-    if plan == 1:
-        tp = 128 if tp > 128 else (tp // 32) * 32
-    ntiles = ceil_div(total, tp)
-    half = plan == 1 or ntiles > 256
-    return dict(grid=ntiles, threads=(1 if half else 2) * (n // 32) * 64, tp=tp, half=half, ntiles=ntiles)
+# ---- launch geometry the launchers must choose: restated in tests/launch_geometry.py (a changed threshold shows up here)
 
 
 def expect_geom(case, plan, got):
@@ -140,7 +109,7 @@ def expect_geom(case, plan, got):
     OH, OW = (H + 2 * (case.k // 2) - case.k) // case.stride + 1, (W + 2 * (case.k // 2) - case.k) // case.stride + 1
     g = case.geom
     if g == "conv1x1":
-        e = geom_conv1x1(case.c, case.n, B * H * W, plan)
+        e = geom_conv1x1(case.c, case.n, B, H, W, plan)
         assert (grid, threads, lds) == (e["grid"], e["threads"], e["lds"]), (plan, e)
         if plan == 1:
             assert e["tp"] % 32 == 0
