@@ -10,6 +10,8 @@
 #include "kargs.h"
 #include <type_traits>
 
+typedef int v2i __attribute__((ext_vector_type(2)));
+
 
 // PI (per-image input quantisation): a thread's image selects its bank entry (kargs.h bank_entry); the weights in LDS are entry 0's
 // (every entry holds the same weights), and out-of-image taps take the image's own zero point instead of the shared pad cells.
@@ -630,33 +632,75 @@ __global__ __launch_bounds__(256, 4) void conv_first_mfma_pool_kernel(const AuxA
     // prefetch stay valid: the stores are YOUNGER than the loads they follow, so a wait for "all but the k youngest loads" can only wait
     // longer, never too short.
     const unsigned rowpitch = (unsigned)(OW + 1) * (unsigned)a.pool_cs;
-    unsigned st_off[2][NM];  // pooled rows 2 wave, 2 wave + 1 of the patch; the lane's pooled column; channels 16 mt + 4 g ..
+    uint32_t dpk[2][NM];
+    unsigned d_out = 0;  // wave-uniform: byte offset of the deferred patch's first pooled cell
+    bool dall = false;   // wave-uniform: every lane of the deferred tile stores
+    // ONE store per lane and tile (WIDE).  The D layout spreads the bytes of a pooled cell over the four k-group lanes pc, pc + 16, pc + 32, pc + 48;
+    // the lane's packed dwords are exchanged across the k-groups at the end of the tile's compute (v_permlane16_swap: rows -- 16 lanes -- 1 / 3 of
+    // the first operand <-> rows 0 / 2 of the second; v_permlane32_swap: rows 2, 3 <-> rows 0, 1), VALU slots instead of vector-memory issues:
+    //   NM = 1: one swap of (dpk[0], dpk[1]); lane g then holds channels 8 (g >> 1) .. + 7 of pooled row 2 wave + (g & 1): an 8-byte store;
+    //   NM = 2: the 4 x 4 transpose of dpk[s][mt] (index 2 s + mt), four swaps; lane g then holds channels 16 mt .. + 15 of pooled row
+    //           2 wave + s, (s, mt) = (g >> 1, g & 1): a 16-byte store (conv_pool16.hip does the same).
+    // The lane's store offset and its mask follow the row it STORES, not the row it computed.
+    // !WIDE: 2 NM dword stores per lane and tile, as before the exchange -- A/B builds (tools/build_variant.sh -DMI355_NARROW_STORES), and the one
+    // instantiation that the exchange pushes over the 128-register edge into scratch (RELU6, wrapping store, 16 filters, cell input, per-image).
+#ifdef MI355_NARROW_STORES
+    constexpr bool WIDE = false;
+#else
+    constexpr bool WIDE = !(ACT == MI355_ACT_RELU6 && !SAT && NM == 1 && !PLANAR && PI);
+#endif
+    const int srow = NM == 1 ? (g & 1) : (g >> 1);
+    const unsigned st_wide = (unsigned)(2 * wave + srow) * rowpitch + pc_off + (NM == 1 ? 8u * (unsigned)(g >> 1) : 16u * (unsigned)(g & 1));
+    unsigned st_off[2][NM];  // !WIDE: pooled rows 2 wave, 2 wave + 1 of the patch; the lane's pooled column; channels 16 mt + 4 g ..
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
         for (int mt = 0; mt < NM; ++mt) st_off[s][mt] = (unsigned)(2 * wave + s) * rowpitch + pc_off + (unsigned)chq[mt];
-    uint32_t dpk[2][NM];
-    unsigned d_out = 0;  // wave-uniform: byte offset of the deferred patch's first pooled cell
-    bool dvalid[2] = {false, false};
-    bool dall = false;   // wave-uniform: every lane of the deferred tile stores
-    auto store_patch = [&](unsigned patch_off, unsigned off, uint32_t data) {
+    using dq_t = std::conditional_t<NM == 1, v2i, v4i>;
+    dq_t dq = {};  // WIDE: the exchanged dpk, what the deferred store writes
+    bool dvalid[2] = {false, false};  // (WIDE: [0] only)
+    auto transpose_dpk = [&]() {
+        if constexpr (NM == 1) {
+            const auto p = __builtin_amdgcn_permlane16_swap(dpk[0][0], dpk[1][0], false, false);
+            dq = v2i{(int)p[0], (int)p[1]};
+        } else {
+            const auto p01 = __builtin_amdgcn_permlane16_swap(dpk[0][0], dpk[0][1], false, false);
+            const auto p23 = __builtin_amdgcn_permlane16_swap(dpk[1][0], dpk[1][1], false, false);
+            const auto q02 = __builtin_amdgcn_permlane32_swap(p01[0], p23[0], false, false);
+            const auto q13 = __builtin_amdgcn_permlane32_swap(p01[1], p23[1], false, false);
+            dq = v4i{(int)q02[0], (int)q13[0], (int)q02[1], (int)q13[1]};
+        }
+    };
+    auto patch_base = [&]() {
         // (the patch pointer is wave-uniform by construction; readfirstlane puts it into scalar registers where the compiler cannot prove it)
-        const uint64_t rp = reinterpret_cast<uint64_t>(a.ypool) + (uint64_t)patch_off;
-        const uint64_t rs = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(rp >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)rp);
+        const uint64_t rp = reinterpret_cast<uint64_t>(a.ypool) + (uint64_t)d_out;
+        return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(rp >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)rp);
+    };
+    auto store_wide = [&]() {
+        const uint64_t rs = patch_base();
+        if constexpr (NM == 1) asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(st_wide), "v"(dq), "s"(rs) : "memory");
+        // (s_nop 1: a store of more than two dwords reads its data registers over several cycles; nothing pads the instruction behind an asm statement)
+        else asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(st_wide), "v"(dq), "s"(rs) : "memory");
+    };
+    auto store_patch = [&](unsigned off, uint32_t data) {
+        const uint64_t rs = patch_base();
         asm volatile("global_store_dword %0, %1, %2" ::"v"(off), "v"(data), "s"(rs) : "memory");
     };
     auto flush_stores = [&]() {
-        if (dall) {
+        if constexpr (WIDE) {
+            if (dall) store_wide();
+            else if (dvalid[0]) store_wide();
+        } else if (dall) {
 #pragma unroll
             for (int s = 0; s < 2; ++s)
 #pragma unroll
-                for (int mt = 0; mt < NM; ++mt) store_patch(d_out, st_off[s][mt], dpk[s][mt]);
+                for (int mt = 0; mt < NM; ++mt) store_patch(st_off[s][mt], dpk[s][mt]);
         } else {
 #pragma unroll
             for (int s = 0; s < 2; ++s)
                 if (dvalid[s]) {
 #pragma unroll
-                    for (int mt = 0; mt < NM; ++mt) store_patch(d_out, st_off[s][mt], dpk[s][mt]);
+                    for (int mt = 0; mt < NM; ++mt) store_patch(st_off[s][mt], dpk[s][mt]);
                 }
         }
     };
@@ -887,11 +931,16 @@ __global__ __launch_bounds__(256, 4) void conv_first_mfma_pool_kernel(const AuxA
             // (ragged right / lower patches) are masked
             d_out = tile_word(T_out, k);
             dall = (fl_cur & 2u) != 0;
+            if constexpr (WIDE) transpose_dpk();  // (here, in the epilogue's VALU stream: not at flush time, in front of the next tile's compute)
             if (!dall) {
                 const int tx = (int)((fl_cur >> 2) & 1023u), ty = (int)((fl_cur >> 12) & 1023u);
                 const bool colvalid = 16 * tx + pc < OW;
-                dvalid[0] = colvalid && 8 * ty + 2 * wave < OH;
-                dvalid[1] = colvalid && 8 * ty + 2 * wave + 1 < OH;
+                if constexpr (WIDE) {
+                    dvalid[0] = colvalid && 8 * ty + 2 * wave + srow < OH;
+                } else {
+                    dvalid[0] = colvalid && 8 * ty + 2 * wave < OH;
+                    dvalid[1] = colvalid && 8 * ty + 2 * wave + 1 < OH;
+                }
             }
             fl_cur = fl_nxt;
 #ifdef MI355_L0_STORES_IN_PLACE  // A/B builds: the stores in place, in front of the staging wait
@@ -1268,6 +1317,8 @@ int conv_first_mfma_pool_launch(AuxArgs &a, hipStream_t st)
     if ((a.n != 16 && a.n != 32) || a.y || a.acc_out || a.y_f32 || (a.H & 1) || (a.W & 1) || !a.cwb) return MI355_EINVAL;
     if (a.planar ? ((a.W & 3) || (reinterpret_cast<size_t>(a.x) & 3)) : a.in_cs != 4) return MI355_EINVAL;
     if ((long)a.in_cells + 64L * (a.W + 1) >= (1L << 31)) return MI355_EINVAL;  // 32-bit cell arithmetic in the kernel
+    // the kernel's one store per lane writes 8 (16 filters) / 16 (32 filters) bytes of a pooled cell at that alignment (a tensor's cell size is a multiple of 16)
+    if ((a.pool_cs | (int)(reinterpret_cast<uintptr_t>(a.ypool) & 15)) & (a.n == 16 ? 7 : 15)) return MI355_EINVAL;
     const int OH = a.H / 2, OW = a.W / 2;
     // 32-bit byte offsets in the kernel: the pooled tensor and (planar) the input planes
     if (((long)a.pool_lead + (long)a.B * (OH + 1) * (OW + 1) + OW + 2) * a.pool_cs >= (1L << 32)) return MI355_EINVAL;

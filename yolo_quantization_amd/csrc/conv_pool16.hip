@@ -157,11 +157,37 @@ __global__ __launch_bounds__(256, 3) void conv_pool16_kernel(const ConvArgs a)
 
     // ---- deferred stores (one tile late, behind the next tile's DMA): hand-written, scalar base + lane offset
     const unsigned rowpitch = (unsigned)(OW + 1) * (unsigned)a.pool_cs;
+    unsigned d_out = 0;
+#ifndef MI355_NARROW_STORES
+    // One 16-byte store per lane and tile.  The D layout leaves the sixteen bytes of a (pooled pixel, m-tile) in the four k-group lanes pc, pc + 16,
+    // pc + 32, pc + 48 -- a vector-memory instruction costs these kernels its issue (~150 clocks), a cross-lane swap one VALU slot: the
+    // lane's four packed dwords dpk[s][mt] (index 2 s + mt) are transposed across the k-groups at the end of the tile's compute, after which lane g
+    // holds channels 16 mt .. 16 mt + 15 of pooled row 2 wave + s for (s, mt) = (g >> 1, g & 1): its store offset and its mask follow the row it STORES.
+    const unsigned st_off = (unsigned)(2 * wave + (g >> 1)) * rowpitch + (unsigned)pc * (unsigned)a.pool_cs + 16u * (unsigned)(g & 1);
+    uint32_t dpk[2][NM];
+    v4i dq = v4i{0, 0, 0, 0};  // the transposed dpk: what the deferred store writes
+    bool dvalid = false;
+    auto transpose_dpk = [&]() {
+        // v_permlane16_swap: rows (16 lanes) 1 / 3 of the first operand <-> rows 0 / 2 of the second; v_permlane32_swap: rows 2, 3 <-> rows 0, 1
+        const auto p01 = __builtin_amdgcn_permlane16_swap(dpk[0][0], dpk[0][1], false, false);
+        const auto p23 = __builtin_amdgcn_permlane16_swap(dpk[1][0], dpk[1][1], false, false);
+        const auto q02 = __builtin_amdgcn_permlane32_swap(p01[0], p23[0], false, false);
+        const auto q13 = __builtin_amdgcn_permlane32_swap(p01[1], p23[1], false, false);
+        dq = v4i{(int)q02[0], (int)q13[0], (int)q02[1], (int)q13[1]};
+    };
+    auto flush_stores = [&]() {
+        if (dvalid) {
+            const uint64_t rp = reinterpret_cast<uint64_t>(a.ypool) + (uint64_t)d_out;
+            const uint64_t rs = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(rp >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)rp);
+            // (s_nop 1: a store of more than two dwords reads its data registers over several cycles; nothing pads the instruction behind an asm statement)
+            asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(st_off), "v"(dq), "s"(rs) : "memory");
+        }
+    };
+#else  // A/B builds (tools/build_variant.sh): four dword stores per lane and tile, as before the transpose
     unsigned st_off[2];  // pooled rows 2 wave, 2 wave + 1 of the patch, the lane's pooled column, channels 4 g .. (+ 16 mt: an immediate)
 #pragma unroll
     for (int s = 0; s < 2; ++s) st_off[s] = (unsigned)(2 * wave + s) * rowpitch + (unsigned)pc * (unsigned)a.pool_cs + 4u * g;
     uint32_t dpk[2][NM];
-    unsigned d_out = 0;
     bool dvalid[2] = {false, false};
     auto store_patch = [&](unsigned patch_off, unsigned off, uint32_t data, auto mt_c) {
         constexpr int MT = decltype(mt_c)::value;
@@ -177,6 +203,7 @@ __global__ __launch_bounds__(256, 3) void conv_pool16_kernel(const ConvArgs a)
                 store_patch(d_out, st_off[s], dpk[s][1], std::integral_constant<int, 1>{});
             }
     };
+#endif
 
     unsigned fl_cur = tile_word(T_fl, 0);
     int buf = 0;
@@ -321,8 +348,13 @@ __global__ __launch_bounds__(256, 3) void conv_pool16_kernel(const ConvArgs a)
             const int tx = (int)((fl_cur >> 2) & 1023u), ty = (int)((fl_cur >> 12) & 1023u);
             const bool all = (fl_cur & 2u) != 0;
             const bool colvalid = all || 16 * tx + pc < OW;
+#ifndef MI355_NARROW_STORES
+            transpose_dpk();  // (here, in the epilogue's VALU stream: not at flush time, in front of the next tile's compute)
+            dvalid = colvalid && (all || 8 * ty + 2 * wave + (g >> 1) < OH);
+#else
             dvalid[0] = colvalid && (all || 8 * ty + 2 * wave < OH);
             dvalid[1] = colvalid && (all || 8 * ty + 2 * wave + 1 < OH);
+#endif
         }
         fl_cur = fl_nxt;
     }
@@ -346,6 +378,8 @@ int conv_pool16_launch(ConvArgs &a, hipStream_t st)
     const int c = a.cb * a.nchunks;
     if (!conv_pool16_eligible(a.n, c, a.ksize) || !a.ypool || a.y || a.acc_out || a.y_f32 || a.res || a.stride != 1 || !a.ept) return MI355_EINVAL;
     if ((a.H & 1) || (a.W & 1) || a.in_cs != c || a.in_lead < 1 || a.pool_w < a.n) return MI355_EINVAL;
+    // the kernel's one store per lane writes bytes 16 mt .. 16 mt + 15 of a pooled cell: cells are 16-byte aligned (a tensor's cell size is a multiple of 16)
+    if ((a.pool_cs & 15) || (reinterpret_cast<uintptr_t>(a.ypool) & 15)) return MI355_EINVAL;
     if ((size_t)a.in_cells * (size_t)a.in_cs >= ((size_t)1 << 31)) return MI355_EINVAL;  // 32-bit cell / byte arithmetic in the kernel
     const int OH = a.H / 2, OW = a.W / 2;
     if (((long)a.pool_lead + (long)a.B * (OH + 1) * (OW + 1) + OW + 2) * a.pool_cs >= (1L << 32)) return MI355_EINVAL;
