@@ -187,11 +187,11 @@ struct network {
     void *pi_idx_gpu, *pi_idx_host; /* [B] int32 entry | [B] float scale | [B] uint8 zero point */
     float *pi_mm_gpu, *pi_mm_host;  /* [B][2] max, min */
     int pi_packed;              /* bank entries packed by the last batch (the others came from the cache) */
-    /* Frame input (network_frames_u8 / _nv12 / _planar_input_gpu): lazily allocated, sized by the batch, freed with the network and on
+    /* Frame input (network_frames_u8 / _nv12 / _planar / _packed / _p010_input_gpu): lazily allocated, sized by the batch, freed with the network and on
      * re-batch.  A replica owns its own. */
     void *fr_arena_gpu;         /* staging of host frames: the bytes as they came, rows at their pitch, 256-byte aligned planes */
     size_t fr_arena_bytes;
-    void *fr_table_gpu, *fr_table_host; /* [fr_cap] entries of the kind last fed (mi355_frame_u8 | _yuv | _planar) and their host mirror:
+    void *fr_table_gpu, *fr_table_host; /* [fr_cap] entries of the kind last fed (mi355_frame_u8 | _yuv | _planar | _packed | _p010) and their host mirror:
                                            one table for every kind, sized for the largest entry */
     int fr_kind;                /* the kind of frames in the table */
     float *fr_mm_gpu, *fr_mm_host; /* [fr_cap][2] max, min */
@@ -263,6 +263,27 @@ void network_frames_nv12_input_gpu(network *net, const uint8_t *const *y, const 
 void network_frames_planar_input_gpu(network *net, const uint8_t *const *p0, const uint8_t *const *p1, const uint8_t *const *p2,
                                      const int *w, const int *h, const int *pitch0, const int *pitch1, const int *pitch2,
                                      int format, int matrix, int frames_on_device);
+/* The same step for frames of one packed plane of 4-byte groups (format: MI355_PACKED_* of mi355_frame_packed, mi355_yolo_int8.h):
+ * RGBA, BGRA, ARGB, ABGR -- a pixel is four bytes, the fourth is never looked at, pitch[b] >= 4 * w[b], matrix must be 0 -- as display
+ * surfaces, screen capture and decoder post-processing deliver them, and YUYV (YUY2), UYVY, YVYU -- a macropixel of two pixels is
+ * four bytes, pitch[b] >= 4 * ((w[b] + 1) / 2), converted in registers with `matrix` (MI355_YUV_BT601 .. MI355_YUV_BT709_FULL) and chroma
+ * at [y][x >> 1] -- as USB / V4L2 cameras deliver them.  frames[b] holds h[b] rows pitch[b] bytes apart (a null pitch array: tightly
+ * packed rows of whole groups); the bytes go up as they are.  The result is, bit for bit, network_frames_u8_input_gpu's on the RGB
+ * frame of the same pixels, and for the 4:2:2 formats network_frames_planar_input_gpu's on the MI355_PLANAR_I422 frame of the
+ * de-interleaved samples.  Arena, min / max and pair buffers, the one host sync and both (scale, zero point) branches are that
+ * function's.  frames_on_device != 0: device pointers, used in place.  3-channel networks only; an unknown format or matrix, a matrix
+ * with an RGB format, a null pointer, w or h outside 1..32768 or a pitch below its minimum die via error() before the device is
+ * touched. */
+void network_frames_packed_input_gpu(network *net, const uint8_t *const *frames, const int *w, const int *h, const int *pitch, int format,
+                                     int matrix, int frames_on_device);
+/* The same step for P010 / P012 / P016 frames as hardware decoders deliver 10-bit streams: NV12's two planes with 16-bit little-endian
+ * samples, the significant bits at the top.  y[b] holds h[b] rows of w[b] samples pitch_y[b] BYTES apart (>= 2 * w[b]), uv[b]
+ * (h[b] + 1) / 2 rows of (w[b] + 1) / 2 (U, V) pairs pitch_uv[b] bytes apart (>= 4 * ((w[b] + 1) / 2)); a null pitch array: tightly
+ * packed.  Both planes go up as they are; the device reads the high byte of every sample (truncation, not rounding) and goes on as
+ * the NV12 source with `matrix`: the result is, bit for bit, network_frames_nv12_input_gpu's on the MI355_YUV_NV12 frame
+ * (y >> 8, uv >> 8).  frames_on_device != 0: device pointers, used in place.  Refusals as above. */
+void network_frames_p010_input_gpu(network *net, const uint8_t *const *y, const uint8_t *const *uv, const int *w, const int *h,
+                                   const int *pitch_y, const int *pitch_uv, int matrix, int frames_on_device);
 /* Per-image input quantisation, opt-in (off: image 0 defines the scale of the whole batch, as before).  On: every image of a batch is
  * quantised with its own min / max, scale and zero point, and layer 0 runs with that image's constants (mi355_conv_forward_per_image):
  * slot b of every layer equals the batch-1 run on image b.  The quantisers above honour it.  Returns 0, or MI355_EINVAL with a message

@@ -400,6 +400,68 @@ int mi355_frames_planar_letterbox_minmax(const mi355_frame_planar *table_dev, co
 int mi355_frames_planar_letterbox_quantize(const mi355_frame_planar *table_dev, const mi355_frame_planar *table_host,
                                            int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev,
                                            uint8_t *out_u8, void *stream);
+/* The same two calls for frames of one packed plane, four bytes per pixel or per pair of pixels, as display surfaces, screen capture,
+ * decoder post-processing (RGBA / BGRA) and USB / V4L2 cameras (YUYV = YUY2, UYVY) deliver them.  Rows lie `pitch` bytes apart.
+ *   MI355_PACKED_RGBA, _BGRA, _ARGB, _ABGR: pixel (x, y) is the four bytes at data + y * pitch + 4 * x; plane k (R, G, B) reads byte
+ *     {0, 1, 2}, {2, 1, 0}, {1, 2, 3}, {3, 2, 1} of them.  The fourth byte (alpha or padding) has no influence on any result.
+ *     pitch >= 4 * w, `matrix` must be 0, no formula is applied.
+ *   MI355_PACKED_YUYV, _UYVY, _YVYU (4:2:2): a macropixel of two neighbouring pixels is the four bytes at
+ *     data + y * pitch + 4 * (x >> 1): Y0 U Y1 V, U Y0 V Y1 or Y0 V Y1 U.  Pixel x takes Y[x & 1] and the macropixel's (U, V) -- chroma
+ *     at [y][x >> 1], MI355_PLANAR_I422's rule --, and its RGB bytes come from the int32 formulas and the `matrix` rows of
+ *     mi355_frame_yuv above, in registers at every bilinear tap.  A row holds (w + 1) / 2 macropixels: pitch >= 4 * ((w + 1) / 2); with
+ *     an odd w the second luma byte of a row's last macropixel is never used.
+ * A pixel / macropixel is one 4-byte load, which the device serves at any alignment: any address and pitch are legal, multiples of 4
+ * are the natural and the aligned case.  From the RGB bytes on nothing is new: min / max and the quantised bytes are, bit for bit, what the u8 calls give for the
+ * interleaved RGB frame of the same pixels, and what the planar calls give for the MI355_PLANAR_I422 frame with the de-interleaved
+ * samples.  A new struct and new calls: MI355_ABI_VERSION is unchanged. */
+#define MI355_PACKED_RGBA 0  /* bytes R G B x */
+#define MI355_PACKED_BGRA 1  /* bytes B G R x */
+#define MI355_PACKED_ARGB 2  /* bytes x R G B */
+#define MI355_PACKED_ABGR 3  /* bytes x B G R */
+#define MI355_PACKED_YUYV 4  /* bytes Y0 U Y1 V (YUY2) */
+#define MI355_PACKED_UYVY 5  /* bytes U Y0 V Y1 */
+#define MI355_PACKED_YVYU 6  /* bytes Y0 V Y1 U */
+typedef struct mi355_frame_packed {   /* 32 bytes */
+    const uint8_t *data;              /* DEVICE pointer to the first byte of row 0 */
+    int w, h;                         /* pixels */
+    int pitch;                        /* bytes from one row to the next */
+    int format, matrix;               /* MI355_PACKED_*; matrix: MI355_YUV_BT601 .. _BT709_FULL, 0 with the four RGB formats */
+    int reserved;                     /* zero */
+} mi355_frame_packed;
+/* The contract of the _yuv_ calls: table_host is validated before anything is launched; a null pointer, w or h outside 1..32768, a
+ * pitch below its minimum, an unknown format or matrix, a non-zero matrix with one of the four RGB formats, or a frame the letterbox
+ * geometry refuses return MI355_EINVAL with a message that starts "frames_packed:", and nothing is written.  B <= 65535. */
+int mi355_frames_packed_letterbox_minmax(const mi355_frame_packed *table_dev, const mi355_frame_packed *table_host,
+                                         int B, int w, int h, float *minmax, void *stream);
+int mi355_frames_packed_letterbox_quantize(const mi355_frame_packed *table_dev, const mi355_frame_packed *table_host,
+                                           int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev,
+                                           uint8_t *out_u8, void *stream);
+/* The same two calls for P010 / P012 / P016 frames, as hardware decoders deliver HEVC / AV1 Main10 streams: NV12's two planes with
+ * 16-bit little-endian samples whose significant bits are at the top.  y holds h rows of w samples, uv (h + 1) / 2 rows of (w + 1) / 2
+ * pairs (U, V) of samples; pitches are in BYTES, pitch_y >= 2 * w and pitch_uv >= 4 * ((w + 1) / 2).  The 8-bit sample is the HIGH BYTE
+ * of the 16-bit one -- a truncation (sample >> 8), NOT a rounding, and so the same for P010, P012 and P016 --:
+ *     Y8[y][x] = y[y * pitch_y + 2 * x + 1]
+ *     U8 = uv[cy * pitch_uv + 4 * cx + 1],  V8 = uv[cy * pitch_uv + 4 * cx + 3]     with cx = x >> 1, cy = y >> 1
+ * Single bytes are loaded: no alignment is required of the planes or pitches, and the low bytes have no influence on any result.  From
+ * these bytes on it is the NV12 source: the results are, bit for bit, what the _yuv_ calls give for the MI355_YUV_NV12 frame
+ * (y >> 8, uv >> 8).  The entry has mi355_frame_yuv's field layout; `layout` is reserved.  A new struct and new calls:
+ * MI355_ABI_VERSION is unchanged. */
+typedef struct mi355_frame_p010 {   /* 48 bytes */
+    const uint8_t *y, *uv; /* DEVICE pointers to the first byte of row 0 of each plane */
+    int w, h;              /* pixels (of the Y plane) */
+    int pitch_y;           /* bytes from one Y row to the next, >= 2 * w */
+    int pitch_uv;          /* bytes from one chroma row to the next, >= 4 * ((w + 1) / 2) */
+    int layout;            /* reserved, zero */
+    int matrix;            /* MI355_YUV_BT601 .. MI355_YUV_BT709_FULL */
+    int reserved[2];       /* zero */
+} mi355_frame_p010;
+/* The contract of the _yuv_ calls: a null plane, w or h outside 1..32768, a pitch below its minimum, an unknown matrix, a non-zero
+ * `layout` or `reserved`, or a frame the letterbox geometry refuses return MI355_EINVAL with a message that starts "frames_p010:",
+ * and nothing is written.  B <= 65535. */
+int mi355_frames_p010_letterbox_minmax(const mi355_frame_p010 *table_dev, const mi355_frame_p010 *table_host, int B, int w, int h,
+                                       float *minmax, void *stream);
+int mi355_frames_p010_letterbox_quantize(const mi355_frame_p010 *table_dev, const mi355_frame_p010 *table_host, int B, int w, int h,
+                                         const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
 /* *sum_dev += an order-independent 64-bit checksum of `dwords` 32-bit words at buf (device pointers; zero *sum_dev first).  The
  * host's determinism self-check compares it between passes over the same input (network_selfcheck, darknet_q.h). */
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream);

@@ -1,6 +1,6 @@
 """Times the input step alone: from the batch's first upload to the network's uint8 input being ready on the device.
 
-yolov3-tiny @416, batch 64, 640 x 480 RGB frames (synthetic bytes, every frame its own range), four variants:
+yolov3-tiny @416, batch 64, 640 x 480 RGB frames (synthetic bytes, every frame its own range), seven variants:
   float   the float entry points: per frame one upload of the planar float image (byte / 255, converted before the clock starts)
           and one network_letterbox_input_gpu, then network_quantize_input_gpu (min / max, host sync, quantise)
   frames  network_frames_u8_input_gpu: the bytes go up as they are, two launches for the whole batch
@@ -8,11 +8,16 @@ yolov3-tiny @416, batch 64, 640 x 480 RGB frames (synthetic bytes, every frame i
           in numpy, chroma of the top-left pixel of every 2 x 2 block), half the bytes go up, converted inside the two launches
   i420    network_frames_planar_input_gpu: the same planes with the chroma de-interleaved into a U and a V plane (made before the
           clock starts), the same number of bytes as nv12 in three host arrays per frame
+  bgra    network_frames_packed_input_gpu: the RGB frames as B G R A pixels, alpha 255 (made before the clock starts): 4 bytes a pixel
+  yuyv    network_frames_packed_input_gpu: the NV12 planes as Y0 U Y1 V macropixels, every chroma row written twice (made before the
+          clock starts): 2 bytes a pixel
+  p010    network_frames_p010_input_gpu: the NV12 planes as 16-bit samples, the byte at the top (made before the clock starts): 3 bytes
+          a pixel
 each in shared-scale and per-image mode.  A step is timed twice: HIP events on the network's stream around it, and the host clock
 from before the first upload to after a stream synchronise.  The variants alternate within a repeat; the same batch is fed every step
 (steady state: layer 0 is not re-derived, the per-image bank serves every key from its cache).  Before timing, the float and frames
 variants' uint8 inputs, scales and zero points are compared for equality, and the nv12 variant's with those of the frames entry point
-fed the RGB frames a numpy restatement of the integer YUV -> RGB formulas makes of the NV12 planes; the i420 variant's are compared with the nv12 variant's.  `host_convert_ms` is the byte -> planar float conversion the float variant
+fed the RGB frames a numpy restatement of the integer YUV -> RGB formulas makes of the NV12 planes; the i420, yuyv and p010 variants' are compared with the nv12 variant's, the bgra variant's with the frames variant's.  `host_convert_ms` is the byte -> planar float conversion the float variant
 needs before its first upload, done with numpy here: an indication only, not part of either timed step.
 Prints one JSON line."""
 import argparse
@@ -122,6 +127,39 @@ class I420Variant:
         self.net.H.network_frames_planar_input_gpu(self.net.h, self.p[0], self.p[1], self.p[2], self.w, self.h, None, None, None, 0, 0, 0)
 
 
+class PackedVariant:
+    """frames: uint8 [h][row_bytes] arrays of one packed plane; fmt: MI355_PACKED_*"""
+
+    def __init__(self, net, frames, w, fmt):
+        B = len(frames)
+        self.net, self.frames, self.fmt = net, frames, fmt
+        self.ptrs, self.w, self.h = (C.c_void_p * B)(), (C.c_int * B)(), (C.c_int * B)()
+        for b, f in enumerate(frames):
+            self.ptrs[b], self.h[b], self.w[b] = f.ctypes.data, f.shape[0], w
+
+    def step(self):
+        self.net.H.network_frames_packed_input_gpu(self.net.h, self.ptrs, self.w, self.h, None, self.fmt, 0, 0)
+
+
+def rgb_to_bgra(f):
+    return np.ascontiguousarray(np.concatenate([f[..., ::-1], np.full(f.shape[:2] + (1,), 255, np.uint8)], axis=-1)).reshape(f.shape[0], -1)
+
+
+def nv12_to_yuyv(y, uv):
+    """Y0 U Y1 V macropixels of an even-width NV12 frame: row r takes chroma row r // 2, so nearest sampling reads the same samples"""
+    h, w = y.shape
+    c = uv[np.arange(h) // 2]
+    return np.ascontiguousarray(np.stack([y[:, 0::2], c[..., 0], y[:, 1::2], c[..., 1]], axis=-1)).reshape(h, 2 * w)
+
+
+class P010Variant(NV12Variant):
+    def __init__(self, net, planes):
+        super().__init__(net, [((y.astype(np.uint16) << 8), (uv.astype(np.uint16) << 8)) for y, uv in planes])
+
+    def step(self):
+        self.net.H.network_frames_p010_input_gpu(self.net.h, self.y, self.uv, self.w, self.h, None, None, 0, 0)
+
+
 def same_input(a, b):
     same = np.array_equal(pull_input(a), pull_input(b))
     qa, qb = a.input_quantization(), b.input_quantization()
@@ -163,6 +201,8 @@ def main():
     wts = "/tmp/input_path_bench.weights"
     synth.synth_weights(CFG, wts, seed=5)
     sw, sh = (int(v) for v in a.src.split("x"))
+    if sw % 2:
+        sys.exit("--src: the yuyv variant is made from the NV12 planes and needs an even width")
     frames = make_frames(a.batch, sw, sh)
     t0 = time.perf_counter()
     for f in frames:
@@ -170,22 +210,27 @@ def main():
     convert_ms = (time.perf_counter() - t0) * 1e3
     planes = [rgb_to_nv12(f) for f in frames]
     converted = [nv12_to_rgb(y, uv) for y, uv in planes]
+    bgra, yuyv = [rgb_to_bgra(f) for f in frames], [nv12_to_yuyv(y, uv) for y, uv in planes]
     ev = Events()
     res = {}
     for mode in ("shared", "per_image"):
-        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("float", "frames", "nv12", "i420")}
+        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("float", "frames", "nv12", "i420", "bgra", "yuyv", "p010")}
         if mode == "per_image":
             for n in nets.values():
                 n.set_input_per_image(True)
         var = {"float": FloatVariant(nets["float"], frames), "frames": FramesVariant(nets["frames"], frames),
-               "nv12": NV12Variant(nets["nv12"], planes), "i420": I420Variant(nets["i420"], planes)}
+               "nv12": NV12Variant(nets["nv12"], planes), "i420": I420Variant(nets["i420"], planes),
+               "bgra": PackedVariant(nets["bgra"], bgra, sw, 1), "yuyv": PackedVariant(nets["yuyv"], yuyv, sw, 4),
+               "p010": P010Variant(nets["p010"], planes)}
         for _ in range(a.warmup):
             for v in var.values():
                 v.step()
         same = same_input(nets["float"], nets["frames"])
+        same_bgra = same_input(nets["bgra"], nets["frames"])
         FramesVariant(nets["frames"], converted).step()  # the frames entry point on the numpy conversion of the NV12 planes
         same_nv12 = same_input(nets["nv12"], nets["frames"])
         same_i420 = same_input(nets["i420"], nets["nv12"])
+        same_yuyv, same_p010 = same_input(nets["yuyv"], nets["nv12"]), same_input(nets["p010"], nets["nv12"])
         for _ in range(a.warmup):
             var["frames"].step()
         runs = {k: {"device_ms": [], "wall_ms": []} for k in var}
@@ -198,6 +243,11 @@ def main():
         res[mode] = {"identical_input": same, "nv12_identical_to_frames_on_converted_rgb": same_nv12,
                      "i420_identical_to_nv12": same_i420, "float": runs["float"], "frames": runs["frames"], "nv12": runs["nv12"],
                      "i420": runs["i420"],
+                     "bgra_identical_to_frames": same_bgra, "yuyv_identical_to_nv12": same_yuyv, "p010_identical_to_nv12": same_p010,
+                     "bgra": runs["bgra"], "yuyv": runs["yuyv"], "p010": runs["p010"],
+                     "bgra_over_frames_device": round(med["frames"]["device_ms"] / med["bgra"]["device_ms"], 3),
+                     "yuyv_over_nv12_device": round(med["nv12"]["device_ms"] / med["yuyv"]["device_ms"], 3),
+                     "p010_over_nv12_device": round(med["nv12"]["device_ms"] / med["p010"]["device_ms"], 3),
                      "speedup_device": round(med["float"]["device_ms"] / med["frames"]["device_ms"], 3),
                      "speedup_wall": round(med["float"]["wall_ms"] / med["frames"]["wall_ms"], 3),
                      "nv12_over_frames_device": round(med["frames"]["device_ms"] / med["nv12"]["device_ms"], 3),
@@ -209,7 +259,7 @@ def main():
     res["host_convert_ms_numpy"] = round(convert_ms, 3)
     res["config"] = {"cfg": "yolov3-tiny_quant.cfg", "batch": a.batch, "src": a.src, "iters": a.iters, "warmup": a.warmup,
                      "repeats": a.repeats, "values": "median of `iters` steps per repeat; speedup = median over repeats, float / frames; "
-                               "nv12_over_frames = frames / nv12; i420_over_nv12 = nv12 / i420"}
+                               "nv12_over_frames = frames / nv12; i420_over_nv12 = nv12 / i420; bgra_over_frames, yuyv_over_nv12, p010_over_nv12 likewise"}
     print(json.dumps(res))
 
 

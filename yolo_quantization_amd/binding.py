@@ -63,6 +63,23 @@ class FramePlanar(C.Structure):
 PLANAR_FORMAT = {"i420": 0, "yv12": 1, "i422": 2, "i444": 3, "rgb": 4, "bgr": 5}  # MI355_PLANAR_I420 .. MI355_PLANAR_BGR
 
 
+class FramePacked(C.Structure):
+    """mi355_frame_packed: one entry of the frame table of mi355_frames_packed_letterbox_minmax / _quantize (data: a DEVICE pointer)."""
+    _fields_ = [("data", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("pitch", C.c_int), ("format", C.c_int), ("matrix", C.c_int),
+                ("reserved", C.c_int)]
+
+
+PACKED_FORMAT = {"rgba": 0, "bgra": 1, "argb": 2, "abgr": 3, "yuyv": 4, "uyvy": 5, "yvyu": 6}  # MI355_PACKED_RGBA .. MI355_PACKED_YVYU
+PACKED_RGBX = ("rgba", "bgra", "argb", "abgr")  # four bytes a pixel; the others: four bytes a macropixel of two pixels (4:2:2)
+
+
+class FrameP010(C.Structure):
+    """mi355_frame_p010: one entry of the frame table of mi355_frames_p010_letterbox_minmax / _quantize (y, uv: DEVICE pointers);
+    mi355_frame_yuv's field layout, `layout` reserved and zero."""
+    _fields_ = [("y", C.c_void_p), ("uv", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("pitch_y", C.c_int), ("pitch_uv", C.c_int),
+                ("layout", C.c_int), ("matrix", C.c_int), ("reserved", C.c_int * 2)]
+
+
 class YoloHead(C.Structure):
     """mi355_yolo_head: one yolo layer of mi355_yolo_detections_batch (yolo_out, anchors, mask: DEVICE pointers)."""
     _fields_ = [("yolo_out", C.c_void_p), ("anchors", C.c_void_p), ("mask", C.c_void_p), ("n", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -148,6 +165,10 @@ def shim():
         L.mi355_frames_yuv_letterbox_quantize.argtypes = [vp, C.POINTER(FrameYUV), ci, ci, ci, vp, vp, vp, vp]
         L.mi355_frames_planar_letterbox_minmax.argtypes = [vp, C.POINTER(FramePlanar), ci, ci, ci, vp, vp]
         L.mi355_frames_planar_letterbox_quantize.argtypes = [vp, C.POINTER(FramePlanar), ci, ci, ci, vp, vp, vp, vp]
+        L.mi355_frames_packed_letterbox_minmax.argtypes = [vp, C.POINTER(FramePacked), ci, ci, ci, vp, vp]
+        L.mi355_frames_packed_letterbox_quantize.argtypes = [vp, C.POINTER(FramePacked), ci, ci, ci, vp, vp, vp, vp]
+        L.mi355_frames_p010_letterbox_minmax.argtypes = [vp, C.POINTER(FrameP010), ci, ci, ci, vp, vp]
+        L.mi355_frames_p010_letterbox_quantize.argtypes = [vp, C.POINTER(FrameP010), ci, ci, ci, vp, vp, vp, vp]
         L.mi355_yolo_detections_sizes.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, C.c_float, ci, vp, ci, vp, vp]
         L.mi355_yolo_detections_batch_work_ints.restype = C.c_long
         L.mi355_yolo_detections_batch_work_ints.argtypes = [C.POINTER(YoloHead), ci, ci]
@@ -386,6 +407,9 @@ def host():
                                                     C.POINTER(ci), ci, ci, ci]
         L.network_frames_planar_input_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(ci), C.POINTER(ci),
                                                       C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, ci, ci]
+        L.network_frames_packed_input_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, ci, ci]
+        L.network_frames_p010_input_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci),
+                                                    C.POINTER(ci), ci, ci]
         L.quantization_prep_host.argtypes = [vp, C.c_float, C.c_uint8]
         L.forward_network_gpu.argtypes = [vp]
         L.network_predict.restype = vp
@@ -467,6 +491,35 @@ def _byte_rows(a, keep):
         a = np.ascontiguousarray(a)
     keep.append(a)
     return a.ctypes.data, a.strides[0]
+
+
+def _sample_rows(f, sample_bytes, inner, keep, what):
+    """(address, pitch in bytes, shape, on_device) of a frame plane [rows][...] + inner of `sample_bytes`-byte samples: a host array
+    (through _byte_rows, as bytes) or a device tensor (anything with data_ptr(), shape, stride() and element_size(), as a torch
+    tensor has; its samples must be contiguous inside a row, rows may be padded; where it has a dtype, that must be the unsigned
+    integer of the sample's size, as a host array's)."""
+    if hasattr(f, "data_ptr"):
+        shape = tuple(f.shape)
+        nd = len(shape)
+        want = 1
+        dtype = str(getattr(f, "dtype", "")).rsplit(".", 1)[-1]  # "torch.uint8" -> "uint8"
+        ok = f.element_size() == sample_bytes and nd >= 2 and shape[nd - len(inner):] == inner and dtype in ("", f"uint{8 * sample_bytes}")
+        for k in range(nd - 1, 0, -1):  # strides are in samples
+            ok = ok and f.stride(k) == want
+            want *= shape[k]
+        if not ok or f.stride(0) < want:
+            raise ValueError(f"{what}: a device tensor must hold uint{8 * sample_bytes} samples, contiguous inside its rows")
+        return f.data_ptr(), f.stride(0) * sample_bytes, shape, True
+    a = np.asarray(f)
+    if a.dtype.itemsize != sample_bytes or a.dtype.kind != "u" or a.ndim < 2 or a.shape[a.ndim - len(inner):] != inner:
+        raise ValueError(f"{what}: a plane must be an array of uint{8 * sample_bytes}")
+    if sample_bytes > 1:
+        a = a.astype(a.dtype.newbyteorder("<"), copy=False)  # little-endian samples (a no-op on little-endian hosts)
+        if a.strides[-1] != sample_bytes:
+            a = np.ascontiguousarray(a)
+        a = a.view(np.uint8)
+    ptr, pitch = _byte_rows(a, keep)
+    return ptr, pitch, tuple(np.asarray(f).shape), False
 
 
 class Net:
@@ -679,6 +732,73 @@ class Net:
             hs[b], ws[b] = h, w
         self.H.network_frames_planar_input_gpu(self.h, ptr[0], ptr[1], ptr[2], ws, hs, pitch[0], pitch[1], pitch[2],
                                                PLANAR_FORMAT[format], YUV_MATRIX[matrix], int(on_device))
+        return self._prepared(self._pull_input())
+
+    def prepare_from_frames_packed(self, frames, format="bgra", matrix="bt601"):
+        """Packed frame input path (network_frames_packed_input_gpu), one plane of 4-byte groups.  `format` = "rgba" | "bgra" | "argb" |
+        "abgr": frames[b] is uint8 [h][w][4], the byte that is not R, G or B is never looked at; leave `matrix` at its default.
+        `format` = "yuyv" (YUY2) | "uyvy" | "yvyu" (4:2:2, a macropixel of two pixels in four bytes): frames[b] is uint8 [h][row_bytes]
+        and w = row_bytes / 2, or a tuple (array, w) -- the only way to name an odd width, whose rows still hold (w + 1) / 2 whole
+        macropixels --; converted with `matrix` = "bt601" | "bt601f" | "bt709" | "bt709f" on the device, inside the letterbox.  A
+        frame is a host array or a device tensor (anything with data_ptr(), shape, stride() and element_size(), as a torch tensor
+        has; used in place: the work that wrote it must have finished, and its memory must belong to the HIP runtime this library
+        is linked to), all frames of a batch the same.  Row strides are passed through as the pitch, as prepare_from_frames_u8 does.
+        Returns what prepare_from_frames_u8 returns."""
+        assert len(frames) == self.batch
+        B = self.batch
+        rgbx = format in PACKED_RGBX
+        if format not in PACKED_FORMAT:
+            raise ValueError(f"prepare_from_frames_packed: format is one of {', '.join(PACKED_FORMAT)}")
+        if rgbx and matrix != "bt601":
+            raise ValueError("prepare_from_frames_packed: matrix goes with yuyv / uyvy / yvyu only")
+        keep, where = [], set()
+        ptrs, ws, hs, ps = (C.c_void_p * B)(), (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)()
+        for b, f in enumerate(frames):
+            f, w = f if isinstance(f, (tuple, list)) else (f, None)
+            if rgbx:
+                if w is not None:
+                    raise ValueError("prepare_from_frames_packed: (array, w) goes with yuyv / uyvy / yvyu only")
+                ptrs[b], ps[b], shape, dev = _sample_rows(f, 1, (4,), keep, "prepare_from_frames_packed")
+                if len(shape) != 3:
+                    raise ValueError(f"prepare_from_frames_packed: a {format} frame must be uint8 [h][w][4]")
+                hs[b], ws[b] = shape[:2]
+            else:
+                ptrs[b], ps[b], shape, dev = _sample_rows(f, 1, (), keep, "prepare_from_frames_packed")
+                if len(shape) != 2 or (w is None and shape[1] % 4) or (w is not None and (w < 1 or shape[1] < 4 * ((w + 1) // 2))):
+                    raise ValueError(f"prepare_from_frames_packed: a {format} frame must be uint8 [h][row_bytes] holding (w + 1) // 2 "
+                                     "macropixels of 4 bytes a row; give (array, w) for an odd w")
+                hs[b], ws[b] = shape[0], shape[1] // 2 if w is None else w
+            where.add(dev)
+        if len(where) != 1:
+            raise ValueError("prepare_from_frames_packed: the frames of a batch are all host arrays or all device tensors")
+        self.H.network_frames_packed_input_gpu(self.h, ptrs, ws, hs, ps, PACKED_FORMAT[format], 0 if rgbx else YUV_MATRIX[matrix],
+                                               int(where.pop()))
+        return self._prepared(self._pull_input())
+
+    def prepare_from_frames_p010(self, frames, matrix="bt601"):
+        """P010 / P012 / P016 frame input path (network_frames_p010_input_gpu): frames[b] is a pair (y, uv) of uint16 little-endian
+        planes, [h][w] and [(h + 1) // 2][(w + 1) // 2][2] with (U, V) pairs, the significant bits of a sample at the top -- host
+        arrays or device tensors (see prepare_from_frames_packed), all frames of a batch the same.  Both planes go up as they are; the
+        device reads the high byte of every sample (sample >> 8: truncation, not rounding) and converts with `matrix` = "bt601" |
+        "bt601f" | "bt709" | "bt709f" inside the letterbox, as prepare_from_frames_nv12 does for (y >> 8, uv >> 8).  Row strides are
+        passed through as pitches.  Returns what prepare_from_frames_u8 returns."""
+        assert len(frames) == self.batch
+        B = self.batch
+        keep, where = [], set()
+        ys, uvs = (C.c_void_p * B)(), (C.c_void_p * B)()
+        ws, hs, py, puv = (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)()
+        for b, f in enumerate(frames):
+            if not isinstance(f, (tuple, list)) or len(f) != 2:
+                raise ValueError("prepare_from_frames_p010: every frame must be a pair (y, uv)")
+            ys[b], py[b], sy, dev_y = _sample_rows(f[0], 2, (), keep, "prepare_from_frames_p010")
+            uvs[b], puv[b], suv, dev_uv = _sample_rows(f[1], 2, (2,), keep, "prepare_from_frames_p010")
+            if len(sy) != 2 or len(suv) != 3 or suv[:2] != ((sy[0] + 1) // 2, (sy[1] + 1) // 2):
+                raise ValueError("prepare_from_frames_p010: every frame must be (uint16 [h][w], uint16 [(h + 1) // 2][(w + 1) // 2][2])")
+            hs[b], ws[b] = sy
+            where |= {dev_y, dev_uv}
+        if len(where) != 1:
+            raise ValueError("prepare_from_frames_p010: the planes of a batch are all host arrays or all device tensors")
+        self.H.network_frames_p010_input_gpu(self.h, ys, uvs, ws, hs, py, puv, YUV_MATRIX[matrix], int(where.pop()))
         return self._prepared(self._pull_input())
 
     def push_input(self, x_u8):

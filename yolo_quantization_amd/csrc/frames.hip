@@ -15,7 +15,12 @@
 //   SourceYUV     NV12 / NV21 (mi355_frames_yuv_*): the bytes of a source pixel are converted from (Y, U, V) in registers at every
 //                 bilinear tap, with the integer formulas of the header (mi355_frame_yuv); no RGB frame is written anywhere;
 //   SourcePlanar  three separate planes (mi355_frames_planar_*: I420, YV12, I422, I444, planar RGB / BGR): the YUV formats share the
-//                 NV12 source's tap walk and arithmetic with their own chroma shifts, the RGB formats take their bytes as they are.
+//                 NV12 source's tap walk and arithmetic with their own chroma shifts, the RGB formats take their bytes as they are;
+//   SourcePacked  one plane of four bytes per pixel (RGBA, BGRA, ARGB, ABGR) or per two pixels (YUYV, UYVY, YVYU)
+//                 (mi355_frames_packed_*): the RGB formats pick three of a pixel's four bytes, the 4:2:2 formats are I422 with luma and
+//                 chroma of a macropixel in one 4-byte group: one 4-byte load per row and macropixel the taps touch;
+//   SourceP010    NV12 with 16-bit little-endian samples (mi355_frames_p010_*: P010, P012, P016): the high byte of every sample is
+//                 the NV12 byte (truncation), loaded on its own.
 #include "kargs.h"
 
 // letterbox_launch's geometry (glue.hip), shared by the host-side validation and the kernels: one function compiled for both sides, so
@@ -115,7 +120,8 @@ __device__ static inline void yuv_rgb(const YuvMatrix &m, int luma, const int t[
 
 // The taps of a YUV source whose chroma sample of pixel (x, y) lies at (x >> sx, y >> sy), sx, sy in {0, 1}.  Columns ix, ix + 1 share
 // a sample when sx = 1 and ix is even, rows iy, iy + 1 when sy = 1 and iy is even: a sample is loaded once; with a shift of 0 the
-// neighbouring tap always has its own.  Src: y, pitch_y, m and chroma(cx, cy, t), the terms of the sample at (cx, cy).
+// neighbouring tap always has its own.  Src: m, pitch_y, luma_at(x, y), the address of the luma byte of pixel (x, y), luma_step, the
+// bytes from there to the next pixel's, and chroma(cx, cy, t), the terms of the sample at (cx, cy).
 template <class Src>
 __device__ static inline void yuv_taps(const Src &s, int sx, int sy, int ix, int iy, bool two_x, bool two_y, uint8_t p[2][2][3])
 {
@@ -133,12 +139,12 @@ __device__ static inline void yuv_taps(const Src &s, int sx, int sy, int ix, int
         copy3(t[1][0], t[0][0]);
         copy3(t[1][1], t[0][1]);
     }
-    const uint8_t *row = s.y + (size_t)iy * s.pitch_y + ix;
+    const uint8_t *row = s.luma_at(ix, iy);
 #pragma unroll
     for (int r = 0; r < 2; ++r, row += s.pitch_y) {
         if (r == 1 && !two_y) break;
         yuv_rgb(s.m, row[0], t[r][0], p[r][0]);
-        if (two_x) yuv_rgb(s.m, row[1], t[r][1], p[r][1]);
+        if (two_x) yuv_rgb(s.m, row[Src::luma_step], t[r][1], p[r][1]);
     }
 }
 
@@ -163,6 +169,8 @@ struct SourceYUV {
         : y(f.y), uv(f.uv), w(f.w), h(f.h), pitch_y(f.pitch_y), pitch_uv(f.pitch_uv), iu(f.layout == MI355_YUV_NV21 ? 1 : 0),
           iv(f.layout == MI355_YUV_NV21 ? 0 : 1), pair_aligned(((reinterpret_cast<size_t>(f.uv) | (size_t)f.pitch_uv) & 1) == 0),
           m(f.matrix) {}
+    static constexpr int luma_step = 1;
+    __device__ const uint8_t *luma_at(int x, int yy) const { return y + (size_t)yy * pitch_y + x; }
     // the chroma terms of the pair at (cx, cy)
     __device__ void chroma(int cx, int cyy, int t[3]) const
     {
@@ -214,6 +222,8 @@ struct SourcePlanar {
         u = f.plane[iu]; pitch_u = f.pitch[iu];
         v = f.plane[iv]; pitch_v = f.pitch[iv];
     }
+    static constexpr int luma_step = 1;
+    __device__ const uint8_t *luma_at(int x, int yy) const { return y + (size_t)yy * pitch_y + x; }
     // the chroma terms of the sample at (cx, cy): one byte from each chroma plane
     __device__ void chroma(int cx, int cyy, int t[3]) const
     {
@@ -237,6 +247,104 @@ struct SourcePlanar {
             }
         }
     }
+};
+
+// One plane of 4-byte groups (mi355_frame_packed): a group is a pixel of the RGB formats (planes 0, 1, 2 = R, G, B pick three of its
+// bytes, the fourth is never looked at) and a macropixel of two pixels in the 4:2:2 formats, which are I422 (chroma at (x >> 1, y))
+// with luma and chroma of a macropixel side by side.  A group is always one 4-byte load, whatever the frame's address and pitch: the
+// load is declared unaligned and gfx950 serves unaligned global loads (hipcc merges four byte loads into this very instruction, so a
+// byte-wise path for frames that are not 4-byte aligned would compile to the same code).  The format is uniform over the workgroup,
+// so its branches do not diverge.
+struct SourcePacked {
+    using Frame = mi355_frame_packed;
+    static constexpr const char *name = "frames_packed";
+    static const char *check_pointers(const Frame &f) { return f.data ? nullptr : "null frame pointer"; }
+    static const char *check(const Frame &f)
+    {
+        if (f.format < MI355_PACKED_RGBA || f.format > MI355_PACKED_YVYU) return "unknown format (MI355_PACKED_RGBA .. _YVYU)";
+        if (f.matrix < MI355_YUV_BT601 || f.matrix > MI355_YUV_BT709_FULL) return "unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)";
+        const bool rgb = f.format <= MI355_PACKED_ABGR;
+        if (rgb && f.matrix != 0) return "matrix must be 0 with MI355_PACKED_RGBA / _BGRA / _ARGB / _ABGR";
+        if (rgb && f.pitch < 4 * f.w) return "pitch < 4 * w";
+        if (!rgb && f.pitch < 4 * ((f.w + 1) / 2)) return "pitch < 4 * ((w + 1) / 2)";
+        return nullptr;
+    }
+    const uint8_t *data;
+    int w, h, pitch;
+    int s0, s1, s2;  // bit positions inside a group (byte k in bits 8 k): of R, G, B, or of Y0, U, V (Y1 lies 16 bits above Y0)
+    bool rgb;
+    YuvMatrix m;
+    __device__ explicit SourcePacked(const mi355_frame_packed &f)
+        : data(f.data), w(f.w), h(f.h), pitch(f.pitch), rgb(f.format <= MI355_PACKED_ABGR), m(f.matrix)
+    {
+        // byte positions of (R, G, B) / (Y0, U, V) by format
+        const int pos[7][3] = {{0, 1, 2}, {2, 1, 0}, {1, 2, 3}, {3, 2, 1}, {0, 1, 3}, {1, 0, 2}, {0, 3, 1}};
+        s0 = 8 * pos[f.format][0]; s1 = 8 * pos[f.format][1]; s2 = 8 * pos[f.format][2];
+    }
+    // the four bytes of group gx of row yy, byte k in bits 8 k: one load at any alignment
+    __device__ uint32_t group(int gx, int yy) const
+    {
+        uint32_t g;
+        __builtin_memcpy(&g, data + (size_t)yy * pitch + 4 * (size_t)gx, 4);
+        return g;
+    }
+    // 4:2:2: the RGB bytes of pixel x from its macropixel g (group x >> 1): Y[x & 1] and the macropixel's (U, V)
+    __device__ void pixel422(uint32_t g, int x, uint8_t out[3]) const
+    {
+        int t[3];
+        yuv_chroma_terms(m, (int)(g >> s1 & 255), (int)(g >> s2 & 255), t);
+        yuv_rgb(m, (int)(g >> (s0 + 16 * (x & 1)) & 255), t, out);
+    }
+    __device__ void taps(int ix, int iy, bool two_x, bool two_y, uint8_t p[2][2][3]) const
+    {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (r == 1 && !two_y) break;
+            if (rgb) {
+                const uint32_t g = group(ix, iy + r);
+                p[r][0][0] = (uint8_t)(g >> s0); p[r][0][1] = (uint8_t)(g >> s1); p[r][0][2] = (uint8_t)(g >> s2);
+                if (two_x) {
+                    const uint32_t g1 = group(ix + 1, iy + r);
+                    p[r][1][0] = (uint8_t)(g1 >> s0); p[r][1][1] = (uint8_t)(g1 >> s1); p[r][1][2] = (uint8_t)(g1 >> s2);
+                }
+            } else {  // one load per row serves both taps of an even ix; an odd ix + 1 opens the next macropixel
+                const uint32_t g = group(ix >> 1, iy + r);
+                pixel422(g, ix, p[r][0]);
+                if (two_x) pixel422((ix & 1) ? group((ix >> 1) + 1, iy + r) : g, ix + 1, p[r][1]);
+            }
+        }
+    }
+};
+
+// NV12 with 16-bit little-endian samples, the significant bits at the top (mi355_frame_p010: P010, P012, P016).  The byte the NV12
+// source would read is the sample's high byte -- truncation, not rounding --, a single byte load at any alignment; the low bytes are
+// never loaded.
+struct SourceP010 {
+    using Frame = mi355_frame_p010;
+    static constexpr const char *name = "frames_p010";
+    static const char *check_pointers(const Frame &f) { return f.y && f.uv ? nullptr : "null plane pointer"; }
+    static const char *check(const Frame &f)
+    {
+        if (f.pitch_y < 2 * f.w) return "pitch_y < 2 * w";
+        if (f.pitch_uv < 4 * ((f.w + 1) / 2)) return "pitch_uv < 4 * ((w + 1) / 2)";
+        if (f.layout != 0 || f.reserved[0] != 0 || f.reserved[1] != 0) return "layout and reserved must be 0";
+        if (f.matrix < MI355_YUV_BT601 || f.matrix > MI355_YUV_BT709_FULL) return "unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)";
+        return nullptr;
+    }
+    const uint8_t *y, *uv;
+    int w, h, pitch_y, pitch_uv;
+    YuvMatrix m;
+    __device__ explicit SourceP010(const mi355_frame_p010 &f)
+        : y(f.y), uv(f.uv), w(f.w), h(f.h), pitch_y(f.pitch_y), pitch_uv(f.pitch_uv), m(f.matrix) {}
+    static constexpr int luma_step = 2;
+    __device__ const uint8_t *luma_at(int x, int yy) const { return y + (size_t)yy * pitch_y + 2 * (size_t)x + 1; }
+    // the chroma terms of the pair at (cx, cy): the high bytes of its U and V samples
+    __device__ void chroma(int cx, int cyy, int t[3]) const
+    {
+        const uint8_t *p = uv + (size_t)cyy * pitch_uv + 4 * (size_t)cx;
+        yuv_chroma_terms(m, p[1], p[3], t);
+    }
+    __device__ void taps(int ix, int iy, bool two_x, bool two_y, uint8_t p[2][2][3]) const { yuv_taps(*this, 1, 1, ix, iy, two_x, two_y, p); }
 };
 
 // the three letterboxed floats (planes 0, 1, 2) of output pixel (x, y)
@@ -416,7 +524,7 @@ int frames_letterbox_quantize_launch(const Frame *table_dev, int B, int w, int h
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }
 
-// the three kinds behind the C-ABI (shim.hip)
+// the five kinds behind the C-ABI (shim.hip)
 #define FRAMES_KIND(S)                                                                                                                \
     template const char *frames_check<S, S::Frame>(const S::Frame *, int, int, int);                                                            \
     template int frames_letterbox_minmax_launch<S, S::Frame>(const S::Frame *, int, int, int, uint32_t *, hipStream_t);                         \
@@ -425,3 +533,5 @@ int frames_letterbox_quantize_launch(const Frame *table_dev, int B, int w, int h
 FRAMES_KIND(SourceU8)
 FRAMES_KIND(SourceYUV)
 FRAMES_KIND(SourcePlanar)
+FRAMES_KIND(SourcePacked)
+FRAMES_KIND(SourceP010)

@@ -239,10 +239,12 @@ int image_minmax_batched_launch(const float *x, int B, long count, uint32_t *mm,
 int image_quantize_per_image_launch(const float *x, int B, long count, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out,
                                     hipStream_t st);
 int image_minmax_seed_launch(uint32_t *mm, int B, hipStream_t st);
-// frames.hip: a kind of frames is a Source (Frame = its table entry in the C-ABI), instantiated there for these three
+// frames.hip: a kind of frames is a Source (Frame = its table entry in the C-ABI), instantiated there for these five
 struct SourceU8;      // mi355_frame_u8
 struct SourceYUV;     // mi355_frame_yuv
 struct SourcePlanar;  // mi355_frame_planar
+struct SourcePacked;  // mi355_frame_packed
+struct SourceP010;    // mi355_frame_p010
 template <class Source, class Frame> const char *frames_check(const Frame *host, int B, int w, int h);  // NULL, or why the batch is refused
 template <class Source, class Frame> int frames_letterbox_minmax_launch(const Frame *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st);
 template <class Source, class Frame>

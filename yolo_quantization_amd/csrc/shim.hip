@@ -1104,6 +1104,31 @@ int mi355_frames_planar_letterbox_quantize(const mi355_frame_planar *table_dev, 
                                          stream);
 }
 
+int mi355_frames_packed_letterbox_minmax(const mi355_frame_packed *table_dev, const mi355_frame_packed *table_host, int B, int w, int h,
+                                         float *minmax, void *stream)
+{
+    return frames_minmax<SourcePacked>("frames_packed: letterbox_minmax: null", table_dev, table_host, B, w, h, minmax, stream);
+}
+
+int mi355_frames_packed_letterbox_quantize(const mi355_frame_packed *table_dev, const mi355_frame_packed *table_host, int B, int w, int h,
+                                           const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream)
+{
+    return frames_quantize<SourcePacked>("frames_packed: letterbox_quantize: null", table_dev, table_host, B, w, h, scale_dev, zp_dev, out_u8,
+                                         stream);
+}
+
+int mi355_frames_p010_letterbox_minmax(const mi355_frame_p010 *table_dev, const mi355_frame_p010 *table_host, int B, int w, int h,
+                                       float *minmax, void *stream)
+{
+    return frames_minmax<SourceP010>("frames_p010: letterbox_minmax: null", table_dev, table_host, B, w, h, minmax, stream);
+}
+
+int mi355_frames_p010_letterbox_quantize(const mi355_frame_p010 *table_dev, const mi355_frame_p010 *table_host, int B, int w, int h,
+                                         const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream)
+{
+    return frames_quantize<SourceP010>("frames_p010: letterbox_quantize: null", table_dev, table_host, B, w, h, scale_dev, zp_dev, out_u8, stream);
+}
+
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream)
 {
     if (!buf || !sum_dev || dwords < 0) return einval("checksum: null");

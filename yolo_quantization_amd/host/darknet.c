@@ -28,6 +28,11 @@
  * letterbox, network_frames_nv12_input_gpu; the output is that of -frames u8 on the converted RGB frame).
  * -frames i420 | yv12 | i422 | i444 [-matrix ...] (the same for raw frames of three tightly packed planes, as software decoders write
  * them, in files named <anything>_<W>x<H>.<format>; network_frames_planar_input_gpu).
+ * -frames rgba | bgra | argb | abgr (raw frames of four bytes a pixel, as display surfaces and screen capture deliver them, 4 * W * H
+ * bytes; no -matrix) and -frames yuyv | uyvy | yvyu [-matrix ...] (raw packed 4:2:2 frames as cameras deliver them,
+ * 4 * ((W + 1) / 2) * H bytes), in files named <anything>_<W>x<H>.<format>; network_frames_packed_input_gpu.
+ * -frames p010 [-matrix ...] (raw P010 frames as hardware decoders deliver 10-bit video, NV12's shape with 16-bit little-endian
+ * samples, in files named <anything>_<W>x<H>.p010; network_frames_p010_input_gpu).
  *
  * Image input: binary PPM (P6) of ANY size (letterboxed like the reference does), a raw `.u8` file holding [c][h][w] bytes at
  * network size, or `synthetic:<seed>`.  JPEG/PNG decoding is third-party code in the reference (stb_image, SURVEY.md 2
@@ -150,8 +155,9 @@ static void dump_layer(const char *dir, network *net, int i)
 
 /* -frames u8: the sources go up as interleaved bytes (network_frames_u8_input_gpu), no host float conversion; nv12 | nv21: they are raw
  * _<W>x<H>.nv12 files (network_frames_nv12_input_gpu); i420 | yv12 | i422 | i444: raw _<W>x<H>.<format> files
- * (network_frames_planar_input_gpu) */
-enum { FRAMES_NONE, FRAMES_U8, FRAMES_NV12, FRAMES_PLANAR };
+ * (network_frames_planar_input_gpu); rgba | bgra | argb | abgr | yuyv | uyvy | yvyu: raw _<W>x<H>.<format> files of one packed plane
+ * (network_frames_packed_input_gpu); p010: raw _<W>x<H>.p010 files (network_frames_p010_input_gpu) */
+enum { FRAMES_NONE, FRAMES_U8, FRAMES_NV12, FRAMES_PLANAR, FRAMES_PACKED, FRAMES_P010 };
 
 typedef struct {
     const char *datacfg, *cfgfile, *weightfile, *filename, *dumpdir, *packed_in, *packed_out;
@@ -159,6 +165,7 @@ typedef struct {
     int frames;            /* -frames: FRAMES_NONE, or how the sources go to the device (feed_frames) */
     int yuv_layout, yuv_matrix; /* MI355_YUV_NV12 / _NV21, MI355_YUV_BT601 .. _BT709_FULL (-matrix) */
     int planar_format;     /* MI355_PLANAR_I420 .. MI355_PLANAR_I444 */
+    int packed_format;     /* MI355_PACKED_RGBA .. MI355_PACKED_YVYU */
     float thresh, hier_thresh;
     int batch, accum, store, use_graph, iters, gpu, boxes, quiet, inflight;
     int rank, nranks;      /* -gpus with -bcast: this replica's rank; rank 0 reads the weights file, the others receive blobs */
@@ -215,8 +222,9 @@ static void feed_frames(const detect_job *job, network *net, char *const *paths,
         } else { /* the file's planes one after the other */
             char why[1024];
             size_t bytes[2];
-            raw[b] = load_raw_frame_file(paths[b], job->frames == FRAMES_NV12 ? RAW_FRAME_NV12 : job->planar_format, &imw[b], &imh[b], bytes,
-                                         why, sizeof(why));
+            const int kind = job->frames == FRAMES_NV12 ? RAW_FRAME_NV12 : job->frames == FRAMES_P010 ? RAW_FRAME_P010
+                           : job->frames == FRAMES_PACKED ? RAW_FRAME_RGBA + job->packed_format : job->planar_format;
+            raw[b] = load_raw_frame_file(paths[b], kind, &imw[b], &imh[b], bytes, why, sizeof(why));
             if (!raw[b]) error(why);
             pl[0][b] = raw[b]; pl[1][b] = raw[b] + bytes[0]; pl[2][b] = pl[1][b] + bytes[1];
         }
@@ -225,6 +233,10 @@ static void feed_frames(const detect_job *job, network *net, char *const *paths,
         network_frames_planar_input_gpu(net, pl[0], pl[1], pl[2], imw, imh, NULL, NULL, NULL, job->planar_format, job->yuv_matrix, 0);
     else if (job->frames == FRAMES_NV12)
         network_frames_nv12_input_gpu(net, pl[0], pl[1], imw, imh, NULL, NULL, job->yuv_layout, job->yuv_matrix, 0);
+    else if (job->frames == FRAMES_PACKED)
+        network_frames_packed_input_gpu(net, pl[0], imw, imh, NULL, job->packed_format, job->yuv_matrix, 0);
+    else if (job->frames == FRAMES_P010)
+        network_frames_p010_input_gpu(net, pl[0], pl[1], imw, imh, NULL, NULL, job->yuv_matrix, 0);
     else
         network_frames_u8_input_gpu(net, pl[0], imw, imh, NULL, MI355_FRAME_RGB, 0);
     for (int b = 0; b < B; ++b) free(raw[b]);
@@ -421,7 +433,7 @@ int main(int argc, char **argv)
     if (argc < 2) {
         fprintf(stderr, "usage: %s detector test <data> <cfg> <weights> <image> [-thresh t] [-i gpu | -gpus a,b,..] [-batch B] "
                         "[-accum exact|ref-f32] [-parity wrap|saturate] [-dump dir] [-graph] [-n iters] [-boxes] "
-                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8|nv12|nv21|i420|yv12|i422|i444] [-matrix bt601|bt601f|bt709|bt709f]\n", argv[0]);
+                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8|nv12|nv21|i420|yv12|i422|i444|rgba|bgra|argb|abgr|yuyv|uyvy|yvyu|p010] [-matrix bt601|bt601f|bt709|bt709f]\n", argv[0]);
         return 0;
     }
     detect_job job;
@@ -453,9 +465,15 @@ int main(int argc, char **argv)
     if (frames_s && (0 == strcmp(frames_s, "nv12") || 0 == strcmp(frames_s, "nv21"))) job.frames = FRAMES_NV12;
     for (int k = 0; k < 4; ++k)
         if (frames_s && 0 == strcmp(frames_s, planar_known[k])) { job.frames = FRAMES_PLANAR; job.planar_format = k; }
+    static const char *const packed_known[7] = {"rgba", "bgra", "argb", "abgr", "yuyv", "uyvy", "yvyu"}; /* MI355_PACKED_RGBA .. _YVYU */
+    for (int k = 0; k < 7; ++k)
+        if (frames_s && 0 == strcmp(frames_s, packed_known[k])) { job.frames = FRAMES_PACKED; job.packed_format = k; }
+    if (frames_s && 0 == strcmp(frames_s, "p010")) job.frames = FRAMES_P010;
     if (frames_s && !job.frames)
         error("-frames: `u8` (8-bit interleaved frames), `nv12` and `nv21` (raw video frames, files named _<W>x<H>.nv12), `i420`, `yv12`, "
-              "`i422` and `i444` (raw planar frames, files named _<W>x<H>.<format>) are known");
+              "`i422` and `i444` (raw planar frames, files named _<W>x<H>.<format>), `rgba`, `bgra`, `argb`, `abgr`, `yuyv`, `uyvy` and "
+              "`yvyu` (raw packed frames, files named _<W>x<H>.<format>) and `p010` (raw 10-bit video frames, files named _<W>x<H>.p010) "
+              "are known");
     job.yuv_layout = frames_s && 0 == strcmp(frames_s, "nv21") ? MI355_YUV_NV21 : MI355_YUV_NV12;
     job.yuv_matrix = MI355_YUV_BT601;
     if (matrix_s) {
@@ -463,7 +481,10 @@ int main(int argc, char **argv)
         int m = -1;
         for (int k = 0; k < 4; ++k) if (0 == strcmp(matrix_s, known[k])) m = k;
         if (m < 0) error("-matrix: bt601 (the default), bt601f, bt709 and bt709f are known");
-        if (job.frames != FRAMES_NV12 && job.frames != FRAMES_PLANAR) error("-matrix goes with -frames nv12 | nv21 | i420 | yv12 | i422 | i444");
+        if (job.frames == FRAMES_PACKED && job.packed_format <= MI355_PACKED_ABGR)
+            error("-matrix does not go with -frames rgba | bgra | argb | abgr: their bytes are RGB already");
+        if (job.frames != FRAMES_NV12 && job.frames != FRAMES_PLANAR && job.frames != FRAMES_PACKED && job.frames != FRAMES_P010)
+            error("-matrix goes with -frames nv12 | nv21 | i420 | yv12 | i422 | i444 | yuyv | uyvy | yvyu | p010");
         job.yuv_matrix = m;
     }
     if (job.iters < 1) job.iters = 1;

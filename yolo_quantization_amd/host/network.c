@@ -691,10 +691,12 @@ void network_quantize_input_gpu(network *net)
 /* ------------------------------------------------------------------------------------------------- frame input
  * Two launches for the whole batch (frames.hip): letterbox + min / max, then letterbox + quantise; the float image exists in registers
  * only.  The (scale, zero point) branches are the float path's (input_pair_shared, input_pairs_per_image).  Interleaved RGB / BGR
- * frames, NV12 / NV21 frames and frames of three separate planes differ in their table entries, the planes they describe and the pair
- * of C-ABI calls; the table, the staging arena and everything else are shared. */
-enum { FR_U8, FR_YUV, FR_PLANAR }; /* the kind of frames an entry point feeds (net->fr_kind) */
-static const size_t fr_entry_bytes[3] = {sizeof(mi355_frame_u8), sizeof(mi355_frame_yuv), sizeof(mi355_frame_planar)};
+ * frames, NV12 / NV21 frames, frames of three separate planes, packed 4-byte frames (RGBA .. ABGR, YUYV .. YVYU) and P010 frames differ
+ * in their table entries, the planes they describe and the pair of C-ABI calls; the table, the staging arena and everything else are
+ * shared. */
+enum { FR_U8, FR_YUV, FR_PLANAR, FR_PACKED, FR_P010 }; /* the kind of frames an entry point feeds (net->fr_kind) */
+static const size_t fr_entry_bytes[5] = {sizeof(mi355_frame_u8), sizeof(mi355_frame_yuv), sizeof(mi355_frame_planar),
+                                         sizeof(mi355_frame_packed), sizeof(mi355_frame_p010)};
 
 static void detb_free(network *net)
 {
@@ -809,6 +811,8 @@ static void fr_finish(network *net)
     const void *tg = net->fr_table_gpu, *th = net->fr_table_host;
     check_mi355(mi355_h2d(net->fr_table_gpu, th, fr_entry_bytes[kind] * (size_t)B, net->stream), "upload frame table");
     if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_planar_letterbox_minmax");
+    else if (kind == FR_PACKED) check_mi355(mi355_frames_packed_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_packed_letterbox_minmax");
+    else if (kind == FR_P010) check_mi355(mi355_frames_p010_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_p010_letterbox_minmax");
     else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_yuv_letterbox_minmax");
     else check_mi355(mi355_frames_u8_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_u8_letterbox_minmax");
     check_mi355(mi355_d2h(net->fr_mm_host, net->fr_mm_gpu, 2 * sizeof(float) * (size_t)B, net->stream), "minmax d2h");
@@ -832,6 +836,8 @@ static void fr_finish(network *net)
     }
     uint8_t *out = net->input_uint8_gpu;
     if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_planar_letterbox_quantize");
+    else if (kind == FR_PACKED) check_mi355(mi355_frames_packed_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_packed_letterbox_quantize");
+    else if (kind == FR_P010) check_mi355(mi355_frames_p010_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_p010_letterbox_quantize");
     else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_yuv_letterbox_quantize");
     else check_mi355(mi355_frames_u8_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_u8_letterbox_quantize");
 }
@@ -922,6 +928,65 @@ void network_frames_planar_input_gpu(network *net, const uint8_t *const *p0, con
         }
     }
     if (!frames_on_device) fr_stage_frames(net, planes, 3);
+    free(planes);
+    fr_finish(net);
+}
+
+void network_frames_packed_input_gpu(network *net, const uint8_t *const *frames, const int *w, const int *h, const int *pitch, int format,
+                                     int matrix, int frames_on_device)
+{
+    const int B = net->batch;
+    if (!frames || !w || !h) error("network_frames_packed_input_gpu: null frames / sizes");
+    if (format < MI355_PACKED_RGBA || format > MI355_PACKED_YVYU) error("network_frames_packed_input_gpu: unknown format (MI355_PACKED_RGBA .. _YVYU)");
+    if (matrix < MI355_YUV_BT601 || matrix > MI355_YUV_BT709_FULL) error("network_frames_packed_input_gpu: unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)");
+    const int rgb = format <= MI355_PACKED_ABGR;
+    if (rgb && matrix != 0) error("network_frames_packed_input_gpu: matrix must be 0 with MI355_PACKED_RGBA / _BGRA / _ARGB / _ABGR");
+    if (net->c != 3) error("network_frames_packed_input_gpu: packed frames feed 3-channel networks only");
+    for (int b = 0; b < B; ++b) {
+        if (!frames[b]) error("network_frames_packed_input_gpu: null frame");
+        if (w[b] < 1 || h[b] < 1 || w[b] > 32768 || h[b] > 32768) error("network_frames_packed_input_gpu: need 1 <= w, h <= 32768 for every frame");
+        if (pitch && pitch[b] < 4 * (rgb ? w[b] : (w[b] + 1) / 2))
+            error("network_frames_packed_input_gpu: need pitch >= 4 * w (RGB formats) or 4 * ((w + 1) / 2) (4:2:2 formats) for every frame");
+    }
+    mi355_frame_packed *tab = fr_begin(net, FR_PACKED);
+    fr_plane *planes = calloc((size_t)B, sizeof(fr_plane));
+    for (int b = 0; b < B; ++b) {
+        const int row = 4 * (rgb ? w[b] : (w[b] + 1) / 2); /* whole groups: a pixel, or a macropixel of two */
+        memset(&tab[b], 0, sizeof(tab[b]));
+        tab[b].data = frames[b];
+        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch = pitch ? pitch[b] : row; tab[b].format = format; tab[b].matrix = matrix;
+        planes[b] = (fr_plane){frames[b], (size_t)row, (size_t)h[b], (size_t)tab[b].pitch, &tab[b].data};
+    }
+    if (!frames_on_device) fr_stage_frames(net, planes, 1);
+    free(planes);
+    fr_finish(net);
+}
+
+void network_frames_p010_input_gpu(network *net, const uint8_t *const *y, const uint8_t *const *uv, const int *w, const int *h,
+                                   const int *pitch_y, const int *pitch_uv, int matrix, int frames_on_device)
+{
+    const int B = net->batch;
+    if (!y || !uv || !w || !h) error("network_frames_p010_input_gpu: null planes / sizes");
+    if (matrix < MI355_YUV_BT601 || matrix > MI355_YUV_BT709_FULL) error("network_frames_p010_input_gpu: unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)");
+    if (net->c != 3) error("network_frames_p010_input_gpu: P010 frames feed 3-channel networks only");
+    for (int b = 0; b < B; ++b) {
+        if (!y[b] || !uv[b]) error("network_frames_p010_input_gpu: null plane");
+        if (w[b] < 1 || h[b] < 1 || w[b] > 32768 || h[b] > 32768) error("network_frames_p010_input_gpu: need 1 <= w, h <= 32768 for every frame");
+        if ((pitch_y && pitch_y[b] < 2 * w[b]) || (pitch_uv && pitch_uv[b] < 4 * ((w[b] + 1) / 2)))
+            error("network_frames_p010_input_gpu: need pitch_y >= 2 * w and pitch_uv >= 4 * ((w + 1) / 2) for every frame");
+    }
+    mi355_frame_p010 *tab = fr_begin(net, FR_P010);
+    fr_plane *planes = calloc(2 * (size_t)B, sizeof(fr_plane));
+    for (int b = 0; b < B; ++b) {
+        const int cw4 = 4 * ((w[b] + 1) / 2), ch = (h[b] + 1) / 2; /* bytes of a row of (U, V) pairs of 16-bit samples */
+        memset(&tab[b], 0, sizeof(tab[b]));
+        tab[b].y = y[b]; tab[b].uv = uv[b];
+        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch_y = pitch_y ? pitch_y[b] : 2 * w[b]; tab[b].pitch_uv = pitch_uv ? pitch_uv[b] : cw4;
+        tab[b].matrix = matrix;
+        planes[2 * b] = (fr_plane){y[b], 2 * (size_t)w[b], (size_t)h[b], (size_t)tab[b].pitch_y, &tab[b].y};
+        planes[2 * b + 1] = (fr_plane){uv[b], (size_t)cw4, (size_t)ch, (size_t)tab[b].pitch_uv, &tab[b].uv};
+    }
+    if (!frames_on_device) fr_stage_frames(net, planes, 2);
     free(planes);
     fr_finish(net);
 }

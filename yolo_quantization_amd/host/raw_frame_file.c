@@ -3,11 +3,18 @@
 #include <stdlib.h>
 #include <string.h>
 
-/* what a kind brings: the extension, the name messages call it by, the shifts of its chroma size, the number of chroma planes */
-typedef struct { int kind; const char *ext, *name; int sx, sy, chroma_planes; } raw_kind;
-static const raw_kind kinds[5] = {{RAW_FRAME_I420, ".i420", "i420", 1, 1, 2}, {RAW_FRAME_YV12, ".yv12", "yv12", 1, 1, 2},
-                                  {RAW_FRAME_I422, ".i422", "i422", 1, 0, 2}, {RAW_FRAME_I444, ".i444", "i444", 0, 0, 2},
-                                  {RAW_FRAME_NV12, ".nv12", "NV12", 1, 1, 1}}; /* one plane of pairs: twice the width */
+/* what a kind brings: the extension, the name messages call it by, the shifts of its chroma size, the number of chroma planes, the
+ * bytes of a sample and, for the packed kinds (one plane, no chroma plane), how many pixels share a 4-byte group */
+typedef struct { int kind; const char *ext, *name; int sx, sy, chroma_planes, sample_bytes, group_pixels; } raw_kind;
+#define N_KINDS 13
+static const raw_kind kinds[N_KINDS] = {{RAW_FRAME_I420, ".i420", "i420", 1, 1, 2, 1, 0}, {RAW_FRAME_YV12, ".yv12", "yv12", 1, 1, 2, 1, 0},
+                                        {RAW_FRAME_I422, ".i422", "i422", 1, 0, 2, 1, 0}, {RAW_FRAME_I444, ".i444", "i444", 0, 0, 2, 1, 0},
+                                        {RAW_FRAME_NV12, ".nv12", "NV12", 1, 1, 1, 1, 0}, /* one plane of pairs: twice the width */
+                                        {RAW_FRAME_RGBA, ".rgba", "rgba", 0, 0, 0, 1, 1}, {RAW_FRAME_BGRA, ".bgra", "bgra", 0, 0, 0, 1, 1},
+                                        {RAW_FRAME_ARGB, ".argb", "argb", 0, 0, 0, 1, 1}, {RAW_FRAME_ABGR, ".abgr", "abgr", 0, 0, 0, 1, 1},
+                                        {RAW_FRAME_YUYV, ".yuyv", "yuyv", 0, 0, 0, 1, 2}, {RAW_FRAME_UYVY, ".uyvy", "uyvy", 0, 0, 0, 1, 2},
+                                        {RAW_FRAME_YVYU, ".yvyu", "yvyu", 0, 0, 0, 1, 2},
+                                        {RAW_FRAME_P010, ".p010", "P010", 1, 1, 1, 2, 0}}; /* NV12's shape, two bytes a sample */
 
 /* decimal digits only (no blank, no sign), value 1..32768; returns the first character after them, or NULL */
 static const char *side(const char *s, int *out)
@@ -25,7 +32,7 @@ static const char *side(const char *s, int *out)
 uint8_t *load_raw_frame_file(const char *path, int kind, int *w, int *h, size_t plane_bytes[2], char *why, size_t why_len)
 {
     const raw_kind *k = NULL;
-    for (int i = 0; i < 5; ++i)
+    for (int i = 0; i < N_KINDS; ++i)
         if (kinds[i].kind == kind) k = &kinds[i];
     if (!k) {
         snprintf(why, why_len, "%s: raw planar files are i420, yv12, i422 or i444", path);
@@ -40,7 +47,8 @@ uint8_t *load_raw_frame_file(const char *path, int kind, int *w, int *h, size_t 
         return NULL;
     }
     const size_t cw = (size_t)((fw + k->sx) >> k->sx) * (k->chroma_planes == 1 ? 2 : 1), ch = (size_t)((fh + k->sy) >> k->sy);
-    const size_t luma = (size_t)fw * fh, chroma = cw * ch, want = luma + (size_t)k->chroma_planes * chroma;
+    const size_t row = k->group_pixels ? 4 * (((size_t)fw + k->group_pixels - 1) / k->group_pixels) : (size_t)fw * k->sample_bytes;
+    const size_t luma = row * fh, chroma = k->chroma_planes ? cw * ch * k->sample_bytes : 0, want = luma + (size_t)k->chroma_planes * chroma;
     FILE *f = fopen(path, "rb");
     if (!f) { snprintf(why, why_len, "%s: cannot open the file", path); return NULL; }
     uint8_t *raw = malloc(want + 1);
