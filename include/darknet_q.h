@@ -205,6 +205,18 @@ struct network {
     int detb_batch, detb_nheads;         /* what detb_ints_* are sized for */
     long detb_work_ints;
     size_t detb_recs_cap;                /* records detb_recs_gpu holds */
+    /* Input quantisation on the device (set_input_quantization_on_device): pairs and layer-0 bank entries are derived in HBM
+     * (mi355_input_pairs, mi355_l0_derive), one slot per image, each initialised with the prepared layer-0 blob.  Lazily allocated,
+     * sized by the batch, freed with the network and on re-batch.  A replica owns its own, its copy of the constant table included. */
+    int input_on_device;
+    void *od_bank_gpu;                   /* [od_cap] layer-0 blobs, pi_entry_bytes apart */
+    int od_cap;
+    void *od_idx_gpu;                    /* [B] int32 entry | [B] float scale | [B] uint8 zero point (pi_idx_gpu's layout) */
+    void *od_kept_gpu;                   /* [B] float scale | [B] uint8 zero point: the pair every image's entry stands for */
+    uint32_t *od_status_gpu;             /* [B] MI355_INPUT_* bits of the last batch */
+    float *od_mm_gpu;                    /* [B][2] max, min of the float path */
+    void *od_const_gpu, *od_const_host;  /* mi355_l0_consts + n mi355_l0_channel */
+    long host_waits;                     /* times network.c waited for the device on this network's behalf (network_host_waits) */
 };
 
 /* ---- construction / IO ------------------------------------------------------------------------------------ */
@@ -293,8 +305,36 @@ int set_input_quantization_per_image(network *net, int on);
 /* layer 0's blob for input scale s / zero point zp into dst (mi355_conv_pack_size bytes): one bank entry, derived by the host prep
  * exactly as the per-image quantisers derive it; the network's layer-0 record is unchanged afterwards.  Host only (no device). */
 void network_layer0_entry(network *net, float s, uint8_t zp, void *dst);
-/* the (scale, zero point) of every image of the last per-image batch: scale[batch], zp[batch] */
+/* layer 0's constant table for mi355_l0_derive (mi355_yolo_int8.h: a mi355_l0_consts and one mi355_l0_channel per filter: the folded
+ * float bias, weight scale, weight zero point and plain weight sum) into dst; returns its size in bytes, with dst == NULL the size
+ * alone.  Host only. */
+size_t network_layer0_consts(network *net, void *dst);
+/* the (scale, zero point) of every image of the last per-image batch: scale[batch], zp[batch] (with the input quantisation on the
+ * device: of the last batch in either scale mode, after waiting for the network's stream) */
 void network_input_quantization(network *net, float *scale, uint8_t *zp);
+/* Input quantisation on the device, opt-in (off: every call behaves as described above).  On: every device input path --
+ * quantization_weights_and_activations_gpu, network_quantize_input_gpu and the five network_frames_*_input_gpu calls -- runs min / max,
+ * the (scale, zero point) of every image (mi355_input_pairs), layer 0's constants for them (mi355_l0_derive) and the quantiser as one
+ * chain of launches on the network's stream: no copy back, no wait, no host arithmetic, no upload of layer-0 data.  With device frames
+ * (frames_on_device != 0) the whole call only enqueues work; host frames are still staged by the call, and since nothing waits for
+ * those uploads any more the caller keeps them valid until the network's stream has run the call.  Layer 0 always runs on the
+ * network's bank, one slot per image: with per-image quantisation every image has its own pair and entry, without it image 0's pair
+ * and entry 0 serve every slot.  Bytes, pairs and bank entries equal the synchronous path's, bit for bit.  A captured graph stays valid
+ * whatever the pairs are, in both scale modes.  A network that is not prepared yet is prepared with (1 / 255, 0) by the first call;
+ * that, the one-time allocations and a growing staging arena may wait for the device, a steady-state call does not.
+ * What kills the synchronous path (an all-zero image, a layer-0 multiplier outside (0, 1), ...) cannot be reported by a call that does
+ * not wait: the image's slot keeps the pair and the entry of its previous batch and network_input_status() names the reason.
+ * Returns 0, or MI355_EINVAL with a message under set_input_quantization_per_image's conditions.  Switching drops a captured graph.
+ * A replica made afterwards inherits the mode. */
+int set_input_quantization_on_device(network *net, int on);
+/* status[batch] of the last on-device input step: MI355_INPUT_* bits (mi355_yolo_int8.h), 0 = the image was quantised with its own
+ * pair.  Waits for the network's stream.  Returns the number of non-zero entries (0, and zeros, with the mode off). */
+int network_input_status(network *net, uint32_t *status /* [batch] */);
+/* image b's layer-0 bank entry as the device holds it (dnq_net_pi_entry_bytes bytes) into dst.  Waits for the network's stream. */
+void network_input_bank_entry(network *net, int b, void *dst);
+/* how often this library has waited for the device on this network's behalf so far (every stream synchronisation, every blocking
+ * copy back): the difference over a sequence of calls is the number of host round trips it made */
+long network_host_waits(network *net);
 /* the host half of the prep only (per-channel integers + packed blobs, no device needed) */
 void quantization_prep_host(network *net, float in_scale, uint8_t in_zp);
 

@@ -301,6 +301,53 @@ int mi355_image_quantize(const float *x_f32, long count, float scale, int zero_p
 int mi355_image_minmax_batched(const float *x_f32, int B, long count_per_image, float *minmax, void *stream);
 int mi355_image_quantize_per_image(const float *x_f32, int B, long count_per_image, const float *scale_dev, const uint8_t *zp_dev,
                                    uint8_t *out_u8, void *stream);
+/* The rest of the input step on the device, so that nothing comes back to the host between the min / max and the quantiser: the
+ * (scale, zero point) of every image from the batch's min / max, and layer 0's bank entries (mi355_conv_forward_per_image) from those
+ * pairs.  Both are stream-ordered launches; every value they write is bit for bit what the host computes from the same inputs.
+ *
+ * mi355_input_pairs: minmax_dev is [B][2] max, min as the min / max calls above leave them.  Image b gets the reference's scale and zero
+ * point (ref: src/blas.c:125-150: scale = (max - min) * (1.0f / 255.0f), zero point = clamp(round(0.0f - min / scale), 0, 255), the
+ * division in float, clamp and round in double) into scale_dev[b], zp_dev[b]; shared != 0: image 0's pair into all B slots.
+ * entry_dev[b] (may be NULL) = b, or 0 with shared: the bank entry of image b.  status_dev[b] = 0, or the MI355_INPUT_* bit of what
+ * the reference asserts against (an all-zero image, a zero scale); such a slot keeps the pair it held before the call, so the arrays
+ * must hold valid pairs when the first call runs.
+ *
+ * mi355_l0_derive: one workgroup per entry rewrites, in a bank whose slots were initialised with this layer's packed blob
+ * (mi355_conv_pack + mi355_conv_pack_epilogue for any input pair), everything that depends on the pair: entry e for (scale_dev[e],
+ * zp_dev[e]), B entries, or entry 0 alone with shared != 0.  The layer's constants come from consts_dev: a mi355_l0_consts followed by
+ * n mi355_l0_channel (consts_host: the same bytes on the host, read for the shape and the activation).  Per channel: the requantisation
+ * multiplier M = s_in * w_scale / s_act in float, its (M0, shift) decomposition (ref: src/blas.c:387-418), biases_int32 =
+ * (int32)(bias / (s_in * w_scale) + (float)weights_sum_int) (ref :333), then the blob's bias, cw + bias, M_value, shift_value, their
+ * product, shift, the header's pow2 and the whole epilogue table (entries, flags, key, byte table, the first layer's per-lane records).
+ * Where the host prep dies or mi355_conv_pack refuses, the MI355_INPUT_* bit is ORed into status_dev of the entry's images, the slot
+ * is left as it was and the images' pairs are set back to kept_scale_dev / kept_zp_dev; otherwise the pair is copied there.  So the
+ * kept arrays always hold the pair each image's entry stands for; they must be initialised with the pair of the blob the slots were
+ * initialised with.  3 -> n 3x3 first layers only; entry_bytes a multiple of 16 and at least mi355_conv_pack_size(n, 3, 3).
+ * New structs and new calls: MI355_ABI_VERSION is unchanged. */
+#define MI355_INPUT_ALL_ZERO   1u   /* max == min == 0 */
+#define MI355_INPUT_ZERO_SCALE 2u   /* (max - min) / 255 underflows to 0 */
+#define MI355_INPUT_M_RANGE    4u   /* some channel's M is outside (0, 1) */
+#define MI355_INPUT_NEG_SHIFT  8u   /* ... or decomposes with a negative shift */
+#define MI355_INPUT_PACK_RANGE 16u  /* ... or fails mi355_conv_pack's 0 < M_value < 1, 0 < shift_value <= 1 */
+#define MI355_INPUT_BIAS_RANGE 32u  /* ... or its float bias sum is outside int32 */
+#define MI355_INPUT_BAD_SLOT   64u  /* the slot does not hold a first-layer blob of this shape */
+typedef struct mi355_l0_channel {
+    float bias;        /* the float bias, batch norm folded in (b of the host prep) */
+    float w_scale;     /* weight_data_uint8_scales */
+    int32_t w_zp;      /* weight_data_uint8_zero_point */
+    int32_t wsum;      /* plain sum of the channel's K uint8 weights */
+} mi355_l0_channel;
+typedef struct mi355_l0_consts {
+    int32_t n, K;      /* filters, c * size * size (27) */
+    int32_t zp_act, activation; /* MI355_ACT_* */
+    float s_act;
+    int32_t reserved[3];
+} mi355_l0_consts;     /* followed by n mi355_l0_channel */
+int mi355_input_pairs(const float *minmax_dev, int B, int shared, int32_t *entry_dev, float *scale_dev, uint8_t *zp_dev,
+                      uint32_t *status_dev, void *stream);
+int mi355_l0_derive(const mi355_l0_consts *consts_dev, const mi355_l0_consts *consts_host, void *bank, size_t entry_bytes, int B,
+                    int shared, float *scale_dev, uint8_t *zp_dev, float *kept_scale_dev, uint8_t *kept_zp_dev, uint32_t *status_dev,
+                    void *stream);
 /* The same input step for a whole batch of 8-bit interleaved frames as a decoder delivers them (RGB or BGR, three bytes per pixel, rows
  * `pitch` bytes apart), in two launches and without a float image in memory.  A source sample is (float)byte / 255.f -- load_image_color's
  * planes (ref: src/image.c:1386) -- and every letterboxed float is the one mi355_letterbox_forward computes from those planes; min / max

@@ -19,6 +19,13 @@ from before the first upload to after a stream synchronise.  The variants altern
 variants' uint8 inputs, scales and zero points are compared for equality, and the nv12 variant's with those of the frames entry point
 fed the RGB frames a numpy restatement of the integer YUV -> RGB formulas makes of the NV12 planes; the i420, yuyv and p010 variants' are compared with the nv12 variant's, the bgra variant's with the frames variant's.  `host_convert_ms` is the byte -> planar float conversion the float variant
 needs before its first upload, done with numpy here: an indication only, not part of either timed step.
+
+--on-device adds, per scale mode, the comparison of the synchronous input step with the one that derives scales and layer-0 constants on
+the device (Net.set_input_on_device): every frame variant four times -- synchronous and on-device, with host frames and with the same
+frames already in HBM (uploaded before the clock starts, frames_on_device = 1) -- and the float variant twice, all alternating within
+a repeat in this one process.  Each reports the two medians above and `call_ms`, the time the host thread spends inside the call; each
+on-device network's input, scales and zero points are compared with its synchronous twin's first, and its host_waits() counted over the
+timed steps.
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -87,58 +94,66 @@ class FloatVariant:
         net.H.network_quantize_input_gpu(net.h)
 
 
+def _addr(a, hbm, keep):
+    """the address of a plane: the host array's, or (hbm) that of a device copy made now, kept in `keep`"""
+    if not hbm:
+        return a.ctypes.data
+    keep.append(binding.DevBuf.from_numpy(a))
+    return keep[-1].ptr.value
+
+
 class FramesVariant:
-    def __init__(self, net, frames):
+    def __init__(self, net, frames, hbm=False):
         B = len(frames)
-        self.net, self.frames = net, frames
+        self.net, self.frames, self.hbm, self.keep = net, frames, int(hbm), []
         self.ptrs, self.w, self.h = (C.c_void_p * B)(), (C.c_int * B)(), (C.c_int * B)()
         for b, f in enumerate(frames):
-            self.ptrs[b], self.h[b], self.w[b] = f.ctypes.data, f.shape[0], f.shape[1]
+            self.ptrs[b], self.h[b], self.w[b] = _addr(f, hbm, self.keep), f.shape[0], f.shape[1]
 
     def step(self):
-        self.net.H.network_frames_u8_input_gpu(self.net.h, self.ptrs, self.w, self.h, None, 0, 0)
+        self.net.H.network_frames_u8_input_gpu(self.net.h, self.ptrs, self.w, self.h, None, 0, self.hbm)
 
 
 class NV12Variant:
-    def __init__(self, net, planes):
+    def __init__(self, net, planes, hbm=False):
         B = len(planes)
-        self.net, self.planes = net, planes
+        self.net, self.planes, self.hbm, self.keep = net, planes, int(hbm), []
         self.y, self.uv, self.w, self.h = (C.c_void_p * B)(), (C.c_void_p * B)(), (C.c_int * B)(), (C.c_int * B)()
         for b, (y, uv) in enumerate(planes):
-            self.y[b], self.uv[b], self.h[b], self.w[b] = y.ctypes.data, uv.ctypes.data, y.shape[0], y.shape[1]
+            self.y[b], self.uv[b], self.h[b], self.w[b] = _addr(y, hbm, self.keep), _addr(uv, hbm, self.keep), y.shape[0], y.shape[1]
 
     def step(self):
-        self.net.H.network_frames_nv12_input_gpu(self.net.h, self.y, self.uv, self.w, self.h, None, None, 0, 0, 0)
+        self.net.H.network_frames_nv12_input_gpu(self.net.h, self.y, self.uv, self.w, self.h, None, None, 0, 0, self.hbm)
 
 
 class I420Variant:
-    def __init__(self, net, planes):
+    def __init__(self, net, planes, hbm=False):
         B = len(planes)
-        self.net = net
+        self.net, self.hbm, self.keep = net, int(hbm), []
         self.planes = [(y, np.ascontiguousarray(uv[..., 0]), np.ascontiguousarray(uv[..., 1])) for y, uv in planes]
         self.p = [(C.c_void_p * B)() for _ in range(3)]
         self.w, self.h = (C.c_int * B)(), (C.c_int * B)()
         for b, yuv in enumerate(self.planes):
             for k in range(3):
-                self.p[k][b] = yuv[k].ctypes.data
+                self.p[k][b] = _addr(yuv[k], hbm, self.keep)
             self.h[b], self.w[b] = yuv[0].shape
 
     def step(self):
-        self.net.H.network_frames_planar_input_gpu(self.net.h, self.p[0], self.p[1], self.p[2], self.w, self.h, None, None, None, 0, 0, 0)
+        self.net.H.network_frames_planar_input_gpu(self.net.h, self.p[0], self.p[1], self.p[2], self.w, self.h, None, None, None, 0, 0, self.hbm)
 
 
 class PackedVariant:
     """frames: uint8 [h][row_bytes] arrays of one packed plane; fmt: MI355_PACKED_*"""
 
-    def __init__(self, net, frames, w, fmt):
+    def __init__(self, net, frames, w, fmt, hbm=False):
         B = len(frames)
-        self.net, self.frames, self.fmt = net, frames, fmt
+        self.net, self.frames, self.fmt, self.hbm, self.keep = net, frames, fmt, int(hbm), []
         self.ptrs, self.w, self.h = (C.c_void_p * B)(), (C.c_int * B)(), (C.c_int * B)()
         for b, f in enumerate(frames):
-            self.ptrs[b], self.h[b], self.w[b] = f.ctypes.data, f.shape[0], w
+            self.ptrs[b], self.h[b], self.w[b] = _addr(f, hbm, self.keep), f.shape[0], w
 
     def step(self):
-        self.net.H.network_frames_packed_input_gpu(self.net.h, self.ptrs, self.w, self.h, None, self.fmt, 0, 0)
+        self.net.H.network_frames_packed_input_gpu(self.net.h, self.ptrs, self.w, self.h, None, self.fmt, 0, self.hbm)
 
 
 def rgb_to_bgra(f):
@@ -153,11 +168,11 @@ def nv12_to_yuyv(y, uv):
 
 
 class P010Variant(NV12Variant):
-    def __init__(self, net, planes):
-        super().__init__(net, [((y.astype(np.uint16) << 8), (uv.astype(np.uint16) << 8)) for y, uv in planes])
+    def __init__(self, net, planes, hbm=False):
+        super().__init__(net, [((y.astype(np.uint16) << 8), (uv.astype(np.uint16) << 8)) for y, uv in planes], hbm)
 
     def step(self):
-        self.net.H.network_frames_p010_input_gpu(self.net.h, self.y, self.uv, self.w, self.h, None, None, 0, 0)
+        self.net.H.network_frames_p010_input_gpu(self.net.h, self.y, self.uv, self.w, self.h, None, None, 0, self.hbm)
 
 
 def same_input(a, b):
@@ -168,17 +183,19 @@ def same_input(a, b):
 
 def timed(variant, ev, iters):
     net, S = variant.net, binding.shim()
-    dev, wall = [], []
+    dev, wall, call = [], [], []
     for _ in range(iters):
         net.sync()
         t0 = time.perf_counter()
         binding.check(S.mi355_event_record(ev.a, net.stream()), "record")
+        t1 = time.perf_counter()
         variant.step()
+        call.append((time.perf_counter() - t1) * 1e3)
         binding.check(S.mi355_event_record(ev.b, net.stream()), "record")
         net.sync()
         wall.append((time.perf_counter() - t0) * 1e3)
         dev.append(ev.ms())
-    return float(np.median(dev)), float(np.median(wall))
+    return float(np.median(dev)), float(np.median(wall)), float(np.median(call))
 
 
 def pull_input(net):
@@ -196,6 +213,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--src", default="640x480")
+    ap.add_argument("--on-device", action="store_true", help="compare the synchronous step with the on-device one instead (see the module text)")
     a = ap.parse_args()
     binding.init(0)  # raises without a gfx950: nothing is timed on a CPU
     wts = "/tmp/input_path_bench.weights"
@@ -213,6 +231,47 @@ def main():
     bgra, yuyv = [rgb_to_bgra(f) for f in frames], [nv12_to_yuyv(y, uv) for y, uv in planes]
     ev = Events()
     res = {}
+    if a.on_device:
+        sources = {"frames": (FramesVariant, (frames,)), "nv12": (NV12Variant, (planes,)), "i420": (I420Variant, (planes,)),
+                   "bgra": (PackedVariant, (bgra, sw, 1)), "yuyv": (PackedVariant, (yuyv, sw, 4)), "p010": (P010Variant, (planes,))}
+        for mode in ("shared", "per_image"):
+            var = {}
+            for k, (cls, args) in sources.items():
+                for where in ("host", "hbm"):
+                    for how in ("sync", "device"):
+                        net = binding.Net(CFG, wts, batch=a.batch)
+                        net.set_input_per_image(mode == "per_image")
+                        net.set_input_on_device(how == "device")
+                        var[f"{k}/{where}/{how}"] = cls(net, *args, hbm=where == "hbm")
+            for how in ("sync", "device"):
+                net = binding.Net(CFG, wts, batch=a.batch)
+                net.set_input_per_image(mode == "per_image")
+                net.set_input_on_device(how == "device")
+                var[f"float/host/{how}"] = FloatVariant(net, frames)
+            for _ in range(a.warmup):
+                for v in var.values():
+                    v.step()
+            out = {k: {"device_ms": [], "wall_ms": [], "call_ms": []} for k in var}
+            for k in var:
+                if k.endswith("/device"):
+                    out[k]["identical_to_sync"] = same_input(var[k].net, var[k[:-len("device")] + "sync"].net)
+            waits = {k: v.net.host_waits() for k, v in var.items()}
+            for _ in range(a.repeats):
+                for k, v in var.items():  # alternating
+                    for name, x in zip(("device_ms", "wall_ms", "call_ms"), timed(v, ev, a.iters)):
+                        out[k][name].append(round(x, 4))
+            for k, v in var.items():
+                out[k]["host_waits_per_step"] = (v.net.host_waits() - waits[k]) / (a.repeats * a.iters)
+                out[k]["median"] = {m: float(np.median(out[k][m])) for m in ("device_ms", "wall_ms", "call_ms")}
+            res[mode] = out
+            for v in var.values():
+                v.net.close()
+        res["config"] = {"cfg": "yolov3-tiny_quant.cfg", "batch": a.batch, "src": a.src, "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats,
+                         "keys": "<source>/<host: frames uploaded by the call | hbm: frames already on the device>/<sync | device>",
+                         "values": "per repeat the median of `iters` steps: device_ms between HIP events around the step, wall_ms host clock "
+                                   "to the end of a stream synchronise after it, call_ms host clock inside the call; `median` over the repeats"}
+        print(json.dumps(res))
+        return
     for mode in ("shared", "per_image"):
         nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("float", "frames", "nv12", "i420", "bgra", "yuyv", "p010")}
         if mode == "per_image":
@@ -236,7 +295,7 @@ def main():
         runs = {k: {"device_ms": [], "wall_ms": []} for k in var}
         for _ in range(a.repeats):
             for k, v in var.items():  # alternating
-                d, w = timed(v, ev, a.iters)
+                d, w, _ = timed(v, ev, a.iters)
                 runs[k]["device_ms"].append(round(d, 4))
                 runs[k]["wall_ms"].append(round(w, 4))
         med = {k: {m: float(np.median(r[m])) for m in r} for k, r in runs.items()}

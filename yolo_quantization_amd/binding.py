@@ -155,6 +155,8 @@ def shim():
         L.mi355_image_quantize.argtypes = [vp, C.c_long, C.c_float, ci, vp, vp]
         L.mi355_image_minmax_batched.argtypes = [vp, ci, C.c_long, vp, vp]
         L.mi355_image_quantize_per_image.argtypes = [vp, ci, C.c_long, vp, vp, vp, vp]
+        L.mi355_input_pairs.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp]
+        L.mi355_l0_derive.argtypes = [vp, vp, vp, sz, ci, ci, vp, vp, vp, vp, vp, vp]
         L.mi355_conv_forward_per_image.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.c_size_t, vp, vp, vp, vp,
                                                    C.POINTER(Tensor), vp, vp, vp]
         L.mi355_conv_pool_forward_per_image.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.c_size_t, vp, vp,
@@ -458,6 +460,15 @@ def host():
         L.dnq_net_pi_entry_bytes.argtypes = [vp]
         L.dnq_net_pi_entry_bytes.restype = C.c_long
         L.network_layer0_entry.argtypes = [vp, C.c_float, C.c_uint8, vp]
+        L.set_input_quantization_on_device.argtypes = [vp, ci]
+        L.set_input_quantization_on_device.restype = ci
+        L.network_input_status.argtypes = [vp, vp]
+        L.network_input_status.restype = ci
+        L.network_input_bank_entry.argtypes = [vp, ci, vp]
+        L.network_host_waits.argtypes = [vp]
+        L.network_host_waits.restype = C.c_long
+        L.network_layer0_consts.argtypes = [vp, vp]
+        L.network_layer0_consts.restype = C.c_size_t
         L.dnq_net_graph.argtypes = [vp]
         L.dnq_net_graph.restype = vp
         L.dnq_net_detb_counts.argtypes = [vp]
@@ -567,6 +578,7 @@ class Net:
         r.n, r.batch, r.inputs, r.info = self.n, self.batch, self.inputs, self.info
         r._parent = self  # keeps the parent alive
         r.per_image = getattr(self, "per_image", False)
+        r.input_on_device = getattr(self, "input_on_device", False)
         return r
 
     def prepare_fixed(self, in_scale=1.0 / 255.0, in_zp=0):
@@ -584,6 +596,43 @@ class Net:
         if rc != 0:
             raise MI355Error(f"set_input_quantization_per_image: code {rc} (layer 0 is not served per image)")
         self.per_image = bool(on)
+
+    def set_input_on_device(self, on=True):
+        """Input quantisation on the device (darknet_q.h set_input_quantization_on_device): the device input paths derive the
+        (scale, zero point) of every image and layer 0's constants in HBM, without a copy back or a wait; combines with
+        set_input_per_image either way.  Raises MI355Error under set_input_per_image's conditions.  While it is on, a
+        prepare_from_frames_* call with frames on the device only enqueues work and returns None: input_quantization(),
+        input_status() and input_bank_entry() are the explicit (waiting) reads."""
+        rc = self.H.set_input_quantization_on_device(self.h, int(bool(on)))
+        if rc != 0:
+            raise MI355Error(f"set_input_quantization_on_device: code {rc} (layer 0 is not served from a bank)")
+        self.input_on_device = bool(on)
+
+    def input_status(self):
+        """uint32[batch] MI355_INPUT_* bits of the last on-device input step (0: the image was quantised with its own pair; else it kept
+        the pair and layer-0 entry of its previous batch).  Waits for the network's stream."""
+        st = np.zeros(self.batch, np.uint32)
+        self.H.network_input_status(self.h, st.ctypes.data)
+        return st
+
+    def input_bank_entry(self, b):
+        """Image b's layer-0 bank entry as the device holds it (bank_entry_bytes() bytes).  Waits for the network's stream."""
+        out = np.zeros(self.bank_entry_bytes(), np.uint8)
+        self.H.network_input_bank_entry(self.h, b, out.ctypes.data)
+        return out
+
+    def layer0_consts(self):
+        """Layer 0's constant table for mi355_l0_derive as bytes (network_layer0_consts; host only)."""
+        out = np.zeros(self.H.network_layer0_consts(self.h, None), np.uint8)
+        self.H.network_layer0_consts(self.h, out.ctypes.data)
+        return out
+
+    def host_waits(self):
+        """How often the host library has waited for the device on this network's behalf so far (network_host_waits)."""
+        return int(self.H.network_host_waits(self.h))
+
+    def _enqueued_only(self, on_device):
+        return bool(on_device) and getattr(self, "input_on_device", False)
 
     def input_quantization(self):
         """(scale[batch] float32, zero_point[batch] uint8) the last batch was quantised with."""
@@ -688,6 +737,8 @@ class Net:
                 raise ValueError("prepare_from_frames_nv12: the chroma plane must be [(h + 1) // 2][(w + 1) // 2][2]")
             (ys[b], py[b]), (uvs[b], puv[b]), hs[b], ws[b] = _byte_rows(y, keep), _byte_rows(uv, keep), h, w
         self.H.network_frames_nv12_input_gpu(self.h, ys, uvs, ws, hs, py, puv, YUV_LAYOUT[layout], YUV_MATRIX[matrix], int(on_device))
+        if self._enqueued_only(on_device):
+            return None
         return self._prepared(self._pull_input())
 
     def prepare_from_frames_planar(self, frames, format="i420", matrix="bt601", on_device=False):
@@ -732,6 +783,8 @@ class Net:
             hs[b], ws[b] = h, w
         self.H.network_frames_planar_input_gpu(self.h, ptr[0], ptr[1], ptr[2], ws, hs, pitch[0], pitch[1], pitch[2],
                                                PLANAR_FORMAT[format], YUV_MATRIX[matrix], int(on_device))
+        if self._enqueued_only(on_device):
+            return None
         return self._prepared(self._pull_input())
 
     def prepare_from_frames_packed(self, frames, format="bgra", matrix="bt601"):
@@ -771,8 +824,11 @@ class Net:
             where.add(dev)
         if len(where) != 1:
             raise ValueError("prepare_from_frames_packed: the frames of a batch are all host arrays or all device tensors")
+        on_device = where.pop()
         self.H.network_frames_packed_input_gpu(self.h, ptrs, ws, hs, ps, PACKED_FORMAT[format], 0 if rgbx else YUV_MATRIX[matrix],
-                                               int(where.pop()))
+                                               int(on_device))
+        if self._enqueued_only(on_device):
+            return None
         return self._prepared(self._pull_input())
 
     def prepare_from_frames_p010(self, frames, matrix="bt601"):
@@ -798,7 +854,10 @@ class Net:
             where |= {dev_y, dev_uv}
         if len(where) != 1:
             raise ValueError("prepare_from_frames_p010: the planes of a batch are all host arrays or all device tensors")
-        self.H.network_frames_p010_input_gpu(self.h, ys, uvs, ws, hs, py, puv, YUV_MATRIX[matrix], int(where.pop()))
+        on_device = where.pop()
+        self.H.network_frames_p010_input_gpu(self.h, ys, uvs, ws, hs, py, puv, YUV_MATRIX[matrix], int(on_device))
+        if self._enqueued_only(on_device):
+            return None
         return self._prepared(self._pull_input())
 
     def push_input(self, x_u8):

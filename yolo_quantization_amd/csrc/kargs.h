@@ -239,6 +239,10 @@ int image_minmax_batched_launch(const float *x, int B, long count, uint32_t *mm,
 int image_quantize_per_image_launch(const float *x, int B, long count, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out,
                                     hipStream_t st);
 int image_minmax_seed_launch(uint32_t *mm, int B, hipStream_t st);
+// input_dev.hip: (scale, zero point) per image from the batch's min / max, and layer 0's bank entries from those pairs, on the device
+int input_pairs_launch(const float *mm, int B, int shared, int32_t *entry, float *scale, uint8_t *zp, uint32_t *status, hipStream_t st);
+int l0_derive_launch(const mi355_l0_consts *consts, int activation, void *bank, long entry_bytes, int B, int shared, float *scale, uint8_t *zp,
+                     float *kept_scale, uint8_t *kept_zp, uint32_t *status, hipStream_t st);
 // frames.hip: a kind of frames is a Source (Frame = its table entry in the C-ABI), instantiated there for these five
 struct SourceU8;      // mi355_frame_u8
 struct SourceYUV;     // mi355_frame_yuv

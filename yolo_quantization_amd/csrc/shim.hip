@@ -1067,6 +1067,29 @@ int mi355_image_quantize_per_image(const float *x_f32, int B, long count_per_ima
     return image_quantize_per_image_launch(x_f32, B, count_per_image, scale_dev, zp_dev, out_u8, (hipStream_t)stream);
 }
 
+int mi355_input_pairs(const float *minmax_dev, int B, int shared, int32_t *entry_dev, float *scale_dev, uint8_t *zp_dev,
+                      uint32_t *status_dev, void *stream)
+{
+    if (!minmax_dev || !scale_dev || !zp_dev || !status_dev || B <= 0 || B > 65535) return einval("input_pairs: null / empty / B > 65535");
+    return input_pairs_launch(minmax_dev, B, shared != 0, entry_dev, scale_dev, zp_dev, status_dev, (hipStream_t)stream);
+}
+
+int mi355_l0_derive(const mi355_l0_consts *consts_dev, const mi355_l0_consts *consts_host, void *bank, size_t entry_bytes, int B,
+                    int shared, float *scale_dev, uint8_t *zp_dev, float *kept_scale_dev, uint8_t *kept_zp_dev, uint32_t *status_dev,
+                    void *stream)
+{
+    if (!consts_dev || !consts_host || !bank || !scale_dev || !zp_dev || !kept_scale_dev || !kept_zp_dev || !status_dev) return einval("l0_derive: null");
+    if (B <= 0 || B > 65535) return einval("l0_derive: B outside 1..65535");
+    const mi355_l0_consts &c = *consts_host;
+    if (c.n < 1 || c.K != 27 || c.zp_act < 0 || c.zp_act > 255 || !(c.s_act > 0.0f))
+        return einval("l0_derive: a 3 -> n 3x3 first layer (K = 27) with 0 <= zp_act <= 255 and s_act > 0 only");
+    if (entry_bytes % 16 || entry_bytes < mi355_conv_pack_size(c.n, 3, 3))
+        return einval("l0_derive: entry_bytes must be a multiple of 16 and hold one mi355_conv_pack blob");
+    const int rc = l0_derive_launch(consts_dev, c.activation, bank, (long)entry_bytes, B, shared != 0, scale_dev, zp_dev, kept_scale_dev,
+                                    kept_zp_dev, status_dev, (hipStream_t)stream);
+    return rc == MI355_EINVAL ? einval("l0_derive: activation") : rc;
+}
+
 int mi355_frames_u8_letterbox_minmax(const mi355_frame_u8 *table_dev, const mi355_frame_u8 *table_host, int B, int w, int h,
                                      float *minmax, void *stream)
 {

@@ -33,6 +33,8 @@
  * 4 * ((W + 1) / 2) * H bytes), in files named <anything>_<W>x<H>.<format>; network_frames_packed_input_gpu.
  * -frames p010 [-matrix ...] (raw P010 frames as hardware decoders deliver 10-bit video, NV12's shape with 16-bit little-endian
  * samples, in files named <anything>_<W>x<H>.p010; network_frames_p010_input_gpu).
+ * -input_device (detector test: the input scales and layer 0's constants are derived on the device, no copy back and no wait inside
+ * the input step -- set_input_quantization_on_device; the output is unchanged).
  *
  * Image input: binary PPM (P6) of ANY size (letterboxed like the reference does), a raw `.u8` file holding [c][h][w] bytes at
  * network size, or `synthetic:<seed>`.  JPEG/PNG decoding is third-party code in the reference (stb_image, SURVEY.md 2
@@ -168,6 +170,7 @@ typedef struct {
     int packed_format;     /* MI355_PACKED_RGBA .. MI355_PACKED_YVYU */
     float thresh, hier_thresh;
     int batch, accum, store, use_graph, iters, gpu, boxes, quiet, inflight;
+    int input_device;      /* -input_device: scales and layer-0 constants are derived on the device (set_input_quantization_on_device) */
     int rank, nranks;      /* -gpus with -bcast: this replica's rank; rank 0 reads the weights file, the others receive blobs */
     const void *comm_id;   /* shared 128-byte RCCL unique id (NULL: every replica reads the file) */
     double seconds; /* out: per forward pass */
@@ -239,6 +242,8 @@ static void feed_frames(const detect_job *job, network *net, char *const *paths,
         network_frames_p010_input_gpu(net, pl[0], pl[1], imw, imh, NULL, NULL, job->yuv_matrix, 0);
     else
         network_frames_u8_input_gpu(net, pl[0], imw, imh, NULL, MI355_FRAME_RGB, 0);
+    /* on the device nothing waits for the uploads: the sources are freed below */
+    if (net->input_on_device && mi355_stream_sync(net->stream)) error("sync");
     for (int b = 0; b < B; ++b) free(raw[b]);
     for (int k = 0; k < 3; ++k) free(pl[k]);
     free(raw);
@@ -343,6 +348,10 @@ static void test_detector(detect_job *job)
         mi355_comm_destroy(comm);
     }
 
+    if (job->input_device) {
+        if (job->inflight > 1) error("-input_device does not go with -inflight: a replica's bank is filled by its own input step");
+        if (set_input_quantization_on_device(net, 1)) error("-input_device: layer 0 cannot run on constants derived on the device");
+    }
     if (job->listfile) {
         if (mi355_init(job->gpu)) error("mi355_init");
         test_detector_list(job, net, names, nnames);
@@ -433,7 +442,7 @@ int main(int argc, char **argv)
     if (argc < 2) {
         fprintf(stderr, "usage: %s detector test <data> <cfg> <weights> <image> [-thresh t] [-i gpu | -gpus a,b,..] [-batch B] "
                         "[-accum exact|ref-f32] [-parity wrap|saturate] [-dump dir] [-graph] [-n iters] [-boxes] "
-                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8|nv12|nv21|i420|yv12|i422|i444|rgba|bgra|argb|abgr|yuyv|uyvy|yvyu|p010] [-matrix bt601|bt601f|bt709|bt709f]\n", argv[0]);
+                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8|nv12|nv21|i420|yv12|i422|i444|rgba|bgra|argb|abgr|yuyv|uyvy|yvyu|p010] [-matrix bt601|bt601f|bt709|bt709f] [-input_device]\n", argv[0]);
         return 0;
     }
     detect_job job;
@@ -452,6 +461,7 @@ int main(int argc, char **argv)
     job.packed_out = find_char_arg(argc, argv, "-save_packed", NULL);
     job.use_graph = find_arg(argc, argv, "-graph");
     job.boxes = find_arg(argc, argv, "-boxes");
+    job.input_device = find_arg(argc, argv, "-input_device");
     const int bcast = find_arg(argc, argv, "-bcast");
     job.iters = atoi(find_char_arg(argc, argv, "-n", "1"));
     job.inflight = atoi(find_char_arg(argc, argv, "-inflight", "1"));

@@ -32,21 +32,27 @@ static void alloc_act_record(layer *l)
 /* The plain convolution and the conv + maxpool pair on the layer's own blob, or (pi: layer 0 under per-image input quantisation,
  * set_input_quantization_per_image) the same launches on the network's bank of layer-0 blobs, one entry per image.  full = 0 is the
  * bare exact-mode launch of the planar-input attempt: no raw weights, no int32 or float copy of the output. */
+/* the bank layer 0 runs on and its index arrays: the one the device derives (set_input_quantization_on_device) or the host's cache */
+static const void *bank_of(const network *net) { return net->input_on_device ? net->od_bank_gpu : net->pi_bank_gpu; }
+static const void *bank_index(const network *net) { return net->input_on_device ? net->od_idx_gpu : net->pi_idx_gpu; }
+
 static int conv_plain(const layer *l, const network *net, const mi355_conv_desc *d, int pi, int full)
 {
     const uint8_t *w = full ? l->weights_uint8_gpu : NULL, *zp_w = full ? l->weight_zero_point_gpu : NULL;
     int32_t *acc = full && net->dump_int32 ? l->output_int32_gpu : NULL;
     float *f32 = full && l->quant_stop_flag ? l->output_gpu : NULL;
     if (!pi) return mi355_conv_forward(d, net->cur_t, l->blob_gpu, w, zp_w, &l->out_t, acc, f32, net->stream);
-    return mi355_conv_forward_per_image(d, net->cur_t, net->pi_bank_gpu, net->pi_entry_bytes, (const int32_t *)net->pi_idx_gpu,
-                                        (const uint8_t *)net->pi_idx_gpu + 8 * (size_t)net->batch, w, zp_w, &l->out_t, acc, f32, net->stream);
+    const void *idx = bank_index(net);
+    return mi355_conv_forward_per_image(d, net->cur_t, bank_of(net), net->pi_entry_bytes, (const int32_t *)idx,
+                                        (const uint8_t *)idx + 8 * (size_t)net->batch, w, zp_w, &l->out_t, acc, f32, net->stream);
 }
 
 static int conv_pool(const layer *l, const network *net, const mi355_conv_desc *d, int pi, const mi355_tensor *keep, const mi355_tensor *pooled)
 {
     if (!pi) return mi355_conv_pool_forward(d, net->cur_t, l->blob_gpu, keep, pooled, net->stream);
-    return mi355_conv_pool_forward_per_image(d, net->cur_t, net->pi_bank_gpu, net->pi_entry_bytes, (const int32_t *)net->pi_idx_gpu,
-                                             (const uint8_t *)net->pi_idx_gpu + 8 * (size_t)net->batch, keep, pooled, net->stream);
+    const void *idx = bank_index(net);
+    return mi355_conv_pool_forward_per_image(d, net->cur_t, bank_of(net), net->pi_entry_bytes, (const int32_t *)idx,
+                                             (const uint8_t *)idx + 8 * (size_t)net->batch, keep, pooled, net->stream);
 }
 
 /* ref: forward_convolutional_layer_quant_inputi_outputi, src/convolutional_layer.c:694-761 */
@@ -67,8 +73,8 @@ static void forward_convolutional_layer_quant_gpu(layer l, network net)
     d.zp_act = l.activ_data_uint8_zero_point[0];
     d.s_act = l.activ_data_uint8_scales[0];
     /* per-image layer 0 is a 3-channel conv (l0_per_image_shape_ok): of the fused forms plan_fusion only offers it the pool */
-    const int pi = net.per_image && net.index == 0;
-    if (pi && !net.pi_bank_gpu) error("per-image input: layer 0 runs before the batch was quantised (no bank)");
+    const int pi = (net.per_image || net.input_on_device) && net.index == 0;
+    if (pi && !bank_of(&net)) error("per-image input: layer 0 runs before the batch was quantised (no bank)");
     /* Fused forms: the executor's plan marks candidates by shape, the launchers decide.  MI355_EINVAL from a fused entry
      * point means "no kernel fuses this shape" (nothing was launched): fuse_next is cleared in the network's layer array
      * (net.layers points at it; `l` is a by-value copy) and the convolution runs unfused below, the layer after it on its

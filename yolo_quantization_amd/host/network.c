@@ -57,6 +57,17 @@ const char *get_layer_string(LAYER_TYPE t)
 
 static void plan_fusion(network *net);
 static void pi_free(network *net);
+static void od_free(network *net);
+static float *od_scale_dev(const network *net);
+
+/* Every wait of this file for the device goes through here and is counted (network_host_waits): a blocking copy back is always
+ * followed by one. */
+static void net_wait(network *net)
+{
+    net->host_waits++;
+    check_mi355(mi355_stream_sync(net->stream), "sync");
+}
+long network_host_waits(network *net) { return net->host_waits; }
 
 /* ------------------------------------------------------------------------------------------------- host prep */
 void quant_multi_smaller_than_one_to_scale_and_shift(float real_multiplier, int32_t *quantized_multiplier,
@@ -114,6 +125,16 @@ void quant_image_with_min_max(int count, const float *input, uint8_t *out, float
     }
 }
 
+/* the float bias of filter ii with batch norm folded in (ref :286 -> :594-600, evaluated in double as the C expression promotes) */
+static float folded_bias(const layer *l, int ii)
+{
+    float b = l->biases[ii];
+    if (l->batch_normalize)
+        b = (float)((double)b - (double)(l->scales[ii] * l->rolling_mean[ii]) /
+                                    (sqrt((double)l->rolling_variance[ii]) + (double).000001f));
+    return b;
+}
+
 static void prep_conv_layer(network *net, int i)
 {
     layer *l = &net->layers[i];
@@ -126,10 +147,7 @@ static void prep_conv_layer(network *net, int i)
     const int zp_in = l->input_data_uint8_zero_point[0];
     if (s_in == 0 || l->activ_data_uint8_scales[0] == 0) error("zero quantisation scale (ref: src/blas.c:312,332 asserts)");
     for (int ii = 0; ii < l->n; ++ii) {
-        float b = l->biases[ii];
-        if (l->batch_normalize) /* ref :286 -> :594-600, evaluated in double as the C expression promotes */
-            b = (float)((double)b - (double)(l->scales[ii] * l->rolling_mean[ii]) /
-                                        (sqrt((double)l->rolling_variance[ii]) + (double).000001f));
+        const float b = folded_bias(l, ii);
         if (l->weight_data_uint8_scales[ii] == 0) error("zero weight scale (ref: src/blas.c:293 assert)");
         l->mult_zero_point[ii] = (uint32_t)(K * zp_in * (int)l->weight_data_uint8_zero_point[ii]);
         int32_t wsum = 0;
@@ -394,11 +412,13 @@ void quantization_weights_and_activations_fixed_input(network *net, float in_sca
     alloc_network_device(net);
     for (int i = 0; i < net->n; ++i)
         if (net->layers[i].type == CONVOLUTIONAL) upload_conv(net, i, net->has_host_weights);
-    check_mi355(mi355_stream_sync(net->stream), "sync");
+    net_wait(net);
     net->prepared = 1;
 }
 
 static void pi_bank_update(network *net, const float *scale, const uint8_t *zp);
+static void od_pairs_from_host(network *net, const float *scale, const uint8_t *zp);
+static void quantize_on_device(network *net, const float *input_gpu);
 
 void quantization_weights_and_activations(network *net)
 {
@@ -408,7 +428,8 @@ void quantization_weights_and_activations(network *net)
         for (int b = 0; b < net->batch; ++b)
             quant_image_with_min_max(net->inputs, net->input + (size_t)b * net->inputs, net->input_uint8 + (size_t)b * net->inputs, &s[b], &zp[b]);
         if (!net->prepared) quantization_weights_and_activations_fixed_input(net, s[0], zp[0]);
-        pi_bank_update(net, s, zp);
+        if (net->input_on_device) od_pairs_from_host(net, s, zp);
+        else pi_bank_update(net, s, zp);
         free(s); free(zp);
         push_network_input_uint8(net, net->input_uint8);
         return;
@@ -417,6 +438,7 @@ void quantization_weights_and_activations(network *net)
     float s; uint8_t zp;
     quant_image_with_min_max(net->inputs, net->input, net->input_uint8, &s, &zp);
     quantization_weights_and_activations_fixed_input(net, s, zp);
+    if (net->input_on_device) od_pairs_from_host(net, &s, &zp); /* layer 0 runs on the bank in this mode */
     for (int b = 1; b < net->batch; ++b) { /* further images: same scale (batch > 1 is our extension) */
         float *x = net->input + (size_t)b * net->inputs;
         uint8_t *o = net->input_uint8 + (size_t)b * net->inputs;
@@ -451,7 +473,7 @@ static void input_pair_shared(network *net, float s, uint8_t zp)
                     "mi355_conv_pack_epilogue");
         check_mi355(mi355_h2d(l0->blob_gpu, l0->blob_host, l0->blob_bytes, net->stream), "upload blob 0");
         if (zp_changed) check_mi355(mi355_tensor_fill(&net->input_t, zp, net->stream), "fill input");  /* pad cells = zero point */
-        check_mi355(mi355_stream_sync(net->stream), "sync");  /* blob_host may be repacked by the next call */
+        net_wait(net);  /* blob_host may be repacked by the next call */
         /* a captured graph holds layer 0's kernel arguments by value: the planar first-layer kernels take the pad value
          * (the input zero point) from there, not from pad cells in memory -> re-capture on the next forward */
         if (net->graph) { mi355_graph_destroy(net->graph); net->graph = NULL; }
@@ -471,12 +493,13 @@ void quantization_weights_and_activations_gpu(network *net, const float *input_g
     if (!input_gpu) error("quantization_weights_and_activations_gpu: null input");
     check_mi355(mi355_init(net->gpu_index), "mi355_init");
     if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
+    if (net->input_on_device) { quantize_on_device(net, input_gpu); return; }
     if (net->per_image) { quantize_per_image_gpu(net, input_gpu); return; }
     if (!net->quant_mm_gpu) check_mi355(mi355_alloc((void **)&net->quant_mm_gpu, 2 * sizeof(float)), "alloc minmax");
     float mm[2];
     check_mi355(mi355_image_minmax(input_gpu, net->inputs, net->quant_mm_gpu, net->stream), "mi355_image_minmax");
     check_mi355(mi355_d2h(mm, net->quant_mm_gpu, sizeof(mm), net->stream), "minmax d2h");
-    check_mi355(mi355_stream_sync(net->stream), "sync");
+    net_wait(net);
     float s; uint8_t zp;
     image_scale_zero_point(mm[1] + 0.0f, mm[0], &s, &zp);
     input_pair_shared(net, s, zp);
@@ -497,6 +520,24 @@ static int l0_per_image_shape_ok(const layer *l)
 
 static network *l0_source(network *net) { return net->replica_of ? net->replica_of : net; } /* who holds layer 0's raw weights */
 
+/* 0, or MI355_EINVAL with a message: can layer 0 run on a bank of blobs derived per input pair? */
+static int l0_bank_refusal(const network *net, const char *who)
+{
+    const layer *l0 = &net->layers[0];
+    if (!l0_per_image_shape_ok(l0)) {
+        fprintf(stderr, "%s: layer 0 (%s %dx%d stride %d, %d -> %d) is not served per image: only a "
+                        "3 -> n 3x3 stride-1 convolution with pad 1 runs on the first-layer kernels\n",
+                who, get_layer_string(l0->type), l0->size, l0->size, l0->stride, l0->c, l0->n);
+        return MI355_EINVAL;
+    }
+    const network *src = net->replica_of ? net->replica_of : net;
+    if (src->prepared && !src->has_host_weights && !src->has_l0_weights) {
+        fprintf(stderr, "%s: this network holds no raw layer-0 weights to derive per-image constants from\n", who);
+        return MI355_EINVAL;
+    }
+    return 0;
+}
+
 int set_input_quantization_per_image(network *net, int on)
 {
     if (!on) {
@@ -504,18 +545,7 @@ int set_input_quantization_per_image(network *net, int on)
         net->per_image = 0;
         return 0;
     }
-    const layer *l0 = &net->layers[0];
-    if (!l0_per_image_shape_ok(l0)) {
-        fprintf(stderr, "set_input_quantization_per_image: layer 0 (%s %dx%d stride %d, %d -> %d) is not served per image: only a "
-                        "3 -> n 3x3 stride-1 convolution with pad 1 runs on the first-layer kernels\n",
-                get_layer_string(l0->type), l0->size, l0->size, l0->stride, l0->c, l0->n);
-        return MI355_EINVAL;
-    }
-    const network *src = l0_source(net);
-    if (src->prepared && !src->has_host_weights && !src->has_l0_weights) {
-        fprintf(stderr, "set_input_quantization_per_image: this network holds no raw layer-0 weights to derive per-image constants from\n");
-        return MI355_EINVAL;
-    }
+    if (l0_bank_refusal(net, "set_input_quantization_per_image")) return MI355_EINVAL;
     if (!net->per_image && net->graph) { mi355_graph_destroy(net->graph); net->graph = NULL; }
     net->per_image = 1;
     return 0;
@@ -524,6 +554,15 @@ int set_input_quantization_per_image(network *net, int on)
 void network_input_quantization(network *net, float *scale, uint8_t *zp)
 {
     const int B = net->batch;
+    if (net->input_on_device && net->od_idx_gpu) { /* the pairs never left the device: wait for them */
+        char *pairs = malloc(5 * (size_t)B);
+        check_mi355(mi355_d2h(pairs, od_scale_dev(net), 5 * (size_t)B, net->stream), "pull input pairs");
+        net_wait(net);
+        memcpy(scale, pairs, sizeof(float) * (size_t)B);
+        memcpy(zp, pairs + 4 * (size_t)B, (size_t)B);
+        free(pairs);
+        return;
+    }
     if (!net->per_image || !net->pi_idx_host) {
         for (int b = 0; b < B; ++b) { scale[b] = net->layers[0].input_data_uint8_scales[0]; zp[b] = net->layers[0].input_data_uint8_zero_point[0]; }
         return;
@@ -663,12 +702,182 @@ static void quantize_per_image_gpu(network *net, const float *input_gpu)
     if (!net->pi_mm_gpu || net->pi_cap < B) pi_alloc(net);
     check_mi355(mi355_image_minmax_batched(input_gpu, B, net->inputs, net->pi_mm_gpu, net->stream), "mi355_image_minmax_batched");
     check_mi355(mi355_d2h(net->pi_mm_host, net->pi_mm_gpu, 2 * sizeof(float) * (size_t)B, net->stream), "minmax d2h");
-    check_mi355(mi355_stream_sync(net->stream), "sync"); /* the batch's one host sync: every earlier upload of the bank is done too */
+    net_wait(net); /* the batch's one host sync: every earlier upload of the bank is done too */
     input_pairs_per_image(net, net->pi_mm_host);
     const char *idx = (const char *)net->pi_idx_gpu;
     check_mi355(mi355_image_quantize_per_image(input_gpu, B, net->inputs, (const float *)(idx + 4 * (size_t)B),
                                                (const uint8_t *)(idx + 8 * (size_t)B), net->input_uint8_gpu, net->stream),
                 "mi355_image_quantize_per_image");
+}
+
+/* ---------------------------------------------------------------------------- input quantisation on the device
+ * The same chain without the host in it: the min / max stay in HBM, mi355_input_pairs turns them into pairs there, mi355_l0_derive
+ * rewrites what depends on the pair in the slots of a bank of the network's own -- one slot per image, each initialised with the
+ * prepared layer-0 blob, so the weights and everything else are in place -- and the quantisers and layer 0 read pairs, entries and
+ * zero points from device memory as they do per image.  Nothing here waits once the buffers exist. */
+int set_input_quantization_on_device(network *net, int on)
+{
+    if (!on) {
+        if (net->input_on_device && net->graph) { mi355_graph_destroy(net->graph); net->graph = NULL; } /* captured with the bank launches */
+        net->input_on_device = 0;
+        return 0;
+    }
+    if (l0_bank_refusal(net, "set_input_quantization_on_device")) return MI355_EINVAL;
+    if (!net->input_on_device && net->graph) { mi355_graph_destroy(net->graph); net->graph = NULL; }
+    net->input_on_device = 1;
+    return 0;
+}
+
+/* mi355_l0_derive's constant table of this network's layer 0 (mi355_l0_consts + n mi355_l0_channel) into dst; returns its size in
+ * bytes (dst == NULL: the size alone).  Host only. */
+size_t network_layer0_consts(network *net, void *dst)
+{
+    const layer *l0 = &l0_source(net)->layers[0];
+    const size_t n = (size_t)l0->n, cbytes = sizeof(mi355_l0_consts) + n * sizeof(mi355_l0_channel);
+    if (!dst) return cbytes;
+    memset(dst, 0, cbytes);
+    mi355_l0_consts *c = dst;
+    mi355_l0_channel *ch = (mi355_l0_channel *)(c + 1);
+    const int K = l0->c * l0->size * l0->size;
+    c->n = l0->n; c->K = K;
+    c->zp_act = l0->activ_data_uint8_zero_point[0]; c->activation = l0->activation; c->s_act = l0->activ_data_uint8_scales[0];
+    for (size_t ii = 0; ii < n; ++ii) {
+        int32_t wsum = 0;
+        for (int jj = 0; jj < K; ++jj) wsum += l0->weights_uint8[ii * K + jj];
+        ch[ii].bias = folded_bias(l0, (int)ii);
+        ch[ii].w_scale = l0->weight_data_uint8_scales[ii];
+        ch[ii].w_zp = l0->weight_data_uint8_zero_point[ii];
+        ch[ii].wsum = wsum;
+    }
+    return cbytes;
+}
+
+static void od_free(network *net)
+{
+    if (net->od_bank_gpu) mi355_free(net->od_bank_gpu);
+    if (net->od_idx_gpu) mi355_free(net->od_idx_gpu);
+    if (net->od_kept_gpu) mi355_free(net->od_kept_gpu);
+    if (net->od_status_gpu) mi355_free(net->od_status_gpu);
+    if (net->od_mm_gpu) mi355_free(net->od_mm_gpu);
+    if (net->od_const_gpu) mi355_free(net->od_const_gpu);
+    free(net->od_const_host);
+    net->od_bank_gpu = net->od_idx_gpu = net->od_kept_gpu = net->od_const_gpu = net->od_const_host = NULL;
+    net->od_status_gpu = NULL; net->od_mm_gpu = NULL;
+    net->od_cap = 0;
+}
+
+/* The buffers of the mode, once per batch size (this may wait; no later call does): the network prepared, the constant table, the bank
+ * with the prepared blob in every slot, and in every image's slot of the pair arrays the pair that blob was derived for. */
+static void od_alloc(network *net)
+{
+    const int B = net->batch;
+    if (!net->prepared) quantization_weights_and_activations_fixed_input(net, 1.0f / 255.0f, 0);
+    network *src = l0_source(net);
+    const layer *l0 = &src->layers[0];
+    const size_t eb = (mi355_conv_pack_size(l0->n, l0->c, l0->size) + 255) & ~(size_t)255;
+    if (net->od_bank_gpu && net->od_cap == B && net->pi_entry_bytes == eb) return;
+    if (!src->has_host_weights && !src->has_l0_weights) error("input quantisation on the device: no raw layer-0 weights to derive the constants from");
+    od_free(net);
+    net->pi_entry_bytes = eb;
+    net->od_cap = B;
+    const size_t cbytes = network_layer0_consts(net, NULL);
+    mi355_l0_consts *c = calloc(1, cbytes);
+    network_layer0_consts(net, c);
+    net->od_const_host = c;
+    check_mi355(mi355_alloc(&net->od_const_gpu, cbytes), "alloc layer-0 constants");
+    check_mi355(mi355_h2d(net->od_const_gpu, c, cbytes, net->stream), "upload layer-0 constants");
+    check_mi355(mi355_alloc(&net->od_bank_gpu, eb * (size_t)B), "alloc layer-0 bank");
+    check_mi355(mi355_memset(net->od_bank_gpu, 0, eb * (size_t)B, net->stream), "clear layer-0 bank");
+    const layer *mine = &net->layers[0]; /* a replica's blob_gpu is its parent's */
+    for (int b = 0; b < B; ++b)
+        check_mi355(mi355_d2d((char *)net->od_bank_gpu + (size_t)b * eb, mine->blob_gpu, mine->blob_bytes, net->stream), "fill layer-0 bank");
+    check_mi355(mi355_alloc(&net->od_idx_gpu, 9 * (size_t)B), "alloc layer-0 index");
+    check_mi355(mi355_alloc(&net->od_kept_gpu, 5 * (size_t)B), "alloc kept pairs");
+    check_mi355(mi355_alloc((void **)&net->od_status_gpu, sizeof(uint32_t) * (size_t)B), "alloc input status");
+    check_mi355(mi355_alloc((void **)&net->od_mm_gpu, 2 * sizeof(float) * (size_t)B), "alloc minmax");
+    char *pairs = calloc(5, (size_t)B);
+    for (int b = 0; b < B; ++b) {
+        ((float *)pairs)[b] = mine->input_data_uint8_scales[0];
+        ((uint8_t *)pairs)[4 * (size_t)B + b] = mine->input_data_uint8_zero_point[0];
+    }
+    check_mi355(mi355_memset(net->od_idx_gpu, 0, 4 * (size_t)B, net->stream), "clear layer-0 index");
+    check_mi355(mi355_h2d((char *)net->od_idx_gpu + 4 * (size_t)B, pairs, 5 * (size_t)B, net->stream), "upload prepared pairs");
+    check_mi355(mi355_h2d(net->od_kept_gpu, pairs, 5 * (size_t)B, net->stream), "upload prepared pairs");
+    check_mi355(mi355_memset(net->od_status_gpu, 0, sizeof(uint32_t) * (size_t)B, net->stream), "clear input status");
+    net_wait(net);
+    free(pairs);
+}
+
+static float *od_scale_dev(const network *net) { return (float *)((char *)net->od_idx_gpu + 4 * (size_t)net->batch); }
+static uint8_t *od_zp_dev(const network *net) { return (uint8_t *)net->od_idx_gpu + 8 * (size_t)net->batch; }
+
+/* bank entries for the pairs in the pair arrays: image b's, or image 0's for everybody */
+static void od_derive(network *net)
+{
+    const int B = net->batch;
+    check_mi355(mi355_l0_derive(net->od_const_gpu, net->od_const_host, net->od_bank_gpu, net->pi_entry_bytes, B, !net->per_image, od_scale_dev(net),
+                                od_zp_dev(net), (float *)net->od_kept_gpu, (uint8_t *)net->od_kept_gpu + 4 * (size_t)B, net->od_status_gpu, net->stream),
+                "mi355_l0_derive");
+}
+
+/* pairs from the batch's [B][2] max / min in HBM (shared-scale mode reads image 0's), then their entries */
+static void od_pairs_and_entries(network *net, const float *mm_gpu)
+{
+    check_mi355(mi355_input_pairs(mm_gpu, net->batch, !net->per_image, (int32_t *)net->od_idx_gpu, od_scale_dev(net), od_zp_dev(net),
+                                  net->od_status_gpu, net->stream), "mi355_input_pairs");
+    od_derive(net);
+}
+
+/* the host quantiser's pairs (quantization_weights_and_activations: the floats are on the host) go up instead, layer 0 is derived
+ * from them on the device all the same */
+static void od_pairs_from_host(network *net, const float *scale, const uint8_t *zp)
+{
+    const int B = net->batch;
+    od_alloc(net);
+    char *idx = calloc(9, (size_t)B);
+    for (int b = 0; b < B; ++b) {
+        ((int32_t *)idx)[b] = net->per_image ? b : 0;
+        ((float *)(idx + 4 * (size_t)B))[b] = scale[net->per_image ? b : 0];
+        ((uint8_t *)idx)[8 * (size_t)B + b] = zp[net->per_image ? b : 0];
+    }
+    check_mi355(mi355_h2d(net->od_idx_gpu, idx, 9 * (size_t)B, net->stream), "upload input pairs");
+    check_mi355(mi355_memset(net->od_status_gpu, 0, sizeof(uint32_t) * (size_t)B, net->stream), "clear input status");
+    od_derive(net);
+    net_wait(net); /* idx is freed */
+    free(idx);
+}
+
+/* float images in HBM: min / max of every image (or of image 0), pairs, entries, quantiser */
+static void quantize_on_device(network *net, const float *input_gpu)
+{
+    const int B = net->batch;
+    od_alloc(net);
+    check_mi355(mi355_image_minmax_batched(input_gpu, net->per_image ? B : 1, net->inputs, net->od_mm_gpu, net->stream), "mi355_image_minmax_batched");
+    od_pairs_and_entries(net, net->od_mm_gpu);
+    check_mi355(mi355_image_quantize_per_image(input_gpu, B, net->inputs, od_scale_dev(net), od_zp_dev(net), net->input_uint8_gpu, net->stream),
+                "mi355_image_quantize_per_image");
+}
+
+int network_input_status(network *net, uint32_t *status)
+{
+    const int B = net->batch;
+    memset(status, 0, sizeof(uint32_t) * (size_t)B);
+    if (!net->input_on_device || !net->od_status_gpu) return 0;
+    check_mi355(mi355_d2h(status, net->od_status_gpu, sizeof(uint32_t) * (size_t)B, net->stream), "pull input status");
+    net_wait(net);
+    int bad = 0;
+    for (int b = 0; b < B; ++b) bad += status[b] != 0;
+    return bad;
+}
+
+void network_input_bank_entry(network *net, int b, void *dst)
+{
+    if (b < 0 || b >= net->batch) error("network_input_bank_entry: image index");
+    const char *bank = net->input_on_device ? net->od_bank_gpu : net->pi_bank_gpu;
+    if (!bank || (!net->input_on_device && !net->pi_idx_host)) error("network_input_bank_entry: no batch has been quantised through a bank yet");
+    int32_t e = net->input_on_device ? (net->per_image ? b : 0) : ((const int32_t *)net->pi_idx_host)[b];
+    check_mi355(mi355_d2h(dst, bank + (size_t)e * net->pi_entry_bytes, net->pi_entry_bytes, net->stream), "pull bank entry");
+    net_wait(net);
 }
 
 void network_letterbox_input_gpu(network *net, int slot, const float *im_gpu, int imw, int imh)
@@ -757,7 +966,7 @@ static size_t fr_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 static void fr_arena_reserve(network *net, size_t need)
 {
     if (need <= net->fr_arena_bytes) return;
-    check_mi355(mi355_stream_sync(net->stream), "sync"); /* nothing in flight reads the arena that is freed */
+    net_wait(net); /* nothing in flight reads the arena that is freed */
     if (net->fr_arena_gpu) mi355_free(net->fr_arena_gpu);
     net->fr_arena_gpu = NULL; net->fr_arena_bytes = 0;
     check_mi355(mi355_alloc(&net->fr_arena_gpu, need), "alloc frame arena");
@@ -809,21 +1018,28 @@ static void fr_finish(network *net)
 {
     const int B = net->batch, kind = net->fr_kind, w = net->w, h = net->h;
     const void *tg = net->fr_table_gpu, *th = net->fr_table_host;
+    if (net->input_on_device) od_alloc(net);
     check_mi355(mi355_h2d(net->fr_table_gpu, th, fr_entry_bytes[kind] * (size_t)B, net->stream), "upload frame table");
     if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_planar_letterbox_minmax");
     else if (kind == FR_PACKED) check_mi355(mi355_frames_packed_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_packed_letterbox_minmax");
     else if (kind == FR_P010) check_mi355(mi355_frames_p010_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_p010_letterbox_minmax");
     else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_yuv_letterbox_minmax");
     else check_mi355(mi355_frames_u8_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_u8_letterbox_minmax");
-    check_mi355(mi355_d2h(net->fr_mm_host, net->fr_mm_gpu, 2 * sizeof(float) * (size_t)B, net->stream), "minmax d2h");
-    check_mi355(mi355_stream_sync(net->stream), "sync"); /* the batch's one host sync: every earlier upload is done too */
     const float *scale_dev;
     const uint8_t *zp_dev;
-    if (net->per_image) {
+    if (net->input_on_device) { /* pairs and layer 0 follow on the stream: nothing comes back, nothing is waited for */
+        od_pairs_and_entries(net, net->fr_mm_gpu);
+        scale_dev = od_scale_dev(net);
+        zp_dev = od_zp_dev(net);
+    } else if (net->per_image) {
+        check_mi355(mi355_d2h(net->fr_mm_host, net->fr_mm_gpu, 2 * sizeof(float) * (size_t)B, net->stream), "minmax d2h");
+        net_wait(net); /* the batch's one host sync: every earlier upload is done too */
         input_pairs_per_image(net, net->fr_mm_host);
         scale_dev = (const float *)((const char *)net->pi_idx_gpu + 4 * (size_t)B);
         zp_dev = (const uint8_t *)net->pi_idx_gpu + 8 * (size_t)B;
     } else { /* image 0 defines the pair of the whole batch */
+        check_mi355(mi355_d2h(net->fr_mm_host, net->fr_mm_gpu, 2 * sizeof(float) * (size_t)B, net->stream), "minmax d2h");
+        net_wait(net); /* the batch's one host sync: every earlier upload is done too */
         float s; uint8_t zp;
         image_scale_zero_point(net->fr_mm_host[1] + 0.0f, net->fr_mm_host[0], &s, &zp);
         input_pair_shared(net, s, zp);
@@ -999,6 +1215,7 @@ void set_batch_network(network *net, int b)
     if (net->n_replicas > 0) error("set_batch_network: free this network's replicas first (they borrow its packed weights on the device)");
     net->batch = b;
     pi_free(net); /* the per-image bank and index arrays are sized by the batch */
+    od_free(net); /* and the device-derived bank, its pair, status and min / max arrays */
     fr_free(net); /* so are the frame table, its min / max and the staging arena */
     detb_free(net); /* and the batched box decode's buffers */
     free(net->input); free(net->input_uint8);
@@ -1014,7 +1231,7 @@ void set_batch_network(network *net, int b)
         alloc_network_device(net);
         for (int i = 0; i < net->n; ++i)
             if (net->layers[i].type == CONVOLUTIONAL) upload_conv(net, i, net->has_host_weights);
-        check_mi355(mi355_stream_sync(net->stream), "sync");
+        net_wait(net);
     }
 }
 
@@ -1123,7 +1340,7 @@ void forward_network_gpu(network *netp)
     if (netp->use_graph) {
         if (!netp->graph) {
             run_layers(netp); /* warm-up outside capture (module load, attribute calls) */
-            check_mi355(mi355_stream_sync(netp->stream), "sync");
+            net_wait(netp);
             check_mi355(mi355_graph_begin(netp->stream), "graph begin");
             run_layers(netp);
             check_mi355(mi355_graph_end(netp->stream, &netp->graph), "graph end");
@@ -1143,7 +1360,7 @@ void network_selfcheck(network *net, int passes)
     check_mi355(mi355_alloc((void **)&net->selfcheck_gpu, (size_t)passes * sizeof(uint64_t)), "alloc selfcheck");
     uint64_t *zeros = calloc((size_t)passes, sizeof(uint64_t));
     check_mi355(mi355_h2d(net->selfcheck_gpu, zeros, (size_t)passes * sizeof(uint64_t), net->stream), "zero selfcheck");
-    check_mi355(mi355_stream_sync(net->stream), "sync");
+    net_wait(net);
     free(zeros);
     net->selfcheck_passes = passes;
     for (int p = 0; p < passes; ++p) {
@@ -1162,7 +1379,7 @@ int network_selfcheck_result(network *net)
     const int passes = net->selfcheck_passes;
     uint64_t *sums = calloc((size_t)passes, sizeof(uint64_t));
     check_mi355(mi355_d2h(sums, net->selfcheck_gpu, (size_t)passes * sizeof(uint64_t), net->stream), "pull selfcheck");
-    check_mi355(mi355_stream_sync(net->stream), "sync");
+    net_wait(net);
     int bad = 0;
     for (int p = 1; p < passes; ++p) bad += sums[p] != sums[0];
     free(sums);
@@ -1179,11 +1396,11 @@ float *network_predict(network *net, float *input)
     (void)input;
     net->train = 0;
     forward_network_gpu(net);
-    check_mi355(mi355_stream_sync(net->stream), "sync");
+    net_wait(net);
     layer *last = &net->layers[net->n - 1];
     if (last->output_gpu) {
         check_mi355(mi355_d2h(last->output, last->output_gpu, (size_t)net->batch * last->outputs * sizeof(float), net->stream), "pull output");
-        check_mi355(mi355_stream_sync(net->stream), "sync");
+        net_wait(net);
     }
     net->output = last->output;
     return net->output;
@@ -1200,7 +1417,7 @@ void pull_layer_output(network *net, int i)
     }
     if (l->output_gpu) check_mi355(mi355_d2h(l->output, l->output_gpu, cnt * sizeof(float), net->stream), "pull f32");
     if (l->output_int32_gpu) check_mi355(mi355_d2h(l->output_int32, l->output_int32_gpu, cnt * sizeof(int32_t), net->stream), "pull i32");
-    check_mi355(mi355_stream_sync(net->stream), "sync");
+    net_wait(net);
 }
 
 static int cmp_rec_rank(const void *a, const void *b)
@@ -1237,13 +1454,13 @@ static void det_pull(network *net, layer *l, float *recs, int max_recs, int *cou
 {
     const int B = net->batch, rl = 6 + l->classes;
     check_mi355(mi355_d2h(counts, l->det_counts_gpu, sizeof(int) * (size_t)B, net->stream), "pull counts");
-    check_mi355(mi355_stream_sync(net->stream), "sync");
+    net_wait(net);
     for (int b = 0; b < B; ++b) { /* only the records that exist cross PCIe; reference order = ascending rank */
         const int k = counts[b] < max_recs ? counts[b] : max_recs;
         if (!k) continue;
         float *dst = recs + (size_t)b * max_recs * rl;
         check_mi355(mi355_d2h(dst, l->det_recs_gpu + (size_t)b * max_recs * rl, sizeof(float) * (size_t)k * rl, net->stream), "pull records");
-        check_mi355(mi355_stream_sync(net->stream), "sync");
+        net_wait(net);
         qsort(dst, (size_t)k, sizeof(float) * rl, cmp_rec_rank);
     }
 }
@@ -1367,7 +1584,7 @@ int network_detb_run(network *net, const int *imw, const int *imh, float thresh,
                                             counts_gpu, offsets_gpu, net->detb_work_gpu, net->detb_work_ints, net->stream),
                 "mi355_yolo_detections_batch");
     check_mi355(mi355_d2h(hs + 2 * B, counts_gpu, sizeof(int) * ((size_t)B * nh + B + 1), net->stream), "pull counts + offsets");
-    check_mi355(mi355_stream_sync(net->stream), "sync");
+    net_wait(net);
     memcpy(counts, hs + 2 * B, sizeof(int) * (size_t)B * nh);
     memcpy(offsets, hs + 2 * B + (size_t)B * nh, sizeof(int) * ((size_t)B + 1));
     return offsets[B];
@@ -1379,7 +1596,7 @@ void network_detb_pull(network *net, float *recs, int total)
     int classes = 0;
     network_detections_batch_shape(net, NULL, &classes, NULL);
     check_mi355(mi355_d2h(recs, net->detb_recs_gpu, sizeof(float) * (size_t)total * (6 + classes), net->stream), "pull records");
-    check_mi355(mi355_stream_sync(net->stream), "sync");
+    net_wait(net);
 }
 
 int network_yolo_detections_batch_gpu(network *net, const int *imw, const int *imh, float thresh, int relative, int max_per_image,
@@ -1555,7 +1772,7 @@ void network_import_packed(network *net, const void *buf, size_t bytes)
     alloc_network_device(net);
     for (int i = 0; i < net->n; ++i)
         if (net->layers[i].type == CONVOLUTIONAL) upload_conv(net, i, 0);
-    check_mi355(mi355_stream_sync(net->stream), "sync");
+    net_wait(net);
     net->prepared = 1;
 }
 
@@ -1587,7 +1804,7 @@ void network_bcast_packed(network *net, void *comm, int rank, int root)
     }
     int rc = mi355_bcast_blob(comm, dev, sz, root, net->stream);
     if (rc) { fprintf(stderr, "%s\n", mi355_comm_last_error()); error("mi355_bcast_blob"); }
-    check_mi355(mi355_stream_sync(net->stream), "sync");
+    net_wait(net);
     free(host);
     if (rank != root) network_import_packed_gpu(net, dev, sz);
     mi355_free(dev);
@@ -1599,7 +1816,7 @@ void network_bcast_packed(network *net, void *comm, int rank, int root)
 static void set_plan_internal(network *net, int plan)
 {
     /* the executor may still have a pass (or its captured graph) in flight on its stream */
-    if (net->prepared && (net->stream || net->on_default_stream)) check_mi355(mi355_stream_sync(net->on_default_stream ? NULL : net->stream), "sync");
+    if (net->prepared && (net->stream || net->on_default_stream)) net_wait(net);
     if (net->graph) { mi355_graph_destroy(net->graph); net->graph = NULL; } /* captured with the other plan's kernels */
     net->plan = plan;
     /* fused calls a launcher refused under the old plan (conv_ws3's fused pools under the throughput plan: flags cleared at run
@@ -1632,6 +1849,7 @@ network *network_replica_ex(network *parent, int default_stream)
     net->fuse_maxpool = parent->fuse_maxpool; net->keep_head_float = parent->keep_head_float;
     net->use_graph = parent->use_graph; net->input_direct_off = parent->input_direct_off;
     net->per_image = parent->per_image; /* its own bank (allocated by its first per-image batch); layer 0's raw weights are the parent's */
+    net->input_on_device = parent->input_on_device; /* its own bank, pair and status arrays and copy of the constant table */
     net->dump_int32 = 0;
     if (parent->accum_mode == MI355_ACC_REF_F32) error("network_replica: MI355_ACC_REF_F32 reads raw weights, which a replica does not hold");
     net->replica_of = parent;
@@ -1668,7 +1886,7 @@ network *network_replica_ex(network *parent, int default_stream)
     net->has_l0_weights = 0;
     plan_fusion(net);
     alloc_network_device(net);
-    check_mi355(mi355_stream_sync(net->stream), "sync");
+    net_wait(net);
     net->prepared = 1;
     return net;
 }
@@ -1698,6 +1916,7 @@ void free_network(network *net)
     if (net->input_gpu) mi355_free(net->input_gpu);
     if (net->quant_mm_gpu) mi355_free(net->quant_mm_gpu);
     pi_free(net);
+    od_free(net);
     fr_free(net);
     detb_free(net);
     if (net->selfcheck_gpu) mi355_free(net->selfcheck_gpu);
