@@ -307,6 +307,10 @@ def _aimed():
     n = Net(12, 12)
     n.conv(64, 3); n.conv(32, 1); n.upsample(2, qs=1); n.head()
     add("fused_upsample_quant_stop", "upsample 2 has a quant_stop float tail: conv 1 (c = 64) must not swallow it", n)
+    n = Net(58, 58)
+    n.conv(16, 3); n.conv(40, 3, stride=7); n.head()
+    add("kxk_stride7_wide_m_tile", "a stride-7 conv on c = 16 reaches the general kernel's 128 x 64 tile through the host (the 256-pixel patch "
+                                   "of 108 x 108 or 220 x 52 cells does not fit in LDS)", n)
     return A
 
 
@@ -432,7 +436,7 @@ def features(cfg_text):
 
 
 REQUIRED_FEATURES = (
-    [f"size{k}" for k in range(1, 12)] + ["conv_stride1", "conv_stride2", "conv_stride3", "pad1", "padding0", "padding_n", "padding_size_minus_1"] +
+    [f"size{k}" for k in range(1, 12)] + ["conv_stride1", "conv_stride2", "conv_stride3", "conv_stride7", "pad1", "padding0", "padding_n", "padding_size_minus_1"] +
     [f"filters{n}" for n in FILTERS] + ["filters3", "filters255", "pool_64_to_64_128", "cell4_conv", "bn0", "bn1"] + [f"act_{a}" for a in ACTS] +
     ["maxpool_on_odd_map", "maxpool_on_even_map", "maxpool2/2", "maxpool2/1", "maxpool3/2", "maxpool5/1", "maxpool9/1", "maxpool13/1", "upsample2", "upsample3", "upsample4",
      "route1", "route2", "route3", "route_negative", "route_absolute", "producer_in_two_routes", "route_mixed_activations", "route_same_layer_twice",

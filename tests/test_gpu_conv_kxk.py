@@ -54,7 +54,7 @@ GRID = [
     (1, 9, 33, 9, 9, 3, 1, 1, "leaky"),
     (2, 17, 40, 15, 31, 1, 1, 0, "linear"),    # 1x1 on c = 17
     (1, 1, 1, 1, 1, 11, 1, 5, "leaky"),        # 1x1 map, 11x11 kernel
-    (1, 32, 40, 60, 60, 11, 6, 5, "leaky"),    # large stride: the 64-pixel tile
+    (1, 32, 40, 60, 60, 11, 6, 5, "leaky"),    # large stride: still the 256-pixel tile, at width 16 (101 x 101 cells: 112 bytes under the LDS limit)
     (1, 40, 17, 19, 23, 7, 4, 3, "relu"),
     (1, 512, 64, 7, 7, 7, 1, 3, "leaky"),      # K = 25088
     (2, 3, 16, 32, 30, 3, 2, 1, "leaky"),      # 3x3 stride-2 stem on the image (yolov4-tiny): the 3x3 blob's general section

@@ -266,6 +266,13 @@ def _x_up_quant_stop(o):
     assert o["after"][1]["fuse_next_upsample"] == 0 and not o["fuses"][1]
 
 
+def _x_stride7(o):
+    import kxk_geometry
+    assert o["kern"][1] == 9 and o["info"][1]["stride"] == 7 and o["info"][1]["c"] == 16
+    g = kxk_geometry.conv_kxk_launch(kxk_geometry.Trace(), B, 58, 58, 16, 40, 3, 7, 1)
+    assert g["inst"] == (16, 1, 4), "the restated launcher: 128 filters x 64 pixels, four waves along M"
+
+
 AIMED_EXPECT = {  # name -> {mode: check}; "default" checks also hold under graph capture
     "view_same_zp": {"default": _x_view_same_zp, "nofuse": _x_view_same_zp},
     "view_zp_differs": {"default": _x_view_zp_differs, "nofuse": _x_view_zp_differs},
@@ -291,6 +298,7 @@ AIMED_EXPECT = {  # name -> {mode: check}; "default" checks also hold under grap
     "kxk_reads_window": {"default": _x_kxk_window},
     "cell4_conv_feeds_conv": {"default": _x_cell4},
     "fused_upsample_quant_stop": {"default": _x_up_quant_stop},
+    "kxk_stride7_wide_m_tile": {m: _x_stride7 for m in ("dump", "default", "throughput", "replica")},
 }
 
 

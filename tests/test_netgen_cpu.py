@@ -188,6 +188,7 @@ CANDIDATES = {
     "kxk_reads_window": {},
     "cell4_conv_feeds_conv": {5: "yolo"},
     "fused_upsample_quant_stop": {3: "yolo"},
+    "kxk_stride7_wide_m_tile": {},
     "cfg/yolov3-tiny_quant.cfg": {0: "pool", 2: "pool", 4: "pool", 6: "pool", 8: "pool+keep", 10: "pool", 15: "yolo", 18: "upsample", 22: "yolo"},
     "cfg/yolov3_quant.cfg": {**{i: "shortcut" for i in (3, 7, 10, 14, 17, 20, 23, 26, 29, 32, 35, 39, 42, 45, 48, 51, 54, 57, 60, 64, 67, 70, 73)},
                              81: "yolo", 84: "upsample", 93: "yolo", 96: "upsample", 105: "yolo"},
