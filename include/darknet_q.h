@@ -197,6 +197,16 @@ struct network {
     float *fr_mm_gpu, *fr_mm_host; /* [fr_cap][2] max, min */
     void *fr_pair_gpu, *fr_pair_host; /* shared-scale mode: [fr_cap] float scale | [fr_cap] uint8 zero point, image 0's in every slot */
     int fr_cap;
+    /* JPEG input (network_jpeg_decode_gpu): lazily allocated, grown when needed, freed with the network.  A replica owns its own. */
+    void *jpg_stage_host;       /* host staging block: plane table | image table | quantiser tables | coefficients */
+    size_t jpg_stage_bytes;
+    void *jpg_in_gpu;           /* its device copy, the same layout */
+    size_t jpg_in_bytes;
+    void *jpg_planes_gpu;       /* the component planes the inverse DCT writes */
+    size_t jpg_planes_bytes;
+    void *jpg_rgb_gpu;          /* the RGB frames of the last call */
+    size_t jpg_rgb_bytes;
+    int jpg_upload_pending;     /* an upload from the staging block may be in flight: wait before rewriting it */
     /* Batched box decode (network_yolo_detections_batch_gpu): lazily allocated, grown when needed, freed with the network and on
      * re-batch.  A replica owns its own. */
     int *detb_ints_gpu, *detb_ints_host; /* [2][batch] source sizes | counts [batch][nheads] | offsets [batch + 1] */
@@ -296,6 +306,31 @@ void network_frames_packed_input_gpu(network *net, const uint8_t *const *frames,
  * (y >> 8, uv >> 8).  frames_on_device != 0: device pointers, used in place.  Refusals as above. */
 void network_frames_p010_input_gpu(network *net, const uint8_t *const *y, const uint8_t *const *uv, const int *w, const int *h,
                                    const int *pitch_y, const int *pitch_uv, int matrix, int frames_on_device);
+/* JPEG images.  The host half (yolo_quantization_amd/host/jpeg.h: jpeg_decode_host, jpeg_info_host, jpeg_free; no device needed) parses
+ * a baseline JPEG and decodes its entropy-coded streams into quantised coefficients; the device does the rest -- dequantisation, inverse
+ * DCT, chroma upsampling, YCbCr -> RGB (mi355_jpeg_idct, mi355_jpeg_to_rgb) -- and leaves the pixels stbi_load(file, .., 3) returns in
+ * the reference (ref: src/image.c:1293-1315), byte for byte, as interleaved RGB frames in device memory.
+ *
+ * network_jpeg_decode_gpu: data[b], bytes[b] are the n images' files in host memory (slots that name the same bytes are decoded
+ * once and share a frame).  All n are entropy-decoded first; if one fails the call returns MI355_EINVAL, network_jpeg_last_error()
+ * (a buffer of the calling thread) names the slot and the reason ("jpeg slot 2: progressive JPEG (SOF2) is not supported") and nothing
+ * has been launched or uploaded.  Otherwise coefficients and tables go up from one staging block in one copy on the network's stream,
+ * the two launches follow, and rgb_dev[b], w[b], h[b], pitch[b] describe image b's frame: device memory the network owns, valid until
+ * the next call (on the network's stream: the call only enqueues).  The staging block is not rewritten before the upload that read it
+ * has completed (the next call waits for the stream if need be).  Device errors die via error() like everywhere else.
+ *
+ * network_frames_jpeg_input_gpu: the above for net->batch images, then network_frames_u8_input_gpu on those device frames: both scale
+ * modes, set_input_quantization_on_device, replicas and graph replay are that function's.  w[b], h[b] receive every image's size, for
+ * the detection calls.  Returns 0, or MI355_EINVAL with network_jpeg_last_error() as above (a frame the letterbox cannot serve still
+ * dies in network_frames_u8_input_gpu). */
+typedef struct dnq_jpeg dnq_jpeg;
+int jpeg_decode_host(const uint8_t *data, size_t bytes, dnq_jpeg *out, char *err, size_t errlen);
+int jpeg_info_host(const uint8_t *data, size_t bytes, dnq_jpeg *out, char *err, size_t errlen);
+void jpeg_free(dnq_jpeg *j);
+int network_jpeg_decode_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int n, uint8_t **rgb_dev, int *w, int *h,
+                            int *pitch);
+int network_frames_jpeg_input_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int *w, int *h);
+const char *network_jpeg_last_error(void);
 /* Per-image input quantisation, opt-in (off: image 0 defines the scale of the whole batch, as before).  On: every image of a batch is
  * quantised with its own min / max, scale and zero point, and layer 0 runs with that image's constants (mi355_conv_forward_per_image):
  * slot b of every layer equals the batch-1 run on image b.  The quantisers above honour it.  Returns 0, or MI355_EINVAL with a message

@@ -509,6 +509,59 @@ int mi355_frames_p010_letterbox_minmax(const mi355_frame_p010 *table_dev, const 
                                        float *minmax, void *stream);
 int mi355_frames_p010_letterbox_quantize(const mi355_frame_p010 *table_dev, const mi355_frame_p010 *table_host, int B, int w, int h,
                                          const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
+/* The device half of a baseline JPEG decoder: everything after the entropy decode, for a whole batch in two launches, leaving interleaved
+ * RGB frames in device memory that the u8 calls above take as they are.  The bytes are the ones stb_image v2.19 returns as the reference
+ * compiles it (ref: src/stb_image.h; load_image_color -> stbi_load(.., 3), src/image.c:1293-1315): all of this is integer arithmetic in
+ * stb, and every step is restated exactly, computed in 32-bit wrapping arithmetic so that no input is undefined.
+ *
+ * mi355_jpeg_idct: one launch for every 8x8 block of every component plane of every image.  A plane is blocks_w x blocks_h blocks;
+ * block (bx, by) reads coef[(by * blocks_w + bx) * 64 ..], 64 quantised coefficients in natural (row-major, de-zigzagged) order, and
+ * the plane's 64 quantiser values, and writes an 8 x 8 byte tile at out[(8 by + r) * 8 * blocks_w + 8 bx ..] (the plane's pitch is
+ * 8 * blocks_w).  Per block, in this order: d = (int16_t)(coefficient * quantiser), the low 16 bits of the product (ref :1969-1999);
+ * the column pass, +512, >> 10; the row pass, +65536 + (128 << 17), >> 17, clamp to 0..255 (ref :2163-2261).  first_block is the
+ * running count of the blocks of the planes before (plane 0: 0).  coef and quant 16-byte aligned, out 8-byte aligned.
+ *
+ * mi355_jpeg_to_rgb: one launch for the batch; image b is w x h pixels, rows `pitch` >= 3 * w bytes apart at `rgb` (any alignment).
+ * Component k of pixel (x, y) is read from comp[k] through stb's resampler for the component's (hs, vs), as a pure function of (x, y)
+ * with w_lores = ceil(w / hs) and `rows` the component's real row count:
+ *     (1, 1)  plane[y][x]                                   (1, 2)  (3 near[x] + far[x] + 2) >> 2
+ *     (2, 1)  ref :3183-3209: 3 : 1 between horizontal neighbours, the first and last pixel of a row take one sample, the pixel before
+ *             the last weighs sample w_lores - 2 three times (stb's own asymmetry), w_lores == 1: the sample
+ *     (2, 2)  ref :3213-3235: t(i) = 3 near[i] + far[i], then (3 t + t' + 8) >> 4 between neighbours, (t + 2) >> 2 at both ends
+ *     other   plane[y / vs][x / hs]
+ * near = row y >> 1, far = row (y >> 1) + 1 for an odd y and (y >> 1) - 1 for an even one, clamped to 0 .. rows - 1 (ref :3630-3644).
+ * mode: MI355_JPEG_YCBCR converts with ref :3367-3391 (20-bit fixed point, the Cb term of G masked with 0xffff0000, clamp),
+ * MI355_JPEG_RGB stores the three samples as they are, MI355_JPEG_GREY replicates comp[0].
+ *
+ * The contract of the frame calls: table_host mirrors table_dev and is validated before anything is launched (null pointers, alignment,
+ * sizes outside 1..32768, a running count that does not add up, hs / vs outside 1..4, rows < ceil(h / vs), a component pitch below
+ * ceil(w / hs), pitch < 3 * w, an unknown mode): MI355_EINVAL with a message that starts "jpeg_idct:" / "jpeg_to_rgb:", nothing is
+ * written.  New structs and new calls: MI355_ABI_VERSION is unchanged. */
+#define MI355_JPEG_YCBCR 0
+#define MI355_JPEG_RGB   1
+#define MI355_JPEG_GREY  2
+typedef struct mi355_jpeg_plane {     /* 48 bytes */
+    const int16_t *coef;              /* DEVICE: [blocks_h * blocks_w][64] */
+    const uint16_t *quant;            /* DEVICE: [64], natural order */
+    uint8_t *out;                     /* DEVICE: 8 * blocks_h rows of 8 * blocks_w bytes */
+    int blocks_w, blocks_h;
+    int first_block;                  /* blocks of the planes before this one in the table */
+    int reserved[3];                  /* zero */
+} mi355_jpeg_plane;
+typedef struct mi355_jpeg_component { /* 24 bytes */
+    const uint8_t *plane;             /* DEVICE: the component's samples (mi355_jpeg_plane.out) */
+    int pitch;                        /* bytes from one row to the next */
+    int rows;                         /* the component's real row count, >= ceil(h / vs) */
+    int hs, vs;                       /* upsampling factors, 1..4 */
+} mi355_jpeg_component;
+typedef struct mi355_jpeg_image {     /* 96 bytes */
+    uint8_t *rgb;                     /* DEVICE: h rows of w interleaved RGB pixels */
+    int w, h, pitch;
+    int mode;                         /* MI355_JPEG_* */
+    mi355_jpeg_component comp[3];     /* MI355_JPEG_GREY reads comp[0] only */
+} mi355_jpeg_image;
+int mi355_jpeg_idct(const mi355_jpeg_plane *table_dev, const mi355_jpeg_plane *table_host, int nplanes, void *stream);
+int mi355_jpeg_to_rgb(const mi355_jpeg_image *table_dev, const mi355_jpeg_image *table_host, int B, void *stream);
 /* *sum_dev += an order-independent 64-bit checksum of `dwords` 32-bit words at buf (device pointers; zero *sum_dev first).  The
  * host's determinism self-check compares it between passes over the same input (network_selfcheck, darknet_q.h). */
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream);

@@ -26,6 +26,15 @@ frames already in HBM (uploaded before the clock starts, frames_on_device = 1) -
 a repeat in this one process.  Each reports the two medians above and `call_ms`, the time the host thread spends inside the call; each
 on-device network's input, scales and zero points are compared with its synchronous twin's first, and its host_waits() counted over the
 timed steps.
+
+--jpeg times the JPEG input path instead: batch 64 of 640 x 480 4:2:0 baseline files (smooth pictures with noise, written with Pillow at
+quality 85 before the clock starts), per scale mode two variants alternating within a repeat:
+  jpeg    network_frames_jpeg_input_gpu: host entropy decode of the batch, one upload of coefficients and tables, mi355_jpeg_idct,
+          mi355_jpeg_to_rgb, then the u8 step on the frames where they lie
+  u8      network_frames_u8_input_gpu on the decoded RGB frames in host memory (what a caller with its own JPEG decoder would feed)
+and, once, the stages of the jpeg variant on their own through the same calls: `host_entropy_ms` (jpeg_decode_host over the batch, host
+clock, one thread), `upload_ms`, `idct_ms`, `to_rgb_ms` (HIP events around one copy of all coefficients and tables and around each
+launch; medians of `iters`).  Before timing, the jpeg network's uint8 input, scales and zero points are compared with the u8 network's.
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -175,6 +184,131 @@ class P010Variant(NV12Variant):
         self.net.H.network_frames_p010_input_gpu(self.net.h, self.y, self.uv, self.w, self.h, None, None, 0, self.hbm)
 
 
+class JpegVariant:
+    def __init__(self, net, files):
+        B = len(files)
+        self.net, self.files = net, files
+        self.ptrs, self.sizes = (C.c_char_p * B)(*files), (C.c_size_t * B)(*[len(f) for f in files])
+        self.w, self.h = (C.c_int * B)(), (C.c_int * B)()
+
+    def step(self):
+        if self.net.H.network_frames_jpeg_input_gpu(self.net.h, self.ptrs, self.sizes, self.w, self.h) != 0:
+            sys.exit(self.net.H.network_jpeg_last_error().decode())
+
+
+def make_jpegs(B, w, h):
+    import io
+    from PIL import Image
+    files = []
+    y, x = np.mgrid[0:h, 0:w]
+    for b in range(B):
+        rng = np.random.default_rng(100 + b)
+        base = np.stack([(x * 255) // (w - 1), (y * 255) // (h - 1), ((x + y + 7 * b) * 255 // (w + h)) % 256], axis=-1)
+        pic = np.clip(base + rng.integers(-25, 26, (h, w, 3)), 0, 255).astype(np.uint8)
+        buf = io.BytesIO()
+        Image.fromarray(pic).save(buf, "JPEG", quality=85, subsampling=2)
+        files.append(buf.getvalue())
+    return files
+
+
+def jpeg_stages(files, ev, iters):
+    """the stages of one batch on the default stream: host entropy decode, one upload, the two launches"""
+    S, H = binding.shim(), binding.host()
+    host_ms = []
+    for _ in range(max(3, iters // 4)):
+        t0 = time.perf_counter()
+        for f in files:
+            j = binding.DnqJpeg()
+            if H.jpeg_decode_host(f, len(f), C.byref(j), None, 0) != 0:
+                sys.exit("a generated file was refused")
+            H.jpeg_free(C.byref(j))
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+    dec = [binding.jpeg_coefficients(f) for f in files]
+    comps = [c for d in dec for c in d["components"]]
+    stage = np.concatenate([c["coef"].ravel().view(np.uint8) for c in comps] + [c["quant"].view(np.uint8) for c in comps])
+    dev = binding.DevBuf(stage.nbytes)
+    planes = binding.DevBuf(sum(64 * c["blocks_w"] * c["blocks_h"] for c in comps))
+    tp = (binding.JpegPlane * len(comps))()
+    ti = (binding.JpegImage * len(dec))()
+    at, out_at, first, k = 0, 0, 0, 0
+    quant_at = sum(c["coef"].nbytes for c in comps)
+    rgb = []
+    for b, d in enumerate(dec):
+        pitch = (3 * d["w"] + 3) & ~3
+        rgb.append(binding.DevBuf(d["h"] * pitch))
+        ti[b].rgb, ti[b].w, ti[b].h, ti[b].pitch, ti[b].mode = rgb[-1].ptr, d["w"], d["h"], pitch, binding.JPEG_MODES.index(d["mode"])
+        for i, c in enumerate(d["components"]):
+            blocks = c["blocks_w"] * c["blocks_h"]
+            tp[k].coef, tp[k].quant, tp[k].out = dev.ptr.value + at, dev.ptr.value + quant_at + 128 * k, planes.ptr.value + out_at
+            tp[k].blocks_w, tp[k].blocks_h, tp[k].first_block = c["blocks_w"], c["blocks_h"], first
+            ti[b].comp[i].plane, ti[b].comp[i].pitch, ti[b].comp[i].rows = tp[k].out, 8 * c["blocks_w"], c["rows"]
+            ti[b].comp[i].hs, ti[b].comp[i].vs = c["hs"], c["vs"]
+            at, out_at, first, k = at + 128 * blocks, out_at + 64 * blocks, first + blocks, k + 1
+    tpd = binding.DevBuf.from_numpy(np.frombuffer(bytes(tp), np.uint8))
+    tid = binding.DevBuf.from_numpy(np.frombuffer(bytes(ti), np.uint8))
+    calls = {"upload_ms": lambda: S.mi355_h2d(dev.ptr, stage.ctypes.data, stage.nbytes, None),
+             "idct_ms": lambda: S.mi355_jpeg_idct(tpd.ptr, tp, len(comps), None),
+             "to_rgb_ms": lambda: S.mi355_jpeg_to_rgb(tid.ptr, ti, len(dec), None)}
+    res = {"host_entropy_ms": round(float(np.median(host_ms)), 4), "coefficient_bytes": int(stage.nbytes), "blocks": int(first),
+           "file_bytes": int(sum(len(f) for f in files))}
+    for name, call in calls.items():
+        ms = []
+        for _ in range(iters + 2):
+            binding.check(S.mi355_stream_sync(None), "sync")
+            binding.check(S.mi355_event_record(ev.a, None), "record")
+            binding.check(call(), name)
+            binding.check(S.mi355_event_record(ev.b, None), "record")
+            binding.check(S.mi355_stream_sync(None), "sync")
+            ms.append(ev.ms())
+        res[name] = round(float(np.median(ms[2:])), 4)
+    frames = []
+    for b, d in enumerate(dec):
+        pitch = (3 * d["w"] + 3) & ~3
+        frames.append(rgb[b].to_numpy(np.uint8, d["h"] * pitch).reshape(d["h"], pitch)[:, :3 * d["w"]].reshape(d["h"], d["w"], 3).copy())
+    for b in rgb + [dev, planes, tpd, tid]:
+        b.free()
+    return res, frames
+
+
+def jpeg_main(a, wts, ev):
+    sw, sh = (int(v) for v in a.src.split("x"))
+    files = make_jpegs(a.batch, sw, sh)
+    res = {}
+    res["stages"], frames = jpeg_stages(files, ev, a.iters)
+    for mode in ("shared", "per_image"):
+        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("jpeg", "u8")}
+        for n in nets.values():
+            n.set_input_per_image(mode == "per_image")
+        var = {"jpeg": JpegVariant(nets["jpeg"], files), "u8": FramesVariant(nets["u8"], frames)}
+        for _ in range(a.warmup):
+            for v in var.values():
+                v.step()
+        out = {k: {"device_ms": [], "wall_ms": [], "call_ms": []} for k in var}
+        same = same_input(nets["jpeg"], nets["u8"])
+        for _ in range(a.repeats):
+            for k, v in var.items():  # alternating
+                for name, x in zip(("device_ms", "wall_ms", "call_ms"), timed(v, ev, a.iters)):
+                    out[k][name].append(round(x, 4))
+        for k in var:
+            out[k]["median"] = {m: float(np.median(out[k][m])) for m in ("device_ms", "wall_ms", "call_ms")}
+        out["jpeg_identical_to_u8_on_the_decoded_frames"] = same
+        res[mode] = out
+        for n in nets.values():
+            n.close()
+    cpu = "unknown"
+    try:
+        with open("/proc/cpuinfo") as f:
+            cpu = next(line.split(":", 1)[1].strip() for line in f if line.startswith("model name"))
+    except (OSError, StopIteration):
+        pass
+    res["config"] = {"cfg": "yolov3-tiny_quant.cfg", "batch": a.batch, "src": a.src, "sampling": "4:2:0", "quality": 85, "iters": a.iters,
+                     "warmup": a.warmup, "repeats": a.repeats, "host_cpu": cpu,
+                     "values": "per repeat the median of `iters` steps: device_ms between HIP events around the step, wall_ms host clock to the "
+                               "end of a stream synchronise after it, call_ms host clock inside the call; `median` over the repeats; stages: "
+                               "see the module text"}
+    print(json.dumps(res))
+
+
 def same_input(a, b):
     same = np.array_equal(pull_input(a), pull_input(b))
     qa, qb = a.input_quantization(), b.input_quantization()
@@ -214,10 +348,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--src", default="640x480")
     ap.add_argument("--on-device", action="store_true", help="compare the synchronous step with the on-device one instead (see the module text)")
+    ap.add_argument("--jpeg", action="store_true", help="time the JPEG input path beside the u8 path on the decoded frames instead (see the module text)")
     a = ap.parse_args()
     binding.init(0)  # raises without a gfx950: nothing is timed on a CPU
     wts = "/tmp/input_path_bench.weights"
     synth.synth_weights(CFG, wts, seed=5)
+    if a.jpeg:
+        jpeg_main(a, wts, Events())
+        return
     sw, sh = (int(v) for v in a.src.split("x"))
     if sw % 2:
         sys.exit("--src: the yuyv variant is made from the NV12 planes and needs an even width")

@@ -92,6 +92,37 @@ _shim = None
 _host = None
 
 
+class JpegPlane(C.Structure):
+    """mi355_jpeg_plane: one component plane of mi355_jpeg_idct's table (device pointers)."""
+    _fields_ = [("coef", C.c_void_p), ("quant", C.c_void_p), ("out", C.c_void_p), ("blocks_w", C.c_int), ("blocks_h", C.c_int),
+                ("first_block", C.c_int), ("reserved", C.c_int * 3)]
+
+
+class JpegComponent(C.Structure):
+    _fields_ = [("plane", C.c_void_p), ("pitch", C.c_int), ("rows", C.c_int), ("hs", C.c_int), ("vs", C.c_int)]
+
+
+class JpegImage(C.Structure):
+    """mi355_jpeg_image: one image of mi355_jpeg_to_rgb's table (device pointers)."""
+    _fields_ = [("rgb", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("pitch", C.c_int), ("mode", C.c_int), ("comp", JpegComponent * 3)]
+
+
+class DnqJpegComp(C.Structure):
+    _fields_ = [("id", C.c_int), ("h", C.c_int), ("v", C.c_int), ("hs", C.c_int), ("vs", C.c_int), ("w", C.c_int), ("rows", C.c_int),
+                ("blocks_w", C.c_int), ("blocks_h", C.c_int), ("tq", C.c_int), ("scans", C.c_int), ("coef", C.POINTER(C.c_int16)),
+                ("quant", C.c_uint16 * 64)]
+
+
+class DnqJpeg(C.Structure):
+    """dnq_jpeg (yolo_quantization_amd/host/jpeg.h): what the host half of the JPEG decoder returns."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("ncomp", C.c_int), ("mode", C.c_int), ("h_max", C.c_int), ("v_max", C.c_int),
+                ("sof", C.c_int), ("jfif", C.c_int), ("adobe_transform", C.c_int), ("restart_interval", C.c_int), ("nscans", C.c_int),
+                ("comp", DnqJpegComp * 3)]
+
+
+JPEG_MODES = ("ycbcr", "rgb", "grey")
+
+
 def shim():
     global _shim
     if _shim is None:
@@ -161,6 +192,9 @@ def shim():
                                                    C.POINTER(Tensor), vp, vp, vp]
         L.mi355_conv_pool_forward_per_image.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.c_size_t, vp, vp,
                                                         C.POINTER(Tensor), C.POINTER(Tensor), vp]
+        if hasattr(L, "mi355_jpeg_idct"):  # MI355_LIB_DIR may name an older build of the libraries (A/B runs): calling them there raises
+            L.mi355_jpeg_idct.argtypes = [vp, C.POINTER(JpegPlane), ci, vp]
+            L.mi355_jpeg_to_rgb.argtypes = [vp, C.POINTER(JpegImage), ci, vp]
         L.mi355_frames_u8_letterbox_minmax.argtypes = [vp, C.POINTER(FrameU8), ci, ci, ci, vp, vp]
         L.mi355_frames_u8_letterbox_quantize.argtypes = [vp, C.POINTER(FrameU8), ci, ci, ci, vp, vp, vp, vp]
         L.mi355_frames_yuv_letterbox_minmax.argtypes = [vp, C.POINTER(FrameYUV), ci, ci, ci, vp, vp]
@@ -412,6 +446,15 @@ def host():
         L.network_frames_packed_input_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, ci, ci]
         L.network_frames_p010_input_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci),
                                                     C.POINTER(ci), ci, ci]
+        if hasattr(L, "jpeg_decode_host"):  # as above: an older build has no JPEG entry points
+            L.jpeg_decode_host.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(DnqJpeg), C.c_char_p, C.c_size_t]
+            L.jpeg_info_host.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(DnqJpeg), C.c_char_p, C.c_size_t]
+            L.jpeg_free.argtypes = [C.POINTER(DnqJpeg)]
+            L.jpeg_free.restype = None
+            L.network_jpeg_decode_gpu.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), ci, C.POINTER(vp), C.POINTER(ci),
+                                                  C.POINTER(ci), C.POINTER(ci)]
+            L.network_frames_jpeg_input_gpu.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(ci), C.POINTER(ci)]
+            L.network_jpeg_last_error.restype = C.c_char_p
         L.quantization_prep_host.argtypes = [vp, C.c_float, C.c_uint8]
         L.forward_network_gpu.argtypes = [vp]
         L.network_predict.restype = vp
@@ -531,6 +574,164 @@ def _sample_rows(f, sample_bytes, inner, keep, what):
         a = a.view(np.uint8)
     ptr, pitch = _byte_rows(a, keep)
     return ptr, pitch, tuple(np.asarray(f).shape), False
+
+
+class JpegError(ValueError):
+    """A JPEG the decoder refuses; the message is the decoder's (with "jpeg slot <b>: " in front where a batch was decoded)."""
+
+
+def _jpeg_bytes(item):
+    """bytes of an item that is bytes-like or a path"""
+    if isinstance(item, (bytes, bytearray, memoryview)):
+        return bytes(item)
+    with open(item, "rb") as f:
+        return f.read()
+
+
+def _jpeg_host(data, headers_only):
+    j = DnqJpeg()
+    err = C.create_string_buffer(256)
+    fn = host().jpeg_info_host if headers_only else host().jpeg_decode_host
+    if fn(data, len(data), C.byref(j), err, len(err)) != 0:
+        raise JpegError(err.value.decode())
+    return j
+
+
+def _jpeg_dict(j):
+    return {"w": j.w, "h": j.h, "ncomp": j.ncomp, "mode": JPEG_MODES[j.mode], "h_max": j.h_max, "v_max": j.v_max, "sof": j.sof,
+            "jfif": bool(j.jfif), "adobe_transform": j.adobe_transform, "restart_interval": j.restart_interval, "nscans": j.nscans,
+            "components": [{k: getattr(j.comp[i], k) for k in ("id", "h", "v", "hs", "vs", "w", "rows", "blocks_w", "blocks_h", "tq")}
+                           for i in range(j.ncomp)]}
+
+
+def jpeg_info(data):
+    """The headers of a JPEG (bytes or a path) as a dict: size, components with their sampling factors and plane sizes, colour mode
+    ("ycbcr" | "rgb" | "grey").  Host only; raises JpegError with the decoder's message for a file it refuses."""
+    j = _jpeg_host(_jpeg_bytes(data), True)
+    d = _jpeg_dict(j)
+    del d["nscans"]
+    return d
+
+
+def jpeg_coefficients(data):
+    """The host half of the decoder on a JPEG (bytes or a path): jpeg_info's dict, plus per component "coef", int16
+    [blocks_h][blocks_w][64] quantised coefficients in natural order, and "quant", uint16 [64], the table its scan was decoded with.
+    Host only."""
+    j = _jpeg_host(_jpeg_bytes(data), False)
+    try:
+        d = _jpeg_dict(j)
+        for i, c in enumerate(d["components"]):
+            n = c["blocks_w"] * c["blocks_h"] * 64
+            c["coef"] = np.ctypeslib.as_array(j.comp[i].coef, shape=(n,)).reshape(c["blocks_h"], c["blocks_w"], 64).copy()
+            c["quant"] = np.array(j.comp[i].quant, np.uint16)
+        return d
+    finally:
+        host().jpeg_free(C.byref(j))
+
+
+def jpeg_idct(planes):
+    """mi355_jpeg_idct on built inputs: planes is a list of (coef int16 [blocks_h][blocks_w][64], quant uint16 [64]); one launch for
+    all of them.  Returns the uint8 planes [8 * blocks_h][8 * blocks_w]."""
+    L = shim()
+    table = (JpegPlane * len(planes))()
+    keep, first = [], 0
+    for i, (coef, quant) in enumerate(planes):
+        coef = np.ascontiguousarray(coef, np.int16)
+        bh, bw = coef.shape[:2]
+        bufs = (DevBuf.from_numpy(coef), DevBuf.from_numpy(np.ascontiguousarray(quant, np.uint16)), DevBuf(64 * bh * bw))
+        keep.append(bufs)
+        table[i].coef, table[i].quant, table[i].out = bufs[0].ptr, bufs[1].ptr, bufs[2].ptr
+        table[i].blocks_w, table[i].blocks_h, table[i].first_block = bw, bh, first
+        first += bw * bh
+    tdev = DevBuf.from_numpy(np.frombuffer(bytes(table), np.uint8))
+    check(L.mi355_jpeg_idct(tdev.ptr, table, len(planes), None), "mi355_jpeg_idct")
+    check(L.mi355_stream_sync(None), "sync")
+    out = [b[2].to_numpy(np.uint8, 64 * table[i].blocks_h * table[i].blocks_w).reshape(8 * table[i].blocks_h, 8 * table[i].blocks_w)
+           for i, b in enumerate(keep)]
+    for bufs in keep:
+        for b in bufs:
+            b.free()
+    tdev.free()
+    return out
+
+
+def jpeg_to_rgb(images, pitch_pad=0):
+    """mi355_jpeg_to_rgb on built inputs: images is a list of dicts {"w", "h", "mode" ("ycbcr" | "rgb" | "grey"), "components":
+    [{"plane": uint8 [rows][pitch], "hs", "vs", "rows" (default: the plane's)}]}; one launch for all of them.  pitch_pad: bytes added
+    to every output row's 3 * w.  Returns uint8 [h][w][3] per image; the pad bytes must come back as they were (0xA5)."""
+    L = shim()
+    table = (JpegImage * len(images))()
+    keep = []
+    for i, im in enumerate(images):
+        w, h = im["w"], im["h"]
+        pitch = 3 * w + pitch_pad
+        out = DevBuf.from_numpy(np.full(h * pitch, 0xA5, np.uint8))
+        bufs = [out]
+        table[i].rgb, table[i].w, table[i].h, table[i].pitch, table[i].mode = out.ptr, w, h, pitch, JPEG_MODES.index(im["mode"])
+        for k, c in enumerate(im["components"]):
+            plane = np.ascontiguousarray(c["plane"], np.uint8)
+            b = DevBuf.from_numpy(plane)
+            bufs.append(b)
+            table[i].comp[k].plane, table[i].comp[k].pitch = b.ptr, plane.shape[1]
+            table[i].comp[k].rows, table[i].comp[k].hs, table[i].comp[k].vs = c.get("rows", plane.shape[0]), c["hs"], c["vs"]
+        keep.append(bufs)
+    tdev = DevBuf.from_numpy(np.frombuffer(bytes(table), np.uint8))
+    check(L.mi355_jpeg_to_rgb(tdev.ptr, table, len(images), None), "mi355_jpeg_to_rgb")
+    check(L.mi355_stream_sync(None), "sync")
+    res = []
+    for i, bufs in enumerate(keep):
+        w, h, pitch = table[i].w, table[i].h, table[i].pitch
+        raw = bufs[0].to_numpy(np.uint8, h * pitch).reshape(h, pitch)
+        if pitch_pad and not (raw[:, 3 * w:] == 0xA5).all():
+            raise MI355Error("mi355_jpeg_to_rgb wrote into the padding of a row")
+        res.append(raw[:, :3 * w].reshape(h, w, 3).copy())
+        for b in bufs:
+            b.free()
+    tdev.free()
+    return res
+
+
+def _jpeg_args(items):
+    datas = [_jpeg_bytes(it) for it in items]
+    n = len(datas)
+    ptrs, sizes = (C.c_char_p * n)(*datas), (C.c_size_t * n)(*[len(d) for d in datas])
+    return datas, ptrs, sizes
+
+
+def jpeg_decode(data, net=None):
+    """Decode a JPEG (bytes or a path) to uint8 [h][w][3], the pixels the reference's stbi_load(.., 3) returns: entropy decode on the
+    host, everything else on the device.  A list of items is decoded as one batch (two launches) and a list comes back.  net: a Net
+    whose buffers and stream serve the call (network_jpeg_decode_gpu); without one the C-ABI calls run on the default stream."""
+    many = isinstance(data, (list, tuple))
+    items = list(data) if many else [data]
+    out = []
+    if net is not None:
+        datas, ptrs, sizes = _jpeg_args(items)
+        n = len(items)
+        rgb, ws, hs, ps = (C.c_void_p * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        if net.H.network_jpeg_decode_gpu(net.h, ptrs, sizes, n, rgb, ws, hs, ps) != 0:
+            raise JpegError(net.H.network_jpeg_last_error().decode())
+        net.sync()
+        for b in range(n):
+            raw = np.empty(hs[b] * ps[b], np.uint8)
+            check(shim().mi355_d2h(raw.ctypes.data, rgb[b], raw.nbytes, None), "d2h")
+            check(shim().mi355_stream_sync(None), "sync")
+            out.append(raw.reshape(hs[b], ps[b])[:, :3 * ws[b]].reshape(hs[b], ws[b], 3).copy())
+        return out if many else out[0]
+    decoded = []
+    for b, it in enumerate(items):
+        try:
+            decoded.append(jpeg_coefficients(it))
+        except JpegError as e:
+            raise JpegError(f"jpeg slot {b}: {e}") from None
+    planes = jpeg_idct([(c["coef"], c["quant"]) for d in decoded for c in d["components"]])
+    images, at = [], 0
+    for d in decoded:
+        comps = [{"plane": planes[at + k], "hs": c["hs"], "vs": c["vs"], "rows": c["rows"]} for k, c in enumerate(d["components"])]
+        at += d["ncomp"]
+        images.append({"w": d["w"], "h": d["h"], "mode": d["mode"], "components": comps})
+    out = jpeg_to_rgb(images)
+    return out if many else out[0]
 
 
 class Net:
@@ -705,6 +906,18 @@ class Net:
             hs[b], ws[b] = a.shape[:2]
         self.H.network_frames_u8_input_gpu(self.h, ptrs, ws, hs, ps, FRAME_ORDER[order], 0)
         return self._prepared(self._pull_input())
+
+    def prepare_from_jpeg(self, items):
+        """JPEG input path (network_frames_jpeg_input_gpu): every item (the bytes of a JPEG file, or a path) is entropy-decoded on the
+        host and finished on the device; the RGB frames stay there and feed the 8-bit frame path.  Returns [(w, h), ...], the images'
+        sizes for the detection calls.  Raises JpegError naming the slot when an image is refused; nothing has been launched then."""
+        assert len(items) == self.batch
+        B = self.batch
+        datas, ptrs, sizes = _jpeg_args(items)
+        ws, hs = (C.c_int * B)(), (C.c_int * B)()
+        if self.H.network_frames_jpeg_input_gpu(self.h, ptrs, sizes, ws, hs) != 0:
+            raise JpegError(self.H.network_jpeg_last_error().decode())
+        return [(ws[b], hs[b]) for b in range(B)]
 
     def _pull_input(self):
         self.sync()

@@ -254,6 +254,12 @@ template <class Source, class Frame> int frames_letterbox_minmax_launch(const Fr
 template <class Source, class Frame>
 int frames_letterbox_quantize_launch(const Frame *table_dev, int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out,
                                      hipStream_t st);
+// jpeg.hip: dequantise + inverse DCT of every block of a batch, then upsampling + colour into RGB frames.  The checks read the host
+// mirror of the table and return NULL or why it is refused; the launchers take the grid from it.
+const char *jpeg_idct_check(const mi355_jpeg_plane *host, int nplanes);
+int jpeg_idct_launch(const mi355_jpeg_plane *table_dev, const mi355_jpeg_plane *table_host, int nplanes, hipStream_t st);
+const char *jpeg_to_rgb_check(const mi355_jpeg_image *host, int B);
+int jpeg_to_rgb_launch(const mi355_jpeg_image *table_dev, const mi355_jpeg_image *table_host, int B, hipStream_t st);
 int yolo_detections_sizes_launch(const float *out, int B, int n, int classes, int h, int w, const float *biases, const int *mask,
                                  int netw, int neth, const int *imw_dev, const int *imh_dev, float thresh, int relative, float *recs,
                                  int max_recs, int *counts, hipStream_t st);

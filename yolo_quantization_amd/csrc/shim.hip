@@ -1152,6 +1152,22 @@ int mi355_frames_p010_letterbox_quantize(const mi355_frame_p010 *table_dev, cons
     return frames_quantize<SourceP010>("frames_p010: letterbox_quantize: null", table_dev, table_host, B, w, h, scale_dev, zp_dev, out_u8, stream);
 }
 
+int mi355_jpeg_idct(const mi355_jpeg_plane *table_dev, const mi355_jpeg_plane *table_host, int nplanes, void *stream)
+{
+    if (!table_dev) return einval("jpeg_idct: null");
+    const char *why = jpeg_idct_check(table_host, nplanes);
+    if (why) return einval(why);
+    return jpeg_idct_launch(table_dev, table_host, nplanes, (hipStream_t)stream);
+}
+
+int mi355_jpeg_to_rgb(const mi355_jpeg_image *table_dev, const mi355_jpeg_image *table_host, int B, void *stream)
+{
+    if (!table_dev) return einval("jpeg_to_rgb: null");
+    const char *why = jpeg_to_rgb_check(table_host, B);
+    if (why) return einval(why);
+    return jpeg_to_rgb_launch(table_dev, table_host, B, (hipStream_t)stream);
+}
+
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream)
 {
     if (!buf || !sum_dev || dwords < 0) return einval("checksum: null");

@@ -36,9 +36,12 @@
  * -input_device (detector test: the input scales and layer 0's constants are derived on the device, no copy back and no wait inside
  * the input step -- set_input_quantization_on_device; the output is unchanged).
  *
- * Image input: binary PPM (P6) of ANY size (letterboxed like the reference does), a raw `.u8` file holding [c][h][w] bytes at
- * network size, or `synthetic:<seed>`.  JPEG/PNG decoding is third-party code in the reference (stb_image, SURVEY.md 2
- * row 21) and not built.
+ * Image input: a baseline JPEG of ANY size -- any file that starts FF D8, whatever its name: entropy decode on the host, inverse DCT,
+ * upsampling and colour conversion on the device (network_frames_jpeg_input_gpu), the pixels stb_image gives the reference, byte for
+ * byte; a JPEG source always takes the byte path on the device, so `-frames u8` is implied --, a binary PPM (P6) of ANY size
+ * (letterboxed like the reference does), a raw `.u8` file holding [c][h][w] bytes at network size, or `synthetic:<seed>`.  A -list may
+ * mix JPEG and PPM files of different sizes.  Progressive and CMYK JPEGs, PNG, BMP, GIF and the other formats of the reference's
+ * stb_image are not built and are refused with a message.
  */
 #include <math.h>
 #include <pthread.h>
@@ -89,7 +92,8 @@ static uint8_t *load_bytes_any(const char *path, int netc, int neth, int netw, i
     char magic[3] = {0};
     int iw = 0, ih = 0, maxv = 0;
     if (fscanf(f, "%2s %d %d %d", magic, &iw, &ih, &maxv) != 4 || strcmp(magic, "P6") || maxv != 255 || iw < 1 || ih < 1)
-        error("image must be a binary PPM (P6, maxval 255), a raw .u8 file or synthetic:<seed>; JPEG/PNG decoding is not built");
+        error("image must be a baseline JPEG, a binary PPM (P6, maxval 255), a raw .u8 file or synthetic:<seed>; PNG, BMP, GIF and the "
+              "other formats of stb_image are not built");
     fgetc(f);
     if (netc != 3) error("PPM input needs a 3-channel network");
     uint8_t *rgb = malloc((size_t)3 * iw * ih);
@@ -97,6 +101,32 @@ static uint8_t *load_bytes_any(const char *path, int netc, int neth, int netw, i
     fclose(f);
     *w = iw; *h = ih; *c = 3; *planar = 0;
     return rgb;
+}
+
+/* A file that starts FF D8 is a JPEG, whatever its name. */
+static int is_jpeg_file(const char *path)
+{
+    if (!path || 0 == strncmp(path, "synthetic", 9)) return 0;
+    FILE *f = fopen(path, "rb");
+    if (!f) return 0; /* the loaders report a missing file */
+    unsigned char two[2] = {0, 0};
+    const size_t got = fread(two, 1, 2, f);
+    fclose(f);
+    return got == 2 && two[0] == 0xFF && two[1] == 0xD8;
+}
+
+static uint8_t *read_file(const char *path, size_t *bytes)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "Cannot load image \"%s\"\n", path); exit(0); }
+    fseek(f, 0, SEEK_END);
+    const long n = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    uint8_t *data = malloc(n > 0 ? (size_t)n : 1);
+    if (n < 0 || fread(data, 1, (size_t)n, f) != (size_t)n) file_error((char *)path);
+    fclose(f);
+    *bytes = (size_t)n;
+    return data;
 }
 
 /* load_image_color's contract (ref: src/image.c:1361-1395: bytes / 255., planar) for PPM / raw / synthetic sources */
@@ -207,12 +237,87 @@ static void print_detections(const detect_job *job, int classes, const detection
             }
 }
 
+/* A JPEG slot failed: the library's message names the slot of the call it was given, which held the JPEG slots only */
+static void jpeg_slot_error(char *const *paths, const int *slot_of, int n)
+{
+    const char *why = network_jpeg_last_error();
+    int k = -1;
+    if (sscanf(why, "jpeg slot %d:", &k) == 1 && k >= 0 && k < n) {
+        const char *colon = strchr(why, ':');
+        fprintf(stderr, "slot %d (%s):%s\n", slot_of[k], paths[slot_of[k]], colon ? colon + 1 : why);
+    } else {
+        fprintf(stderr, "%s\n", why);
+    }
+    error("cannot decode a JPEG source");
+}
+
+/* -frames u8 with JPEG files among the sources: every JPEG slot is decoded into a frame on the device (one network_jpeg_decode_gpu call
+ * for all of them; with nothing but JPEGs, network_frames_jpeg_input_gpu does the whole input step), the other sources go up as the
+ * bytes they are, and one network_frames_u8_input_gpu call takes the batch's frames where they lie. */
+static void feed_frames_jpeg(network *net, char *const *paths, int *imw, int *imh)
+{
+    const int B = net->batch;
+    uint8_t **file = calloc((size_t)B, sizeof(uint8_t *)); /* per slot: the JPEG file's bytes, or the decoded PPM / raw frame */
+    size_t *bytes = calloc((size_t)B, sizeof(size_t));
+    int *is_jpg = calloc((size_t)B, sizeof(int)), *slot_of = calloc((size_t)B, sizeof(int));
+    const uint8_t **jdata = calloc((size_t)B, sizeof(uint8_t *));
+    size_t *jbytes = calloc((size_t)B, sizeof(size_t));
+    int nj = 0;
+    for (int b = 0; b < B; ++b) {
+        if (b && paths[b] == paths[b - 1]) { /* the same source again: the same bytes, decoded and uploaded once */
+            file[b] = file[b - 1]; bytes[b] = bytes[b - 1]; is_jpg[b] = is_jpg[b - 1];
+            imw[b] = imw[b - 1]; imh[b] = imh[b - 1];
+        } else if ((is_jpg[b] = is_jpeg_file(paths[b]))) {
+            file[b] = read_file(paths[b], &bytes[b]);
+        } else {
+            file[b] = load_frame_u8(paths[b], net->c, net->h, net->w, &imw[b], &imh[b]);
+            bytes[b] = (size_t)3 * imw[b] * imh[b];
+        }
+        if (is_jpg[b]) { jdata[nj] = file[b]; jbytes[nj] = bytes[b]; slot_of[nj++] = b; }
+    }
+    if (nj == B) {
+        if (network_frames_jpeg_input_gpu(net, jdata, jbytes, imw, imh)) jpeg_slot_error(paths, slot_of, nj);
+    } else {
+        uint8_t **jrgb = calloc((size_t)B, sizeof(uint8_t *));
+        int *jw = calloc((size_t)B, sizeof(int)), *jh = calloc((size_t)B, sizeof(int)), *jp = calloc((size_t)B, sizeof(int));
+        const uint8_t **frame = calloc((size_t)B, sizeof(uint8_t *));
+        int *pitch = calloc((size_t)B, sizeof(int));
+        void **up = calloc((size_t)B, sizeof(void *));
+        if (network_jpeg_decode_gpu(net, jdata, jbytes, nj, jrgb, jw, jh, jp)) jpeg_slot_error(paths, slot_of, nj);
+        for (int k = 0; k < nj; ++k) {
+            const int b = slot_of[k];
+            frame[b] = jrgb[k]; imw[b] = jw[k]; imh[b] = jh[k]; pitch[b] = jp[k];
+        }
+        for (int b = 0; b < B; ++b) {
+            if (is_jpg[b]) continue;
+            pitch[b] = 3 * imw[b];
+            if (b && file[b] == file[b - 1]) { frame[b] = frame[b - 1]; continue; }
+            if (mi355_alloc(&up[b], bytes[b]) || mi355_h2d(up[b], file[b], bytes[b], net->stream)) {
+                fprintf(stderr, "MI355: %s\n", mi355_last_error());
+                error("cannot stage the image on the device");
+            }
+            frame[b] = up[b];
+        }
+        network_frames_u8_input_gpu(net, frame, imw, imh, pitch, MI355_FRAME_RGB, 1);
+        if (mi355_stream_sync(net->stream)) error("sync"); /* the uploaded frames are freed below */
+        for (int b = 0; b < B; ++b) if (up[b]) mi355_free(up[b]);
+        free(jrgb); free(jw); free(jh); free(jp); free(frame); free(pitch); free(up);
+    }
+    /* on the device nothing waits for the uploads: the sources are freed below */
+    if (net->input_on_device && mi355_stream_sync(net->stream)) error("sync");
+    for (int b = 0; b < B; ++b) if (!b || file[b] != file[b - 1]) free(file[b]);
+    free(file); free(bytes); free(is_jpg); free(slot_of); free(jdata); free(jbytes);
+}
+
 /* -frames: the batch's sources, one path per slot, through the entry point of the kind that is set: one call for the whole input step.
  * A slot whose path is the slot's before it (one image in every slot, the free slots of a short last batch) shares its bytes, which
  * then go up once.  imw, imh: the sources' sizes. */
 static void feed_frames(const detect_job *job, network *net, char *const *paths, int *imw, int *imh)
 {
     const int B = net->batch;
+    if (job->frames == FRAMES_U8)
+        for (int b = 0; b < B; ++b)
+            if ((!b || paths[b] != paths[b - 1]) && is_jpeg_file(paths[b])) { feed_frames_jpeg(net, paths, imw, imh); return; }
     uint8_t **raw = calloc((size_t)B, sizeof(uint8_t *));
     const uint8_t **pl[3];
     for (int k = 0; k < 3; ++k) pl[k] = calloc((size_t)B, sizeof(uint8_t *));
@@ -268,6 +373,12 @@ static void test_detector_list(detect_job *job, network *net, char **names, int 
         memcpy(paths[np++], line, n + 1);
     }
     fclose(f);
+    for (int i = 0; i < np; ++i)
+        if (is_jpeg_file(paths[i])) { /* a JPEG source takes the byte path on the device: -frames u8 is implied for the whole list */
+            if (job->frames != FRAMES_NONE && job->frames != FRAMES_U8) error("-list: a JPEG file does not go with raw -frames formats");
+            job->frames = FRAMES_U8;
+            break;
+        }
     if (set_input_quantization_per_image(net, 1)) error("-list: layer 0 cannot quantise every image on its own");
     const int B = net->batch;
     int *imw = calloc((size_t)B, sizeof(int)), *imh = calloc((size_t)B, sizeof(int));
@@ -517,6 +628,10 @@ int main(int argc, char **argv)
         return 0;
     }
     job.datacfg = argv[3]; job.cfgfile = argv[4]; job.weightfile = argv[5]; job.filename = argv[6];
+    if (is_jpeg_file(job.filename)) { /* a JPEG source takes the byte path on the device: -frames u8 is implied */
+        if (job.frames != FRAMES_NONE && job.frames != FRAMES_U8) error("a JPEG image does not go with raw -frames formats");
+        job.frames = FRAMES_U8;
+    }
     if (!gpu_list) {
         test_detector(&job);
         return 0;

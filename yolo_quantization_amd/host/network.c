@@ -16,6 +16,7 @@
 #include <string.h>
 #include <sys/time.h>
 #include "host_internal.h"
+#include "jpeg.h"
 
 /* ------------------------------------------------------------------------------------------------------ utils */
 void error(const char *s) /* ref: src/utils.c:232-237 */
@@ -1207,6 +1208,155 @@ void network_frames_p010_input_gpu(network *net, const uint8_t *const *y, const 
     fr_finish(net);
 }
 
+/* ------------------------------------------------------------------------------------------------- JPEG input
+ * The host decodes the entropy-coded streams (jpeg.c), the device does the rest (jpeg.hip): one staging block -- plane table, image
+ * table, quantiser tables, coefficients, laid out exactly like its device copy -- goes up in one copy, then mi355_jpeg_idct over every
+ * block of the batch and mi355_jpeg_to_rgb over every image.  The frames stay on the device for the 8-bit frame path. */
+static _Thread_local char jpg_err[320];
+const char *network_jpeg_last_error(void) { return jpg_err; }
+
+static int jpg_refuse(const char *why)
+{
+    snprintf(jpg_err, sizeof(jpg_err), "%s", why);
+    return MI355_EINVAL;
+}
+
+static void jpg_free(network *net)
+{
+    if (net->jpg_in_gpu) mi355_free(net->jpg_in_gpu);
+    if (net->jpg_planes_gpu) mi355_free(net->jpg_planes_gpu);
+    if (net->jpg_rgb_gpu) mi355_free(net->jpg_rgb_gpu);
+    free(net->jpg_stage_host);
+    net->jpg_in_gpu = net->jpg_planes_gpu = net->jpg_rgb_gpu = net->jpg_stage_host = NULL;
+    net->jpg_in_bytes = net->jpg_planes_bytes = net->jpg_rgb_bytes = net->jpg_stage_bytes = 0;
+    net->jpg_upload_pending = 0;
+}
+
+/* the device buffer holds at least `need` bytes; *waited: the stream has been waited for (nothing in flight reads what is freed) */
+static void jpg_reserve(network *net, void **buf, size_t *have, size_t need, int *waited, const char *what)
+{
+    if (need <= *have) return;
+    if (!*waited) { net_wait(net); *waited = 1; }
+    if (*buf) mi355_free(*buf);
+    *buf = NULL; *have = 0;
+    check_mi355(mi355_alloc(buf, need), what);
+    *have = need;
+}
+
+int network_jpeg_decode_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int n, uint8_t **rgb_dev, int *w, int *h, int *pitch)
+{
+    if (!net || !data || !bytes || !rgb_dev || !w || !h || !pitch || n < 1 || n > 65535)
+        return jpg_refuse("network_jpeg_decode_gpu: null argument / need 1 <= n <= 65535");
+    /* 1. the host half; a slot that names the bytes of an earlier slot (one image in every slot) shares its decode and its frame */
+    dnq_jpeg *im = calloc((size_t)n, sizeof(dnq_jpeg));
+    int *first = calloc((size_t)n, sizeof(int)), *frame = calloc((size_t)n, sizeof(int));
+    int rc = MI355_OK, nu = 0, nplanes = 0;
+    for (int b = 0; b < n && rc == MI355_OK; ++b) {
+        first[b] = b;
+        for (int k = 0; k < b && first[b] == b; ++k)
+            if (data[k] == data[b] && bytes[k] == bytes[b]) first[b] = k;
+        if (first[b] != b) continue;
+        char why[256];
+        if (!data[b]) {
+            snprintf(jpg_err, sizeof(jpg_err), "jpeg slot %d: null data", b);
+            rc = MI355_EINVAL;
+        } else if (jpeg_decode_host(data[b], bytes[b], &im[b], why, sizeof(why))) {
+            snprintf(jpg_err, sizeof(jpg_err), "jpeg slot %d: %s", b, why);
+            rc = MI355_EINVAL;
+        } else {
+            frame[b] = nu++;
+            nplanes += im[b].ncomp;
+        }
+    }
+    if (rc != MI355_OK) { /* nothing has touched the device */
+        for (int b = 0; b < n; ++b) jpeg_free(&im[b]);
+        free(im); free(first); free(frame);
+        return rc;
+    }
+    /* 2. the layout of the staging block (= of its device copy), of the component planes and of the frames */
+    const size_t off_images = fr_round(sizeof(mi355_jpeg_plane) * (size_t)nplanes);
+    const size_t off_quant = off_images + fr_round(sizeof(mi355_jpeg_image) * (size_t)nu);
+    const size_t off_coef = off_quant + fr_round(128 * (size_t)nplanes);
+    size_t in_bytes = off_coef, planes_bytes = 0, rgb_bytes = 0;
+    for (int b = 0; b < n; ++b) {
+        if (first[b] != b) continue;
+        for (int k = 0; k < im[b].ncomp; ++k) {
+            const size_t blocks = (size_t)im[b].comp[k].blocks_w * im[b].comp[k].blocks_h;
+            in_bytes += fr_round(128 * blocks);
+            planes_bytes += fr_round(64 * blocks);
+        }
+        rgb_bytes += fr_round((size_t)im[b].h * (((size_t)3 * im[b].w + 3) & ~(size_t)3));
+    }
+    check_mi355(mi355_init(net->gpu_index), "mi355_init");
+    if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
+    int waited = 0;
+    jpg_reserve(net, &net->jpg_in_gpu, &net->jpg_in_bytes, in_bytes, &waited, "alloc jpeg coefficients");
+    jpg_reserve(net, &net->jpg_planes_gpu, &net->jpg_planes_bytes, planes_bytes, &waited, "alloc jpeg planes");
+    jpg_reserve(net, &net->jpg_rgb_gpu, &net->jpg_rgb_bytes, rgb_bytes, &waited, "alloc jpeg frames");
+    /* 3. the staging block is rewritten only after the upload that read it last has completed */
+    if (net->jpg_upload_pending && !waited) net_wait(net);
+    net->jpg_upload_pending = 0;
+    if (net->jpg_stage_bytes < in_bytes) {
+        free(net->jpg_stage_host);
+        net->jpg_stage_host = malloc(in_bytes);
+        if (!net->jpg_stage_host) error("network_jpeg_decode_gpu: out of memory");
+        net->jpg_stage_bytes = in_bytes;
+    }
+    uint8_t *stage = net->jpg_stage_host, *in_gpu = net->jpg_in_gpu;
+    memset(stage, 0, off_coef);
+    mi355_jpeg_plane *planes = (mi355_jpeg_plane *)stage;
+    mi355_jpeg_image *images = (mi355_jpeg_image *)(stage + off_images);
+    size_t coef_at = off_coef, plane_at = 0, rgb_at = 0;
+    int pi = 0, blocks_before = 0;
+    for (int b = 0; b < n; ++b) {
+        if (first[b] != b) continue;
+        mi355_jpeg_image *g = &images[frame[b]];
+        g->rgb = (uint8_t *)net->jpg_rgb_gpu + rgb_at;
+        g->w = im[b].w; g->h = im[b].h; g->pitch = (3 * im[b].w + 3) & ~3; g->mode = im[b].mode;
+        rgb_at += fr_round((size_t)g->h * (size_t)g->pitch);
+        for (int k = 0; k < im[b].ncomp; ++k, ++pi) {
+            const dnq_jpeg_comp *c = &im[b].comp[k];
+            const size_t blocks = (size_t)c->blocks_w * c->blocks_h;
+            memcpy(stage + off_quant + 128 * (size_t)pi, c->quant, 128);
+            memcpy(stage + coef_at, c->coef, 128 * blocks);
+            planes[pi].coef = (const int16_t *)(in_gpu + coef_at);
+            planes[pi].quant = (const uint16_t *)(in_gpu + off_quant + 128 * (size_t)pi);
+            planes[pi].out = (uint8_t *)net->jpg_planes_gpu + plane_at;
+            planes[pi].blocks_w = c->blocks_w; planes[pi].blocks_h = c->blocks_h; planes[pi].first_block = blocks_before;
+            g->comp[k].plane = planes[pi].out; g->comp[k].pitch = 8 * c->blocks_w; g->comp[k].rows = c->rows;
+            g->comp[k].hs = c->hs; g->comp[k].vs = c->vs;
+            blocks_before += (int)blocks;
+            coef_at += fr_round(128 * blocks);
+            plane_at += fr_round(64 * blocks);
+        }
+    }
+    for (int b = 0; b < n; ++b) {
+        const mi355_jpeg_image *g = &images[frame[first[b]]];
+        rgb_dev[b] = g->rgb; w[b] = g->w; h[b] = g->h; pitch[b] = g->pitch;
+        jpeg_free(&im[b]);
+    }
+    free(im); free(first); free(frame);
+    /* 4. one copy, two launches */
+    check_mi355(mi355_h2d(in_gpu, stage, in_bytes, net->stream), "upload jpeg coefficients");
+    net->jpg_upload_pending = 1;
+    check_mi355(mi355_jpeg_idct((const mi355_jpeg_plane *)in_gpu, planes, nplanes, net->stream), "mi355_jpeg_idct");
+    check_mi355(mi355_jpeg_to_rgb((const mi355_jpeg_image *)(in_gpu + off_images), images, nu, net->stream), "mi355_jpeg_to_rgb");
+    return MI355_OK;
+}
+
+int network_frames_jpeg_input_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int *w, int *h)
+{
+    if (!net || !w || !h) return jpg_refuse("network_frames_jpeg_input_gpu: null argument");
+    if (net->c != 3) return jpg_refuse("network_frames_jpeg_input_gpu: JPEG images feed 3-channel networks only");
+    const int B = net->batch;
+    uint8_t **rgb = calloc((size_t)B, sizeof(uint8_t *));
+    int *pitch = calloc((size_t)B, sizeof(int));
+    const int rc = network_jpeg_decode_gpu(net, data, bytes, B, rgb, w, h, pitch);
+    if (rc == MI355_OK) network_frames_u8_input_gpu(net, (const uint8_t *const *)rgb, w, h, pitch, MI355_FRAME_RGB, 1);
+    free(rgb); free(pitch);
+    return rc;
+}
+
 void set_batch_network(network *net, int b)
 {
     if (b < 1) error("set_batch_network: batch < 1");
@@ -1918,6 +2068,7 @@ void free_network(network *net)
     pi_free(net);
     od_free(net);
     fr_free(net);
+    jpg_free(net);
     detb_free(net);
     if (net->selfcheck_gpu) mi355_free(net->selfcheck_gpu);
     if (net->stream) mi355_stream_release(net->stream);
