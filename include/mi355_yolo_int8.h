@@ -247,7 +247,8 @@ int mi355_conv_set_tile(int bm, int bn);
  * layers never use conv1x1.hip, 4096 = 32 -> 64 conv + maxpool on conv_small32.hip (round 6: eight waves per workgroup, measured slower; conv_small.hip without the bit), 16384 = 3x3 layers never use conv_ws3.hip, 2^20 = the row-image 3x3 kernel on the 32x32x32 MFMA
  * (conv_rows.hip) instead of the 16x16x64 one (conv_rows16.hip), 2^21 = mi355_conv_pool_forward refuses the 128 / 256-channel
  * layers (the host then runs conv and maxpool separately), 2048 = plain tile walk in the first-layer kernels, 131072 = no raised
- * priority around the MFMA chains of the conv+pool kernels. */
+ * priority around the MFMA chains of the conv+pool kernels, 65536 (2^16) = 1x1 layers with fewer than 32 filters (the detection heads)
+ * keep conv1x1.hip's eight-wave workgroups and per-wave V_DOT4 channel sums instead of the sum-row form sized to its groups. */
 int mi355_debug_flags(int flags);
 /* Which kernel family served the calling thread's most recent mi355_conv_*forward call (tests assert that a shape reaches
  * the kernel it is meant to exercise): 0 none yet, 1 first layer (conv_aux.hip), 2 conv_small.hip (few-channel / 64-channel

@@ -7,7 +7,11 @@
 // between them.  The tile's input cells are DMAed once (global_load_lds) into LDS in the rows kernel's chunk layout
 // [64-channel chunk][16 pixels x 4 pieces x 16 B]; there is no K loop, no barrier besides the one after the load, and
 // the receptive field of a 1x1 tap is the pixel itself: sum(x') is the pixel's channel sum, taken once per tile by all waves together
-// (one filter quad: by the wave from its B fragments).
+// (one filter quad of 32 filters: by the wave from its B fragments).
+// The detection heads (one quad with fewer than 32 filters: 512 -> 30, 256 -> 30) run the ROW form: the quad's unused accumulator row 31
+// gets an A row of ones, so the MFMAs deliver sum(x') with the filters; the epilogue's launch constants are hoisted into two masks and a
+// 32-bit float index; and under the throughput plan a workgroup has as many waves as its tile has groups of 32 pixels (four for the
+// 13 x 13 head, six for the 26 x 26 one) instead of eight, of which six / two had nothing to do.
 // Same mathematics and the same bytes as conv_rows.hip (signed-operand decomposition: see conv_igemm.hip); optional
 // float tail of a quant_stop head, fused yolo activations (byte -> logistic table) and nearest-neighbour upsample store.
 #include "kargs.h"
@@ -18,6 +22,9 @@
                  : "memory", "m0")
 
 constexpr int P1_GMAX = 8;  // groups of 32 pixels per tile
+#ifndef C1_HEAD_GROUPS
+#define C1_HEAD_GROUPS 4     // heads, throughput plan: groups (= waves) per workgroup the launcher aims for (-D through tools/build_variant.sh for A/B runs)
+#endif
 
 #ifdef MI355_ABLATE
 // phase timestamps (100 MHz wall clock) of wave 0 of every workgroup: tools/conv_microbench.py --timeline1 (-DMI355_ABLATE builds only)
@@ -34,9 +41,15 @@ extern "C" int mi355_debug_read_ts1(long long *host)
 // (HIP's second launch-bound is WAVES PER SIMD, not workgroups per CU: with (512, 2) the LEAKY instantiations took 131-138 registers,
 // three waves per SIMD, i.e. ONE 8-wave workgroup per CU -- every multi-round launch (YOLOv3's 1x1 layers) ran its tile loads with
 // nothing beside them.  Four waves per SIMD = two workgroups per CU wherever the stationary weights leave room: C <= 256.)
-template <int KST, int ACT, bool SAT, bool COOP>  // COOP: the per-pixel channel sums are taken once per tile by all waves (more than one filter quad)
-__global__ __launch_bounds__(512, (KST <= 8 ? 4 : 2)) void conv1x1_ws_kernel(const ConvArgs a)
+// COOP: the per-pixel channel sums are taken once per tile by all waves (more than one filter quad)
+// ROW:  one filter quad with fewer than 32 filters (the 30-filter heads).  Accumulator row 31 belongs to no filter: its A row is set to ones
+//       in registers, so the MFMAs leave the pixel's channel sum there for nothing; the epilogue's launch constants (which filters exist, which
+//       yolo entries stay linear) are two 32-bit masks per wave and the float index is one 32-bit base per lane and group.  The 512 -> 30 head
+//       then fits 128 registers: four waves per SIMD, so that the small workgroups the throughput plan launches really share a CU.
+template <int KST, int ACT, bool SAT, bool COOP, bool ROW>
+__global__ __launch_bounds__(512, (KST <= (ROW ? 16 : 8) ? 4 : 2)) void conv1x1_ws_kernel(const ConvArgs a)
 {
+    static_assert(!(COOP && ROW), "the sum row serves a single filter quad");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // filter tiles: layers with more than 256 filters (YOLOv3's 1024 -> 512 necks) split them over a.mtiles workgroups per pixel
     // tile, 256 each (workgroup = tile * mtiles + filter tile: the filter tiles of a pixel tile run next to each other and share
@@ -112,6 +125,17 @@ __global__ __launch_bounds__(512, (KST <= 8 ? 4 : 2)) void conv1x1_ws_kernel(con
 #pragma unroll
     for (int s = 0; s < KST; ++s) wf[s] = *reinterpret_cast<const v4i *>(a.ws + ((size_t)(((f0 >> 5) + wq) * KST + s) * 64 + lane) * 16);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned fmask = 0, lmask = 0;  // ROW: filters of the quad that exist and fit the output cell; those whose yolo entry stays linear (x, y)
+    if constexpr (ROW) {
+        // A row 31 holds filter 31 (ws_row_filter), which a quad of fewer than 32 filters does not have: ones in every k byte of both halves
+        if (lj == 31) {
+#pragma unroll
+            for (int s = 0; s < KST; ++s) wf[s] = v4i{0x01010101, 0x01010101, 0x01010101, 0x01010101};
+        }
+        const int lim = min(a.n, a.out_w);
+        fmask = lim >= 32 ? ~0u : (1u << lim) - 1u;
+        if (a.yolo_out) lmask = (unsigned)__ballot((unsigned)(lane % a.yolo_per) - 2u < 2u);  // lanes 0..31 stand for the filters
+    }
     __syncthreads();
     TS1(2);
     // ---- sum of x' per pixel, ONCE per tile by all waves together (round 5).  Every wave used to sum its B fragments with four V_DOT4 per
@@ -135,7 +159,8 @@ __global__ __launch_bounds__(512, (KST <= 8 ? 4 : 2)) void conv1x1_ws_kernel(con
     }
 
     const char *X = smem;
-    const int chw = 32 * wq;
+    const int chw = ROW ? 0 : 32 * wq;
+    const unsigned myf = fmask >> (16 * kh), myl = lmask >> (16 * kh);  // bit 4 grp + r: the lane's filter 16 kh + 4 grp + r
 #pragma unroll 1
     for (int g = wset; g < G; g += nset) {
         // K-step s: channels 32 s + 16 kh .. + 15 = chunk s / 2, piece 2 (s % 2) + kh
@@ -146,7 +171,11 @@ __global__ __launch_bounds__(512, (KST <= 8 ? 4 : 2)) void conv1x1_ws_kernel(con
             const int4 c4 = *reinterpret_cast<const int4 *>(ldsCB + chw + 16 * kh + 4 * grp);  // accumulator rows 8 grp + 4 kh + r hold filters 16 kh + 4 grp + r (kargs.h ws_row_filter)
             acc[grp * 4 + 0] = c4.x; acc[grp * 4 + 1] = c4.y; acc[grp * 4 + 2] = c4.z; acc[grp * 4 + 3] = c4.w;
         }
-        int sx;
+        int sx, cb31 = 0;
+        if constexpr (ROW) {  // the sum row starts at zero whatever the blob holds behind its last filter
+            cb31 = acc[15];
+            acc[15] = kh ? 0 : cb31;
+        }
         if constexpr (COOP) {
 #pragma unroll
             for (int s = 0; s < KST; ++s) {
@@ -155,6 +184,18 @@ __global__ __launch_bounds__(512, (KST <= 8 ? 4 : 2)) void conv1x1_ws_kernel(con
                 if ((s & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // bound the number of B fragments in flight (registers)
             }
             sx = ldsSX[g * 32 + lj];
+        } else if constexpr (ROW) {
+#pragma unroll
+            for (int s = 0; s < KST; ++s) {
+                const v4i bf = *reinterpret_cast<const v4i *>(X + base + (s >> 1) * qb + (s & 1) * 512);
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(wf[s], bf, acc, 0, 0, 0);
+                if ((s & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+            }
+            // row 31 = acc[15] of lanes 32..63 (kh = 1), already summed over both k halves; v_permlane32_swap hands lanes 0..31 their pixel's
+            // copy.  The filter-31 slot then gets back what it held before: its seed (the A row was zeros), so the pad byte is stored as ever
+            const int t = acc[15];
+            sx = (int)__builtin_amdgcn_permlane32_swap(t, t, false, false)[1];
+            acc[15] = kh ? cb31 : t;
         } else {
             int sxr = 0;
 #pragma unroll
@@ -175,6 +216,7 @@ __global__ __launch_bounds__(512, (KST <= 8 ? 4 : 2)) void conv1x1_ws_kernel(con
         const bool valid = ocell >= 0;
         const int b = ldsImg[g * 32 + lj], rem = ldsRem[g * 32 + lj];
         const int up = a.up;
+        const unsigned fbase = ROW ? ((unsigned)b * (unsigned)a.n + 16u * kh) * (unsigned)hw + (unsigned)rem : 0u;  // float index of filter 16 kh (the launcher checks 32 bits)
         uint32_t pk[4];  // the lane's sixteen consecutive filters 16 kh .. + 15 of its quad, stored together
         // a group's constants are read while the group before it is requantised (conv_small.hip has the measurement: read where they are used,
         // every group waits for its LDS round trips with one other wave on the SIMD to cover them)
@@ -238,7 +280,19 @@ __global__ __launch_bounds__(512, (KST <= 8 ? 4 : 2)) void conv1x1_ws_kernel(con
                             *reinterpret_cast<uint4 *>(a.y + (size_t)(ocell + uy * rowc + ux) * a.out_cs + co) = packed;
                 }
             }
-            if (valid && f0 + ch0 < a.out_w) {
+            if constexpr (ROW) {
+                if (valid && (a.y_f32 || a.yolo_out)) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if ((myf >> (4 * grp + r)) & 1) {
+                            const int u8 = v[r][0] & 0xFF;
+                            const float f = (float)(u8 - a.zp_act) * a.s_act;
+                            const unsigned ridx = fbase + (unsigned)((4 * grp + r) * hw);
+                            if (a.y_f32) a.y_f32[ridx] = f;
+                            if (a.yolo_out) a.yolo_out[ridx] = ((myl >> (4 * grp + r)) & 1) ? f : ldsYL[u8];
+                        }
+                }
+            } else if (valid && f0 + ch0 < a.out_w) {
                 if (a.y_f32 || a.yolo_out) {  // quant_stop tail (ref :752-760) and, fused, the yolo layer's activations (y_f32 may be
                                               // null then: the head's own float tensor is an intermediate nobody reads)
 #pragma unroll
@@ -262,12 +316,20 @@ __global__ __launch_bounds__(512, (KST <= 8 ? 4 : 2)) void conv1x1_ws_kernel(con
     TS1(3);
 }
 
+// One filter quad with a spare accumulator row (n < 32: the detection heads) runs the ROW kernel.  mi355_debug_flags bit 16 keeps such a launch
+// on the kernel and the geometry of before (A/B runs; the tests cross-check the bytes); the float index of the ROW epilogue is 32-bit
+static bool c1_sum_row(const ConvArgs &a)
+{
+    return a.n < 32 && !(mi355_debug_flags_get() & (1 << 16)) && (size_t)a.total_n * (size_t)a.n < ((size_t)1 << 31);
+}
+
 template <int KST, int ACT, bool SAT>
 static int c1_launch_kern(ConvArgs &a, hipStream_t st, int grid, int threads, size_t lds)
 {
     const int n32 = (a.n + 31) & ~31;
-    if (n32 > 32) return launch_big_lds<conv1x1_ws_kernel<KST, ACT, SAT, true>>(grid, threads, lds, st, a);
-    return launch_big_lds<conv1x1_ws_kernel<KST, ACT, SAT, false>>(grid, threads, lds, st, a);
+    if (n32 > 32) return launch_big_lds<conv1x1_ws_kernel<KST, ACT, SAT, true, false>>(grid, threads, lds, st, a);
+    if (c1_sum_row(a)) return launch_big_lds<conv1x1_ws_kernel<KST, ACT, SAT, false, true>>(grid, threads, lds, st, a);
+    return launch_big_lds<conv1x1_ws_kernel<KST, ACT, SAT, false, false>>(grid, threads, lds, st, a);
 }
 
 template <int KST, int ACT>
@@ -322,6 +384,12 @@ int conv1x1_ws_launch(ConvArgs &a, hipStream_t st)
         const long abytes = (long)(n32 < 256 ? n32 : 256) * c;
         while (abytes > 2L * tp * c && (long)(c / 64) * 2 * ((tp + 32) / 32) * 1024 <= 128 * 1024) tp += 32;
     }
+    // ... and the heads (one quad, the ROW kernel): a workgroup has as many waves as its tile has groups (below), so a short tile means many
+    // workgroups of one or two waves, each with its own parameter and logistic tables, DMA bookkeeping and barrier.  C1_HEAD_GROUPS groups per
+    // tile where the launch has that many pixels and two such tiles still share a CU's LDS (DESIGN 4.9 has the measurement that chose it)
+    const bool head = c1_sum_row(a) && a.plan == MI355_PLAN_THROUGHPUT && !(mi355_debug_flags_get() & (1 << 29));
+    if (head)
+        while (tp < 32 * C1_HEAD_GROUPS && tp < total && (long)(c / 64) * 2 * ((tp + 32) / 32) * 1024 <= 64 * 1024) tp += 32;
     const int ntiles = (int)((total + tp - 1) / tp);
     const int G = (tp + 31) / 32;
     a.sm_tp = tp;
@@ -335,7 +403,10 @@ int conv1x1_ws_launch(ConvArgs &a, hipStream_t st)
     if (mtiles > 1 && (a.y_f32 || a.yolo_out || a.up != 1)) return MI355_EINVAL;  // (heads / fused upsample: single filter tile only)
     a.mtiles = mtiles;
     const int nq = nfw / 32;
-    const int sets = 8 / nq > 0 ? 8 / nq : 1;  // at most 8 waves per workgroup
+    int sets = 8 / nq > 0 ? 8 / nq : 1;  // at most 8 waves per workgroup
+    // heads under the throughput plan: no wave without a group (of the 512 -> 30 head's eight waves six loaded their A fragments, helped
+    // with the tables, sat in the barrier and left), and the groups dealt evenly: G = 9 runs five waves (2 2 2 2 1), not eight (2 1 1 ..)
+    if (head) sets = (G + (G + 7) / 8 - 1) / ((G + 7) / 8);
     const int threads = sets * nq * 64;
     switch (c) {
     case 64: return c1_launch_act<2>(a, st, ntiles * mtiles, threads, lds);
