@@ -207,6 +207,15 @@ struct network {
     void *jpg_rgb_gpu;          /* the RGB frames of the last call */
     size_t jpg_rgb_bytes;
     int jpg_upload_pending;     /* an upload from the staging block may be in flight: wait before rewriting it */
+    /* set_jpeg_entropy_on_device: the staging block then holds plane table | image table | quantiser tables | segment table | Huffman
+     * tables | unstuffed scan bytes, and the coefficients exist on the device only */
+    int jpg_entropy_on_device;
+    int jpg_subseq_bits;        /* bits a lane decodes per round (mi355_jpeg_entropy); 0: the default, 1024 */
+    void *jpg_coef_gpu;         /* the coefficient planes mi355_jpeg_entropy fills */
+    size_t jpg_coef_bytes;
+    void *jpg_status_gpu;       /* one status word per segment of the last call */
+    int *jpg_status_host;       /* their host copy */
+    size_t jpg_status_bytes;
     /* Batched box decode (network_yolo_detections_batch_gpu): lazily allocated, grown when needed, freed with the network and on
      * re-batch.  A replica owns its own. */
     int *detb_ints_gpu, *detb_ints_host; /* [2][batch] source sizes | counts [batch][nheads] | offsets [batch + 1] */
@@ -331,6 +340,22 @@ int network_jpeg_decode_gpu(network *net, const uint8_t *const *data, const size
                             int *pitch);
 int network_frames_jpeg_input_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int *w, int *h);
 const char *network_jpeg_last_error(void);
+/* Entropy decoding on the device, opt-in (off: every call above does what it always did).  On: network_jpeg_decode_gpu only FINDS the
+ * scans on the host (yolo_quantization_amd/host/jpeg_scan.h: the same headers and the same refusals, which still launch nothing) and
+ * uploads their unstuffed bytes and Huffman tables instead of coefficients; mi355_jpeg_entropy decodes every restart interval of every
+ * scan of the batch in one launch into planes zeroed on the device, and mi355_jpeg_idct / mi355_jpeg_to_rgb follow as before.  For a
+ * file the host decoder accepts and decodes in full the coefficients, and so the frames, are the host path's, bit for bit.  The call
+ * reads the segments' status words back and WAITS for them once (it shows in network_host_waits(), also with
+ * set_input_quantization_on_device, whose input step is otherwise wait-free): a symbol that decodes to nothing returns MI355_EINVAL
+ * with "jpeg slot 2: bad huffman code (device)" (or "bad DC category", "coefficient index past the end of the block"), the frames
+ * are not produced and network_frames_jpeg_input_gpu does not go on.  What the host decoder makes of truncated or corrupt data is
+ * not reproduced: such a file gives a status or some image, never an access outside the buffers.  A replica made afterwards inherits
+ * the mode.  set_jpeg_entropy_subseq_bits: the bits a lane decodes per round, a multiple of 32 in 32 .. 8192 (default 1024). */
+void set_jpeg_entropy_on_device(network *net, int on);
+void set_jpeg_entropy_subseq_bits(network *net, int bits);
+struct dnq_jpeg_scan_list;
+int jpeg_scan_host(const uint8_t *data, size_t bytes, dnq_jpeg *out, struct dnq_jpeg_scan_list *scans, char *err, size_t errlen);
+void jpeg_scan_free(struct dnq_jpeg_scan_list *scans);
 /* Per-image input quantisation, opt-in (off: image 0 defines the scale of the whole batch, as before).  On: every image of a batch is
  * quantised with its own min / max, scale and zero point, and layer 0 runs with that image's constants (mi355_conv_forward_per_image):
  * slot b of every layer equals the batch-1 run on image b.  The quantisers above honour it.  Returns 0, or MI355_EINVAL with a message

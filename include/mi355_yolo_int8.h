@@ -563,6 +563,51 @@ typedef struct mi355_jpeg_image {     /* 96 bytes */
 } mi355_jpeg_image;
 int mi355_jpeg_idct(const mi355_jpeg_plane *table_dev, const mi355_jpeg_plane *table_host, int nplanes, void *stream);
 int mi355_jpeg_to_rgb(const mi355_jpeg_image *table_dev, const mi355_jpeg_image *table_host, int B, void *stream);
+/* Entropy decoding of baseline JPEG scans on the device: the step in front of mi355_jpeg_idct.  The host finds the scans and copies
+ * their bytes out unstuffed (yolo_quantization_amd/host/jpeg_scan.h); a SEGMENT is one restart interval of a scan, or the whole scan
+ * where there is none, and decodes on its own: the DC predictions start at zero.  mi355_jpeg_entropy is one launch for every segment
+ * of a batch, one 256-thread workgroup per segment with the segment's Huffman tables in LDS.  The segment's bits are cut into
+ * subsequences of subseq_bits bits (a multiple of 32 in 32..8192) that the lanes decode speculatively and re-decode until every
+ * lane's entry state (bit position, block slot inside the unit, zigzag index) is its predecessor's exit state; then every lane stores
+ * the non-zero coefficients of its blocks at coef[c][block * 64 + natural position].  THE PLANES MUST BE ZERO BEFORE THE LAUNCH.
+ *
+ * A unit is what the scan interleaves: bh[c] x bv[c] blocks of each of its ncomp components in turn, unit u at column u % units_x and
+ * row u / units_x of the unit grid; block (x, y) of component c of that unit is block (ux * bh[c] + x, uy * bv[c] + y) of a plane
+ * blocks_w[c] blocks wide.  A one-component scan has bh = bv = 1 and the grid of the component's real size.  The segment holds units
+ * first_unit .. first_unit + nunits - 1 and nothing is stored for a block beyond them.  `bits`: nbytes bytes of unstuffed data, 4-byte
+ * aligned, followed by zero bytes up to at least ((nbytes + 3) & ~3) + 8.  huff[dc[c]], huff[ac[c]]: the tables of component c.
+ * status_dev[s]: 0, or the MI355_JPEG_E* of the first symbol of segment s that decodes to nothing (what was stored before it stays).
+ *
+ * table_host mirrors table_dev and is validated before anything is launched (null or misaligned pointers, ncomp outside 1..3, bh / bv
+ * outside 1..4, a unit grid larger than a plane, units outside the grid, a table index outside 0..nhuff - 1, nbytes above 2^28,
+ * subseq_bits): MI355_EINVAL with a message that starts "jpeg_entropy:", nothing is launched.  What the tables at `huff` hold cannot
+ * be checked from the host: they decide what is decoded, never where it is stored, and every loop is bounded by the bits of the
+ * segment.  New structs and a new call: MI355_ABI_VERSION is unchanged. */
+#define MI355_JPEG_EHUFF 1            /* no code of the table matches */
+#define MI355_JPEG_EDC   2            /* DC category above 15 */
+#define MI355_JPEG_EINDEX 3           /* coefficient index past 63 */
+typedef struct mi355_jpeg_huff {      /* 976 bytes: one Huffman table, canonical codes (T.81 C.2) */
+    uint16_t look[256];               /* by the next 8 bits: (length << 8) | symbol of a code of <= 8 bits, 0: a longer code */
+    int32_t maxcode[17], mincode[17], first[17]; /* per code length 1..16: largest code + 1, smallest code, index of its first symbol */
+    int32_t nvalues;
+    uint8_t values[256];
+} mi355_jpeg_huff;
+typedef struct mi355_jpeg_segment {   /* 144 bytes */
+    const uint32_t *bits;             /* DEVICE */
+    const mi355_jpeg_huff *huff;      /* DEVICE: [nhuff] */
+    int16_t *coef[3];                 /* DEVICE: the plane of scan component c, [blocks_h[c] * blocks_w[c]][64] */
+    uint32_t nbytes;
+    int ncomp;
+    int bh[3], bv[3];
+    int blocks_w[3], blocks_h[3];
+    int dc[3], ac[3];
+    int units_x, units_y;
+    int first_unit, nunits;
+    int nhuff;
+    int reserved;                     /* zero */
+} mi355_jpeg_segment;
+int mi355_jpeg_entropy(const mi355_jpeg_segment *table_dev, const mi355_jpeg_segment *table_host, int nsegments, int subseq_bits,
+                       int *status_dev, void *stream);
 /* *sum_dev += an order-independent 64-bit checksum of `dwords` 32-bit words at buf (device pointers; zero *sum_dev first).  The
  * host's determinism self-check compares it between passes over the same input (network_selfcheck, darknet_q.h). */
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream);

@@ -28,10 +28,14 @@ on-device network's input, scales and zero points are compared with its synchron
 timed steps.
 
 --jpeg times the JPEG input path instead: batch 64 of 640 x 480 4:2:0 baseline files (smooth pictures with noise, written with Pillow at
-quality 85 before the clock starts), per scale mode two variants alternating within a repeat:
+quality 85 before the clock starts), per scale mode three variants alternating within a repeat:
   jpeg    network_frames_jpeg_input_gpu: host entropy decode of the batch, one upload of coefficients and tables, mi355_jpeg_idct,
           mi355_jpeg_to_rgb, then the u8 step on the frames where they lie
   u8      network_frames_u8_input_gpu on the decoded RGB frames in host memory (what a caller with its own JPEG decoder would feed)
+  jpeg_device  the same call with set_jpeg_entropy_on_device: host scan + unstuff, one upload of bytes and tables, mi355_jpeg_entropy,
+          one wait for its status words, then as above (alternating with `jpeg` in one process; its input, scales and zero points are
+          compared with the jpeg network's first).  `stages_jpeg_device`: host_scan_ms, upload_ms / upload_bytes, entropy_ms per
+          subseq_bits between device events, and the settle steps of the slowest round (host emulation of the first 8 files)
 and, once, the stages of the jpeg variant on their own through the same calls: `host_entropy_ms` (jpeg_decode_host over the batch, host
 clock, one thread), `upload_ms`, `idct_ms`, `to_rgb_ms` (HIP events around one copy of all coefficients and tables and around each
 launch; medians of `iters`).  Before timing, the jpeg network's uint8 input, scales and zero points are compared with the u8 network's.
@@ -270,21 +274,73 @@ def jpeg_stages(files, ev, iters):
     return res, frames
 
 
+SUBSEQ_BITS = (128, 256, 512, 1024, 2048, 4096, 8192)
+
+
+def entropy_stages(files, ev, iters, steps_files=8):
+    """the stages of the jpeg_device variant on their own, on the default stream: host scan + unstuff, one upload of the unstuffed
+    bytes and tables, mi355_jpeg_entropy at every SUBSEQ_BITS; and, from the host emulation, the settle steps of the slowest round"""
+    S, H = binding.shim(), binding.host()
+    scan_ms = []
+    for _ in range(max(3, iters // 4)):
+        t0 = time.perf_counter()
+        for f in files:
+            j, sl = binding.DnqJpeg(), binding.DnqJpegScanList()
+            if H.jpeg_scan_host(f, len(f), C.byref(j), C.byref(sl), None, 0) != 0:
+                sys.exit("a generated file was refused")
+            H.jpeg_scan_free(C.byref(sl))
+        scan_ms.append((time.perf_counter() - t0) * 1e3)
+    job = binding.JpegEntropyJob(files)
+    want = [binding.jpeg_coefficients(f) for f in files]
+    planes, status, _ = job.run(1024)
+    exact = all(not any(st) for st in status) and all(np.array_equal(a, c["coef"]) for per, d in zip(planes, want) for a, c in zip(per, d["components"]))
+    stage = np.zeros(job.stream_bytes + job.huff_bytes + C.sizeof(job.table), np.uint8)
+    dev = binding.DevBuf(stage.nbytes)
+    res = {"host_scan_ms": round(float(np.median(scan_ms)), 4), "upload_bytes": int(stage.nbytes), "stream_bytes": job.stream_bytes,
+           "segments": job.nseg, "coefficients_identical_to_jpeg_decode_host": bool(exact), "entropy_ms": {}}
+
+    def timed_call(call, name):
+        ms = []
+        for _ in range(iters + 2):
+            binding.check(S.mi355_stream_sync(None), "sync")
+            binding.check(S.mi355_event_record(ev.a, None), "record")
+            binding.check(call(), name)
+            binding.check(S.mi355_event_record(ev.b, None), "record")
+            binding.check(S.mi355_stream_sync(None), "sync")
+            ms.append(ev.ms())
+        return round(float(np.median(ms[2:])), 4)
+
+    res["upload_ms"] = timed_call(lambda: S.mi355_h2d(dev.ptr, stage.ctypes.data, stage.nbytes, None), "upload")
+    for bits in SUBSEQ_BITS:
+        res["entropy_ms"][str(bits)] = timed_call(lambda: job.launch(bits), "mi355_jpeg_entropy")
+    job.free()
+    dev.free()
+    emu = binding.JpegEntropyJob(files[:steps_files], emulate=True)
+    res["settle_steps_of_the_slowest_round"] = {"files": min(steps_files, len(files))}
+    for bits in SUBSEQ_BITS:
+        steps = [s for per in emu.run(bits)[2] for s in per]
+        res["settle_steps_of_the_slowest_round"][str(bits)] = {"max": int(max(steps)), "median": float(np.median(steps))}
+    return res
+
+
 def jpeg_main(a, wts, ev):
     sw, sh = (int(v) for v in a.src.split("x"))
     files = make_jpegs(a.batch, sw, sh)
     res = {}
     res["stages"], frames = jpeg_stages(files, ev, a.iters)
+    res["stages_jpeg_device"] = entropy_stages(files, ev, a.iters)
     for mode in ("shared", "per_image"):
-        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("jpeg", "u8")}
+        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("jpeg", "jpeg_device", "u8")}
         for n in nets.values():
             n.set_input_per_image(mode == "per_image")
-        var = {"jpeg": JpegVariant(nets["jpeg"], files), "u8": FramesVariant(nets["u8"], frames)}
+        nets["jpeg_device"].set_jpeg_entropy_on_device(True, subseq_bits=a.subseq_bits)
+        var = {"jpeg": JpegVariant(nets["jpeg"], files), "jpeg_device": JpegVariant(nets["jpeg_device"], files), "u8": FramesVariant(nets["u8"], frames)}
         for _ in range(a.warmup):
             for v in var.values():
                 v.step()
         out = {k: {"device_ms": [], "wall_ms": [], "call_ms": []} for k in var}
         same = same_input(nets["jpeg"], nets["u8"])
+        out["jpeg_device_identical_to_jpeg"] = same_input(nets["jpeg_device"], nets["jpeg"])
         for _ in range(a.repeats):
             for k, v in var.items():  # alternating
                 for name, x in zip(("device_ms", "wall_ms", "call_ms"), timed(v, ev, a.iters)):
@@ -302,6 +358,7 @@ def jpeg_main(a, wts, ev):
     except (OSError, StopIteration):
         pass
     res["config"] = {"cfg": "yolov3-tiny_quant.cfg", "batch": a.batch, "src": a.src, "sampling": "4:2:0", "quality": 85, "iters": a.iters,
+                     "subseq_bits": a.subseq_bits,
                      "warmup": a.warmup, "repeats": a.repeats, "host_cpu": cpu,
                      "values": "per repeat the median of `iters` steps: device_ms between HIP events around the step, wall_ms host clock to the "
                                "end of a stream synchronise after it, call_ms host clock inside the call; `median` over the repeats; stages: "
@@ -349,6 +406,7 @@ def main():
     ap.add_argument("--src", default="640x480")
     ap.add_argument("--on-device", action="store_true", help="compare the synchronous step with the on-device one instead (see the module text)")
     ap.add_argument("--jpeg", action="store_true", help="time the JPEG input path beside the u8 path on the decoded frames instead (see the module text)")
+    ap.add_argument("--subseq-bits", type=int, default=1024, help="--jpeg: bits a lane decodes per round in the jpeg_device variant")
     a = ap.parse_args()
     binding.init(0)  # raises without a gfx950: nothing is timed on a CPU
     wts = "/tmp/input_path_bench.weights"

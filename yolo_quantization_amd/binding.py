@@ -120,7 +120,35 @@ class DnqJpeg(C.Structure):
                 ("comp", DnqJpegComp * 3)]
 
 
+class JpegHuff(C.Structure):
+    """mi355_jpeg_huff: one Huffman table as mi355_jpeg_entropy reads it."""
+    _fields_ = [("look", C.c_uint16 * 256), ("maxcode", C.c_int32 * 17), ("mincode", C.c_int32 * 17), ("first", C.c_int32 * 17),
+                ("nvalues", C.c_int32), ("values", C.c_uint8 * 256)]
+
+
+class JpegSegment(C.Structure):
+    """mi355_jpeg_segment: one restart interval (or whole scan) of mi355_jpeg_entropy's table."""
+    _fields_ = [("bits", C.c_void_p), ("huff", C.c_void_p), ("coef", C.c_void_p * 3), ("nbytes", C.c_uint32), ("ncomp", C.c_int),
+                ("bh", C.c_int * 3), ("bv", C.c_int * 3), ("blocks_w", C.c_int * 3), ("blocks_h", C.c_int * 3), ("dc", C.c_int * 3),
+                ("ac", C.c_int * 3), ("units_x", C.c_int), ("units_y", C.c_int), ("first_unit", C.c_int), ("nunits", C.c_int),
+                ("nhuff", C.c_int), ("reserved", C.c_int)]
+
+
+class DnqJpegScanSeg(C.Structure):
+    """dnq_jpeg_scan_seg (yolo_quantization_amd/host/jpeg_scan.h)."""
+    _fields_ = [("ncomp", C.c_int), ("comp", C.c_int * 3), ("bh", C.c_int * 3), ("bv", C.c_int * 3), ("dc", C.c_int * 3), ("ac", C.c_int * 3),
+                ("units_x", C.c_int), ("units_y", C.c_int), ("first_unit", C.c_int), ("nunits", C.c_int), ("scan", C.c_int),
+                ("nbytes", C.c_uint32), ("offset", C.c_size_t)]
+
+
+class DnqJpegScanList(C.Structure):
+    """dnq_jpeg_scan_list: what jpeg_scan_host returns beside the headers."""
+    _fields_ = [("nsegs", C.c_int), ("nhuff", C.c_int), ("segs", C.POINTER(DnqJpegScanSeg)), ("huff", C.POINTER(JpegHuff)),
+                ("bytes", C.POINTER(C.c_uint8)), ("nbytes", C.c_size_t), ("cap_segs", C.c_int), ("cap_huff", C.c_int), ("cap_bytes", C.c_size_t)]
+
+
 JPEG_MODES = ("ycbcr", "rgb", "grey")
+JPEG_ENTROPY_ERRORS = {1: "bad huffman code", 2: "bad DC category", 3: "coefficient index past the end of the block"}
 
 
 def shim():
@@ -195,6 +223,8 @@ def shim():
         if hasattr(L, "mi355_jpeg_idct"):  # MI355_LIB_DIR may name an older build of the libraries (A/B runs): calling them there raises
             L.mi355_jpeg_idct.argtypes = [vp, C.POINTER(JpegPlane), ci, vp]
             L.mi355_jpeg_to_rgb.argtypes = [vp, C.POINTER(JpegImage), ci, vp]
+        if hasattr(L, "mi355_jpeg_entropy"):
+            L.mi355_jpeg_entropy.argtypes = [vp, C.POINTER(JpegSegment), ci, ci, vp, vp]
         L.mi355_frames_u8_letterbox_minmax.argtypes = [vp, C.POINTER(FrameU8), ci, ci, ci, vp, vp]
         L.mi355_frames_u8_letterbox_quantize.argtypes = [vp, C.POINTER(FrameU8), ci, ci, ci, vp, vp, vp, vp]
         L.mi355_frames_yuv_letterbox_minmax.argtypes = [vp, C.POINTER(FrameYUV), ci, ci, ci, vp, vp]
@@ -455,6 +485,15 @@ def host():
                                                   C.POINTER(ci), C.POINTER(ci)]
             L.network_frames_jpeg_input_gpu.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(ci), C.POINTER(ci)]
             L.network_jpeg_last_error.restype = C.c_char_p
+        if hasattr(L, "jpeg_scan_host"):
+            L.jpeg_scan_host.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(DnqJpeg), C.POINTER(DnqJpegScanList), C.c_char_p, C.c_size_t]
+            L.jpeg_scan_free.argtypes = [C.POINTER(DnqJpegScanList)]
+            L.jpeg_scan_free.restype = None
+            L.jpeg_entropy_emulate_host.argtypes = [C.POINTER(JpegSegment), ci, ci, C.POINTER(ci), C.POINTER(ci)]
+            L.set_jpeg_entropy_on_device.argtypes = [vp, ci]
+            L.set_jpeg_entropy_on_device.restype = None
+            L.set_jpeg_entropy_subseq_bits.argtypes = [vp, ci]
+            L.set_jpeg_entropy_subseq_bits.restype = None
         L.quantization_prep_host.argtypes = [vp, C.c_float, C.c_uint8]
         L.forward_network_gpu.argtypes = [vp]
         L.network_predict.restype = vp
@@ -627,6 +666,133 @@ def jpeg_coefficients(data):
         return d
     finally:
         host().jpeg_free(C.byref(j))
+
+
+def jpeg_scan(data):
+    """jpeg_scan_host on a JPEG (bytes or a path): jpeg_coefficients' dict without "coef" (the same headers, "quant" included), plus
+    "segments", one dict per restart interval of every scan -- "ncomp", "comp", "bh", "bv", "dc", "ac" (lists in scan order), the unit
+    grid, "first_unit", "nunits", "scan" and "data", the segment's unstuffed bytes -- and "huff", the JpegHuff tables "dc" / "ac" index.
+    Host only."""
+    data = _jpeg_bytes(data)
+    j, sl = DnqJpeg(), DnqJpegScanList()
+    err = C.create_string_buffer(256)
+    if host().jpeg_scan_host(data, len(data), C.byref(j), C.byref(sl), err, len(err)) != 0:
+        raise JpegError(err.value.decode())
+    try:
+        d = _jpeg_dict(j)
+        for i, c in enumerate(d["components"]):
+            c["quant"] = np.array(j.comp[i].quant, np.uint16)
+        raw = bytes(np.ctypeslib.as_array(sl.bytes, shape=(sl.nbytes,))) if sl.nbytes else b""
+        d["segments"] = []
+        for i in range(sl.nsegs):
+            g = sl.segs[i]
+            assert g.offset % 4 == 0 and not any(raw[g.offset + g.nbytes:g.offset + ((g.nbytes + 3) & ~3) + 8])
+            seg = {k: list(getattr(g, k))[:g.ncomp] for k in ("comp", "bh", "bv", "dc", "ac")}
+            seg.update({k: getattr(g, k) for k in ("ncomp", "units_x", "units_y", "first_unit", "nunits", "scan")})
+            seg["data"] = raw[g.offset:g.offset + g.nbytes]
+            d["segments"].append(seg)
+        d["huff"] = [JpegHuff.from_buffer_copy(sl.huff[i]) for i in range(sl.nhuff)]
+        return d
+    finally:
+        host().jpeg_scan_free(C.byref(sl))
+
+
+class JpegEntropyJob:
+    """Every segment of every item (a JPEG, or a jpeg_scan dict) in one mi355_jpeg_segment table: device buffers and device pointers,
+    or, with emulate, numpy arrays and host pointers for jpeg_entropy_emulate_host.  run() is one call for all of them."""
+
+    def __init__(self, items, emulate=False):
+        self.emulate = emulate
+        self.scans = scans = [it if isinstance(it, dict) else jpeg_scan(it) for it in items]
+        self.nseg = nseg = sum(len(d["segments"]) for d in scans)
+        self.table = table = (JpegSegment * max(nseg, 1))()
+        huffs = [h for d in scans for h in d["huff"]]
+        huff_np = np.frombuffer(b"".join(bytes(h) for h in huffs), np.uint8).copy() if huffs else np.zeros(C.sizeof(JpegHuff), np.uint8)
+        chunks = [g["data"] + bytes(((len(g["data"]) + 3) & ~3) + 8 - len(g["data"])) for d in scans for g in d["segments"]]
+        bits_np = np.frombuffer(b"".join(chunks), np.uint8).copy() if chunks else np.zeros(8, np.uint8)
+        self.stream_bytes, self.huff_bytes = int(bits_np.nbytes), int(huff_np.nbytes)
+        self.planes = [[np.zeros((c["blocks_h"], c["blocks_w"], 64), np.int16) for c in d["components"]] for d in scans]
+        self.keep, self.plane_bufs = [huff_np, bits_np], []
+        if emulate:
+            huff_ptr, bits_ptr = huff_np.ctypes.data, bits_np.ctypes.data
+            plane_ptr = [[a.ctypes.data for a in per] for per in self.planes]
+        else:
+            hb, bb = DevBuf.from_numpy(huff_np), DevBuf.from_numpy(bits_np)
+            self.plane_bufs = [[DevBuf.from_numpy(a.ravel()) for a in per] for per in self.planes]  # zero: only non-zeros are stored
+            self.keep += [hb, bb] + [b for bufs in self.plane_bufs for b in bufs]
+            huff_ptr, bits_ptr = hb.ptr.value, bb.ptr.value
+            plane_ptr = [[b.ptr.value for b in bufs] for bufs in self.plane_bufs]
+        i, at, huff_at = 0, 0, 0
+        for n, d in enumerate(scans):
+            for g in d["segments"]:
+                t = table[i]
+                t.bits, t.huff, t.nbytes, t.ncomp, t.nhuff = bits_ptr + at, huff_ptr, len(g["data"]), g["ncomp"], len(huffs)
+                for c in range(g["ncomp"]):
+                    comp = d["components"][g["comp"][c]]
+                    t.coef[c] = plane_ptr[n][g["comp"][c]]
+                    t.bh[c], t.bv[c], t.blocks_w[c], t.blocks_h[c] = g["bh"][c], g["bv"][c], comp["blocks_w"], comp["blocks_h"]
+                    t.dc[c], t.ac[c] = huff_at + g["dc"][c], huff_at + g["ac"][c]
+                t.units_x, t.units_y, t.first_unit, t.nunits = g["units_x"], g["units_y"], g["first_unit"], g["nunits"]
+                at += ((len(g["data"]) + 3) & ~3) + 8
+                i += 1
+            huff_at += len(d["huff"])
+        self.status, self.steps = (C.c_int * max(nseg, 1))(), (C.c_int * max(nseg, 1))()
+        if not emulate:
+            self.tdev, self.sdev = DevBuf.from_numpy(np.frombuffer(bytes(table), np.uint8)), DevBuf(4 * max(nseg, 1))
+            self.keep += [self.tdev, self.sdev]
+
+    def launch(self, subseq_bits):
+        """mi355_jpeg_entropy on the default stream; the return code"""
+        return shim().mi355_jpeg_entropy(self.tdev.ptr, self.table, self.nseg, subseq_bits, self.sdev.ptr, None)
+
+    def run(self, subseq_bits):
+        """(planes, status per item, settle steps per item | None)"""
+        if self.emulate:
+            if host().jpeg_entropy_emulate_host(self.table, self.nseg, subseq_bits, self.status, self.steps) != 0:
+                raise MI355Error("jpeg_entropy_emulate_host refused its arguments")
+        else:
+            check(self.launch(subseq_bits), "mi355_jpeg_entropy")
+            check(shim().mi355_stream_sync(None), "sync")
+            st = self.sdev.to_numpy(np.int32, max(self.nseg, 1))
+            for k in range(self.nseg):
+                self.status[k] = int(st[k])
+            for per, bufs in zip(self.planes, self.plane_bufs):
+                for a, b in zip(per, bufs):
+                    a[...] = b.to_numpy(np.int16, a.size).reshape(a.shape)
+        out_status, out_steps, i = [], [], 0
+        for d in self.scans:
+            k = len(d["segments"])
+            out_status.append([self.status[i + x] for x in range(k)])
+            out_steps.append([self.steps[i + x] for x in range(k)])
+            i += k
+        return self.planes, out_status, (out_steps if self.emulate else None)
+
+    def free(self):
+        for b in self.keep:
+            if isinstance(b, DevBuf):
+                b.free()
+        self.keep = []
+
+
+def _jpeg_entropy_run(items, subseq_bits, emulate):
+    job = JpegEntropyJob(items, emulate)
+    try:
+        return job.run(subseq_bits)
+    finally:
+        job.free()
+
+
+def jpeg_entropy(items, subseq_bits=1024, emulate=False):
+    """mi355_jpeg_entropy on every segment of every item (JPEG bytes, a path, or a jpeg_scan dict) in ONE launch, or, with emulate,
+    jpeg_entropy_emulate_host (no device).  Returns (coef, status): per item, the int16 [blocks_h][blocks_w][64] planes of its
+    components (jpeg_coefficients' "coef") and the status word of each of its segments."""
+    planes, status, _ = _jpeg_entropy_run(list(items), subseq_bits, emulate)
+    return planes, status
+
+
+def jpeg_entropy_steps(items, subseq_bits=1024):
+    """Per item, per segment: the settle steps of the segment's slowest round (jpeg_entropy_emulate_host; no device)."""
+    return _jpeg_entropy_run(list(items), subseq_bits, True)[2]
 
 
 def jpeg_idct(planes):
@@ -906,6 +1072,13 @@ class Net:
             hs[b], ws[b] = a.shape[:2]
         self.H.network_frames_u8_input_gpu(self.h, ptrs, ws, hs, ps, FRAME_ORDER[order], 0)
         return self._prepared(self._pull_input())
+
+    def set_jpeg_entropy_on_device(self, on=True, subseq_bits=None):
+        """JPEG scans are entropy-decoded on the device (set_jpeg_entropy_on_device): the input the network sees is unchanged; the
+        JPEG calls then wait once, for the segments' status words.  subseq_bits: the bits a lane decodes per round."""
+        self.H.set_jpeg_entropy_on_device(self.h, 1 if on else 0)
+        if subseq_bits is not None:
+            self.H.set_jpeg_entropy_subseq_bits(self.h, int(subseq_bits))
 
     def prepare_from_jpeg(self, items):
         """JPEG input path (network_frames_jpeg_input_gpu): every item (the bytes of a JPEG file, or a path) is entropy-decoded on the

@@ -260,6 +260,9 @@ const char *jpeg_idct_check(const mi355_jpeg_plane *host, int nplanes);
 int jpeg_idct_launch(const mi355_jpeg_plane *table_dev, const mi355_jpeg_plane *table_host, int nplanes, hipStream_t st);
 const char *jpeg_to_rgb_check(const mi355_jpeg_image *host, int B);
 int jpeg_to_rgb_launch(const mi355_jpeg_image *table_dev, const mi355_jpeg_image *table_host, int B, hipStream_t st);
+// jpeg_entropy.hip: Huffman decoding of every segment of a batch, one workgroup each
+const char *jpeg_entropy_check(const mi355_jpeg_segment *host, int nsegments, int subseq_bits);
+int jpeg_entropy_launch(const mi355_jpeg_segment *table_dev, int nsegments, int subseq_bits, int *status_dev, hipStream_t st);
 int yolo_detections_sizes_launch(const float *out, int B, int n, int classes, int h, int w, const float *biases, const int *mask,
                                  int netw, int neth, const int *imw_dev, const int *imh_dev, float thresh, int relative, float *recs,
                                  int max_recs, int *counts, hipStream_t st);

@@ -1168,6 +1168,15 @@ int mi355_jpeg_to_rgb(const mi355_jpeg_image *table_dev, const mi355_jpeg_image 
     return jpeg_to_rgb_launch(table_dev, table_host, B, (hipStream_t)stream);
 }
 
+int mi355_jpeg_entropy(const mi355_jpeg_segment *table_dev, const mi355_jpeg_segment *table_host, int nsegments, int subseq_bits,
+                       int *status_dev, void *stream)
+{
+    if (!table_dev || !status_dev) return einval("jpeg_entropy: null");
+    const char *why = jpeg_entropy_check(table_host, nsegments, subseq_bits);
+    if (why) return einval(why);
+    return jpeg_entropy_launch(table_dev, nsegments, subseq_bits, status_dev, (hipStream_t)stream);
+}
+
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream)
 {
     if (!buf || !sum_dev || dwords < 0) return einval("checksum: null");

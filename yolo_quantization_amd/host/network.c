@@ -17,6 +17,7 @@
 #include <sys/time.h>
 #include "host_internal.h"
 #include "jpeg.h"
+#include "jpeg_scan.h"
 
 /* ------------------------------------------------------------------------------------------------------ utils */
 void error(const char *s) /* ref: src/utils.c:232-237 */
@@ -1226,9 +1227,13 @@ static void jpg_free(network *net)
     if (net->jpg_in_gpu) mi355_free(net->jpg_in_gpu);
     if (net->jpg_planes_gpu) mi355_free(net->jpg_planes_gpu);
     if (net->jpg_rgb_gpu) mi355_free(net->jpg_rgb_gpu);
+    if (net->jpg_coef_gpu) mi355_free(net->jpg_coef_gpu);
+    if (net->jpg_status_gpu) mi355_free(net->jpg_status_gpu);
     free(net->jpg_stage_host);
-    net->jpg_in_gpu = net->jpg_planes_gpu = net->jpg_rgb_gpu = net->jpg_stage_host = NULL;
-    net->jpg_in_bytes = net->jpg_planes_bytes = net->jpg_rgb_bytes = net->jpg_stage_bytes = 0;
+    free(net->jpg_status_host);
+    net->jpg_in_gpu = net->jpg_planes_gpu = net->jpg_rgb_gpu = net->jpg_stage_host = net->jpg_coef_gpu = net->jpg_status_gpu = NULL;
+    net->jpg_status_host = NULL;
+    net->jpg_in_bytes = net->jpg_planes_bytes = net->jpg_rgb_bytes = net->jpg_stage_bytes = net->jpg_coef_bytes = net->jpg_status_bytes = 0;
     net->jpg_upload_pending = 0;
 }
 
@@ -1243,10 +1248,177 @@ static void jpg_reserve(network *net, void **buf, size_t *have, size_t need, int
     *have = need;
 }
 
+void set_jpeg_entropy_on_device(network *net, int on) { net->jpg_entropy_on_device = on != 0; }
+
+void set_jpeg_entropy_subseq_bits(network *net, int bits)
+{
+    if (bits < 32 || bits > 8192 || (bits & 31)) error("set_jpeg_entropy_subseq_bits: a multiple of 32 in 32 .. 8192");
+    net->jpg_subseq_bits = bits;
+}
+
+static const char *jpg_entropy_reason(int code)
+{
+    return code == MI355_JPEG_EHUFF ? "bad huffman code" : code == MI355_JPEG_EDC ? "bad DC category" :
+           code == MI355_JPEG_EINDEX ? "coefficient index past the end of the block" : "unknown status";
+}
+
+/* network_jpeg_decode_gpu with set_jpeg_entropy_on_device: the host only finds the scans (jpeg_scan.c).  One staging block -- plane
+ * table, image table, quantiser tables, segment table, Huffman tables, the unstuffed bytes of every segment -- goes up in one copy;
+ * the coefficient planes are zeroed on the device, mi355_jpeg_entropy fills them, the status words come back (the call's one wait),
+ * and the two launches of the host-decode path follow on the same planes. */
+static int jpg_decode_entropy_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int n, uint8_t **rgb_dev, int *w, int *h, int *pitch)
+{
+    dnq_jpeg *im = calloc((size_t)n, sizeof(dnq_jpeg));
+    dnq_jpeg_scan_list *sl = calloc((size_t)n, sizeof(dnq_jpeg_scan_list));
+    int *first = calloc((size_t)n, sizeof(int)), *frame = calloc((size_t)n, sizeof(int));
+    int rc = MI355_OK, nu = 0, nplanes = 0, nsegs = 0, nhuff = 0;
+    size_t stream_bytes = 0;
+    for (int b = 0; b < n && rc == MI355_OK; ++b) {
+        first[b] = b;
+        for (int k = 0; k < b && first[b] == b; ++k)
+            if (data[k] == data[b] && bytes[k] == bytes[b]) first[b] = k;
+        if (first[b] != b) continue;
+        char why[256];
+        if (!data[b]) {
+            snprintf(jpg_err, sizeof(jpg_err), "jpeg slot %d: null data", b);
+            rc = MI355_EINVAL;
+        } else if (jpeg_scan_host(data[b], bytes[b], &im[b], &sl[b], why, sizeof(why))) {
+            snprintf(jpg_err, sizeof(jpg_err), "jpeg slot %d: %s", b, why);
+            rc = MI355_EINVAL;
+        } else {
+            frame[b] = nu++;
+            nplanes += im[b].ncomp;
+            nsegs += sl[b].nsegs;
+            nhuff += sl[b].nhuff;
+            stream_bytes += sl[b].nbytes;
+        }
+    }
+    if (rc != MI355_OK) { /* nothing has touched the device */
+        for (int b = 0; b < n; ++b) { jpeg_free(&im[b]); jpeg_scan_free(&sl[b]); }
+        free(im); free(sl); free(first); free(frame);
+        return rc;
+    }
+    const size_t off_images = fr_round(sizeof(mi355_jpeg_plane) * (size_t)nplanes);
+    const size_t off_quant = off_images + fr_round(sizeof(mi355_jpeg_image) * (size_t)nu);
+    const size_t off_segs = off_quant + fr_round(128 * (size_t)nplanes);
+    const size_t off_huff = off_segs + fr_round(sizeof(mi355_jpeg_segment) * (size_t)nsegs);
+    const size_t off_bits = off_huff + fr_round(sizeof(mi355_jpeg_huff) * (size_t)nhuff);
+    const size_t in_bytes = off_bits + fr_round(stream_bytes);
+    size_t coef_bytes = 0, planes_bytes = 0, rgb_bytes = 0;
+    for (int b = 0; b < n; ++b) {
+        if (first[b] != b) continue;
+        for (int k = 0; k < im[b].ncomp; ++k) {
+            const size_t blocks = (size_t)im[b].comp[k].blocks_w * im[b].comp[k].blocks_h;
+            coef_bytes += fr_round(128 * blocks);
+            planes_bytes += fr_round(64 * blocks);
+        }
+        rgb_bytes += fr_round((size_t)im[b].h * (((size_t)3 * im[b].w + 3) & ~(size_t)3));
+    }
+    check_mi355(mi355_init(net->gpu_index), "mi355_init");
+    if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
+    int waited = 0;
+    jpg_reserve(net, &net->jpg_in_gpu, &net->jpg_in_bytes, in_bytes, &waited, "alloc jpeg streams");
+    jpg_reserve(net, &net->jpg_coef_gpu, &net->jpg_coef_bytes, coef_bytes, &waited, "alloc jpeg coefficients");
+    jpg_reserve(net, &net->jpg_planes_gpu, &net->jpg_planes_bytes, planes_bytes, &waited, "alloc jpeg planes");
+    jpg_reserve(net, &net->jpg_rgb_gpu, &net->jpg_rgb_bytes, rgb_bytes, &waited, "alloc jpeg frames");
+    if (net->jpg_status_bytes < sizeof(int) * (size_t)nsegs) {
+        free(net->jpg_status_host);
+        net->jpg_status_host = malloc(sizeof(int) * (size_t)nsegs);
+        if (!net->jpg_status_host) error("network_jpeg_decode_gpu: out of memory");
+    }
+    jpg_reserve(net, &net->jpg_status_gpu, &net->jpg_status_bytes, sizeof(int) * (size_t)nsegs, &waited, "alloc jpeg status");
+    if (net->jpg_upload_pending && !waited) net_wait(net);
+    net->jpg_upload_pending = 0;
+    if (net->jpg_stage_bytes < in_bytes) {
+        free(net->jpg_stage_host);
+        net->jpg_stage_host = malloc(in_bytes);
+        if (!net->jpg_stage_host) error("network_jpeg_decode_gpu: out of memory");
+        net->jpg_stage_bytes = in_bytes;
+    }
+    uint8_t *stage = net->jpg_stage_host, *in_gpu = net->jpg_in_gpu, *coef_gpu = net->jpg_coef_gpu;
+    memset(stage, 0, off_huff);
+    mi355_jpeg_plane *planes = (mi355_jpeg_plane *)stage;
+    mi355_jpeg_image *images = (mi355_jpeg_image *)(stage + off_images);
+    mi355_jpeg_segment *segs = (mi355_jpeg_segment *)(stage + off_segs);
+    int *slot_of_seg = calloc((size_t)nsegs, sizeof(int));
+    size_t coef_at = 0, plane_at = 0, rgb_at = 0, bits_at = off_bits;
+    int pi = 0, si = 0, hi = 0, blocks_before = 0;
+    for (int b = 0; b < n; ++b) {
+        if (first[b] != b) continue;
+        mi355_jpeg_image *g = &images[frame[b]];
+        int16_t *coef_of[3] = {NULL, NULL, NULL};
+        g->rgb = (uint8_t *)net->jpg_rgb_gpu + rgb_at;
+        g->w = im[b].w; g->h = im[b].h; g->pitch = (3 * im[b].w + 3) & ~3; g->mode = im[b].mode;
+        rgb_at += fr_round((size_t)g->h * (size_t)g->pitch);
+        for (int k = 0; k < im[b].ncomp; ++k, ++pi) {
+            const dnq_jpeg_comp *c = &im[b].comp[k];
+            const size_t blocks = (size_t)c->blocks_w * c->blocks_h;
+            memcpy(stage + off_quant + 128 * (size_t)pi, c->quant, 128);
+            coef_of[k] = (int16_t *)(coef_gpu + coef_at);
+            planes[pi].coef = coef_of[k];
+            planes[pi].quant = (const uint16_t *)(in_gpu + off_quant + 128 * (size_t)pi);
+            planes[pi].out = (uint8_t *)net->jpg_planes_gpu + plane_at;
+            planes[pi].blocks_w = c->blocks_w; planes[pi].blocks_h = c->blocks_h; planes[pi].first_block = blocks_before;
+            g->comp[k].plane = planes[pi].out; g->comp[k].pitch = 8 * c->blocks_w; g->comp[k].rows = c->rows;
+            g->comp[k].hs = c->hs; g->comp[k].vs = c->vs;
+            blocks_before += (int)blocks;
+            coef_at += fr_round(128 * blocks);
+            plane_at += fr_round(64 * blocks);
+        }
+        memcpy(stage + off_huff + sizeof(mi355_jpeg_huff) * (size_t)hi, sl[b].huff, sizeof(mi355_jpeg_huff) * (size_t)sl[b].nhuff);
+        memcpy(stage + bits_at, sl[b].bytes, sl[b].nbytes);
+        for (int q = 0; q < sl[b].nsegs; ++q, ++si) {
+            const dnq_jpeg_scan_seg *z = &sl[b].segs[q];
+            mi355_jpeg_segment *t = &segs[si];
+            slot_of_seg[si] = b;
+            t->bits = (const uint32_t *)(in_gpu + bits_at + z->offset);
+            t->huff = (const mi355_jpeg_huff *)(in_gpu + off_huff);
+            t->nhuff = nhuff;
+            t->nbytes = z->nbytes;
+            t->ncomp = z->ncomp;
+            for (int c = 0; c < z->ncomp; ++c) {
+                const dnq_jpeg_comp *k = &im[b].comp[z->comp[c]];
+                t->coef[c] = coef_of[z->comp[c]];
+                t->bh[c] = z->bh[c]; t->bv[c] = z->bv[c];
+                t->blocks_w[c] = k->blocks_w; t->blocks_h[c] = k->blocks_h;
+                t->dc[c] = hi + z->dc[c]; t->ac[c] = hi + z->ac[c];
+            }
+            t->units_x = z->units_x; t->units_y = z->units_y; t->first_unit = z->first_unit; t->nunits = z->nunits;
+        }
+        hi += sl[b].nhuff;
+        bits_at += sl[b].nbytes; /* a multiple of 4: every segment is padded to one */
+    }
+    for (int b = 0; b < n; ++b) {
+        const mi355_jpeg_image *g = &images[frame[first[b]]];
+        rgb_dev[b] = g->rgb; w[b] = g->w; h[b] = g->h; pitch[b] = g->pitch;
+        jpeg_free(&im[b]);
+        jpeg_scan_free(&sl[b]);
+    }
+    free(im); free(sl); free(first); free(frame);
+    /* one copy, the entropy decode, the one wait of the call (for its status words), then the two launches of the host-decode path */
+    check_mi355(mi355_h2d(in_gpu, stage, in_bytes, net->stream), "upload jpeg streams");
+    check_mi355(mi355_memset(coef_gpu, 0, coef_bytes, net->stream), "zero jpeg coefficients");
+    check_mi355(mi355_jpeg_entropy((const mi355_jpeg_segment *)(in_gpu + off_segs), segs, nsegs, net->jpg_subseq_bits ? net->jpg_subseq_bits : 1024,
+                                   (int *)net->jpg_status_gpu, net->stream), "mi355_jpeg_entropy");
+    check_mi355(mi355_d2h(net->jpg_status_host, net->jpg_status_gpu, sizeof(int) * (size_t)nsegs, net->stream), "read jpeg status");
+    net_wait(net);
+    for (int q = 0; q < nsegs; ++q)
+        if (net->jpg_status_host[q]) {
+            snprintf(jpg_err, sizeof(jpg_err), "jpeg slot %d: %s (device)", slot_of_seg[q], jpg_entropy_reason(net->jpg_status_host[q]));
+            free(slot_of_seg);
+            return MI355_EINVAL;
+        }
+    free(slot_of_seg);
+    check_mi355(mi355_jpeg_idct((const mi355_jpeg_plane *)in_gpu, planes, nplanes, net->stream), "mi355_jpeg_idct");
+    check_mi355(mi355_jpeg_to_rgb((const mi355_jpeg_image *)(in_gpu + off_images), images, nu, net->stream), "mi355_jpeg_to_rgb");
+    return MI355_OK;
+}
+
 int network_jpeg_decode_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int n, uint8_t **rgb_dev, int *w, int *h, int *pitch)
 {
     if (!net || !data || !bytes || !rgb_dev || !w || !h || !pitch || n < 1 || n > 65535)
         return jpg_refuse("network_jpeg_decode_gpu: null argument / need 1 <= n <= 65535");
+    if (net->jpg_entropy_on_device) return jpg_decode_entropy_gpu(net, data, bytes, n, rgb_dev, w, h, pitch);
     /* 1. the host half; a slot that names the bytes of an earlier slot (one image in every slot) shares its decode and its frame */
     dnq_jpeg *im = calloc((size_t)n, sizeof(dnq_jpeg));
     int *first = calloc((size_t)n, sizeof(int)), *frame = calloc((size_t)n, sizeof(int));
@@ -2000,6 +2172,7 @@ network *network_replica_ex(network *parent, int default_stream)
     net->use_graph = parent->use_graph; net->input_direct_off = parent->input_direct_off;
     net->per_image = parent->per_image; /* its own bank (allocated by its first per-image batch); layer 0's raw weights are the parent's */
     net->input_on_device = parent->input_on_device; /* its own bank, pair and status arrays and copy of the constant table */
+    net->jpg_entropy_on_device = parent->jpg_entropy_on_device; net->jpg_subseq_bits = parent->jpg_subseq_bits;
     net->dump_int32 = 0;
     if (parent->accum_mode == MI355_ACC_REF_F32) error("network_replica: MI355_ACC_REF_F32 reads raw weights, which a replica does not hold");
     net->replica_of = parent;
