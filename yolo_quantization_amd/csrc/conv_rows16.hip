@@ -17,12 +17,17 @@
 // fragments are reloaded during the last two rounds -- 40 fragment registers instead of 60, no register-set rotation.
 //   step:  lgkmcnt(2) | for ni in 0..3: 4 MFMAs (A0..A3, B[ni]); read B[ni]' | lgkmcnt(4) |
 //          for mi in 0..3: MFMA(A[mi], B4), MFMA(A[mi], B5); read A[mi]' | read B4', B5'
+// The sums of x' (DESIGN.md 4.10): where a thread owns one cell of the row image (128 x 128, 64 x 128, 128 x 256 tiles) its running sum
+// stays in a register for the whole K loop; the cell's four pieces are one more counted ds_read_b128 on K-steps 0, 2, 4, 6 of a chunk,
+// behind the step's first MFMAs, reduced one step later, and the S plane is written once in front of the epilogue (COUNTED below).
 // D layout of the instruction: lane l holds rows (= filters) 4 (l / 16) .. + 3 of column (= pixel) l % 16.
 #include "kargs.h"
 #include <type_traits>
 
-#define DBG(bit) (false)
+// timing-ablation switches (tools/conv_microbench.py --ablate: bit 16 = no cell sums, results are then wrong) exist only in builds
+// made with -DMI355_ABLATE; in the product build DBG(x) is the constant 0 and every switch folds away.
 #if defined(MI355_ABLATE)
+#define DBG(bit) ((a.debug & (bit)) != 0)
 // phase timestamps (100 MHz wall clock) of wave 0 of every workgroup: tools/conv_microbench.py --timeline16 (-DMI355_ABLATE builds only)
 __device__ long long g_rows16_ts[6][4096];
 #define TS(k) do { if (threadIdx.x == 0 && blockIdx.x < 4096) g_rows16_ts[k][blockIdx.x] = wall_clock64(); } while (0)
@@ -31,6 +36,7 @@ extern "C" int mi355_debug_read_ts16(long long *host)
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_rows16_ts), sizeof(long long) * 6 * 4096) == hipSuccess ? 0 : -5;
 }
 #else
+#define DBG(bit) (false)
 #define TS(k) do { } while (0)
 #endif
 #define WP_DECL do { } while (0)
@@ -101,6 +107,17 @@ __global__ __launch_bounds__(64 * WMW * WNW, (BM / WMW > 64 ? 1 : 2)) void conv_
     constexpr int NBS = rows16_nb_slots(BN, RS, DW, KS) + NBX;  // B DMA slots per (DMA) wave per chunk
     constexpr int SPS = (NBS + 3) / 4;                  // ... issued per K-step over a chunk's first four steps (3x3 loop)
     static_assert(TM % 16 == 0 && TN % 32 == 0, "wave tile: 16-row tiles, 32-column sub-tiles");
+    // Sums of x' per cell of the row image.  Cell id is owned by thread id % NT in every chunk, so its running sum stays
+    // in a register for the whole K loop and reaches the S plane once, in front of the epilogue.  The launcher refuses a tile whose
+    // rows need more than NBS DMA slots per DMA wave: a workgroup has at most NBS * DW KiB of row image = NBS * DW * 16 cells.
+    constexpr int CPT = (NBS * DW * 16 + NT - 1) / NT;  // cells per thread, at most
+    static_assert(CPT * NT >= NBS * DW * 16 && CPT >= 1 && CPT <= 2, "a chunk's 4 CPT piece reads ride on its K-steps 0..7, one each");
+    // COUNTED: the four 16-byte pieces of a cell are read by this kernel's own counted ds_read_b128, one per K-step, between the MFMAs.
+    // Built where a thread owns one cell.  With two (128 x 192, 64 x 256, 128 x 384) the form compiles to more registers than the
+    // per-chunk cell_sums() call between two drains, which those tiles keep (128 x 384 sits at 256 registers with scratch already).
+    constexpr bool COUNTED = CPT == 1;
+    // step t of a chunk carries piece read cs_slot(t) (cell cs_slot / 4, piece cs_slot % 4), or none (-1); its v_dot4 run in step t + 1
+    constexpr auto cs_slot = [](int t) { return !COUNTED ? -1 : CPT == 2 ? (t >= 0 && t < 8 ? t : -1) : (t >= 0 && t < 8 && !(t & 1) ? t >> 1 : -1); };
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // smem: [RA_STAGES][BM*64] A ring first
@@ -272,8 +289,11 @@ __global__ __launch_bounds__(64 * WMW * WNW, (BM / WMW > 64 ? 1 : 2)) void conv_
         for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = v4i{c4.x, c4.y, c4.z, c4.w};
     }
 
-    // zero the S plane, stage the epilogue parameters (both visible after the first barrier of the K loop)
-    for (int i = tid; i < a.rows_cap * RS; i += NT) ldsS[i] = 0;
+    // stage the epilogue parameters (visible after the first barrier of the K loop).  The S plane is zeroed only where the chunks add
+    // into it: in the COUNTED form every cell the box sums read is written once behind the K loop -- they read rows 0 .. nrows - 1
+    // (the last pixel's bottom tap row is gr1 - gr0 + 2 = nrows - 1) and cells 0 .. W + 1 < RS, all below nrows * RS <= CPT * NT
+    if constexpr (!COUNTED)
+        for (int i = tid; i < a.rows_cap * RS; i += NT) ldsS[i] = 0;
     if (a.yolo_out)  // a head's float outputs take 256 values: one table instead of a double-precision exp per element
         for (int i = tid; i < 256; i += NT) ldsYL[i] = yolo_entry_act((float)(i - a.zp_act) * a.s_act, 0);
     for (int i = tid; i < BM; i += NT) {
@@ -327,6 +347,19 @@ __global__ __launch_bounds__(64 * WMW * WNW, (BM / WMW > 64 ? 1 : 2)) void conv_
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) baddr[ni] = lds0 + R * BM * 64 + bbase[ni];
 #define LDS_READ128(dst, addr, imm) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(imm))
+        // COUNTED cell sums: cell k of this thread is id = tid + k * NT; a thread without one (id >= nrows * RS) reads cell 0 and
+        // drops the sum -- every wave issues the same reads, which the counted waits below rely on.  caddr: the cell's piece 0 in the
+        // row image of the chunk being summed (moved to the other buffer with baddr, on a chunk's last step)
+        int csum[CPT];
+        unsigned caddr[CPT];
+        v4i cv;  // the piece in flight: read in step t, reduced in step t + 1 in front of the next read
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) {
+            const int id = tid + k * NT, cid = id < nrows * RS ? id : 0;
+            const int r = cid / RS, c = cid - r * RS;
+            caddr[k] = lds0 + R * BM * 64 + r * rowb + c * 16;
+            csum[k] = 0;
+        }
         using std::integral_constant;
         using std::true_type;
         using std::false_type;
@@ -361,7 +394,33 @@ __global__ __launch_bounds__(64 * WMW * WNW, (BM / WMW > 64 ? 1 : 2)) void conv_
                 // A(g+1) was issued R - 2 steps ago as the last DMA of its step: younger than it are the DMAs of the R - 3 steps in between
                 constexpr int YOUNG = n_a(t - 1) + n_b(t - 1) + (R > 4 ? n_a(t - 2) + n_b(t - 2) : 0) + (R > 5 ? n_a(t - 3) + n_b(t - 3) : 0);
                 constexpr int BLO = t * SPS < NBS ? t * SPS : NBS, BHI = (t + 1) * SPS < NBS ? (t + 1) * SPS : NBS;
+                // cell sums: CJ = the piece read this step issues (it has returned at the next step's first wait, and so before this
+                // thread passes the next chunk's first barrier, behind which the DMA of chunk + 2 overwrites this image: t <= 7),
+                // DJ = the piece read by the step before, reduced here
+                constexpr int CJ = cs_slot(t), DJ = cs_slot(t - 1);
+                static_assert(CJ < 4 * CPT && (CJ < 0 || RD), "cell reads ride on steps that read fragments");
+                auto cell_piece = [&] {  // in the gap behind the step's first MFMAs
+                    if constexpr (DJ >= 0) {
+                        if (!DBG(16)) {
+                            int s = csum[DJ / 4];
+                            s = __builtin_amdgcn_sdot4(cv[0], 0x01010101, s, false);
+                            s = __builtin_amdgcn_sdot4(cv[1], 0x01010101, s, false);
+                            s = __builtin_amdgcn_sdot4(cv[2], 0x01010101, s, false);
+                            s = __builtin_amdgcn_sdot4(cv[3], 0x01010101, s, false);
+                            csum[DJ / 4] = s;
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    if constexpr (CJ >= 0) {
+                        LDS_READ128(cv, caddr[CJ / 4], (CJ % 4) * PIECEB);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                };
                 if (t == 8 && !LAST) {
+                    if constexpr (COUNTED) {
+#pragma unroll
+                        for (int k = 0; k < CPT; ++k) caddr[k] += odd ? -bbytes : bbytes;
+                    }
                     const int bdelta = (odd ? -bbytes : bbytes) - 2 * rowb;  // the other row image, back to its tap row 0
                     unsigned rot[R];
 #pragma unroll
@@ -415,9 +474,11 @@ __global__ __launch_bounds__(64 * WMW * WNW, (BM / WMW > 64 ? 1 : 2)) void conv_
                     __builtin_amdgcn_sched_barrier(0);
                     if (RD) LDS_READ128(fb[ni], baddr[ni], TAPN);  // in place: its MFMAs have been issued
                     __builtin_amdgcn_sched_barrier(0);
+                    if (ni == 0) cell_piece();
                 }
                 // the last two B fragments of this step (read at the end of the previous one): the reads issued since may be in flight
-                if (RD) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(NI - 2) : "memory");
+                // (NI - 2 fragments and, behind the first of them, the step's cell piece)
+                if (RD) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(NI - 2 + (NI > 2 && CJ >= 0 ? 1 : 0)) : "memory");
                 else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -428,13 +489,14 @@ __global__ __launch_bounds__(64 * WMW * WNW, (BM / WMW > 64 ? 1 : 2)) void conv_
                     __builtin_amdgcn_sched_barrier(0);
                     if (RD) LDS_READ128(fa[mi], aaddr[SN], mi * 1024);
                     __builtin_amdgcn_sched_barrier(0);
+                    if (NI == 2 && mi == 0) cell_piece();  // (32-column wave tiles: older than the step's last two reads, no wait moves)
                 }
                 if (RD) {
                     LDS_READ128(fb[NI - 2], baddr[NI - 2], TAPN);
                     LDS_READ128(fb[NI - 1], baddr[NI - 1], TAPN);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if (t == 1) {
+                if (!COUNTED && t == 1 && !DBG(16)) {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // our reads are invisible to hipcc's counters
                     cell_sums(Bt);
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -448,6 +510,11 @@ __global__ __launch_bounds__(64 * WMW * WNW, (BM / WMW > 64 ? 1 : 2)) void conv_
         for (int chunk = 0; chunk + 1 < a.nchunks; ++chunk) chunk_body(false_type{}, chunk);
         chunk_body(true_type{}, a.nchunks - 1);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if constexpr (COUNTED) {  // hand S over to the epilogue: every cell once, by its owner (visible behind the barrier below)
+#pragma unroll
+            for (int k = 0; k < CPT; ++k)
+                if (tid + k * NT < nrows * RS) ldsS[tid + k * NT] = csum[k];
+        }
 #undef LDS_READ128
     }
 
