@@ -187,11 +187,11 @@ struct network {
     void *pi_idx_gpu, *pi_idx_host; /* [B] int32 entry | [B] float scale | [B] uint8 zero point */
     float *pi_mm_gpu, *pi_mm_host;  /* [B][2] max, min */
     int pi_packed;              /* bank entries packed by the last batch (the others came from the cache) */
-    /* Frame input (network_frames_u8 / _nv12 / _planar / _packed / _p010_input_gpu): lazily allocated, sized by the batch, freed with the network and on
+    /* Frame input (network_frames_u8 / _nv12 / _planar / _packed / _p010 / _bayer_input_gpu): lazily allocated, sized by the batch, freed with the network and on
      * re-batch.  A replica owns its own. */
     void *fr_arena_gpu;         /* staging of host frames: the bytes as they came, rows at their pitch, 256-byte aligned planes */
     size_t fr_arena_bytes;
-    void *fr_table_gpu, *fr_table_host; /* [fr_cap] entries of the kind last fed (mi355_frame_u8 | _yuv | _planar | _packed | _p010) and their host mirror:
+    void *fr_table_gpu, *fr_table_host; /* [fr_cap] entries of the kind last fed (mi355_frame_u8 | _yuv | _planar | _packed | _p010 | _bayer) and their host mirror:
                                            one table for every kind, sized for the largest entry */
     int fr_kind;                /* the kind of frames in the table */
     float *fr_mm_gpu, *fr_mm_host; /* [fr_cap][2] max, min */
@@ -356,6 +356,23 @@ void set_jpeg_entropy_subseq_bits(network *net, int bits);
 struct dnq_jpeg_scan_list;
 int jpeg_scan_host(const uint8_t *data, size_t bytes, dnq_jpeg *out, struct dnq_jpeg_scan_list *scans, char *err, size_t errlen);
 void jpeg_scan_free(struct dnq_jpeg_scan_list *scans);
+/* The same step for raw sensor frames: one plane with one sample per pixel behind a Bayer colour filter (pattern: MI355_BAYER_RGGB,
+ * _BGGR, _GRBG, _GBRG) or none (MI355_BAYER_MONO), as machine-vision cameras (BayerRG8 .., Mono8 .. Mono16) and MIPI CSI-2 sensors
+ * without an ISP (RAW10, RAW12) deliver them.  sample: MI355_RAW_U8 (pitch[b] >= w[b]), MI355_RAW_U16 (little-endian, reduced to
+ * min(v >> shift, 255), shift 0..8; pitch[b] >= 2 * w[b]), MI355_RAW_MIPI10 (pitch[b] >= 5 * ((w[b] + 3) / 4)) or MI355_RAW_MIPI12
+ * (pitch[b] >= 3 * ((w[b] + 1) / 2)); shift must be 0 with the others.  tone: NULL, or [batch] pointers each NULL (identity) or 768
+ * bytes, the [3][256] tables (R, G, B) every sample of that frame goes through by the colour of its site before anything is averaged
+ * (MONO: table 0).  frames[b] holds h[b] rows pitch[b] bytes apart (a null pitch array: tightly packed); the bytes go up as they are,
+ * a frame or a tone table that several slots share goes up once, and the frame is demosaiced bilinearly in registers inside the
+ * letterbox: the result is, bit for bit, network_frames_u8_input_gpu's on the RGB frame D(frame) that mi355_yolo_int8.h defines at
+ * mi355_frame_bayer.  Arena, min / max and pair buffers, the one host sync and both (scale, zero point) branches are that function's.
+ * frames_on_device != 0: frames[b] and tone[b] are device pointers, used in place.  3-channel networks only; an unknown pattern or
+ * sample layout, a shift outside 0..8 or without MI355_RAW_U16, a null frame, w or h outside 1..32768, a Bayer frame below 2 x 2 or
+ * a pitch below its minimum die via error() before the device is touched. */
+void network_frames_bayer_input_gpu(network *net, const uint8_t *const *frames, const int *w, const int *h,
+                                    const int *pitch /* NULL: tight */, int pattern, int sample, int shift,
+                                    const uint8_t *const *tone /* NULL, or [batch] of NULL | 768 bytes */,
+                                    int frames_on_device);
 /* Per-image input quantisation, opt-in (off: image 0 defines the scale of the whole batch, as before).  On: every image of a batch is
  * quantised with its own min / max, scale and zero point, and layer 0 runs with that image's constants (mi355_conv_forward_per_image):
  * slot b of every layer equals the batch-1 run on image b.  The quantisers above honour it.  Returns 0, or MI355_EINVAL with a message

@@ -510,6 +510,63 @@ int mi355_frames_p010_letterbox_minmax(const mi355_frame_p010 *table_dev, const 
                                        float *minmax, void *stream);
 int mi355_frames_p010_letterbox_quantize(const mi355_frame_p010 *table_dev, const mi355_frame_p010 *table_host, int B, int w, int h,
                                          const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
+/* The same two calls for raw sensor frames: one sample per pixel behind a Bayer colour filter (machine-vision cameras: BayerRG8 and its
+ * kin; MIPI CSI-2 sensors without an ISP: RAW10 / RAW12) or no filter at all (Mono8 .. Mono16).  The frame is demosaiced in registers
+ * at the taps of the letterbox; no RGB frame is written.  D(frame), the interleaved RGB frame the calls stand for, is defined here, all
+ * arithmetic in int32:
+ *   raw8(x, y), the 8-bit sample, by `sample`:
+ *     MI355_RAW_U8      the byte data[y * pitch + x];
+ *     MI355_RAW_U16     min(v >> shift, 255) of the little-endian 16-bit value v at data[y * pitch + 2 * x], any address parity,
+ *                       shift in 0..8: 2, 4, 6 serve LSB-aligned 10-, 12-, 14-bit samples, 8 MSB-aligned or 16-bit ones.  A truncation
+ *                       as in the P010 kind, and a saturation where a sample exceeds its nominal range;
+ *     MI355_RAW_MIPI10  CSI-2 RAW10, four pixels in five bytes: data[y * pitch + 5 * (x >> 2) + (x & 3)]; the fifth byte of a group
+ *                       holds the low bits and is never read;
+ *     MI355_RAW_MIPI12  CSI-2 RAW12, two pixels in three bytes: data[y * pitch + 3 * (x >> 1) + (x & 1)]; the third byte is never read.
+ *   c(x, y), the colour of site (x, y): P[y & 1][x & 1] of `pattern` P = MI355_BAYER_RGGB (R G / G B), _BGGR (B G / G R), _GRBG
+ *     (G R / B G), _GBRG (G B / R G); MI355_BAYER_MONO: no mosaic.
+ *   s(x, y) = tone[c(x, y)][raw8(x, y)], the toned sample: `tone` is a table of 3 x 256 bytes (R, G, B) of this frame, or NULL for the
+ *     identity.  It carries black level, white-balance gain and the transfer curve in one lookup, and is applied to samples, before
+ *     any averaging.  MONO uses table 0.
+ *   Neighbour coordinates outside the frame are reflected without repeating the edge, -1 -> 1 and w -> w - 2, rows likewise, which
+ *     keeps the colour phase: Bayer frames need w, h >= 2, MONO frames w, h >= 1.
+ *   Bilinear demosaic, >> on non-negative sums.  At an R or B site with own colour A and opposite colour C:
+ *       out[A] = s(x, y)
+ *       out[G] = (s(x-1, y) + s(x+1, y) + s(x, y-1) + s(x, y+1) + 2) >> 2
+ *       out[C] = (s(x-1, y-1) + s(x+1, y-1) + s(x-1, y+1) + s(x+1, y+1) + 2) >> 2
+ *     at a G site with Hc = c(x ^ 1, y) and Vc the other of R and B:
+ *       out[G] = s(x, y),  out[Hc] = (s(x-1, y) + s(x+1, y) + 1) >> 1,  out[Vc] = (s(x, y-1) + s(x, y+1) + 1) >> 1
+ *     MONO: out = (s, s, s).
+ * Min / max and the quantised bytes are, bit for bit, what the u8 calls give for the interleaved RGB frame D(frame).  No equality with
+ * any other demosaic (OpenCV, camera SDKs) is claimed: their filters and border rules differ.  16-bit samples and MIPI groups are read
+ * with byte-granular loads: any address and pitch are legal.  A new struct and new calls: MI355_ABI_VERSION is unchanged. */
+#define MI355_BAYER_RGGB 0  /* R G / G B */
+#define MI355_BAYER_BGGR 1  /* B G / G R */
+#define MI355_BAYER_GRBG 2  /* G R / B G */
+#define MI355_BAYER_GBRG 3  /* G B / R G */
+#define MI355_BAYER_MONO 4  /* no mosaic: R = G = B = the sample */
+#define MI355_RAW_U8 0      /* one byte a sample */
+#define MI355_RAW_U16 1     /* two bytes a sample, little-endian, reduced by `shift` */
+#define MI355_RAW_MIPI10 2  /* CSI-2 RAW10 */
+#define MI355_RAW_MIPI12 3  /* CSI-2 RAW12 */
+typedef struct mi355_frame_bayer {   /* 48 bytes */
+    const uint8_t *data;             /* DEVICE pointer to the first byte of row 0 */
+    const uint8_t *tone;             /* DEVICE pointer to [3][256] bytes, or NULL: identity */
+    int w, h;                        /* pixels */
+    int pitch;                       /* bytes from one row to the next */
+    int pattern;                     /* MI355_BAYER_* */
+    int sample;                      /* MI355_RAW_* */
+    int shift;                       /* 0..8 with MI355_RAW_U16, else 0 */
+    int reserved[2];                 /* zero */
+} mi355_frame_bayer;
+/* The contract of the _yuv_ calls: table_host is validated before anything is launched, and each of these returns MI355_EINVAL with a
+ * message of its own behind "frames_bayer: ", nothing written: a null data pointer; w or h outside 1..32768; an unknown pattern; an
+ * unknown sample layout; a shift outside 0..8; a non-zero shift without MI355_RAW_U16; a non-zero `reserved`; pitch < w (U8),
+ * < 2 * w (U16), < 5 * ((w + 3) / 4) (MIPI10) or < 3 * ((w + 1) / 2) (MIPI12); a Bayer frame below 2 x 2; a frame the letterbox
+ * geometry refuses.  B <= 65535. */
+int mi355_frames_bayer_letterbox_minmax(const mi355_frame_bayer *table_dev, const mi355_frame_bayer *table_host, int B, int w, int h,
+                                        float *minmax, void *stream);
+int mi355_frames_bayer_letterbox_quantize(const mi355_frame_bayer *table_dev, const mi355_frame_bayer *table_host, int B, int w, int h,
+                                          const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
 /* The device half of a baseline JPEG decoder: everything after the entropy decode, for a whole batch in two launches, leaving interleaved
  * RGB frames in device memory that the u8 calls above take as they are.  The bytes are the ones stb_image v2.19 returns as the reference
  * compiles it (ref: src/stb_image.h; load_image_color -> stbi_load(.., 3), src/image.c:1293-1315): all of this is integer arithmetic in

@@ -1,6 +1,6 @@
 """Times the input step alone: from the batch's first upload to the network's uint8 input being ready on the device.
 
-yolov3-tiny @416, batch 64, 640 x 480 RGB frames (synthetic bytes, every frame its own range), seven variants:
+yolov3-tiny @416, batch 64, 640 x 480 RGB frames (synthetic bytes, every frame its own range), nine variants:
   float   the float entry points: per frame one upload of the planar float image (byte / 255, converted before the clock starts)
           and one network_letterbox_input_gpu, then network_quantize_input_gpu (min / max, host sync, quantise)
   frames  network_frames_u8_input_gpu: the bytes go up as they are, two launches for the whole batch
@@ -13,11 +13,15 @@ yolov3-tiny @416, batch 64, 640 x 480 RGB frames (synthetic bytes, every frame i
           clock starts): 2 bytes a pixel
   p010    network_frames_p010_input_gpu: the NV12 planes as 16-bit samples, the byte at the top (made before the clock starts): 3 bytes
           a pixel
+  bayer   network_frames_bayer_input_gpu: the mosaic an RGGB sensor samples from the RGB frames, 8-bit samples, no tone table (made
+          before the clock starts): 1 byte a pixel, demosaiced inside the two launches
+  bayer_mipi10  the same samples as CSI-2 RAW10 rows, four pixels in five bytes: 1.25 bytes a pixel
 each in shared-scale and per-image mode.  A step is timed twice: HIP events on the network's stream around it, and the host clock
 from before the first upload to after a stream synchronise.  The variants alternate within a repeat; the same batch is fed every step
 (steady state: layer 0 is not re-derived, the per-image bank serves every key from its cache).  Before timing, the float and frames
 variants' uint8 inputs, scales and zero points are compared for equality, and the nv12 variant's with those of the frames entry point
-fed the RGB frames a numpy restatement of the integer YUV -> RGB formulas makes of the NV12 planes; the i420, yuyv and p010 variants' are compared with the nv12 variant's, the bgra variant's with the frames variant's.  `host_convert_ms` is the byte -> planar float conversion the float variant
+fed the RGB frames a numpy restatement of the integer YUV -> RGB formulas makes of the NV12 planes; the i420, yuyv and p010 variants' are compared with the nv12 variant's, the bgra variant's with the frames variant's, and the two bayer variants' with those of the frames entry point fed D(frame), the
+numpy restatement of the bilinear demosaic (tests/frames_bayer_util.py).  `host_convert_ms` is the byte -> planar float conversion the float variant
 needs before its first upload, done with numpy here: an indication only, not part of either timed step.
 
 --on-device adds, per scale mode, the comparison of the synchronous input step with the one that derives scales and layer-0 constants on
@@ -51,6 +55,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from frames_bayer_util import demosaic, mosaic, pack  # noqa: E402  (numpy only: the definition of the Bayer source)
 from yolo_quantization_amd import binding, synth  # noqa: E402
 
 CFG = os.path.join(ROOT, "cfg", "yolov3-tiny_quant.cfg")
@@ -167,6 +173,20 @@ class PackedVariant:
 
     def step(self):
         self.net.H.network_frames_packed_input_gpu(self.net.h, self.ptrs, self.w, self.h, None, self.fmt, 0, self.hbm)
+
+
+class BayerVariant:
+    """frames: uint8 [h][row_bytes] arrays of raw samples behind an RGGB filter; sample: MI355_RAW_*"""
+
+    def __init__(self, net, frames, w, sample, hbm=False):
+        B = len(frames)
+        self.net, self.frames, self.sample, self.hbm, self.keep = net, frames, sample, int(hbm), []
+        self.ptrs, self.w, self.h = (C.c_void_p * B)(), (C.c_int * B)(), (C.c_int * B)()
+        for b, f in enumerate(frames):
+            self.ptrs[b], self.h[b], self.w[b] = _addr(f, hbm, self.keep), f.shape[0], w
+
+    def step(self):
+        self.net.H.network_frames_bayer_input_gpu(self.net.h, self.ptrs, self.w, self.h, None, 0, self.sample, 0, None, self.hbm)
 
 
 def rgb_to_bgra(f):
@@ -425,6 +445,8 @@ def main():
     planes = [rgb_to_nv12(f) for f in frames]
     converted = [nv12_to_rgb(y, uv) for y, uv in planes]
     bgra, yuyv = [rgb_to_bgra(f) for f in frames], [nv12_to_yuyv(y, uv) for y, uv in planes]
+    mosaics = [mosaic(f, "rggb") for f in frames]
+    raw10, demosaiced = [pack(m, "mipi10") for m in mosaics], [demosaic(m, "rggb") for m in mosaics]
     ev = Events()
     res = {}
     if a.on_device:
@@ -469,14 +491,15 @@ def main():
         print(json.dumps(res))
         return
     for mode in ("shared", "per_image"):
-        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("float", "frames", "nv12", "i420", "bgra", "yuyv", "p010")}
+        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("float", "frames", "nv12", "i420", "bgra", "yuyv", "p010", "bayer", "bayer_mipi10")}
         if mode == "per_image":
             for n in nets.values():
                 n.set_input_per_image(True)
         var = {"float": FloatVariant(nets["float"], frames), "frames": FramesVariant(nets["frames"], frames),
                "nv12": NV12Variant(nets["nv12"], planes), "i420": I420Variant(nets["i420"], planes),
                "bgra": PackedVariant(nets["bgra"], bgra, sw, 1), "yuyv": PackedVariant(nets["yuyv"], yuyv, sw, 4),
-               "p010": P010Variant(nets["p010"], planes)}
+               "p010": P010Variant(nets["p010"], planes), "bayer": BayerVariant(nets["bayer"], mosaics, sw, 0),
+               "bayer_mipi10": BayerVariant(nets["bayer_mipi10"], raw10, sw, 2)}
         for _ in range(a.warmup):
             for v in var.values():
                 v.step()
@@ -486,6 +509,8 @@ def main():
         same_nv12 = same_input(nets["nv12"], nets["frames"])
         same_i420 = same_input(nets["i420"], nets["nv12"])
         same_yuyv, same_p010 = same_input(nets["yuyv"], nets["nv12"]), same_input(nets["p010"], nets["nv12"])
+        FramesVariant(nets["frames"], demosaiced).step()  # the frames entry point on D(frame) of the mosaics
+        same_bayer, same_raw10 = same_input(nets["bayer"], nets["frames"]), same_input(nets["bayer_mipi10"], nets["frames"])
         for _ in range(a.warmup):
             var["frames"].step()
         runs = {k: {"device_ms": [], "wall_ms": []} for k in var}
@@ -500,6 +525,11 @@ def main():
                      "i420": runs["i420"],
                      "bgra_identical_to_frames": same_bgra, "yuyv_identical_to_nv12": same_yuyv, "p010_identical_to_nv12": same_p010,
                      "bgra": runs["bgra"], "yuyv": runs["yuyv"], "p010": runs["p010"],
+                     "bayer_identical_to_frames_on_demosaiced_rgb": same_bayer,
+                     "bayer_mipi10_identical_to_frames_on_demosaiced_rgb": same_raw10,
+                     "bayer": runs["bayer"], "bayer_mipi10": runs["bayer_mipi10"],
+                     "bayer_over_frames_device": round(med["frames"]["device_ms"] / med["bayer"]["device_ms"], 3),
+                     "bayer_mipi10_over_frames_device": round(med["frames"]["device_ms"] / med["bayer_mipi10"]["device_ms"], 3),
                      "bgra_over_frames_device": round(med["frames"]["device_ms"] / med["bgra"]["device_ms"], 3),
                      "yuyv_over_nv12_device": round(med["nv12"]["device_ms"] / med["yuyv"]["device_ms"], 3),
                      "p010_over_nv12_device": round(med["nv12"]["device_ms"] / med["p010"]["device_ms"], 3),
@@ -514,7 +544,7 @@ def main():
     res["host_convert_ms_numpy"] = round(convert_ms, 3)
     res["config"] = {"cfg": "yolov3-tiny_quant.cfg", "batch": a.batch, "src": a.src, "iters": a.iters, "warmup": a.warmup,
                      "repeats": a.repeats, "values": "median of `iters` steps per repeat; speedup = median over repeats, float / frames; "
-                               "nv12_over_frames = frames / nv12; i420_over_nv12 = nv12 / i420; bgra_over_frames, yuyv_over_nv12, p010_over_nv12 likewise"}
+                               "nv12_over_frames = frames / nv12; i420_over_nv12 = nv12 / i420; bgra_over_frames, yuyv_over_nv12, p010_over_nv12, bayer_over_frames, bayer_mipi10_over_frames likewise"}
     print(json.dumps(res))
 
 

@@ -80,6 +80,22 @@ class FrameP010(C.Structure):
                 ("layout", C.c_int), ("matrix", C.c_int), ("reserved", C.c_int * 2)]
 
 
+class FrameBayer(C.Structure):
+    """mi355_frame_bayer: one entry of the frame table of mi355_frames_bayer_letterbox_minmax / _quantize (data, tone: DEVICE
+    pointers; tone may be NULL)."""
+    _fields_ = [("data", C.c_void_p), ("tone", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("pitch", C.c_int), ("pattern", C.c_int),
+                ("sample", C.c_int), ("shift", C.c_int), ("reserved", C.c_int * 2)]
+
+
+BAYER_PATTERN = {"rggb": 0, "bggr": 1, "grbg": 2, "gbrg": 3, "mono": 4}  # MI355_BAYER_RGGB .. MI355_BAYER_MONO
+RAW_SAMPLE = {"u8": 0, "u16": 1, "mipi10": 2, "mipi12": 3}  # MI355_RAW_U8 .. MI355_RAW_MIPI12
+
+
+def raw_row_bytes(sample, w):
+    """The bytes of a row of w raw samples of layout `sample` (a key of RAW_SAMPLE)."""
+    return {"u8": w, "u16": 2 * w, "mipi10": 5 * ((w + 3) // 4), "mipi12": 3 * ((w + 1) // 2)}[sample]
+
+
 class YoloHead(C.Structure):
     """mi355_yolo_head: one yolo layer of mi355_yolo_detections_batch (yolo_out, anchors, mask: DEVICE pointers)."""
     _fields_ = [("yolo_out", C.c_void_p), ("anchors", C.c_void_p), ("mask", C.c_void_p), ("n", C.c_int), ("H", C.c_int), ("W", C.c_int),
@@ -235,6 +251,9 @@ def shim():
         L.mi355_frames_packed_letterbox_quantize.argtypes = [vp, C.POINTER(FramePacked), ci, ci, ci, vp, vp, vp, vp]
         L.mi355_frames_p010_letterbox_minmax.argtypes = [vp, C.POINTER(FrameP010), ci, ci, ci, vp, vp]
         L.mi355_frames_p010_letterbox_quantize.argtypes = [vp, C.POINTER(FrameP010), ci, ci, ci, vp, vp, vp, vp]
+        if hasattr(L, "mi355_frames_bayer_letterbox_minmax"):  # as above: an older build has no Bayer calls
+            L.mi355_frames_bayer_letterbox_minmax.argtypes = [vp, C.POINTER(FrameBayer), ci, ci, ci, vp, vp]
+            L.mi355_frames_bayer_letterbox_quantize.argtypes = [vp, C.POINTER(FrameBayer), ci, ci, ci, vp, vp, vp, vp]
         L.mi355_yolo_detections_sizes.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, C.c_float, ci, vp, ci, vp, vp]
         L.mi355_yolo_detections_batch_work_ints.restype = C.c_long
         L.mi355_yolo_detections_batch_work_ints.argtypes = [C.POINTER(YoloHead), ci, ci]
@@ -494,6 +513,9 @@ def host():
             L.set_jpeg_entropy_on_device.restype = None
             L.set_jpeg_entropy_subseq_bits.argtypes = [vp, ci]
             L.set_jpeg_entropy_subseq_bits.restype = None
+        if hasattr(L, "network_frames_bayer_input_gpu"):  # as above
+            L.network_frames_bayer_input_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, ci, ci,
+                                                         C.POINTER(vp), ci]
         L.quantization_prep_host.argtypes = [vp, C.c_float, C.c_uint8]
         L.forward_network_gpu.argtypes = [vp]
         L.network_predict.restype = vp
@@ -1242,6 +1264,73 @@ class Net:
             raise ValueError("prepare_from_frames_p010: the planes of a batch are all host arrays or all device tensors")
         on_device = where.pop()
         self.H.network_frames_p010_input_gpu(self.h, ys, uvs, ws, hs, py, puv, YUV_MATRIX[matrix], int(on_device))
+        if self._enqueued_only(on_device):
+            return None
+        return self._prepared(self._pull_input())
+
+    def prepare_from_frames_bayer(self, frames, pattern="rggb", sample="u8", shift=0, tone=None, on_device=False):
+        """Raw sensor frame input path (network_frames_bayer_input_gpu): one sample per pixel behind a Bayer filter, `pattern` = "rggb" |
+        "bggr" | "grbg" | "gbrg" (the 2 x 2 tile from the top left corner), or behind none, "mono".  `sample` = "u8": frames[b] is
+        uint8 [h][w]; "u16": uint16 [h][w], little-endian, every sample reduced to min(v >> shift, 255) with `shift` in 0..8 (2, 4, 6 for
+        LSB-aligned 10-, 12-, 14-bit samples, 8 for MSB-aligned or 16-bit ones); "mipi10" | "mipi12" (CSI-2 RAW10: four pixels in five
+        bytes, RAW12: two in three): a tuple (uint8 [h][row_bytes], w).  `tone`: None, one uint8 [3][256] array for all frames, or a
+        sequence of one per frame (None: identity) -- the (R, G, B) tables every sample goes through by the colour of its site before
+        anything is averaged (black level, white balance, transfer curve; "mono" uses table 0).  The frames go up as they are and are
+        demosaiced bilinearly on the device, inside the letterbox, as mi355_yolo_int8.h defines at mi355_frame_bayer.  on_device:
+        frames and tone tables are device tensors (see prepare_from_frames_packed) used in place; otherwise host arrays.  Row strides
+        are passed through as the pitch, as prepare_from_frames_u8 does.  Returns what prepare_from_frames_u8 returns."""
+        me = "prepare_from_frames_bayer"
+        assert len(frames) == self.batch
+        B = self.batch
+        if pattern not in BAYER_PATTERN:
+            raise ValueError(f"{me}: pattern is one of {', '.join(BAYER_PATTERN)}")
+        if sample not in RAW_SAMPLE:
+            raise ValueError(f"{me}: sample is one of {', '.join(RAW_SAMPLE)}")
+        if not isinstance(shift, int) or not 0 <= shift <= 8 or (shift and sample != "u16"):
+            raise ValueError(f"{me}: shift is 0..8 and goes with sample u16 only")
+        mipi = sample in ("mipi10", "mipi12")
+        keep, where = [], set()
+        ptrs, ws, hs, ps = (C.c_void_p * B)(), (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)()
+        for b, f in enumerate(frames):
+            f, w = f if isinstance(f, (tuple, list)) else (f, None)
+            if mipi != (w is not None):
+                raise ValueError(f"{me}: a frame is (uint8 [h][row_bytes], w) with mipi10 / mipi12 and a plain [h][w] array otherwise")
+            ptrs[b], ps[b], shape, dev = _sample_rows(f, 2 if sample == "u16" else 1, (), keep, me)
+            if len(shape) != 2 or (mipi and (not isinstance(w, int) or w < 1 or shape[1] < raw_row_bytes(sample, w))):
+                raise ValueError(f"{me}: a {sample} frame must be [h][w]" + (f" bytes holding {raw_row_bytes(sample, max(w, 1))} a row" if mipi else ""))
+            hs[b], ws[b] = shape[0], w if mipi else shape[1]
+            if pattern != "mono" and (hs[b] < 2 or ws[b] < 2):
+                raise ValueError(f"{me}: a Bayer frame needs w, h >= 2")
+            where.add(dev)
+        tones = None
+        if tone is not None:
+            per_frame = isinstance(tone, (tuple, list))
+            if per_frame and len(tone) != B:
+                raise ValueError(f"{me}: tone is None, one uint8 [3][256] table or one per frame")
+            tones = (C.c_void_p * B)()
+            for b, t in enumerate(tone if per_frame else [tone] * B):
+                if t is None:
+                    continue
+                if hasattr(t, "data_ptr"):
+                    if tuple(t.shape) != (3, 256) or t.element_size() != 1 or t.stride(1) != 1 or t.stride(0) != 256:
+                        raise ValueError(f"{me}: a tone table must be a contiguous uint8 [3][256]")
+                    tones[b] = t.data_ptr()
+                    where.add(True)
+                else:
+                    a = np.asarray(t)
+                    if a.dtype != np.uint8 or a.shape != (3, 256):
+                        raise ValueError(f"{me}: a tone table must be a contiguous uint8 [3][256]")
+                    if not per_frame and b:  # the one table of all frames: one address, so it goes up once
+                        tones[b] = tones[0]
+                        continue
+                    a = np.ascontiguousarray(a)
+                    keep.append(a)
+                    tones[b] = a.ctypes.data
+                    where.add(False)
+        if where != {bool(on_device)}:
+            raise ValueError(f"{me}: frames and tone tables are all host arrays, or all device tensors with on_device=True")
+        self.H.network_frames_bayer_input_gpu(self.h, ptrs, ws, hs, ps, BAYER_PATTERN[pattern], RAW_SAMPLE[sample], shift, tones,
+                                              int(bool(on_device)))
         if self._enqueued_only(on_device):
             return None
         return self._prepared(self._pull_input())

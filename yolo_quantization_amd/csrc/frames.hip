@@ -20,7 +20,9 @@
 //                 (mi355_frames_packed_*): the RGB formats pick three of a pixel's four bytes, the 4:2:2 formats are I422 with luma and
 //                 chroma of a macropixel in one 4-byte group: one 4-byte load per row and macropixel the taps touch;
 //   SourceP010    NV12 with 16-bit little-endian samples (mi355_frames_p010_*: P010, P012, P016): the high byte of every sample is
-//                 the NV12 byte (truncation), loaded on its own.
+//                 the NV12 byte (truncation), loaded on its own;
+//   SourceBayer   one plane of raw sensor samples (mi355_frames_bayer_*: 8-bit, 16-bit, CSI-2 RAW10 / RAW12; RGGB, BGGR, GRBG, GBRG or
+//                 no mosaic): toned through the frame's optional tables and demosaiced bilinearly in registers at every tap.
 #include "kargs.h"
 
 // letterbox_launch's geometry (glue.hip), shared by the host-side validation and the kernels: one function compiled for both sides, so
@@ -347,6 +349,133 @@ struct SourceP010 {
     __device__ void taps(int ix, int iy, bool two_x, bool two_y, uint8_t p[2][2][3]) const { yuv_taps(*this, 1, 1, ix, iy, two_x, two_y, p); }
 };
 
+// The tone tables of the workgroup's Bayer frame, [3][256] bytes.  Only the Bayer kernels name it, so only they carry it.
+__shared__ __attribute__((aligned(4))) uint8_t bayer_tone_lds[768];
+
+// Stages the frame's tone table, if it has one; the barrier of fill_byte_lut, which follows in both kernel bodies, publishes it.  The
+// table may sit at any address: a dword load declared unaligned, as SourcePacked::group's.
+__device__ static inline void bayer_stage_tone(const uint8_t *tone)
+{
+    if (tone && threadIdx.x < 192) {
+        uint32_t four;
+        __builtin_memcpy(&four, tone + 4 * threadIdx.x, 4);
+        reinterpret_cast<uint32_t *>(bayer_tone_lds)[threadIdx.x] = four;
+    }
+}
+
+// One plane of raw sensor samples behind a Bayer filter, or behind none (mi355_frame_bayer; the header defines D(frame), the RGB frame
+// this source stands for).  The up to 2 x 2 taps of an output pixel are demosaiced from the 4 x 4 window of toned samples around them,
+// (ix - 1 .. ix + 2, iy - 1 .. iy + 2) with coordinates outside the frame reflected: every sample of the window is loaded and toned
+// once, then each tap picks its own sample and the averages of its neighbours by the colour of its site.  A site's colour is
+// (a, b) = ((x ^ rx) & 1, (y ^ ry) & 1) with (rx, ry) the R site of the pattern: R at (0, 0), B at (1, 1), G elsewhere, so the
+// tone table of a sample is a + b.  Pattern, sample layout and tone are uniform over the workgroup: no branch on them diverges;
+// every array index is a constant after unrolling.
+struct SourceBayer {
+    using Frame = mi355_frame_bayer;
+    static constexpr const char *name = "frames_bayer";
+    static const char *check_pointers(const Frame &f) { return f.data ? nullptr : "null frame pointer"; }
+    static const char *check(const Frame &f)
+    {
+        if (f.pattern < MI355_BAYER_RGGB || f.pattern > MI355_BAYER_MONO) return "unknown pattern (MI355_BAYER_RGGB .. _MONO)";
+        if (f.sample < MI355_RAW_U8 || f.sample > MI355_RAW_MIPI12) return "unknown sample layout (MI355_RAW_U8 .. _MIPI12)";
+        if (f.shift < 0 || f.shift > 8) return "shift outside 0..8";
+        if (f.shift != 0 && f.sample != MI355_RAW_U16) return "shift must be 0 without MI355_RAW_U16";
+        if (f.reserved[0] != 0 || f.reserved[1] != 0) return "reserved must be 0";
+        if (f.sample == MI355_RAW_U8 && f.pitch < f.w) return "pitch < w";
+        if (f.sample == MI355_RAW_U16 && f.pitch < 2 * f.w) return "pitch < 2 * w";
+        if (f.sample == MI355_RAW_MIPI10 && f.pitch < 5 * ((f.w + 3) / 4)) return "pitch < 5 * ((w + 3) / 4)";
+        if (f.sample == MI355_RAW_MIPI12 && f.pitch < 3 * ((f.w + 1) / 2)) return "pitch < 3 * ((w + 1) / 2)";
+        if (f.pattern != MI355_BAYER_MONO && (f.w < 2 || f.h < 2)) return "a Bayer frame needs w, h >= 2";
+        return nullptr;
+    }
+    const uint8_t *data;
+    int w, h, pitch;
+    int sample, shift;
+    int rx, ry;  // the R site of the pattern
+    bool mono, toned;
+    __device__ explicit SourceBayer(const mi355_frame_bayer &f)
+        : data(f.data), w(f.w), h(f.h), pitch(f.pitch), sample(f.sample), shift(f.shift),
+          rx(f.pattern == MI355_BAYER_BGGR || f.pattern == MI355_BAYER_GRBG ? 1 : 0),
+          ry(f.pattern == MI355_BAYER_BGGR || f.pattern == MI355_BAYER_GBRG ? 1 : 0), mono(f.pattern == MI355_BAYER_MONO),
+          toned(f.tone != nullptr) {}
+    // the byte offset of sample x inside its row
+    __device__ int column(int x) const
+    {
+        if (sample == MI355_RAW_U16) return 2 * x;
+        if (sample == MI355_RAW_MIPI10) return 5 * (x >> 2) + (x & 3);
+        if (sample == MI355_RAW_MIPI12) return 3 * (x >> 1) + (x & 1);
+        return x;
+    }
+    // raw8 of the sample at `at`
+    __device__ int raw8(const uint8_t *at) const
+    {
+        if (sample != MI355_RAW_U16) return at[0];
+        uint16_t v;
+        __builtin_memcpy(&v, at, 2);
+        const int r = (int)v >> shift;
+        return r > 255 ? 255 : r;
+    }
+    // s of a sample of colour table t (0, 1, 2)
+    __device__ int tone(int t, int raw) const
+    {
+        return toned ? bayer_tone_lds[256 * t + raw] : raw;
+    }
+    __device__ void taps(int ix, int iy, bool two_x, bool two_y, uint8_t p[2][2][3]) const
+    {
+        if (mono) {
+            const uint8_t *row = data + (size_t)iy * pitch;
+            const int c0 = column(ix), c1 = two_x ? column(ix + 1) : c0;
+#pragma unroll
+            for (int r = 0; r < 2; ++r, row += pitch) {
+                if (r == 1 && !two_y) break;
+                p[r][0][0] = p[r][0][1] = p[r][0][2] = (uint8_t)tone(0, raw8(row + c0));
+                if (two_x) p[r][1][0] = p[r][1][1] = p[r][1][2] = (uint8_t)tone(0, raw8(row + c1));
+            }
+            return;
+        }
+        // the window's columns and rows, reflected (w, h >= 2; ix + 1 < w when two_x, iy + 1 < h when two_y); column 3 and row 3 serve
+        // the second taps only
+        const int x2 = ix + 1 < w ? ix + 1 : w - 2, y2 = iy + 1 < h ? iy + 1 : h - 2;
+        const int xo[4] = {column(ix > 0 ? ix - 1 : 1), column(ix), column(x2), column(two_x && ix + 2 < w ? ix + 2 : w - 2)};
+        const int yy[4] = {iy > 0 ? iy - 1 : 1, iy, y2, two_y && iy + 2 < h ? iy + 2 : h - 2};
+        const int a0 = (ix ^ rx) & 1, b0 = (iy ^ ry) & 1;  // of window position [1][1], the first tap
+        int s[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i == 3 && !two_y) break;
+            const uint8_t *row = data + (size_t)yy[i] * pitch;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j == 3 && !two_x) break;
+                s[i][j] = tone((a0 ^ ((j + 1) & 1)) + (b0 ^ ((i + 1) & 1)), raw8(row + xo[j]));
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (r == 1 && !two_y) break;
+#pragma unroll
+            for (int d = 0; d < 2; ++d) {
+                if (d == 1 && !two_x) break;
+                const int a = a0 ^ d, b = b0 ^ r, i = 1 + r, j = 1 + d;
+                const int own = s[i][j], left_right = s[i][j - 1] + s[i][j + 1], up_down = s[i - 1][j] + s[i + 1][j];
+                int red, green, blue;
+                if (a != b) {  // a G site: its row neighbours are R in an R row (b == 0), B in a B row
+                    const int hc = (left_right + 1) >> 1, vc = (up_down + 1) >> 1;
+                    green = own;
+                    red = b == 0 ? hc : vc;
+                    blue = b == 0 ? vc : hc;
+                } else {
+                    const int diagonal = (s[i - 1][j - 1] + s[i - 1][j + 1] + s[i + 1][j - 1] + s[i + 1][j + 1] + 2) >> 2;
+                    green = (left_right + up_down + 2) >> 2;
+                    red = a == 0 ? own : diagonal;
+                    blue = a == 0 ? diagonal : own;
+                }
+                p[r][d][0] = (uint8_t)red; p[r][d][1] = (uint8_t)green; p[r][d][2] = (uint8_t)blue;
+            }
+        }
+    }
+};
+
 // the three letterboxed floats (planes 0, 1, 2) of output pixel (x, y)
 template <class Source>
 __device__ static inline void letterbox_px3(const Source &f, const FrameGeo &g, const float *lut, int x, int y, float v[3])
@@ -470,6 +599,25 @@ __global__ __launch_bounds__(256) void frames_letterbox_quantize_kernel(const ty
     letterbox_quantize_body<Source>(table, w, h, scale_dev, zp_dev, out, lut);
 }
 
+// The Bayer kind's kernels: the shared bodies behind the staging of the frame's tone table, so that no other kind's kernel gains its LDS.
+template <>
+__global__ __launch_bounds__(256) void frames_letterbox_minmax_kernel<SourceBayer>(const mi355_frame_bayer *table, int w, int h, uint32_t *mm)
+{
+    __shared__ float lut[256];
+    bayer_stage_tone(table[blockIdx.y].tone);
+    letterbox_minmax_body<SourceBayer>(table, w, h, mm, lut);
+}
+
+template <>
+__global__ __launch_bounds__(256) void frames_letterbox_quantize_kernel<SourceBayer>(const mi355_frame_bayer *table, int w, int h,
+                                                                                     const float *scale_dev, const uint8_t *zp_dev,
+                                                                                     uint8_t *out)
+{
+    __shared__ float lut[256];
+    bayer_stage_tone(table[blockIdx.y].tone);
+    letterbox_quantize_body<SourceBayer>(table, w, h, scale_dev, zp_dev, out, lut);
+}
+
 // Host-side check of the table's host mirror, before anything is launched: NULL when every frame can be served, else what is wrong
 // ("<Source::name>: <reason>", in a buffer of the calling thread).  The conditions every kind shares are here, a kind's own in its
 // Source::check_pointers and Source::check.
@@ -524,7 +672,7 @@ int frames_letterbox_quantize_launch(const Frame *table_dev, int B, int w, int h
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }
 
-// the five kinds behind the C-ABI (shim.hip)
+// the six kinds behind the C-ABI (shim.hip)
 #define FRAMES_KIND(S)                                                                                                                \
     template const char *frames_check<S, S::Frame>(const S::Frame *, int, int, int);                                                            \
     template int frames_letterbox_minmax_launch<S, S::Frame>(const S::Frame *, int, int, int, uint32_t *, hipStream_t);                         \
@@ -535,3 +683,4 @@ FRAMES_KIND(SourceYUV)
 FRAMES_KIND(SourcePlanar)
 FRAMES_KIND(SourcePacked)
 FRAMES_KIND(SourceP010)
+FRAMES_KIND(SourceBayer)

@@ -243,12 +243,13 @@ int image_minmax_seed_launch(uint32_t *mm, int B, hipStream_t st);
 int input_pairs_launch(const float *mm, int B, int shared, int32_t *entry, float *scale, uint8_t *zp, uint32_t *status, hipStream_t st);
 int l0_derive_launch(const mi355_l0_consts *consts, int activation, void *bank, long entry_bytes, int B, int shared, float *scale, uint8_t *zp,
                      float *kept_scale, uint8_t *kept_zp, uint32_t *status, hipStream_t st);
-// frames.hip: a kind of frames is a Source (Frame = its table entry in the C-ABI), instantiated there for these five
+// frames.hip: a kind of frames is a Source (Frame = its table entry in the C-ABI), instantiated there for these six
 struct SourceU8;      // mi355_frame_u8
 struct SourceYUV;     // mi355_frame_yuv
 struct SourcePlanar;  // mi355_frame_planar
 struct SourcePacked;  // mi355_frame_packed
 struct SourceP010;    // mi355_frame_p010
+struct SourceBayer;   // mi355_frame_bayer
 template <class Source, class Frame> const char *frames_check(const Frame *host, int B, int w, int h);  // NULL, or why the batch is refused
 template <class Source, class Frame> int frames_letterbox_minmax_launch(const Frame *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st);
 template <class Source, class Frame>

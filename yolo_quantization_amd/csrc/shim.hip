@@ -1177,6 +1177,19 @@ int mi355_jpeg_entropy(const mi355_jpeg_segment *table_dev, const mi355_jpeg_seg
     return jpeg_entropy_launch(table_dev, nsegments, subseq_bits, status_dev, (hipStream_t)stream);
 }
 
+int mi355_frames_bayer_letterbox_minmax(const mi355_frame_bayer *table_dev, const mi355_frame_bayer *table_host, int B, int w, int h,
+                                        float *minmax, void *stream)
+{
+    return frames_minmax<SourceBayer>("frames_bayer: letterbox_minmax: null", table_dev, table_host, B, w, h, minmax, stream);
+}
+
+int mi355_frames_bayer_letterbox_quantize(const mi355_frame_bayer *table_dev, const mi355_frame_bayer *table_host, int B, int w, int h,
+                                          const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream)
+{
+    return frames_quantize<SourceBayer>("frames_bayer: letterbox_quantize: null", table_dev, table_host, B, w, h, scale_dev, zp_dev, out_u8,
+                                        stream);
+}
+
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream)
 {
     if (!buf || !sum_dev || dwords < 0) return einval("checksum: null");

@@ -33,6 +33,11 @@
  * 4 * ((W + 1) / 2) * H bytes), in files named <anything>_<W>x<H>.<format>; network_frames_packed_input_gpu.
  * -frames p010 [-matrix ...] (raw P010 frames as hardware decoders deliver 10-bit video, NV12's shape with 16-bit little-endian
  * samples, in files named <anything>_<W>x<H>.p010; network_frames_p010_input_gpu).
+ * -frames rggb | bggr | grbg | gbrg | mono [-raw u8|u16|mipi10|mipi12] [-raw_shift N] [-tone file] (raw sensor frames, one sample per
+ * pixel behind a Bayer filter or none, in files named <anything>_<W>x<H>.<pattern>: W * H bytes (u8, the default), 2 * W * H (u16,
+ * little-endian, reduced to min(v >> N, 255)), CSI-2 RAW10 or RAW12 rows; -tone: a file of 768 bytes, the [3][256] tables every sample
+ * goes through by the colour of its site; network_frames_bayer_input_gpu; no -matrix; the output is that of -frames u8 on the
+ * demosaiced RGB frame mi355_yolo_int8.h defines).
  * -input_device (detector test: the input scales and layer 0's constants are derived on the device, no copy back and no wait inside
  * the input step -- set_input_quantization_on_device; the output is unchanged).
  * -jpeg_device (JPEG sources: their scans are entropy-decoded on the device too -- set_jpeg_entropy_on_device; the output is unchanged).
@@ -189,8 +194,9 @@ static void dump_layer(const char *dir, network *net, int i)
 /* -frames u8: the sources go up as interleaved bytes (network_frames_u8_input_gpu), no host float conversion; nv12 | nv21: they are raw
  * _<W>x<H>.nv12 files (network_frames_nv12_input_gpu); i420 | yv12 | i422 | i444: raw _<W>x<H>.<format> files
  * (network_frames_planar_input_gpu); rgba | bgra | argb | abgr | yuyv | uyvy | yvyu: raw _<W>x<H>.<format> files of one packed plane
- * (network_frames_packed_input_gpu); p010: raw _<W>x<H>.p010 files (network_frames_p010_input_gpu) */
-enum { FRAMES_NONE, FRAMES_U8, FRAMES_NV12, FRAMES_PLANAR, FRAMES_PACKED, FRAMES_P010 };
+ * (network_frames_packed_input_gpu); p010: raw _<W>x<H>.p010 files (network_frames_p010_input_gpu); rggb | bggr | grbg | gbrg | mono:
+ * raw _<W>x<H>.<pattern> files of sensor samples (network_frames_bayer_input_gpu) */
+enum { FRAMES_NONE, FRAMES_U8, FRAMES_NV12, FRAMES_PLANAR, FRAMES_PACKED, FRAMES_P010, FRAMES_BAYER };
 
 typedef struct {
     const char *datacfg, *cfgfile, *weightfile, *filename, *dumpdir, *packed_in, *packed_out;
@@ -199,6 +205,8 @@ typedef struct {
     int yuv_layout, yuv_matrix; /* MI355_YUV_NV12 / _NV21, MI355_YUV_BT601 .. _BT709_FULL (-matrix) */
     int planar_format;     /* MI355_PLANAR_I420 .. MI355_PLANAR_I444 */
     int packed_format;     /* MI355_PACKED_RGBA .. MI355_PACKED_YVYU */
+    int bayer_pattern, raw_sample, raw_shift; /* MI355_BAYER_RGGB .. _MONO, MI355_RAW_U8 .. _MIPI12 (-raw), 0..8 (-raw_shift) */
+    const uint8_t *tone;   /* -tone: the file's 768 bytes, or NULL */
     float thresh, hier_thresh;
     int batch, accum, store, use_graph, iters, gpu, boxes, quiet, inflight;
     int jpeg_device;       /* -jpeg_device: JPEG scans are entropy-decoded on the device (set_jpeg_entropy_on_device) */
@@ -333,7 +341,8 @@ static void feed_frames(const detect_job *job, network *net, char *const *paths,
             char why[1024];
             size_t bytes[2];
             const int kind = job->frames == FRAMES_NV12 ? RAW_FRAME_NV12 : job->frames == FRAMES_P010 ? RAW_FRAME_P010
-                           : job->frames == FRAMES_PACKED ? RAW_FRAME_RGBA + job->packed_format : job->planar_format;
+                           : job->frames == FRAMES_PACKED ? RAW_FRAME_RGBA + job->packed_format
+                           : job->frames == FRAMES_BAYER ? RAW_FRAME_SENSOR + 8 * job->raw_sample + job->bayer_pattern : job->planar_format;
             raw[b] = load_raw_frame_file(paths[b], kind, &imw[b], &imh[b], bytes, why, sizeof(why));
             if (!raw[b]) error(why);
             pl[0][b] = raw[b]; pl[1][b] = raw[b] + bytes[0]; pl[2][b] = pl[1][b] + bytes[1];
@@ -347,7 +356,11 @@ static void feed_frames(const detect_job *job, network *net, char *const *paths,
         network_frames_packed_input_gpu(net, pl[0], imw, imh, NULL, job->packed_format, job->yuv_matrix, 0);
     else if (job->frames == FRAMES_P010)
         network_frames_p010_input_gpu(net, pl[0], pl[1], imw, imh, NULL, NULL, job->yuv_matrix, 0);
-    else
+    else if (job->frames == FRAMES_BAYER) {
+        for (int b = 0; b < B; ++b) pl[1][b] = job->tone; /* one table for every slot: it goes up once */
+        network_frames_bayer_input_gpu(net, pl[0], imw, imh, NULL, job->bayer_pattern, job->raw_sample, job->raw_shift,
+                                       job->tone ? pl[1] : NULL, 0);
+    } else
         network_frames_u8_input_gpu(net, pl[0], imw, imh, NULL, MI355_FRAME_RGB, 0);
     /* on the device nothing waits for the uploads: the sources are freed below */
     if (net->input_on_device && mi355_stream_sync(net->stream)) error("sync");
@@ -556,7 +569,7 @@ int main(int argc, char **argv)
     if (argc < 2) {
         fprintf(stderr, "usage: %s detector test <data> <cfg> <weights> <image> [-thresh t] [-i gpu | -gpus a,b,..] [-batch B] "
                         "[-accum exact|ref-f32] [-parity wrap|saturate] [-dump dir] [-graph] [-n iters] [-boxes] "
-                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8|nv12|nv21|i420|yv12|i422|i444|rgba|bgra|argb|abgr|yuyv|uyvy|yvyu|p010] [-matrix bt601|bt601f|bt709|bt709f] [-input_device] [-jpeg_device]\n", argv[0]);
+                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8|nv12|nv21|i420|yv12|i422|i444|rgba|bgra|argb|abgr|yuyv|uyvy|yvyu|p010|rggb|bggr|grbg|gbrg|mono] [-matrix bt601|bt601f|bt709|bt709f] [-raw u8|u16|mipi10|mipi12] [-raw_shift N] [-tone file] [-input_device] [-jpeg_device]\n", argv[0]);
         return 0;
     }
     detect_job job;
@@ -594,11 +607,15 @@ int main(int argc, char **argv)
     for (int k = 0; k < 7; ++k)
         if (frames_s && 0 == strcmp(frames_s, packed_known[k])) { job.frames = FRAMES_PACKED; job.packed_format = k; }
     if (frames_s && 0 == strcmp(frames_s, "p010")) job.frames = FRAMES_P010;
+    static const char *const bayer_known[5] = {"rggb", "bggr", "grbg", "gbrg", "mono"}; /* MI355_BAYER_RGGB .. _MONO */
+    for (int k = 0; k < 5; ++k)
+        if (frames_s && 0 == strcmp(frames_s, bayer_known[k])) { job.frames = FRAMES_BAYER; job.bayer_pattern = k; }
     if (frames_s && !job.frames)
         error("-frames: `u8` (8-bit interleaved frames), `nv12` and `nv21` (raw video frames, files named _<W>x<H>.nv12), `i420`, `yv12`, "
               "`i422` and `i444` (raw planar frames, files named _<W>x<H>.<format>), `rgba`, `bgra`, `argb`, `abgr`, `yuyv`, `uyvy` and "
               "`yvyu` (raw packed frames, files named _<W>x<H>.<format>) and `p010` (raw 10-bit video frames, files named _<W>x<H>.p010) "
-              "are known");
+              "are known, and `rggb`, `bggr`, `grbg`, `gbrg` and `mono` (raw sensor frames, files named _<W>x<H>.<pattern>; -raw names "
+              "their sample layout)");
     job.yuv_layout = frames_s && 0 == strcmp(frames_s, "nv21") ? MI355_YUV_NV21 : MI355_YUV_NV12;
     job.yuv_matrix = MI355_YUV_BT601;
     if (matrix_s) {
@@ -611,6 +628,31 @@ int main(int argc, char **argv)
         if (job.frames != FRAMES_NV12 && job.frames != FRAMES_PLANAR && job.frames != FRAMES_PACKED && job.frames != FRAMES_P010)
             error("-matrix goes with -frames nv12 | nv21 | i420 | yv12 | i422 | i444 | yuyv | uyvy | yvyu | p010");
         job.yuv_matrix = m;
+    }
+    const char *raw_s = find_char_arg(argc, argv, "-raw", NULL), *shift_s = find_char_arg(argc, argv, "-raw_shift", NULL);
+    const char *tone_s = find_char_arg(argc, argv, "-tone", NULL);
+    job.raw_sample = MI355_RAW_U8; job.raw_shift = 0; job.tone = NULL;
+    if ((raw_s || shift_s || tone_s) && job.frames != FRAMES_BAYER) error("-raw, -raw_shift and -tone go with -frames rggb | bggr | grbg | gbrg | mono");
+    if (raw_s) {
+        static const char *const known[4] = {"u8", "u16", "mipi10", "mipi12"}; /* MI355_RAW_U8 .. MI355_RAW_MIPI12 */
+        int r = -1;
+        for (int k = 0; k < 4; ++k) if (0 == strcmp(raw_s, known[k])) r = k;
+        if (r < 0) error("-raw: u8 (the default), u16, mipi10 and mipi12 are known");
+        job.raw_sample = r;
+    }
+    if (shift_s) {
+        if (strlen(shift_s) != 1 || shift_s[0] < '0' || shift_s[0] > '8') error("-raw_shift: 0 .. 8");
+        job.raw_shift = shift_s[0] - '0';
+        if (job.raw_shift && job.raw_sample != MI355_RAW_U16) error("-raw_shift goes with -raw u16");
+    }
+    if (tone_s) { /* exactly 768 bytes: [3][256] */
+        static uint8_t table[769];
+        FILE *tf = fopen(tone_s, "rb");
+        if (!tf) file_error(tone_s);
+        const size_t got = fread(table, 1, sizeof(table), tf);
+        fclose(tf);
+        if (got != 768) error("-tone: the file must hold exactly 768 bytes, the [3][256] tables of R, G and B");
+        job.tone = table;
     }
     if (job.iters < 1) job.iters = 1;
     if (job.batch < 1) job.batch = 1;

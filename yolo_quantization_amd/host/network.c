@@ -902,12 +902,12 @@ void network_quantize_input_gpu(network *net)
 /* ------------------------------------------------------------------------------------------------- frame input
  * Two launches for the whole batch (frames.hip): letterbox + min / max, then letterbox + quantise; the float image exists in registers
  * only.  The (scale, zero point) branches are the float path's (input_pair_shared, input_pairs_per_image).  Interleaved RGB / BGR
- * frames, NV12 / NV21 frames, frames of three separate planes, packed 4-byte frames (RGBA .. ABGR, YUYV .. YVYU) and P010 frames differ
- * in their table entries, the planes they describe and the pair of C-ABI calls; the table, the staging arena and everything else are
+ * frames, NV12 / NV21 frames, frames of three separate planes, packed 4-byte frames (RGBA .. ABGR, YUYV .. YVYU), P010 frames and raw
+ * Bayer / mono sensor frames differ in their table entries, the planes they describe and the pair of C-ABI calls; the table, the staging arena and everything else are
  * shared. */
-enum { FR_U8, FR_YUV, FR_PLANAR, FR_PACKED, FR_P010 }; /* the kind of frames an entry point feeds (net->fr_kind) */
-static const size_t fr_entry_bytes[5] = {sizeof(mi355_frame_u8), sizeof(mi355_frame_yuv), sizeof(mi355_frame_planar),
-                                         sizeof(mi355_frame_packed), sizeof(mi355_frame_p010)};
+enum { FR_U8, FR_YUV, FR_PLANAR, FR_PACKED, FR_P010, FR_BAYER }; /* the kind of frames an entry point feeds (net->fr_kind) */
+static const size_t fr_entry_bytes[6] = {sizeof(mi355_frame_u8), sizeof(mi355_frame_yuv), sizeof(mi355_frame_planar),
+                                         sizeof(mi355_frame_packed), sizeof(mi355_frame_p010), sizeof(mi355_frame_bayer)};
 
 static void detb_free(network *net)
 {
@@ -994,11 +994,12 @@ typedef struct {
 static size_t fr_plane_bytes(const fr_plane *p) { return (p->rows - 1) * p->pitch + p->row_bytes; }
 
 /* Host frames go up to the arena: planes[b * np + k] is plane k of the frame in slot b.  Frame by frame, plane by plane, each at a
- * 256-byte boundary; one frame in several slots (`-batch B` of one image: the same pointers and geometry) goes up once. */
-static void fr_stage_frames(network *net, const fr_plane *planes, int np)
+ * 256-byte boundary; one frame in several slots (`-batch B` of one image: the same pointers and geometry) goes up once.  The arena
+ * is reserved with `extra` bytes behind the frames for what the caller stages after them; returns where those start. */
+static size_t fr_stage_frames_and(network *net, const fr_plane *planes, int np, size_t extra)
 {
     const int B = net->batch;
-    size_t need = 0, off = 0;
+    size_t need = extra, off = 0;
     for (int i = 0; i < B * np; ++i) need += fr_round(fr_plane_bytes(&planes[i]));
     fr_arena_reserve(net, need);
     for (int b = 0; b < B; ++b) {
@@ -1012,7 +1013,10 @@ static void fr_stage_frames(network *net, const fr_plane *planes, int np)
         }
         for (int i = 0; i < np; ++i) *f[i].dev = same ? *same[i].dev : fr_stage(net, f[i].host, fr_plane_bytes(&f[i]), &off);
     }
+    return off;
 }
+
+static void fr_stage_frames(network *net, const fr_plane *planes, int np) { (void)fr_stage_frames_and(net, planes, np, 0); }
 
 /* The common tail, the host mirror of the table filled with device pointers: table upload, min / max launch, the batch's one host
  * sync, the (scale, zero point) branch, quantiser launch, with the calls of the frames' kind. */
@@ -1025,6 +1029,7 @@ static void fr_finish(network *net)
     if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_planar_letterbox_minmax");
     else if (kind == FR_PACKED) check_mi355(mi355_frames_packed_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_packed_letterbox_minmax");
     else if (kind == FR_P010) check_mi355(mi355_frames_p010_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_p010_letterbox_minmax");
+    else if (kind == FR_BAYER) check_mi355(mi355_frames_bayer_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_bayer_letterbox_minmax");
     else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_yuv_letterbox_minmax");
     else check_mi355(mi355_frames_u8_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_u8_letterbox_minmax");
     const float *scale_dev;
@@ -1056,6 +1061,7 @@ static void fr_finish(network *net)
     if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_planar_letterbox_quantize");
     else if (kind == FR_PACKED) check_mi355(mi355_frames_packed_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_packed_letterbox_quantize");
     else if (kind == FR_P010) check_mi355(mi355_frames_p010_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_p010_letterbox_quantize");
+    else if (kind == FR_BAYER) check_mi355(mi355_frames_bayer_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_bayer_letterbox_quantize");
     else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_yuv_letterbox_quantize");
     else check_mi355(mi355_frames_u8_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_u8_letterbox_quantize");
 }
@@ -1205,6 +1211,57 @@ void network_frames_p010_input_gpu(network *net, const uint8_t *const *y, const 
         planes[2 * b + 1] = (fr_plane){uv[b], (size_t)cw4, (size_t)ch, (size_t)tab[b].pitch_uv, &tab[b].uv};
     }
     if (!frames_on_device) fr_stage_frames(net, planes, 2);
+    free(planes);
+    fr_finish(net);
+}
+
+/* the bytes of a tightly packed row of w raw samples, by layout */
+static int bayer_row_bytes(int sample, int w)
+{
+    return sample == MI355_RAW_U16 ? 2 * w : sample == MI355_RAW_MIPI10 ? 5 * ((w + 3) / 4) : sample == MI355_RAW_MIPI12 ? 3 * ((w + 1) / 2) : w;
+}
+
+void network_frames_bayer_input_gpu(network *net, const uint8_t *const *frames, const int *w, const int *h, const int *pitch, int pattern,
+                                    int sample, int shift, const uint8_t *const *tone, int frames_on_device)
+{
+    const int B = net->batch;
+    if (!frames || !w || !h) error("network_frames_bayer_input_gpu: null frames / sizes");
+    if (pattern < MI355_BAYER_RGGB || pattern > MI355_BAYER_MONO) error("network_frames_bayer_input_gpu: unknown pattern (MI355_BAYER_RGGB .. _MONO)");
+    if (sample < MI355_RAW_U8 || sample > MI355_RAW_MIPI12) error("network_frames_bayer_input_gpu: unknown sample layout (MI355_RAW_U8 .. _MIPI12)");
+    if (shift < 0 || shift > 8) error("network_frames_bayer_input_gpu: shift outside 0..8");
+    if (shift != 0 && sample != MI355_RAW_U16) error("network_frames_bayer_input_gpu: shift must be 0 without MI355_RAW_U16");
+    if (net->c != 3) error("network_frames_bayer_input_gpu: raw sensor frames feed 3-channel networks only");
+    for (int b = 0; b < B; ++b) {
+        if (!frames[b]) error("network_frames_bayer_input_gpu: null frame");
+        if (w[b] < 1 || h[b] < 1 || w[b] > 32768 || h[b] > 32768) error("network_frames_bayer_input_gpu: need 1 <= w, h <= 32768 for every frame");
+        if (pattern != MI355_BAYER_MONO && (w[b] < 2 || h[b] < 2)) error("network_frames_bayer_input_gpu: a Bayer frame needs w, h >= 2");
+        if (pitch && pitch[b] < bayer_row_bytes(sample, w[b]))
+            error("network_frames_bayer_input_gpu: need pitch >= w (U8), 2 * w (U16), 5 * ((w + 3) / 4) (MIPI10) or 3 * ((w + 1) / 2) (MIPI12) "
+                  "for every frame");
+    }
+    mi355_frame_bayer *tab = fr_begin(net, FR_BAYER);
+    fr_plane *planes = calloc((size_t)B, sizeof(fr_plane));
+    size_t tone_bytes = 0;
+    for (int b = 0; b < B; ++b) {
+        const int row = bayer_row_bytes(sample, w[b]);
+        memset(&tab[b], 0, sizeof(tab[b]));
+        tab[b].data = frames[b];
+        tab[b].tone = tone ? tone[b] : NULL;
+        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch = pitch ? pitch[b] : row;
+        tab[b].pattern = pattern; tab[b].sample = sample; tab[b].shift = shift;
+        planes[b] = (fr_plane){frames[b], (size_t)row, (size_t)h[b], (size_t)tab[b].pitch, &tab[b].data};
+        if (tab[b].tone) tone_bytes += fr_round(768);
+    }
+    if (!frames_on_device) { /* the tone tables go up behind the frames; a table several slots share goes up once */
+        size_t off = fr_stage_frames_and(net, planes, 1, tone_bytes);
+        for (int b = 0; b < B; ++b) {
+            if (!tone || !tone[b]) continue;
+            int same = -1;
+            for (int k = 0; k < b && same < 0; ++k)
+                if (tone[k] == tone[b]) same = k;
+            tab[b].tone = same >= 0 ? tab[same].tone : fr_stage(net, tone[b], 768, &off);
+        }
+    }
     free(planes);
     fr_finish(net);
 }

@@ -16,6 +16,11 @@ static const raw_kind kinds[N_KINDS] = {{RAW_FRAME_I420, ".i420", "i420", 1, 1, 
                                         {RAW_FRAME_YVYU, ".yvyu", "yvyu", 0, 0, 0, 1, 2},
                                         {RAW_FRAME_P010, ".p010", "P010", 1, 1, 1, 2, 0}}; /* NV12's shape, two bytes a sample */
 
+/* the raw sensor kinds, RAW_FRAME_SENSOR + 8 * layout + pattern: extensions by pattern (MI355_BAYER_RGGB .. _MONO), names of the
+ * sample layouts (MI355_RAW_U8 .. _MIPI12) */
+static const char *const sensor_ext[5] = {".rggb", ".bggr", ".grbg", ".gbrg", ".mono"};
+static const char *const sensor_layout[4] = {"u8", "u16", "mipi10", "mipi12"};
+
 /* decimal digits only (no blank, no sign), value 1..32768; returns the first character after them, or NULL */
 static const char *side(const char *s, int *out)
 {
@@ -32,8 +37,16 @@ static const char *side(const char *s, int *out)
 uint8_t *load_raw_frame_file(const char *path, int kind, int *w, int *h, size_t plane_bytes[2], char *why, size_t why_len)
 {
     const raw_kind *k = NULL;
+    raw_kind sensor;
+    char sensor_name[24];
     for (int i = 0; i < N_KINDS; ++i)
         if (kinds[i].kind == kind) k = &kinds[i];
+    const int pattern = (kind - RAW_FRAME_SENSOR) & 7, layout = (kind - RAW_FRAME_SENSOR) >> 3;
+    if (kind >= RAW_FRAME_SENSOR && pattern < 5 && layout < 4) { /* one plane of raw samples: the pattern names the extension */
+        snprintf(sensor_name, sizeof(sensor_name), "%s %s", sensor_ext[pattern] + 1, sensor_layout[layout]);
+        sensor = (raw_kind){kind, sensor_ext[pattern], sensor_name, 0, 0, 0, 1, 0};
+        k = &sensor;
+    }
     if (!k) {
         snprintf(why, why_len, "%s: raw planar files are i420, yv12, i422 or i444", path);
         return NULL;
@@ -47,7 +60,8 @@ uint8_t *load_raw_frame_file(const char *path, int kind, int *w, int *h, size_t 
         return NULL;
     }
     const size_t cw = (size_t)((fw + k->sx) >> k->sx) * (k->chroma_planes == 1 ? 2 : 1), ch = (size_t)((fh + k->sy) >> k->sy);
-    const size_t row = k->group_pixels ? 4 * (((size_t)fw + k->group_pixels - 1) / k->group_pixels) : (size_t)fw * k->sample_bytes;
+    size_t row = k->group_pixels ? 4 * (((size_t)fw + k->group_pixels - 1) / k->group_pixels) : (size_t)fw * k->sample_bytes;
+    if (k == &sensor) row = layout == 1 ? 2 * (size_t)fw : layout == 2 ? 5 * (((size_t)fw + 3) / 4) : layout == 3 ? 3 * (((size_t)fw + 1) / 2) : (size_t)fw;
     const size_t luma = row * fh, chroma = k->chroma_planes ? cw * ch * k->sample_bytes : 0, want = luma + (size_t)k->chroma_planes * chroma;
     FILE *f = fopen(path, "rb");
     if (!f) { snprintf(why, why_len, "%s: cannot open the file", path); return NULL; }
