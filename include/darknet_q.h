@@ -216,6 +216,16 @@ struct network {
     void *jpg_status_gpu;       /* one status word per segment of the last call */
     int *jpg_status_host;       /* their host copy */
     size_t jpg_status_bytes;
+    /* PNG input (network_png_decode_gpu): lazily allocated, grown when needed, freed with the network.  A replica owns its own. */
+    void *png_stage_host;       /* host staging block: segment table | image table | palettes | filtered bytes */
+    size_t png_stage_bytes;
+    void *png_in_gpu;           /* its device copy, the same layout */
+    size_t png_in_bytes;
+    void *png_rows_gpu;         /* the reconstructed passes mi355_png_unfilter writes */
+    size_t png_rows_bytes;
+    void *png_rgb_gpu;          /* the RGB frames of the last call */
+    size_t png_rgb_bytes;
+    int png_upload_pending;     /* an upload from the staging block may be in flight: wait before rewriting it */
     /* Batched box decode (network_yolo_detections_batch_gpu): lazily allocated, grown when needed, freed with the network and on
      * re-batch.  A replica owns its own. */
     int *detb_ints_gpu, *detb_ints_host; /* [2][batch] source sizes | counts [batch][nheads] | offsets [batch + 1] */
@@ -356,6 +366,30 @@ void set_jpeg_entropy_subseq_bits(network *net, int bits);
 struct dnq_jpeg_scan_list;
 int jpeg_scan_host(const uint8_t *data, size_t bytes, dnq_jpeg *out, struct dnq_jpeg_scan_list *scans, char *err, size_t errlen);
 void jpeg_scan_free(struct dnq_jpeg_scan_list *scans);
+/* PNG images, the mirror of the JPEG calls above.  The host half (yolo_quantization_amd/host/png.h: png_decode_host, png_info_host,
+ * png_free; no device needed) parses the chunks and inflates; the device does the rest -- scanline reconstruction, de-interlacing,
+ * bit-depth and palette expansion, the reduction to RGB (mi355_png_unfilter, mi355_png_to_rgb) -- and leaves the pixels
+ * stbi_load(file, .., 3) returns in the reference, byte for byte, for every colour type, bit depth, filter and for Adam7, as
+ * interleaved RGB frames in device memory.
+ *
+ * network_png_decode_gpu: data[b], bytes[b] are the n images' files in host memory (slots that name the same bytes are decoded once
+ * and share a frame).  All n are parsed and inflated first; if one fails the call returns MI355_EINVAL, network_png_last_error() (a
+ * buffer of the calling thread) names the slot and the reason ("png slot 2: invalid filter") and nothing has been launched or
+ * uploaded.  Otherwise the segment table, the image table, the palettes and the filtered bytes go up from one staging block in one
+ * copy on the network's stream, the two launches follow, and rgb_dev[b], w[b], h[b], pitch[b] describe image b's frame: device memory
+ * the network owns, valid until the next call (on the network's stream: the call only enqueues and waits for nothing -- "invalid
+ * filter" is found on the host).  The staging block is not rewritten before the upload that read it has completed.
+ *
+ * network_frames_png_input_gpu: the above for net->batch images, then network_frames_u8_input_gpu on those device frames: both scale
+ * modes, set_input_quantization_on_device, replicas and graph replay are that function's.  3-channel networks only. */
+typedef struct dnq_png dnq_png;
+int png_decode_host(const uint8_t *data, size_t bytes, dnq_png *out, char *err, size_t errlen);
+int png_info_host(const uint8_t *data, size_t bytes, dnq_png *out, char *err, size_t errlen);
+void png_free(dnq_png *p);
+int network_png_decode_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int n, uint8_t **rgb_dev, int *w, int *h,
+                           int *pitch);
+int network_frames_png_input_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int *w, int *h);
+const char *network_png_last_error(void);
 /* The same step for raw sensor frames: one plane with one sample per pixel behind a Bayer colour filter (pattern: MI355_BAYER_RGGB,
  * _BGGR, _GRBG, _GBRG) or none (MI355_BAYER_MONO), as machine-vision cameras (BayerRG8 .., Mono8 .. Mono16) and MIPI CSI-2 sensors
  * without an ISP (RAW10, RAW12) deliver them.  sample: MI355_RAW_U8 (pitch[b] >= w[b]), MI355_RAW_U16 (little-endian, reduced to

@@ -665,6 +665,50 @@ typedef struct mi355_jpeg_segment {   /* 144 bytes */
 } mi355_jpeg_segment;
 int mi355_jpeg_entropy(const mi355_jpeg_segment *table_dev, const mi355_jpeg_segment *table_host, int nsegments, int subseq_bits,
                        int *status_dev, void *stream);
+/* The device half of a PNG decoder: everything after the inflate, for a whole batch in two launches, leaving interleaved RGB frames in
+ * device memory that the u8 calls above take as they are.  The bytes are the ones stb_image v2.19 returns as the reference compiles it
+ * (ref: src/stb_image.h:4307-4931; load_image_color -> stbi_load(.., 3)); PNG is lossless, so this holds for every colour type, bit
+ * depth, filter and for Adam7.  The host parses the chunks and inflates (yolo_quantization_amd/host/png.h).
+ *
+ * mi355_png_unfilter: one launch for every SEGMENT of a batch; a segment is one pass of one image (a file that is not interlaced is one
+ * segment).  `filtered`: rows rows of 1 + row_bytes bytes, each led by its filter byte 0..4 (None, Sub, Up, Average, Paeth; the host
+ * has refused anything else, a larger value reconstructs as None); `out`: the reconstructed rows, row_bytes apart.  bpp is the filter
+ * unit: channels * depth / 8 for depths 8 and 16, 1 for depths 1, 2 and 4, where the filters run over the packed bytes (ref :4364-4367);
+ * row_bytes is a multiple of it.  The row above the first row is zero (ref :4372, first_row_filter).  One wave per segment, four
+ * segments per workgroup: lane r owns row y0 + r of a band of 64 rows and is r units behind the lane above it, so that `up` arrives
+ * from that lane by one cross-lane move per step; see DESIGN.md.  Any alignment of filtered and out.
+ *
+ * mi355_png_to_rgb: one launch for the batch, one thread per output pixel.  Image b is w x h pixels, rows `pitch` >= 3 * w bytes apart
+ * at `rgb` (any alignment).  The pixel's pass and position in it follow stb's xorig / yorig / xspc / yspc (ref :4554-4557); pass[k] is
+ * the reconstructed pass k (0..6; a plain image reads pass[0]; a pass without pixels may be null), its rows ceil(pw * channels * depth
+ * / 8) bytes apart with pw the pass's width.  Depths 1 / 2 / 4 are unpacked MSB first, grey scaled by 0xff / 0x55 / 0x11, palette
+ * indices not scaled; depth 16 keeps the first (high) byte of each sample; grey is replicated, alpha dropped, a palette index becomes
+ * its entry of `palette` (R, G, B per entry) and an index at or above pal_len gives (0, 0, 0).
+ *
+ * The contract of the frame calls: table_host mirrors table_dev and is validated before anything is launched (null pointers, bpp outside
+ * {1, 2, 3, 4, 6, 8}, a zero size, sizes above 32768 pixels, row_bytes no multiple of bpp, pitch < 3 * w, an unknown depth / colour
+ * pair, a palette image without palette): MI355_EINVAL with a message that starts "png_unfilter:" / "png_to_rgb:", nothing is written.
+ * New structs and new calls: MI355_ABI_VERSION is unchanged. */
+typedef struct mi355_png_segment {    /* 32 bytes */
+    const uint8_t *filtered;          /* DEVICE: rows * (1 + row_bytes) bytes */
+    uint8_t *out;                     /* DEVICE: rows * row_bytes bytes */
+    int row_bytes, rows;
+    int bpp;                          /* 1, 2, 3, 4, 6 or 8 */
+    int reserved;                     /* zero */
+} mi355_png_segment;
+typedef struct mi355_png_image {      /* 104 bytes */
+    uint8_t *rgb;                     /* DEVICE: h rows of w interleaved RGB pixels */
+    const uint8_t *palette;           /* DEVICE: [256][3], colour type 3 only */
+    const uint8_t *pass[7];           /* DEVICE: the reconstructed passes (mi355_png_segment.out) */
+    int w, h, pitch;
+    int depth;                        /* 1, 2, 4, 8, 16 */
+    int color;                        /* 0 grey, 2 RGB, 3 palette, 4 grey + alpha, 6 RGBA */
+    int interlace;                    /* 0, or 1: Adam7 */
+    int pal_len;
+    int reserved;                     /* zero */
+} mi355_png_image;
+int mi355_png_unfilter(const mi355_png_segment *table_dev, const mi355_png_segment *table_host, int nsegments, void *stream);
+int mi355_png_to_rgb(const mi355_png_image *table_dev, const mi355_png_image *table_host, int B, void *stream);
 /* *sum_dev += an order-independent 64-bit checksum of `dwords` 32-bit words at buf (device pointers; zero *sum_dev first).  The
  * host's determinism self-check compares it between passes over the same input (network_selfcheck, darknet_q.h). */
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream);

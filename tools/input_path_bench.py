@@ -43,6 +43,15 @@ quality 85 before the clock starts), per scale mode three variants alternating w
 and, once, the stages of the jpeg variant on their own through the same calls: `host_entropy_ms` (jpeg_decode_host over the batch, host
 clock, one thread), `upload_ms`, `idct_ms`, `to_rgb_ms` (HIP events around one copy of all coefficients and tables and around each
 launch; medians of `iters`).  Before timing, the jpeg network's uint8 input, scales and zero points are compared with the u8 network's.
+
+--png times the PNG input path in the same way: batch 64 of 640 x 480 8-bit RGB files (the same pictures, filtered with Paeth and
+deflated by zlib at its default level before the clock starts), per scale mode two variants alternating within a repeat:
+  png     network_frames_png_input_gpu: host chunk parse + inflate of the batch, one upload of tables and filtered bytes,
+          mi355_png_unfilter, mi355_png_to_rgb, then the u8 step on the frames where they lie
+  u8      network_frames_u8_input_gpu on the decoded RGB frames in host memory
+and, once, the stages on their own: `host_inflate_ms` (png_decode_host over the batch, host clock, one thread), `upload_ms`,
+`unfilter_ms`, `to_rgb_ms` (HIP events around one copy of all filtered bytes and around each launch; medians of `iters`).  Before
+timing, the png network's uint8 input, scales and zero points are compared with the u8 network's.
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -294,6 +303,135 @@ def jpeg_stages(files, ev, iters):
     return res, frames
 
 
+class PngVariant(JpegVariant):
+    def step(self):
+        if self.net.H.network_frames_png_input_gpu(self.net.h, self.ptrs, self.sizes, self.w, self.h) != 0:
+            sys.exit(self.net.H.network_png_last_error().decode())
+
+
+def make_pngs(B, w, h):
+    """the pictures of make_jpegs as 8-bit RGB PNG files, every row under the Paeth filter; and the pictures"""
+    import struct
+    import zlib
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data))
+
+    files, pics = [], []
+    y, x = np.mgrid[0:h, 0:w]
+    for b in range(B):
+        rng = np.random.default_rng(100 + b)
+        base = np.stack([(x * 255) // (w - 1), (y * 255) // (h - 1), ((x + y + 7 * b) * 255 // (w + h)) % 256], axis=-1)
+        pic = np.clip(base + rng.integers(-25, 26, (h, w, 3)), 0, 255).astype(np.uint8)
+        r = pic.reshape(h, 3 * w).astype(np.int32)
+        a, up, c = np.zeros_like(r), np.zeros_like(r), np.zeros_like(r)
+        a[:, 3:], up[1:], c[1:, 3:] = r[:, :-3], r[:-1], r[:-1, :-3]
+        pa, pb, pc = np.abs(up - c), np.abs(a - c), np.abs(a + up - 2 * c)
+        pred = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, up, c))
+        rows = np.concatenate([np.full((h, 1), 4, np.uint8), ((r - pred) & 255).astype(np.uint8)], axis=1)
+        files.append(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(rows.tobytes()))
+                     + chunk(b"IEND", b""))
+        pics.append(pic)
+    return files, pics
+
+
+def png_stages(files, ev, iters):
+    """the stages of one batch on the default stream: host parse + inflate, one upload, the two launches"""
+    S, H = binding.shim(), binding.host()
+    host_ms = []
+    for _ in range(max(3, iters // 4)):
+        t0 = time.perf_counter()
+        for f in files:
+            p = binding.DnqPng()
+            if H.png_decode_host(f, len(f), C.byref(p), None, 0) != 0:
+                sys.exit("a generated file was refused")
+            H.png_free(C.byref(p))
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+    dec = [binding.png_scanlines(f) for f in files]
+    stage = np.concatenate([d["filtered"] for d in dec])
+    dev = binding.DevBuf(stage.nbytes)
+    nseg = sum(len(d["passes"]) for d in dec)
+    rows = binding.DevBuf(sum(q["rows"] * q["row_bytes"] for d in dec for q in d["passes"]))
+    ts = (binding.PngSegment * nseg)()
+    ti = (binding.PngImage * len(dec))()
+    at, out_at, k, rgb = 0, 0, 0, []
+    for b, d in enumerate(dec):
+        pitch = (3 * d["w"] + 3) & ~3
+        rgb.append(binding.DevBuf(d["h"] * pitch))
+        ti[b].rgb, ti[b].w, ti[b].h, ti[b].pitch = rgb[-1].ptr, d["w"], d["h"], pitch
+        ti[b].depth, ti[b].color, ti[b].interlace = d["depth"], d["color"], d["interlace"]
+        for q in d["passes"]:
+            ts[k].filtered, ts[k].out = dev.ptr.value + at + q["offset"], rows.ptr.value + out_at
+            ts[k].row_bytes, ts[k].rows, ts[k].bpp = q["row_bytes"], q["rows"], d["bpp"]
+            ti[b].pass_[q["index"]] = ts[k].out
+            out_at, k = out_at + q["rows"] * q["row_bytes"], k + 1
+        at += d["filtered_bytes"]
+    tsd = binding.DevBuf.from_numpy(np.frombuffer(bytes(ts), np.uint8))
+    tid = binding.DevBuf.from_numpy(np.frombuffer(bytes(ti), np.uint8))
+    calls = {"upload_ms": lambda: S.mi355_h2d(dev.ptr, stage.ctypes.data, stage.nbytes, None),
+             "unfilter_ms": lambda: S.mi355_png_unfilter(tsd.ptr, ts, nseg, None),
+             "to_rgb_ms": lambda: S.mi355_png_to_rgb(tid.ptr, ti, len(dec), None)}
+    res = {"host_inflate_ms": round(float(np.median(host_ms)), 4), "filtered_bytes": int(stage.nbytes), "segments": int(nseg),
+           "file_bytes": int(sum(len(f) for f in files))}
+    for name, call in calls.items():
+        ms = []
+        for _ in range(iters + 2):
+            binding.check(S.mi355_stream_sync(None), "sync")
+            binding.check(S.mi355_event_record(ev.a, None), "record")
+            binding.check(call(), name)
+            binding.check(S.mi355_event_record(ev.b, None), "record")
+            binding.check(S.mi355_stream_sync(None), "sync")
+            ms.append(ev.ms())
+        res[name] = round(float(np.median(ms[2:])), 4)
+    frames = []
+    for b, d in enumerate(dec):
+        pitch = (3 * d["w"] + 3) & ~3
+        frames.append(rgb[b].to_numpy(np.uint8, d["h"] * pitch).reshape(d["h"], pitch)[:, :3 * d["w"]].reshape(d["h"], d["w"], 3).copy())
+    for b in rgb + [dev, rows, tsd, tid]:
+        b.free()
+    return res, frames
+
+
+def png_main(a, wts, ev):
+    sw, sh = (int(v) for v in a.src.split("x"))
+    files, pics = make_pngs(a.batch, sw, sh)
+    res = {}
+    res["stages"], frames = png_stages(files, ev, a.iters)
+    res["frames_identical_to_the_pictures"] = bool(all(np.array_equal(f, p) for f, p in zip(frames, pics)))
+    for mode in ("shared", "per_image"):
+        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("png", "u8")}
+        for n in nets.values():
+            n.set_input_per_image(mode == "per_image")
+        var = {"png": PngVariant(nets["png"], files), "u8": FramesVariant(nets["u8"], frames)}
+        for _ in range(a.warmup):
+            for v in var.values():
+                v.step()
+        out = {k: {"device_ms": [], "wall_ms": [], "call_ms": []} for k in var}
+        same = same_input(nets["png"], nets["u8"])
+        for _ in range(a.repeats):
+            for k, v in var.items():  # alternating
+                for name, x in zip(("device_ms", "wall_ms", "call_ms"), timed(v, ev, a.iters)):
+                    out[k][name].append(round(x, 4))
+        for k in var:
+            out[k]["median"] = {m: float(np.median(out[k][m])) for m in ("device_ms", "wall_ms", "call_ms")}
+        out["png_identical_to_u8_on_the_decoded_frames"] = same
+        res[mode] = out
+        for n in nets.values():
+            n.close()
+    cpu = "unknown"
+    try:
+        with open("/proc/cpuinfo") as f:
+            cpu = next(line.split(":", 1)[1].strip() for line in f if line.startswith("model name"))
+    except (OSError, StopIteration):
+        pass
+    res["config"] = {"cfg": "yolov3-tiny_quant.cfg", "batch": a.batch, "src": a.src, "format": "RGB 8-bit, Paeth on every row, zlib level 6",
+                     "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "host_cpu": cpu,
+                     "values": "per repeat the median of `iters` steps: device_ms between HIP events around the step, wall_ms host clock to the "
+                               "end of a stream synchronise after it, call_ms host clock inside the call; `median` over the repeats; stages: "
+                               "see the module text"}
+    print(json.dumps(res))
+
+
 SUBSEQ_BITS = (128, 256, 512, 1024, 2048, 4096, 8192)
 
 
@@ -426,6 +564,7 @@ def main():
     ap.add_argument("--src", default="640x480")
     ap.add_argument("--on-device", action="store_true", help="compare the synchronous step with the on-device one instead (see the module text)")
     ap.add_argument("--jpeg", action="store_true", help="time the JPEG input path beside the u8 path on the decoded frames instead (see the module text)")
+    ap.add_argument("--png", action="store_true", help="time the PNG input path beside the u8 path on the decoded frames instead (see the module text)")
     ap.add_argument("--subseq-bits", type=int, default=1024, help="--jpeg: bits a lane decodes per round in the jpeg_device variant")
     a = ap.parse_args()
     binding.init(0)  # raises without a gfx950: nothing is timed on a CPU
@@ -433,6 +572,9 @@ def main():
     synth.synth_weights(CFG, wts, seed=5)
     if a.jpeg:
         jpeg_main(a, wts, Events())
+        return
+    if a.png:
+        png_main(a, wts, Events())
         return
     sw, sh = (int(v) for v in a.src.split("x"))
     if sw % 2:

@@ -163,6 +163,31 @@ class DnqJpegScanList(C.Structure):
                 ("bytes", C.POINTER(C.c_uint8)), ("nbytes", C.c_size_t), ("cap_segs", C.c_int), ("cap_huff", C.c_int), ("cap_bytes", C.c_size_t)]
 
 
+class PngSegment(C.Structure):
+    """mi355_png_segment: one pass of one image of mi355_png_unfilter's table (device pointers)."""
+    _fields_ = [("filtered", C.c_void_p), ("out", C.c_void_p), ("row_bytes", C.c_int), ("rows", C.c_int), ("bpp", C.c_int),
+                ("reserved", C.c_int)]
+
+
+class PngImage(C.Structure):
+    """mi355_png_image: one image of mi355_png_to_rgb's table (device pointers)."""
+    _fields_ = [("rgb", C.c_void_p), ("palette", C.c_void_p), ("pass_", C.c_void_p * 7), ("w", C.c_int), ("h", C.c_int),
+                ("pitch", C.c_int), ("depth", C.c_int), ("color", C.c_int), ("interlace", C.c_int), ("pal_len", C.c_int),
+                ("reserved", C.c_int)]
+
+
+class DnqPngPass(C.Structure):
+    _fields_ = [("w", C.c_int), ("rows", C.c_int), ("row_bytes", C.c_int), ("index", C.c_int), ("offset", C.c_size_t)]
+
+
+class DnqPng(C.Structure):
+    """dnq_png (yolo_quantization_amd/host/png.h): what the host half of the PNG decoder returns."""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("depth", C.c_int), ("color", C.c_int), ("interlace", C.c_int), ("channels", C.c_int),
+                ("bpp", C.c_int), ("pal_len", C.c_int), ("has_trns", C.c_int), ("npasses", C.c_int), ("pass_", DnqPngPass * 7),
+                ("palette", C.c_uint8 * 768), ("filtered_bytes", C.c_size_t), ("filtered", C.POINTER(C.c_uint8))]
+
+
+PNG_MAX_DIM = 32768  # DNQ_PNG_MAX_DIM
 JPEG_MODES = ("ycbcr", "rgb", "grey")
 JPEG_ENTROPY_ERRORS = {1: "bad huffman code", 2: "bad DC category", 3: "coefficient index past the end of the block"}
 
@@ -239,6 +264,9 @@ def shim():
         if hasattr(L, "mi355_jpeg_idct"):  # MI355_LIB_DIR may name an older build of the libraries (A/B runs): calling them there raises
             L.mi355_jpeg_idct.argtypes = [vp, C.POINTER(JpegPlane), ci, vp]
             L.mi355_jpeg_to_rgb.argtypes = [vp, C.POINTER(JpegImage), ci, vp]
+        if hasattr(L, "mi355_png_unfilter"):
+            L.mi355_png_unfilter.argtypes = [vp, C.POINTER(PngSegment), ci, vp]
+            L.mi355_png_to_rgb.argtypes = [vp, C.POINTER(PngImage), ci, vp]
         if hasattr(L, "mi355_jpeg_entropy"):
             L.mi355_jpeg_entropy.argtypes = [vp, C.POINTER(JpegSegment), ci, ci, vp, vp]
         L.mi355_frames_u8_letterbox_minmax.argtypes = [vp, C.POINTER(FrameU8), ci, ci, ci, vp, vp]
@@ -504,6 +532,16 @@ def host():
                                                   C.POINTER(ci), C.POINTER(ci)]
             L.network_frames_jpeg_input_gpu.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(ci), C.POINTER(ci)]
             L.network_jpeg_last_error.restype = C.c_char_p
+        if hasattr(L, "png_decode_host"):
+            L.png_decode_host.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(DnqPng), C.c_char_p, C.c_size_t]
+            L.png_info_host.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(DnqPng), C.c_char_p, C.c_size_t]
+            L.png_free.argtypes = [C.POINTER(DnqPng)]
+            L.png_free.restype = None
+            L.png_inflate_host.argtypes = [C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t]
+            L.network_png_decode_gpu.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), ci, C.POINTER(vp), C.POINTER(ci),
+                                                 C.POINTER(ci), C.POINTER(ci)]
+            L.network_frames_png_input_gpu.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.POINTER(ci), C.POINTER(ci)]
+            L.network_png_last_error.restype = C.c_char_p
         if hasattr(L, "jpeg_scan_host"):
             L.jpeg_scan_host.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(DnqJpeg), C.POINTER(DnqJpegScanList), C.c_char_p, C.c_size_t]
             L.jpeg_scan_free.argtypes = [C.POINTER(DnqJpegScanList)]
@@ -922,6 +960,178 @@ def jpeg_decode(data, net=None):
     return out if many else out[0]
 
 
+class PngError(ValueError):
+    """A PNG the decoder refuses; the message is the decoder's (with "png slot <b>: " in front where a batch was decoded)."""
+
+
+def _png_host(data, headers_only):
+    p = DnqPng()
+    err = C.create_string_buffer(256)
+    fn = host().png_info_host if headers_only else host().png_decode_host
+    if fn(data, len(data), C.byref(p), err, len(err)) != 0:
+        raise PngError(err.value.decode())
+    return p
+
+
+def _png_dict(p):
+    return {"w": p.w, "h": p.h, "depth": p.depth, "color": p.color, "interlace": p.interlace, "channels": p.channels, "bpp": p.bpp,
+            "pal_len": p.pal_len, "has_trns": bool(p.has_trns), "palette": np.array(p.palette, np.uint8).reshape(256, 3),
+            "filtered_bytes": p.filtered_bytes,
+            "passes": [{k: getattr(p.pass_[i], k) for k in ("w", "rows", "row_bytes", "index", "offset")} for i in range(p.npasses)]}
+
+
+def png_info(data):
+    """The headers of a PNG (bytes or a path) as a dict: size, depth, colour type, interlace flag, channels, filter unit "bpp", the
+    palette ([256][3], zero beyond "pal_len") and "passes", the layout of the filtered stream: per pass that holds pixels its width,
+    rows, row bytes, Adam7 index and offset.  Host only, nothing is inflated; raises PngError with the decoder's message."""
+    return _png_dict(_png_host(_jpeg_bytes(data), True))
+
+
+def png_scanlines(data):
+    """The host half of the decoder on a PNG (bytes or a path): png_info's dict plus "filtered", the inflated bytes (uint8
+    [filtered_bytes]: per pass, rows of one filter byte and row_bytes bytes).  Host only."""
+    p = _png_host(_jpeg_bytes(data), False)
+    try:
+        d = _png_dict(p)
+        d["filtered"] = np.ctypeslib.as_array(p.filtered, shape=(p.filtered_bytes,)).copy()
+        return d
+    finally:
+        host().png_free(C.byref(p))
+
+
+def png_inflate(z, cap):
+    """png_inflate_host: the decoder's inflate on a zlib stream, at most cap bytes of output.  Host only."""
+    out = np.empty(max(cap, 1), np.uint8)
+    n = C.c_size_t(0)
+    err = C.create_string_buffer(256)
+    if host().png_inflate_host(bytes(z), len(z), out.ctypes.data, cap, C.byref(n), err, len(err)) != 0:
+        raise PngError(err.value.decode())
+    return out[:n.value].tobytes()
+
+
+def png_unfilter(segments, src_offset=0, dst_offset=0):
+    """mi355_png_unfilter on built inputs: segments is a list of (filtered uint8 [rows][1 + row_bytes], bpp); one launch for all of
+    them.  src_offset / dst_offset: bytes by which every segment's source / destination is moved off its allocation's alignment.
+    Returns the reconstructed uint8 [rows][row_bytes] per segment; the bytes around a destination must come back as they were."""
+    L = shim()
+    table = (PngSegment * len(segments))()
+    keep = []
+    for i, (filt, bpp) in enumerate(segments):
+        filt = np.ascontiguousarray(filt, np.uint8)
+        rows, rb = filt.shape[0], filt.shape[1] - 1
+        src = DevBuf.from_numpy(np.concatenate([np.zeros(src_offset, np.uint8), filt.ravel()]))
+        dst = DevBuf.from_numpy(np.full(dst_offset + rows * rb + 16, 0xA5, np.uint8))
+        keep.append((src, dst))
+        table[i].filtered, table[i].out = src.ptr.value + src_offset, dst.ptr.value + dst_offset
+        table[i].row_bytes, table[i].rows, table[i].bpp = rb, rows, bpp
+    tdev = DevBuf.from_numpy(np.frombuffer(bytes(table), np.uint8))
+    try:
+        check(L.mi355_png_unfilter(tdev.ptr, table, len(segments), None), "mi355_png_unfilter")
+        check(L.mi355_stream_sync(None), "sync")
+        res = []
+        for i, (src, dst) in enumerate(keep):
+            n = table[i].rows * table[i].row_bytes
+            raw = dst.to_numpy(np.uint8, dst_offset + n + 16)
+            if not ((raw[:dst_offset] == 0xA5).all() and (raw[dst_offset + n:] == 0xA5).all()):
+                raise MI355Error("mi355_png_unfilter wrote outside a segment's rows")
+            res.append(raw[dst_offset:dst_offset + n].reshape(table[i].rows, table[i].row_bytes).copy())
+        return res
+    finally:
+        for src, dst in keep:
+            src.free()
+            dst.free()
+        tdev.free()
+
+
+def png_to_rgb(images, pitch_pad=0):
+    """mi355_png_to_rgb on built inputs: images is a list of dicts {"w", "h", "depth", "color", "interlace", "passes": {index: uint8
+    [rows][row_bytes] reconstructed rows} (a plain image: {0: ...}), "palette": uint8 [n][3] (colour type 3), "pal_len" (default: n)};
+    one launch for all of them.  pitch_pad: bytes added to every output row's 3 * w.  Returns uint8 [h][w][3] per image; the pad bytes
+    must come back as they were (0xA5)."""
+    L = shim()
+    table = (PngImage * len(images))()
+    keep = []
+    for i, im in enumerate(images):
+        w, h = im["w"], im["h"]
+        pitch = 3 * w + pitch_pad
+        out = DevBuf.from_numpy(np.full(max(h * pitch, 1), 0xA5, np.uint8))
+        bufs = [out]
+        t = table[i]
+        t.rgb, t.w, t.h, t.pitch = out.ptr, w, h, pitch
+        t.depth, t.color, t.interlace = im["depth"], im["color"], im.get("interlace", 0)
+        if im.get("palette") is not None:
+            pal = np.zeros((256, 3), np.uint8)
+            src = np.asarray(im["palette"], np.uint8).reshape(-1, 3)
+            pal[:len(src)] = src
+            b = DevBuf.from_numpy(pal)
+            bufs.append(b)
+            t.palette, t.pal_len = b.ptr, im.get("pal_len", len(src))
+        for k, rows in im["passes"].items():
+            b = DevBuf.from_numpy(np.ascontiguousarray(rows, np.uint8))
+            bufs.append(b)
+            t.pass_[k] = b.ptr
+        keep.append(bufs)
+    tdev = DevBuf.from_numpy(np.frombuffer(bytes(table), np.uint8))
+    try:
+        check(L.mi355_png_to_rgb(tdev.ptr, table, len(images), None), "mi355_png_to_rgb")
+        check(L.mi355_stream_sync(None), "sync")
+        res = []
+        for i, bufs in enumerate(keep):
+            w, h, pitch = table[i].w, table[i].h, table[i].pitch
+            raw = bufs[0].to_numpy(np.uint8, h * pitch).reshape(h, pitch)
+            if pitch_pad and not (raw[:, 3 * w:] == 0xA5).all():
+                raise MI355Error("mi355_png_to_rgb wrote into the padding of a row")
+            res.append(raw[:, :3 * w].reshape(h, w, 3).copy())
+        return res
+    finally:
+        for bufs in keep:
+            for b in bufs:
+                b.free()
+        tdev.free()
+
+
+def png_decode(data, net=None):
+    """Decode a PNG (bytes or a path) to uint8 [h][w][3], the pixels the reference's stbi_load(.., 3) returns: chunk parse and inflate
+    on the host, everything else on the device.  A list of items is decoded as one batch (two launches) and a list comes back.  net: a
+    Net whose buffers and stream serve the call (network_png_decode_gpu); without one the C-ABI calls run on the default stream."""
+    many = isinstance(data, (list, tuple))
+    items = list(data) if many else [data]
+    out = []
+    if net is not None:
+        datas, ptrs, sizes = _jpeg_args(items)
+        n = len(items)
+        rgb, ws, hs, ps = (C.c_void_p * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        if net.H.network_png_decode_gpu(net.h, ptrs, sizes, n, rgb, ws, hs, ps) != 0:
+            raise PngError(net.H.network_png_last_error().decode())
+        net.sync()
+        for b in range(n):
+            raw = np.empty(hs[b] * ps[b], np.uint8)
+            check(shim().mi355_d2h(raw.ctypes.data, rgb[b], raw.nbytes, None), "d2h")
+            check(shim().mi355_stream_sync(None), "sync")
+            out.append(raw.reshape(hs[b], ps[b])[:, :3 * ws[b]].reshape(hs[b], ws[b], 3).copy())
+        return out if many else out[0]
+    decoded = []
+    for b, it in enumerate(items):
+        try:
+            decoded.append(png_scanlines(it))
+        except PngError as e:
+            raise PngError(f"png slot {b}: {e}") from None
+    segs = []
+    for d in decoded:
+        for q in d["passes"]:
+            n = q["rows"] * (q["row_bytes"] + 1)
+            segs.append((d["filtered"][q["offset"]:q["offset"] + n].reshape(q["rows"], q["row_bytes"] + 1), d["bpp"]))
+    rows = png_unfilter(segs)
+    images, at = [], 0
+    for d in decoded:
+        passes = {q["index"]: rows[at + k] for k, q in enumerate(d["passes"])}
+        at += len(d["passes"])
+        images.append({"w": d["w"], "h": d["h"], "depth": d["depth"], "color": d["color"], "interlace": d["interlace"], "passes": passes,
+                       "palette": d["palette"] if d["color"] == 3 else None, "pal_len": d["pal_len"]})
+    out = png_to_rgb(images)
+    return out if many else out[0]
+
+
 class Net:
     """The darknet host network (libdarknet_q.so): load_network -> prep -> forward_network_gpu."""
 
@@ -1112,6 +1322,18 @@ class Net:
         ws, hs = (C.c_int * B)(), (C.c_int * B)()
         if self.H.network_frames_jpeg_input_gpu(self.h, ptrs, sizes, ws, hs) != 0:
             raise JpegError(self.H.network_jpeg_last_error().decode())
+        return [(ws[b], hs[b]) for b in range(B)]
+
+    def prepare_from_png(self, items):
+        """PNG input path (network_frames_png_input_gpu): every item (the bytes of a PNG file, or a path) is parsed and inflated on the
+        host and finished on the device; the RGB frames stay there and feed the 8-bit frame path.  Returns [(w, h), ...], the images'
+        sizes for the detection calls.  Raises PngError naming the slot when an image is refused; nothing has been launched then."""
+        assert len(items) == self.batch
+        B = self.batch
+        datas, ptrs, sizes = _jpeg_args(items)
+        ws, hs = (C.c_int * B)(), (C.c_int * B)()
+        if self.H.network_frames_png_input_gpu(self.h, ptrs, sizes, ws, hs) != 0:
+            raise PngError(self.H.network_png_last_error().decode())
         return [(ws[b], hs[b]) for b in range(B)]
 
     def _pull_input(self):

@@ -261,6 +261,11 @@ const char *jpeg_idct_check(const mi355_jpeg_plane *host, int nplanes);
 int jpeg_idct_launch(const mi355_jpeg_plane *table_dev, const mi355_jpeg_plane *table_host, int nplanes, hipStream_t st);
 const char *jpeg_to_rgb_check(const mi355_jpeg_image *host, int B);
 int jpeg_to_rgb_launch(const mi355_jpeg_image *table_dev, const mi355_jpeg_image *table_host, int B, hipStream_t st);
+// png.hip: scanline reconstruction of every segment of a batch (one wave each), then de-interlacing + expansion into RGB frames
+const char *png_unfilter_check(const mi355_png_segment *host, int nsegments);
+int png_unfilter_launch(const mi355_png_segment *table_dev, int nsegments, hipStream_t st);
+const char *png_to_rgb_check(const mi355_png_image *host, int B);
+int png_to_rgb_launch(const mi355_png_image *table_dev, const mi355_png_image *table_host, int B, hipStream_t st);
 // jpeg_entropy.hip: Huffman decoding of every segment of a batch, one workgroup each
 const char *jpeg_entropy_check(const mi355_jpeg_segment *host, int nsegments, int subseq_bits);
 int jpeg_entropy_launch(const mi355_jpeg_segment *table_dev, int nsegments, int subseq_bits, int *status_dev, hipStream_t st);

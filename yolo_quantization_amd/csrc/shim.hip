@@ -1168,6 +1168,22 @@ int mi355_jpeg_to_rgb(const mi355_jpeg_image *table_dev, const mi355_jpeg_image 
     return jpeg_to_rgb_launch(table_dev, table_host, B, (hipStream_t)stream);
 }
 
+int mi355_png_unfilter(const mi355_png_segment *table_dev, const mi355_png_segment *table_host, int nsegments, void *stream)
+{
+    if (!table_dev) return einval("png_unfilter: null");
+    const char *why = png_unfilter_check(table_host, nsegments);
+    if (why) return einval(why);
+    return png_unfilter_launch(table_dev, nsegments, (hipStream_t)stream);
+}
+
+int mi355_png_to_rgb(const mi355_png_image *table_dev, const mi355_png_image *table_host, int B, void *stream)
+{
+    if (!table_dev) return einval("png_to_rgb: null");
+    const char *why = png_to_rgb_check(table_host, B);
+    if (why) return einval(why);
+    return png_to_rgb_launch(table_dev, table_host, B, (hipStream_t)stream);
+}
+
 int mi355_jpeg_entropy(const mi355_jpeg_segment *table_dev, const mi355_jpeg_segment *table_host, int nsegments, int subseq_bits,
                        int *status_dev, void *stream)
 {

@@ -45,9 +45,12 @@
  * Image input: a baseline JPEG of ANY size -- any file that starts FF D8, whatever its name: entropy decode on the host, inverse DCT,
  * upsampling and colour conversion on the device (network_frames_jpeg_input_gpu), the pixels stb_image gives the reference, byte for
  * byte; a JPEG source always takes the byte path on the device, so `-frames u8` is implied --, a binary PPM (P6) of ANY size
- * (letterboxed like the reference does), a raw `.u8` file holding [c][h][w] bytes at network size, or `synthetic:<seed>`.  A -list may
- * mix JPEG and PPM files of different sizes.  Progressive and CMYK JPEGs, PNG, BMP, GIF and the other formats of the reference's
- * stb_image are not built and are refused with a message.
+ * (letterboxed like the reference does), a raw `.u8` file holding [c][h][w] bytes at network size, or `synthetic:<seed>`.  A PNG of
+ * ANY size, colour type and bit depth, interlaced or not -- any file whose first 16 bytes are the PNG signature and the head of an IHDR
+ * chunk, whatever its name: chunk parse and inflate on the host, scanline reconstruction, de-interlacing and expansion to RGB on the
+ * device (network_frames_png_input_gpu), stb_image's pixels again, `-frames u8` implied like for a JPEG.  A -list may mix PNG, JPEG
+ * and PPM files of different sizes.  Progressive and CMYK JPEGs, BMP, GIF and the other formats of the reference's stb_image are not
+ * built and are refused with a message (which still lists PNG: a file with the PNG signature but no IHDR behind it gets it).
  */
 #include <math.h>
 #include <pthread.h>
@@ -120,6 +123,23 @@ static int is_jpeg_file(const char *path)
     fclose(f);
     return got == 2 && two[0] == 0xFF && two[1] == 0xD8;
 }
+
+/* A file whose first 16 bytes are the PNG signature and the length and type of an IHDR chunk is a PNG, whatever its name. */
+static int is_png_file(const char *path)
+{
+    static const unsigned char head[16] = {137, 80, 78, 71, 13, 10, 26, 10, 0, 0, 0, 13, 'I', 'H', 'D', 'R'};
+    if (!path || 0 == strncmp(path, "synthetic", 9)) return 0;
+    FILE *f = fopen(path, "rb");
+    if (!f) return 0;
+    unsigned char got[16];
+    const size_t n = fread(got, 1, 16, f);
+    fclose(f);
+    return n == 16 && 0 == memcmp(got, head, 16);
+}
+
+/* the files decoded on the device: 0 none of them, CODED_JPEG, CODED_PNG */
+enum { CODED_NONE = 0, CODED_JPEG = 1, CODED_PNG = 2 };
+static int coded_kind(const char *path) { return is_jpeg_file(path) ? CODED_JPEG : is_png_file(path) ? CODED_PNG : CODED_NONE; }
 
 static uint8_t *read_file(const char *path, size_t *bytes)
 {
@@ -247,59 +267,69 @@ static void print_detections(const detect_job *job, int classes, const detection
             }
 }
 
-/* A JPEG slot failed: the library's message names the slot of the call it was given, which held the JPEG slots only */
-static void jpeg_slot_error(char *const *paths, const int *slot_of, int n)
+/* A JPEG or PNG slot failed: the library's message names the slot of the call it was given, which held the slots of that kind only */
+static void coded_slot_error(int kind, char *const *paths, const int *slot_of, int n)
 {
-    const char *why = network_jpeg_last_error();
+    const char *why = kind == CODED_PNG ? network_png_last_error() : network_jpeg_last_error();
     int k = -1;
-    if (sscanf(why, "jpeg slot %d:", &k) == 1 && k >= 0 && k < n) {
+    if (sscanf(why, kind == CODED_PNG ? "png slot %d:" : "jpeg slot %d:", &k) == 1 && k >= 0 && k < n) {
         const char *colon = strchr(why, ':');
         fprintf(stderr, "slot %d (%s):%s\n", slot_of[k], paths[slot_of[k]], colon ? colon + 1 : why);
     } else {
         fprintf(stderr, "%s\n", why);
     }
-    error("cannot decode a JPEG source");
+    error(kind == CODED_PNG ? "cannot decode a PNG source" : "cannot decode a JPEG source");
 }
 
-/* -frames u8 with JPEG files among the sources: every JPEG slot is decoded into a frame on the device (one network_jpeg_decode_gpu call
- * for all of them; with nothing but JPEGs, network_frames_jpeg_input_gpu does the whole input step), the other sources go up as the
+/* -frames u8 with JPEG or PNG files among the sources: every such slot is decoded into a frame on the device (one
+ * network_jpeg_decode_gpu call for all the JPEGs and one network_png_decode_gpu call for all the PNGs; with nothing but JPEGs or nothing
+ * but PNGs, network_frames_jpeg_input_gpu / network_frames_png_input_gpu does the whole input step), the other sources go up as the
  * bytes they are, and one network_frames_u8_input_gpu call takes the batch's frames where they lie. */
-static void feed_frames_jpeg(network *net, char *const *paths, int *imw, int *imh)
+static void feed_frames_coded(network *net, char *const *paths, int *imw, int *imh)
 {
     const int B = net->batch;
-    uint8_t **file = calloc((size_t)B, sizeof(uint8_t *)); /* per slot: the JPEG file's bytes, or the decoded PPM / raw frame */
+    uint8_t **file = calloc((size_t)B, sizeof(uint8_t *)); /* per slot: the coded file's bytes, or the decoded PPM / raw frame */
     size_t *bytes = calloc((size_t)B, sizeof(size_t));
-    int *is_jpg = calloc((size_t)B, sizeof(int)), *slot_of = calloc((size_t)B, sizeof(int));
-    const uint8_t **jdata = calloc((size_t)B, sizeof(uint8_t *));
-    size_t *jbytes = calloc((size_t)B, sizeof(size_t));
-    int nj = 0;
+    int *kind = calloc((size_t)B, sizeof(int));
+    int *slot_of[3] = {NULL, calloc((size_t)B, sizeof(int)), calloc((size_t)B, sizeof(int))};
+    const uint8_t **cdata[3] = {NULL, calloc((size_t)B, sizeof(uint8_t *)), calloc((size_t)B, sizeof(uint8_t *))};
+    size_t *cbytes[3] = {NULL, calloc((size_t)B, sizeof(size_t)), calloc((size_t)B, sizeof(size_t))};
+    int nc[3] = {0, 0, 0};
     for (int b = 0; b < B; ++b) {
         if (b && paths[b] == paths[b - 1]) { /* the same source again: the same bytes, decoded and uploaded once */
-            file[b] = file[b - 1]; bytes[b] = bytes[b - 1]; is_jpg[b] = is_jpg[b - 1];
+            file[b] = file[b - 1]; bytes[b] = bytes[b - 1]; kind[b] = kind[b - 1];
             imw[b] = imw[b - 1]; imh[b] = imh[b - 1];
-        } else if ((is_jpg[b] = is_jpeg_file(paths[b]))) {
+        } else if ((kind[b] = coded_kind(paths[b]))) {
             file[b] = read_file(paths[b], &bytes[b]);
         } else {
             file[b] = load_frame_u8(paths[b], net->c, net->h, net->w, &imw[b], &imh[b]);
             bytes[b] = (size_t)3 * imw[b] * imh[b];
         }
-        if (is_jpg[b]) { jdata[nj] = file[b]; jbytes[nj] = bytes[b]; slot_of[nj++] = b; }
+        const int k = kind[b];
+        if (k) { cdata[k][nc[k]] = file[b]; cbytes[k][nc[k]] = bytes[b]; slot_of[k][nc[k]++] = b; }
     }
-    if (nj == B) {
-        if (network_frames_jpeg_input_gpu(net, jdata, jbytes, imw, imh)) jpeg_slot_error(paths, slot_of, nj);
+    if (nc[CODED_JPEG] == B) {
+        if (network_frames_jpeg_input_gpu(net, cdata[CODED_JPEG], cbytes[CODED_JPEG], imw, imh)) coded_slot_error(CODED_JPEG, paths, slot_of[CODED_JPEG], B);
+    } else if (nc[CODED_PNG] == B) {
+        if (network_frames_png_input_gpu(net, cdata[CODED_PNG], cbytes[CODED_PNG], imw, imh)) coded_slot_error(CODED_PNG, paths, slot_of[CODED_PNG], B);
     } else {
-        uint8_t **jrgb = calloc((size_t)B, sizeof(uint8_t *));
-        int *jw = calloc((size_t)B, sizeof(int)), *jh = calloc((size_t)B, sizeof(int)), *jp = calloc((size_t)B, sizeof(int));
+        uint8_t **crgb = calloc((size_t)B, sizeof(uint8_t *));
+        int *cw = calloc((size_t)B, sizeof(int)), *ch = calloc((size_t)B, sizeof(int)), *cp = calloc((size_t)B, sizeof(int));
         const uint8_t **frame = calloc((size_t)B, sizeof(uint8_t *));
         int *pitch = calloc((size_t)B, sizeof(int));
         void **up = calloc((size_t)B, sizeof(void *));
-        if (network_jpeg_decode_gpu(net, jdata, jbytes, nj, jrgb, jw, jh, jp)) jpeg_slot_error(paths, slot_of, nj);
-        for (int k = 0; k < nj; ++k) {
-            const int b = slot_of[k];
-            frame[b] = jrgb[k]; imw[b] = jw[k]; imh[b] = jh[k]; pitch[b] = jp[k];
+        for (int k = CODED_JPEG; k <= CODED_PNG; ++k) {
+            if (!nc[k]) continue;
+            const int rc = k == CODED_PNG ? network_png_decode_gpu(net, cdata[k], cbytes[k], nc[k], crgb, cw, ch, cp)
+                                          : network_jpeg_decode_gpu(net, cdata[k], cbytes[k], nc[k], crgb, cw, ch, cp);
+            if (rc) coded_slot_error(k, paths, slot_of[k], nc[k]);
+            for (int i = 0; i < nc[k]; ++i) {
+                const int b = slot_of[k][i];
+                frame[b] = crgb[i]; imw[b] = cw[i]; imh[b] = ch[i]; pitch[b] = cp[i];
+            }
         }
         for (int b = 0; b < B; ++b) {
-            if (is_jpg[b]) continue;
+            if (kind[b]) continue;
             pitch[b] = 3 * imw[b];
             if (b && file[b] == file[b - 1]) { frame[b] = frame[b - 1]; continue; }
             if (mi355_alloc(&up[b], bytes[b]) || mi355_h2d(up[b], file[b], bytes[b], net->stream)) {
@@ -311,12 +341,13 @@ static void feed_frames_jpeg(network *net, char *const *paths, int *imw, int *im
         network_frames_u8_input_gpu(net, frame, imw, imh, pitch, MI355_FRAME_RGB, 1);
         if (mi355_stream_sync(net->stream)) error("sync"); /* the uploaded frames are freed below */
         for (int b = 0; b < B; ++b) if (up[b]) mi355_free(up[b]);
-        free(jrgb); free(jw); free(jh); free(jp); free(frame); free(pitch); free(up);
+        free(crgb); free(cw); free(ch); free(cp); free(frame); free(pitch); free(up);
     }
     /* on the device nothing waits for the uploads: the sources are freed below */
     if (net->input_on_device && mi355_stream_sync(net->stream)) error("sync");
     for (int b = 0; b < B; ++b) if (!b || file[b] != file[b - 1]) free(file[b]);
-    free(file); free(bytes); free(is_jpg); free(slot_of); free(jdata); free(jbytes);
+    free(file); free(bytes); free(kind);
+    for (int k = CODED_JPEG; k <= CODED_PNG; ++k) { free(slot_of[k]); free(cdata[k]); free(cbytes[k]); }
 }
 
 /* -frames: the batch's sources, one path per slot, through the entry point of the kind that is set: one call for the whole input step.
@@ -327,7 +358,7 @@ static void feed_frames(const detect_job *job, network *net, char *const *paths,
     const int B = net->batch;
     if (job->frames == FRAMES_U8)
         for (int b = 0; b < B; ++b)
-            if ((!b || paths[b] != paths[b - 1]) && is_jpeg_file(paths[b])) { feed_frames_jpeg(net, paths, imw, imh); return; }
+            if ((!b || paths[b] != paths[b - 1]) && coded_kind(paths[b])) { feed_frames_coded(net, paths, imw, imh); return; }
     uint8_t **raw = calloc((size_t)B, sizeof(uint8_t *));
     const uint8_t **pl[3];
     for (int k = 0; k < 3; ++k) pl[k] = calloc((size_t)B, sizeof(uint8_t *));
@@ -389,8 +420,9 @@ static void test_detector_list(detect_job *job, network *net, char **names, int 
     }
     fclose(f);
     for (int i = 0; i < np; ++i)
-        if (is_jpeg_file(paths[i])) { /* a JPEG source takes the byte path on the device: -frames u8 is implied for the whole list */
-            if (job->frames != FRAMES_NONE && job->frames != FRAMES_U8) error("-list: a JPEG file does not go with raw -frames formats");
+        if (coded_kind(paths[i])) { /* a JPEG or PNG source takes the byte path on the device: -frames u8 is implied for the whole list */
+            if (job->frames != FRAMES_NONE && job->frames != FRAMES_U8)
+                error(is_jpeg_file(paths[i]) ? "-list: a JPEG file does not go with raw -frames formats" : "-list: a PNG file does not go with raw -frames formats");
             job->frames = FRAMES_U8;
             break;
         }
@@ -674,8 +706,9 @@ int main(int argc, char **argv)
         return 0;
     }
     job.datacfg = argv[3]; job.cfgfile = argv[4]; job.weightfile = argv[5]; job.filename = argv[6];
-    if (is_jpeg_file(job.filename)) { /* a JPEG source takes the byte path on the device: -frames u8 is implied */
-        if (job.frames != FRAMES_NONE && job.frames != FRAMES_U8) error("a JPEG image does not go with raw -frames formats");
+    if (coded_kind(job.filename)) { /* a JPEG or PNG source takes the byte path on the device: -frames u8 is implied */
+        if (job.frames != FRAMES_NONE && job.frames != FRAMES_U8)
+            error(is_jpeg_file(job.filename) ? "a JPEG image does not go with raw -frames formats" : "a PNG image does not go with raw -frames formats");
         job.frames = FRAMES_U8;
     }
     if (!gpu_list) {

@@ -18,6 +18,7 @@
 #include "host_internal.h"
 #include "jpeg.h"
 #include "jpeg_scan.h"
+#include "png.h"
 
 /* ------------------------------------------------------------------------------------------------------ utils */
 void error(const char *s) /* ref: src/utils.c:232-237 */
@@ -1586,6 +1587,143 @@ int network_frames_jpeg_input_gpu(network *net, const uint8_t *const *data, cons
     return rc;
 }
 
+/* ------------------------------------------------------------------------------------------------- PNG input
+ * The host parses the chunks and inflates (png.c), the device does the rest (png.hip): one staging block -- segment table, image
+ * table, palettes, filtered bytes, laid out exactly like its device copy -- goes up in one copy, then mi355_png_unfilter over every
+ * pass of every image and mi355_png_to_rgb over every image.  The frames stay on the device for the 8-bit frame path. */
+static _Thread_local char png_err[320];
+const char *network_png_last_error(void) { return png_err; }
+
+static int png_refuse(const char *why)
+{
+    snprintf(png_err, sizeof(png_err), "%s", why);
+    return MI355_EINVAL;
+}
+
+static void pngin_free(network *net)
+{
+    if (net->png_in_gpu) mi355_free(net->png_in_gpu);
+    if (net->png_rows_gpu) mi355_free(net->png_rows_gpu);
+    if (net->png_rgb_gpu) mi355_free(net->png_rgb_gpu);
+    free(net->png_stage_host);
+    net->png_in_gpu = net->png_rows_gpu = net->png_rgb_gpu = net->png_stage_host = NULL;
+    net->png_in_bytes = net->png_rows_bytes = net->png_rgb_bytes = net->png_stage_bytes = 0;
+    net->png_upload_pending = 0;
+}
+
+int network_png_decode_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int n, uint8_t **rgb_dev, int *w, int *h, int *pitch)
+{
+    if (!net || !data || !bytes || !rgb_dev || !w || !h || !pitch || n < 1 || n > 65535)
+        return png_refuse("network_png_decode_gpu: null argument / need 1 <= n <= 65535");
+    /* 1. the host half; a slot that names the bytes of an earlier slot (one image in every slot) shares its decode and its frame */
+    dnq_png *im = calloc((size_t)n, sizeof(dnq_png));
+    int *first = calloc((size_t)n, sizeof(int)), *frame = calloc((size_t)n, sizeof(int));
+    if (!im || !first || !frame) error("network_png_decode_gpu: out of memory");
+    int rc = MI355_OK, nu = 0, nsegs = 0;
+    for (int b = 0; b < n && rc == MI355_OK; ++b) {
+        first[b] = b;
+        for (int k = 0; k < b && first[b] == b; ++k)
+            if (data[k] == data[b] && bytes[k] == bytes[b]) first[b] = k;
+        if (first[b] != b) continue;
+        char why[256];
+        if (!data[b]) {
+            snprintf(png_err, sizeof(png_err), "png slot %d: null data", b);
+            rc = MI355_EINVAL;
+        } else if (png_decode_host(data[b], bytes[b], &im[b], why, sizeof(why))) {
+            snprintf(png_err, sizeof(png_err), "png slot %d: %s", b, why);
+            rc = MI355_EINVAL;
+        } else {
+            frame[b] = nu++;
+            nsegs += im[b].npasses;
+        }
+    }
+    if (rc != MI355_OK) { /* nothing has touched the device */
+        for (int b = 0; b < n; ++b) png_free(&im[b]);
+        free(im); free(first); free(frame);
+        return rc;
+    }
+    /* 2. the layout of the staging block (= of its device copy), of the reconstructed passes and of the frames */
+    const size_t off_images = fr_round(sizeof(mi355_png_segment) * (size_t)nsegs);
+    const size_t off_pal = off_images + fr_round(sizeof(mi355_png_image) * (size_t)nu);
+    const size_t off_bytes = off_pal + 768 * (size_t)nu;
+    size_t in_bytes = fr_round(off_bytes), rows_bytes = 0, rgb_bytes = 0;
+    for (int b = 0; b < n; ++b) {
+        if (first[b] != b) continue;
+        in_bytes += fr_round(im[b].filtered_bytes);
+        for (int k = 0; k < im[b].npasses; ++k) rows_bytes += fr_round((size_t)im[b].pass[k].rows * (size_t)im[b].pass[k].row_bytes);
+        rgb_bytes += fr_round((size_t)im[b].h * (((size_t)3 * im[b].w + 3) & ~(size_t)3));
+    }
+    check_mi355(mi355_init(net->gpu_index), "mi355_init");
+    if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
+    int waited = 0;
+    jpg_reserve(net, &net->png_in_gpu, &net->png_in_bytes, in_bytes, &waited, "alloc png scanlines");
+    jpg_reserve(net, &net->png_rows_gpu, &net->png_rows_bytes, rows_bytes, &waited, "alloc png passes");
+    jpg_reserve(net, &net->png_rgb_gpu, &net->png_rgb_bytes, rgb_bytes, &waited, "alloc png frames");
+    /* 3. the staging block is rewritten only after the upload that read it last has completed */
+    if (net->png_upload_pending && !waited) net_wait(net);
+    net->png_upload_pending = 0;
+    if (net->png_stage_bytes < in_bytes) {
+        free(net->png_stage_host);
+        net->png_stage_host = malloc(in_bytes);
+        if (!net->png_stage_host) error("network_png_decode_gpu: out of memory");
+        net->png_stage_bytes = in_bytes;
+    }
+    uint8_t *stage = net->png_stage_host, *in_gpu = net->png_in_gpu;
+    memset(stage, 0, fr_round(off_bytes));
+    mi355_png_segment *segs = (mi355_png_segment *)stage;
+    mi355_png_image *images = (mi355_png_image *)(stage + off_images);
+    size_t bytes_at = fr_round(off_bytes), rows_at = 0, rgb_at = 0;
+    int si = 0;
+    for (int b = 0; b < n; ++b) {
+        if (first[b] != b) continue;
+        const dnq_png *p = &im[b];
+        mi355_png_image *g = &images[frame[b]];
+        g->rgb = (uint8_t *)net->png_rgb_gpu + rgb_at;
+        g->w = p->w; g->h = p->h; g->pitch = (3 * p->w + 3) & ~3;
+        g->depth = p->depth; g->color = p->color; g->interlace = p->interlace; g->pal_len = p->pal_len;
+        rgb_at += fr_round((size_t)g->h * (size_t)g->pitch);
+        if (p->color == 3) {
+            memcpy(stage + off_pal + 768 * (size_t)frame[b], p->palette, 768);
+            g->palette = in_gpu + off_pal + 768 * (size_t)frame[b];
+        }
+        memcpy(stage + bytes_at, p->filtered, p->filtered_bytes);
+        for (int k = 0; k < p->npasses; ++k, ++si) {
+            const dnq_png_pass *q = &p->pass[k];
+            segs[si].filtered = in_gpu + bytes_at + q->offset;
+            segs[si].out = (uint8_t *)net->png_rows_gpu + rows_at;
+            segs[si].row_bytes = q->row_bytes; segs[si].rows = q->rows; segs[si].bpp = p->bpp;
+            g->pass[q->index] = segs[si].out;
+            rows_at += fr_round((size_t)q->rows * (size_t)q->row_bytes);
+        }
+        bytes_at += fr_round(p->filtered_bytes);
+    }
+    for (int b = 0; b < n; ++b) {
+        const mi355_png_image *g = &images[frame[first[b]]];
+        rgb_dev[b] = g->rgb; w[b] = g->w; h[b] = g->h; pitch[b] = g->pitch;
+        png_free(&im[b]);
+    }
+    free(im); free(first); free(frame);
+    /* 4. one copy, two launches */
+    check_mi355(mi355_h2d(in_gpu, stage, in_bytes, net->stream), "upload png scanlines");
+    net->png_upload_pending = 1;
+    check_mi355(mi355_png_unfilter((const mi355_png_segment *)in_gpu, segs, nsegs, net->stream), "mi355_png_unfilter");
+    check_mi355(mi355_png_to_rgb((const mi355_png_image *)(in_gpu + off_images), images, nu, net->stream), "mi355_png_to_rgb");
+    return MI355_OK;
+}
+
+int network_frames_png_input_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int *w, int *h)
+{
+    if (!net || !w || !h) return png_refuse("network_frames_png_input_gpu: null argument");
+    if (net->c != 3) return png_refuse("network_frames_png_input_gpu: PNG images feed 3-channel networks only");
+    const int B = net->batch;
+    uint8_t **rgb = calloc((size_t)B, sizeof(uint8_t *));
+    int *pitch = calloc((size_t)B, sizeof(int));
+    const int rc = network_png_decode_gpu(net, data, bytes, B, rgb, w, h, pitch);
+    if (rc == MI355_OK) network_frames_u8_input_gpu(net, (const uint8_t *const *)rgb, w, h, pitch, MI355_FRAME_RGB, 1);
+    free(rgb); free(pitch);
+    return rc;
+}
+
 void set_batch_network(network *net, int b)
 {
     if (b < 1) error("set_batch_network: batch < 1");
@@ -2299,6 +2437,7 @@ void free_network(network *net)
     od_free(net);
     fr_free(net);
     jpg_free(net);
+    pngin_free(net);
     detb_free(net);
     if (net->selfcheck_gpu) mi355_free(net->selfcheck_gpu);
     if (net->stream) mi355_stream_release(net->stream);
