@@ -115,6 +115,19 @@ struct layer {
     int prepared;
 };
 
+/* The buffers of one coded-image input path (JPEG, PNG): lazily allocated, grown when needed, freed with the network. */
+typedef struct coded_bufs {
+    void *stage_host;           /* host staging block: the format's tables, then the bytes the device reads */
+    size_t stage_bytes;
+    void *in_gpu;               /* its device copy, the same layout */
+    size_t in_bytes;
+    void *work_gpu;             /* what the first launch writes for the second: component planes (JPEG), reconstructed passes (PNG) */
+    size_t work_bytes;
+    void *rgb_gpu;              /* the RGB frames of the last call */
+    size_t rgb_bytes;
+    int upload_pending;         /* an upload from the staging block may be in flight: wait before rewriting it */
+} coded_bufs;
+
 struct network {
     int n, batch;
     layer *layers;
@@ -197,16 +210,9 @@ struct network {
     float *fr_mm_gpu, *fr_mm_host; /* [fr_cap][2] max, min */
     void *fr_pair_gpu, *fr_pair_host; /* shared-scale mode: [fr_cap] float scale | [fr_cap] uint8 zero point, image 0's in every slot */
     int fr_cap;
-    /* JPEG input (network_jpeg_decode_gpu): lazily allocated, grown when needed, freed with the network.  A replica owns its own. */
-    void *jpg_stage_host;       /* host staging block: plane table | image table | quantiser tables | coefficients */
-    size_t jpg_stage_bytes;
-    void *jpg_in_gpu;           /* its device copy, the same layout */
-    size_t jpg_in_bytes;
-    void *jpg_planes_gpu;       /* the component planes the inverse DCT writes */
-    size_t jpg_planes_bytes;
-    void *jpg_rgb_gpu;          /* the RGB frames of the last call */
-    size_t jpg_rgb_bytes;
-    int jpg_upload_pending;     /* an upload from the staging block may be in flight: wait before rewriting it */
+    /* JPEG input (network_jpeg_decode_gpu).  The staging block holds plane table | image table | quantiser tables | coefficients, the
+     * work buffer the component planes the inverse DCT writes.  A replica owns its own. */
+    coded_bufs jpg;
     /* set_jpeg_entropy_on_device: the staging block then holds plane table | image table | quantiser tables | segment table | Huffman
      * tables | unstuffed scan bytes, and the coefficients exist on the device only */
     int jpg_entropy_on_device;
@@ -216,16 +222,9 @@ struct network {
     void *jpg_status_gpu;       /* one status word per segment of the last call */
     int *jpg_status_host;       /* their host copy */
     size_t jpg_status_bytes;
-    /* PNG input (network_png_decode_gpu): lazily allocated, grown when needed, freed with the network.  A replica owns its own. */
-    void *png_stage_host;       /* host staging block: segment table | image table | palettes | filtered bytes */
-    size_t png_stage_bytes;
-    void *png_in_gpu;           /* its device copy, the same layout */
-    size_t png_in_bytes;
-    void *png_rows_gpu;         /* the reconstructed passes mi355_png_unfilter writes */
-    size_t png_rows_bytes;
-    void *png_rgb_gpu;          /* the RGB frames of the last call */
-    size_t png_rgb_bytes;
-    int png_upload_pending;     /* an upload from the staging block may be in flight: wait before rewriting it */
+    /* PNG input (network_png_decode_gpu).  The staging block holds segment table | image table | palettes | filtered bytes, the work
+     * buffer the reconstructed passes mi355_png_unfilter writes.  A replica owns its own. */
+    coded_bufs png;
     /* Batched box decode (network_yolo_detections_batch_gpu): lazily allocated, grown when needed, freed with the network and on
      * re-batch.  A replica owns its own. */
     int *detb_ints_gpu, *detb_ints_host; /* [2][batch] source sizes | counts [batch][nheads] | offsets [batch + 1] */
@@ -245,7 +244,7 @@ struct network {
     uint32_t *od_status_gpu;             /* [B] MI355_INPUT_* bits of the last batch */
     float *od_mm_gpu;                    /* [B][2] max, min of the float path */
     void *od_const_gpu, *od_const_host;  /* mi355_l0_consts + n mi355_l0_channel */
-    long host_waits;                     /* times network.c waited for the device on this network's behalf (network_host_waits) */
+    long host_waits;                     /* times the host library waited for the device on this network's behalf (network_host_waits) */
 };
 
 /* ---- construction / IO ------------------------------------------------------------------------------------ */

@@ -917,11 +917,28 @@ def jpeg_to_rgb(images, pitch_pad=0):
     return res
 
 
-def _jpeg_args(items):
+def _file_args(items):
     datas = [_jpeg_bytes(it) for it in items]
     n = len(datas)
     ptrs, sizes = (C.c_char_p * n)(*datas), (C.c_size_t * n)(*[len(d) for d in datas])
     return datas, ptrs, sizes
+
+
+def _decode_on_net(net, items, decode, last_error, exc):
+    """network_jpeg_decode_gpu / network_png_decode_gpu (`decode`) on the items, the frames pulled back: [uint8 [h][w][3], ...]"""
+    datas, ptrs, sizes = _file_args(items)
+    n = len(items)
+    rgb, ws, hs, ps = (C.c_void_p * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+    if decode(net.h, ptrs, sizes, n, rgb, ws, hs, ps) != 0:
+        raise exc(last_error().decode())
+    net.sync()
+    out = []
+    for b in range(n):
+        raw = np.empty(hs[b] * ps[b], np.uint8)
+        check(shim().mi355_d2h(raw.ctypes.data, rgb[b], raw.nbytes, None), "d2h")
+        check(shim().mi355_stream_sync(None), "sync")
+        out.append(raw.reshape(hs[b], ps[b])[:, :3 * ws[b]].reshape(hs[b], ws[b], 3).copy())
+    return out
 
 
 def jpeg_decode(data, net=None):
@@ -930,19 +947,8 @@ def jpeg_decode(data, net=None):
     whose buffers and stream serve the call (network_jpeg_decode_gpu); without one the C-ABI calls run on the default stream."""
     many = isinstance(data, (list, tuple))
     items = list(data) if many else [data]
-    out = []
     if net is not None:
-        datas, ptrs, sizes = _jpeg_args(items)
-        n = len(items)
-        rgb, ws, hs, ps = (C.c_void_p * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        if net.H.network_jpeg_decode_gpu(net.h, ptrs, sizes, n, rgb, ws, hs, ps) != 0:
-            raise JpegError(net.H.network_jpeg_last_error().decode())
-        net.sync()
-        for b in range(n):
-            raw = np.empty(hs[b] * ps[b], np.uint8)
-            check(shim().mi355_d2h(raw.ctypes.data, rgb[b], raw.nbytes, None), "d2h")
-            check(shim().mi355_stream_sync(None), "sync")
-            out.append(raw.reshape(hs[b], ps[b])[:, :3 * ws[b]].reshape(hs[b], ws[b], 3).copy())
+        out = _decode_on_net(net, items, net.H.network_jpeg_decode_gpu, net.H.network_jpeg_last_error, JpegError)
         return out if many else out[0]
     decoded = []
     for b, it in enumerate(items):
@@ -1096,19 +1102,8 @@ def png_decode(data, net=None):
     Net whose buffers and stream serve the call (network_png_decode_gpu); without one the C-ABI calls run on the default stream."""
     many = isinstance(data, (list, tuple))
     items = list(data) if many else [data]
-    out = []
     if net is not None:
-        datas, ptrs, sizes = _jpeg_args(items)
-        n = len(items)
-        rgb, ws, hs, ps = (C.c_void_p * n)(), (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        if net.H.network_png_decode_gpu(net.h, ptrs, sizes, n, rgb, ws, hs, ps) != 0:
-            raise PngError(net.H.network_png_last_error().decode())
-        net.sync()
-        for b in range(n):
-            raw = np.empty(hs[b] * ps[b], np.uint8)
-            check(shim().mi355_d2h(raw.ctypes.data, rgb[b], raw.nbytes, None), "d2h")
-            check(shim().mi355_stream_sync(None), "sync")
-            out.append(raw.reshape(hs[b], ps[b])[:, :3 * ws[b]].reshape(hs[b], ws[b], 3).copy())
+        out = _decode_on_net(net, items, net.H.network_png_decode_gpu, net.H.network_png_last_error, PngError)
         return out if many else out[0]
     decoded = []
     for b, it in enumerate(items):
@@ -1316,24 +1311,21 @@ class Net:
         """JPEG input path (network_frames_jpeg_input_gpu): every item (the bytes of a JPEG file, or a path) is entropy-decoded on the
         host and finished on the device; the RGB frames stay there and feed the 8-bit frame path.  Returns [(w, h), ...], the images'
         sizes for the detection calls.  Raises JpegError naming the slot when an image is refused; nothing has been launched then."""
-        assert len(items) == self.batch
-        B = self.batch
-        datas, ptrs, sizes = _jpeg_args(items)
-        ws, hs = (C.c_int * B)(), (C.c_int * B)()
-        if self.H.network_frames_jpeg_input_gpu(self.h, ptrs, sizes, ws, hs) != 0:
-            raise JpegError(self.H.network_jpeg_last_error().decode())
-        return [(ws[b], hs[b]) for b in range(B)]
+        return self._prepare_from_files(items, self.H.network_frames_jpeg_input_gpu, self.H.network_jpeg_last_error, JpegError)
 
     def prepare_from_png(self, items):
         """PNG input path (network_frames_png_input_gpu): every item (the bytes of a PNG file, or a path) is parsed and inflated on the
         host and finished on the device; the RGB frames stay there and feed the 8-bit frame path.  Returns [(w, h), ...], the images'
         sizes for the detection calls.  Raises PngError naming the slot when an image is refused; nothing has been launched then."""
+        return self._prepare_from_files(items, self.H.network_frames_png_input_gpu, self.H.network_png_last_error, PngError)
+
+    def _prepare_from_files(self, items, frames_input, last_error, exc):
         assert len(items) == self.batch
         B = self.batch
-        datas, ptrs, sizes = _jpeg_args(items)
+        datas, ptrs, sizes = _file_args(items)
         ws, hs = (C.c_int * B)(), (C.c_int * B)()
-        if self.H.network_frames_png_input_gpu(self.h, ptrs, sizes, ws, hs) != 0:
-            raise PngError(self.H.network_png_last_error().decode())
+        if frames_input(self.h, ptrs, sizes, ws, hs) != 0:
+            raise exc(last_error().decode())
         return [(ws[b], hs[b]) for b in range(B)]
 
     def _pull_input(self):

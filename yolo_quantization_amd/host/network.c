@@ -16,9 +16,6 @@
 #include <string.h>
 #include <sys/time.h>
 #include "host_internal.h"
-#include "jpeg.h"
-#include "jpeg_scan.h"
-#include "png.h"
 
 /* ------------------------------------------------------------------------------------------------------ utils */
 void error(const char *s) /* ref: src/utils.c:232-237 */
@@ -61,11 +58,10 @@ const char *get_layer_string(LAYER_TYPE t)
 static void plan_fusion(network *net);
 static void pi_free(network *net);
 static void od_free(network *net);
-static float *od_scale_dev(const network *net);
 
 /* Every wait of this file for the device goes through here and is counted (network_host_waits): a blocking copy back is always
  * followed by one. */
-static void net_wait(network *net)
+void net_wait(network *net)
 {
     net->host_waits++;
     check_mi355(mi355_stream_sync(net->stream), "sync");
@@ -96,7 +92,7 @@ void quant_multi_smaller_than_one_to_scale_and_shift(float real_multiplier, int3
 }
 
 /* scale / zero point of the layer-0 quantiser from the image's min / max (both seeded with 0.0f), ref: src/blas.c:125-150 */
-static void image_scale_zero_point(float min_value, float max_value, float *scale, uint8_t *zero_point)
+void image_scale_zero_point(float min_value, float max_value, float *scale, uint8_t *zero_point)
 {
     if (min_value == 0 && max_value == 0) error("input image is all zero (ref: src/blas.c:125-128 assert)");
     /* the reference binary (gcc -Ofast) multiplies by the reciprocal constant here; see oracle/oracle.c */
@@ -456,7 +452,7 @@ void quantization_weights_and_activations(network *net)
 /* One (scale, zero point) for the whole batch, as image 0 defines it: the first call prepares the network with it; a later call
  * with another pair re-derives and re-uploads layer 0's multipliers and blob in place (no other layer depends on the input scale).
  * Shared by the device input paths (float images, 8-bit frames). */
-static void input_pair_shared(network *net, float s, uint8_t zp)
+void input_pair_shared(network *net, float s, uint8_t zp)
 {
     layer *l0 = &net->layers[0];
     if (!net->prepared) {
@@ -688,7 +684,7 @@ static void pi_bank_update(network *net, const float *scale, const uint8_t *zp)
 /* One (scale, zero point) per image from the batch's [B][2] max / min: the first call prepares the network with image 0's pair, then
  * the bank and the index arrays (entry, scale, zero point per image) go up on the network's stream.  Shared by the device input
  * paths (float images, 8-bit frames). */
-static void input_pairs_per_image(network *net, const float *mm)
+void input_pairs_per_image(network *net, const float *mm)
 {
     const int B = net->batch;
     float *s = malloc(sizeof(float) * (size_t)B);
@@ -771,7 +767,7 @@ static void od_free(network *net)
 
 /* The buffers of the mode, once per batch size (this may wait; no later call does): the network prepared, the constant table, the bank
  * with the prepared blob in every slot, and in every image's slot of the pair arrays the pair that blob was derived for. */
-static void od_alloc(network *net)
+void od_alloc(network *net)
 {
     const int B = net->batch;
     if (!net->prepared) quantization_weights_and_activations_fixed_input(net, 1.0f / 255.0f, 0);
@@ -811,8 +807,8 @@ static void od_alloc(network *net)
     free(pairs);
 }
 
-static float *od_scale_dev(const network *net) { return (float *)((char *)net->od_idx_gpu + 4 * (size_t)net->batch); }
-static uint8_t *od_zp_dev(const network *net) { return (uint8_t *)net->od_idx_gpu + 8 * (size_t)net->batch; }
+float *od_scale_dev(const network *net) { return (float *)((char *)net->od_idx_gpu + 4 * (size_t)net->batch); }
+uint8_t *od_zp_dev(const network *net) { return (uint8_t *)net->od_idx_gpu + 8 * (size_t)net->batch; }
 
 /* bank entries for the pairs in the pair arrays: image b's, or image 0's for everybody */
 static void od_derive(network *net)
@@ -824,7 +820,7 @@ static void od_derive(network *net)
 }
 
 /* pairs from the batch's [B][2] max / min in HBM (shared-scale mode reads image 0's), then their entries */
-static void od_pairs_and_entries(network *net, const float *mm_gpu)
+void od_pairs_and_entries(network *net, const float *mm_gpu)
 {
     check_mi355(mi355_input_pairs(mm_gpu, net->batch, !net->per_image, (int32_t *)net->od_idx_gpu, od_scale_dev(net), od_zp_dev(net),
                                   net->od_status_gpu, net->stream), "mi355_input_pairs");
@@ -900,16 +896,6 @@ void network_quantize_input_gpu(network *net)
     quantization_weights_and_activations_gpu(net, net->input_gpu);
 }
 
-/* ------------------------------------------------------------------------------------------------- frame input
- * Two launches for the whole batch (frames.hip): letterbox + min / max, then letterbox + quantise; the float image exists in registers
- * only.  The (scale, zero point) branches are the float path's (input_pair_shared, input_pairs_per_image).  Interleaved RGB / BGR
- * frames, NV12 / NV21 frames, frames of three separate planes, packed 4-byte frames (RGBA .. ABGR, YUYV .. YVYU), P010 frames and raw
- * Bayer / mono sensor frames differ in their table entries, the planes they describe and the pair of C-ABI calls; the table, the staging arena and everything else are
- * shared. */
-enum { FR_U8, FR_YUV, FR_PLANAR, FR_PACKED, FR_P010, FR_BAYER }; /* the kind of frames an entry point feeds (net->fr_kind) */
-static const size_t fr_entry_bytes[6] = {sizeof(mi355_frame_u8), sizeof(mi355_frame_yuv), sizeof(mi355_frame_planar),
-                                         sizeof(mi355_frame_packed), sizeof(mi355_frame_p010), sizeof(mi355_frame_bayer)};
-
 static void detb_free(network *net)
 {
     if (net->detb_ints_gpu) mi355_free(net->detb_ints_gpu);
@@ -921,807 +907,6 @@ static void detb_free(network *net)
     net->detb_batch = net->detb_nheads = 0;
     net->detb_work_ints = 0;
     net->detb_recs_cap = 0;
-}
-
-static void fr_free(network *net)
-{
-    if (net->fr_arena_gpu) mi355_free(net->fr_arena_gpu);
-    if (net->fr_table_gpu) mi355_free(net->fr_table_gpu);
-    if (net->fr_mm_gpu) mi355_free(net->fr_mm_gpu);
-    if (net->fr_pair_gpu) mi355_free(net->fr_pair_gpu);
-    free(net->fr_table_host); free(net->fr_mm_host); free(net->fr_pair_host);
-    net->fr_arena_gpu = NULL; net->fr_table_gpu = NULL; net->fr_table_host = NULL;
-    net->fr_mm_gpu = net->fr_mm_host = NULL;
-    net->fr_pair_gpu = net->fr_pair_host = NULL;
-    net->fr_arena_bytes = 0;
-    net->fr_cap = 0;
-}
-
-/* Everything but the arena, sized by the batch; the one table holds entries of any kind (the planar entry is the largest). */
-static void fr_alloc(network *net)
-{
-    const size_t B = (size_t)net->batch;
-    if (net->fr_cap == net->batch) return;
-    fr_free(net);
-    check_mi355(mi355_alloc((void **)&net->fr_mm_gpu, 2 * sizeof(float) * B), "alloc minmax");
-    check_mi355(mi355_alloc(&net->fr_pair_gpu, 5 * B), "alloc input pairs");
-    check_mi355(mi355_alloc(&net->fr_table_gpu, sizeof(mi355_frame_planar) * B), "alloc frame table");
-    net->fr_mm_host = calloc(2 * B, sizeof(float));
-    net->fr_pair_host = calloc(5, B);
-    net->fr_table_host = calloc(B, sizeof(mi355_frame_planar));
-    net->fr_cap = net->batch;
-}
-
-/* The first touch of the device, after every refusal of an entry point.  Returns the host mirror of the table, [batch] entries of `kind`
- * for the entry point to fill. */
-static void *fr_begin(network *net, int kind)
-{
-    check_mi355(mi355_init(net->gpu_index), "mi355_init");
-    if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
-    fr_alloc(net);
-    net->fr_kind = kind;
-    return net->fr_table_host;
-}
-
-static size_t fr_round(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-/* the staging arena holds at least `need` bytes */
-static void fr_arena_reserve(network *net, size_t need)
-{
-    if (need <= net->fr_arena_bytes) return;
-    net_wait(net); /* nothing in flight reads the arena that is freed */
-    if (net->fr_arena_gpu) mi355_free(net->fr_arena_gpu);
-    net->fr_arena_gpu = NULL; net->fr_arena_bytes = 0;
-    check_mi355(mi355_alloc(&net->fr_arena_gpu, need), "alloc frame arena");
-    net->fr_arena_bytes = need;
-}
-
-/* `bytes` host bytes go up as they are to the arena at *off, which moves on to the next 256-byte boundary */
-static const uint8_t *fr_stage(network *net, const uint8_t *src, size_t bytes, size_t *off)
-{
-    uint8_t *dst = (uint8_t *)net->fr_arena_gpu + *off;
-    check_mi355(mi355_h2d(dst, src, bytes, net->stream), "upload frame");
-    *off += fr_round(bytes);
-    return dst;
-}
-
-/* One plane of a frame in host memory, as it is: rows keep their pitch, the last row ends with its last sample. */
-typedef struct {
-    const uint8_t *host;
-    size_t row_bytes, rows, pitch;
-    const uint8_t **dev; /* the table entry's pointer to this plane: set to where the bytes went */
-} fr_plane;
-
-static size_t fr_plane_bytes(const fr_plane *p) { return (p->rows - 1) * p->pitch + p->row_bytes; }
-
-/* Host frames go up to the arena: planes[b * np + k] is plane k of the frame in slot b.  Frame by frame, plane by plane, each at a
- * 256-byte boundary; one frame in several slots (`-batch B` of one image: the same pointers and geometry) goes up once.  The arena
- * is reserved with `extra` bytes behind the frames for what the caller stages after them; returns where those start. */
-static size_t fr_stage_frames_and(network *net, const fr_plane *planes, int np, size_t extra)
-{
-    const int B = net->batch;
-    size_t need = extra, off = 0;
-    for (int i = 0; i < B * np; ++i) need += fr_round(fr_plane_bytes(&planes[i]));
-    fr_arena_reserve(net, need);
-    for (int b = 0; b < B; ++b) {
-        const fr_plane *f = planes + (size_t)b * np, *same = NULL;
-        for (int k = 0; k < b && !same; ++k) {
-            const fr_plane *g = planes + (size_t)k * np;
-            int eq = 1;
-            for (int i = 0; i < np; ++i)
-                eq &= g[i].host == f[i].host && g[i].row_bytes == f[i].row_bytes && g[i].rows == f[i].rows && g[i].pitch == f[i].pitch;
-            if (eq) same = g;
-        }
-        for (int i = 0; i < np; ++i) *f[i].dev = same ? *same[i].dev : fr_stage(net, f[i].host, fr_plane_bytes(&f[i]), &off);
-    }
-    return off;
-}
-
-static void fr_stage_frames(network *net, const fr_plane *planes, int np) { (void)fr_stage_frames_and(net, planes, np, 0); }
-
-/* The common tail, the host mirror of the table filled with device pointers: table upload, min / max launch, the batch's one host
- * sync, the (scale, zero point) branch, quantiser launch, with the calls of the frames' kind. */
-static void fr_finish(network *net)
-{
-    const int B = net->batch, kind = net->fr_kind, w = net->w, h = net->h;
-    const void *tg = net->fr_table_gpu, *th = net->fr_table_host;
-    if (net->input_on_device) od_alloc(net);
-    check_mi355(mi355_h2d(net->fr_table_gpu, th, fr_entry_bytes[kind] * (size_t)B, net->stream), "upload frame table");
-    if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_planar_letterbox_minmax");
-    else if (kind == FR_PACKED) check_mi355(mi355_frames_packed_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_packed_letterbox_minmax");
-    else if (kind == FR_P010) check_mi355(mi355_frames_p010_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_p010_letterbox_minmax");
-    else if (kind == FR_BAYER) check_mi355(mi355_frames_bayer_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_bayer_letterbox_minmax");
-    else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_yuv_letterbox_minmax");
-    else check_mi355(mi355_frames_u8_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_u8_letterbox_minmax");
-    const float *scale_dev;
-    const uint8_t *zp_dev;
-    if (net->input_on_device) { /* pairs and layer 0 follow on the stream: nothing comes back, nothing is waited for */
-        od_pairs_and_entries(net, net->fr_mm_gpu);
-        scale_dev = od_scale_dev(net);
-        zp_dev = od_zp_dev(net);
-    } else if (net->per_image) {
-        check_mi355(mi355_d2h(net->fr_mm_host, net->fr_mm_gpu, 2 * sizeof(float) * (size_t)B, net->stream), "minmax d2h");
-        net_wait(net); /* the batch's one host sync: every earlier upload is done too */
-        input_pairs_per_image(net, net->fr_mm_host);
-        scale_dev = (const float *)((const char *)net->pi_idx_gpu + 4 * (size_t)B);
-        zp_dev = (const uint8_t *)net->pi_idx_gpu + 8 * (size_t)B;
-    } else { /* image 0 defines the pair of the whole batch */
-        check_mi355(mi355_d2h(net->fr_mm_host, net->fr_mm_gpu, 2 * sizeof(float) * (size_t)B, net->stream), "minmax d2h");
-        net_wait(net); /* the batch's one host sync: every earlier upload is done too */
-        float s; uint8_t zp;
-        image_scale_zero_point(net->fr_mm_host[1] + 0.0f, net->fr_mm_host[0], &s, &zp);
-        input_pair_shared(net, s, zp);
-        float *sc = (float *)net->fr_pair_host;
-        uint8_t *zq = (uint8_t *)net->fr_pair_host + 4 * (size_t)B;
-        for (int b = 0; b < B; ++b) { sc[b] = s; zq[b] = zp; }
-        check_mi355(mi355_h2d(net->fr_pair_gpu, net->fr_pair_host, 5 * (size_t)B, net->stream), "upload input pair");
-        scale_dev = (const float *)net->fr_pair_gpu;
-        zp_dev = (const uint8_t *)net->fr_pair_gpu + 4 * (size_t)B;
-    }
-    uint8_t *out = net->input_uint8_gpu;
-    if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_planar_letterbox_quantize");
-    else if (kind == FR_PACKED) check_mi355(mi355_frames_packed_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_packed_letterbox_quantize");
-    else if (kind == FR_P010) check_mi355(mi355_frames_p010_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_p010_letterbox_quantize");
-    else if (kind == FR_BAYER) check_mi355(mi355_frames_bayer_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_bayer_letterbox_quantize");
-    else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_yuv_letterbox_quantize");
-    else check_mi355(mi355_frames_u8_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_u8_letterbox_quantize");
-}
-
-/* Every entry point: refuse what it must before the device is touched, fill its table entries with the caller's pointers, describe the
- * planes, stage them unless they are on the device already, fr_finish. */
-void network_frames_u8_input_gpu(network *net, const uint8_t *const *frames, const int *w, const int *h, const int *pitch, int order,
-                                 int frames_on_device)
-{
-    const int B = net->batch;
-    if (!frames || !w || !h) error("network_frames_u8_input_gpu: null frames / sizes");
-    if (net->c != 3) error("network_frames_u8_input_gpu: 8-bit frames feed 3-channel networks only");
-    for (int b = 0; b < B; ++b) {
-        if (!frames[b]) error("network_frames_u8_input_gpu: null frame");
-        if (w[b] < 1 || h[b] < 1 || (pitch && pitch[b] < 3 * w[b])) error("network_frames_u8_input_gpu: need w, h >= 1 and pitch >= 3 * w for every frame");
-    }
-    mi355_frame_u8 *tab = fr_begin(net, FR_U8);
-    fr_plane *planes = calloc((size_t)B, sizeof(fr_plane));
-    for (int b = 0; b < B; ++b) {
-        memset(&tab[b], 0, sizeof(tab[b]));
-        tab[b].data = frames[b];
-        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch = pitch ? pitch[b] : 3 * w[b]; tab[b].order = order;
-        planes[b] = (fr_plane){frames[b], 3 * (size_t)w[b], (size_t)h[b], (size_t)tab[b].pitch, &tab[b].data};
-    }
-    if (!frames_on_device) fr_stage_frames(net, planes, 1);
-    free(planes);
-    fr_finish(net);
-}
-
-void network_frames_nv12_input_gpu(network *net, const uint8_t *const *y, const uint8_t *const *uv, const int *w, const int *h,
-                                   const int *pitch_y, const int *pitch_uv, int layout, int matrix, int frames_on_device)
-{
-    const int B = net->batch;
-    if (!y || !uv || !w || !h) error("network_frames_nv12_input_gpu: null planes / sizes");
-    if (net->c != 3) error("network_frames_nv12_input_gpu: NV12 / NV21 frames feed 3-channel networks only");
-    for (int b = 0; b < B; ++b) {
-        if (!y[b] || !uv[b]) error("network_frames_nv12_input_gpu: null plane");
-        if (w[b] < 1 || h[b] < 1) error("network_frames_nv12_input_gpu: need w, h >= 1 for every frame");
-        if ((pitch_y && pitch_y[b] < w[b]) || (pitch_uv && pitch_uv[b] < 2 * ((w[b] + 1) / 2)))
-            error("network_frames_nv12_input_gpu: need pitch_y >= w and pitch_uv >= 2 * ((w + 1) / 2) for every frame");
-    }
-    mi355_frame_yuv *tab = fr_begin(net, FR_YUV);
-    fr_plane *planes = calloc(2 * (size_t)B, sizeof(fr_plane));
-    for (int b = 0; b < B; ++b) {
-        const int cw2 = 2 * ((w[b] + 1) / 2), ch = (h[b] + 1) / 2;
-        memset(&tab[b], 0, sizeof(tab[b]));
-        tab[b].y = y[b]; tab[b].uv = uv[b];
-        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch_y = pitch_y ? pitch_y[b] : w[b]; tab[b].pitch_uv = pitch_uv ? pitch_uv[b] : cw2;
-        tab[b].layout = layout; tab[b].matrix = matrix;
-        planes[2 * b] = (fr_plane){y[b], (size_t)w[b], (size_t)h[b], (size_t)tab[b].pitch_y, &tab[b].y};
-        planes[2 * b + 1] = (fr_plane){uv[b], (size_t)cw2, (size_t)ch, (size_t)tab[b].pitch_uv, &tab[b].uv};
-    }
-    if (!frames_on_device) fr_stage_frames(net, planes, 2);
-    free(planes);
-    fr_finish(net);
-}
-
-void network_frames_planar_input_gpu(network *net, const uint8_t *const *p0, const uint8_t *const *p1, const uint8_t *const *p2,
-                                     const int *w, const int *h, const int *pitch0, const int *pitch1, const int *pitch2,
-                                     int format, int matrix, int frames_on_device)
-{
-    const int B = net->batch;
-    const uint8_t *const *const src[3] = {p0, p1, p2};
-    const int *const pitches[3] = {pitch0, pitch1, pitch2};
-    if (!p0 || !p1 || !p2 || !w || !h) error("network_frames_planar_input_gpu: null planes / sizes");
-    if (format < MI355_PLANAR_I420 || format > MI355_PLANAR_BGR) error("network_frames_planar_input_gpu: unknown format (MI355_PLANAR_I420 .. _BGR)");
-    if (matrix < MI355_YUV_BT601 || matrix > MI355_YUV_BT709_FULL) error("network_frames_planar_input_gpu: unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)");
-    const int rgb = format == MI355_PLANAR_RGB || format == MI355_PLANAR_BGR;
-    if (rgb && matrix != 0) error("network_frames_planar_input_gpu: matrix must be 0 with MI355_PLANAR_RGB / _BGR");
-    const int half_w = !rgb && format != MI355_PLANAR_I444, half_h = format == MI355_PLANAR_I420 || format == MI355_PLANAR_YV12;
-    if (net->c != 3) error("network_frames_planar_input_gpu: planar frames feed 3-channel networks only");
-    for (int b = 0; b < B; ++b) {
-        if (!p0[b] || !p1[b] || !p2[b]) error("network_frames_planar_input_gpu: null plane");
-        if (w[b] < 1 || h[b] < 1 || w[b] > 32768 || h[b] > 32768) error("network_frames_planar_input_gpu: need 1 <= w, h <= 32768 for every frame");
-        for (int k = 0; k < 3; ++k)
-            if (pitches[k] && pitches[k][b] < (k && half_w ? (w[b] + 1) / 2 : w[b]))
-                error("network_frames_planar_input_gpu: need pitch >= the width of its plane for every plane");
-    }
-    mi355_frame_planar *tab = fr_begin(net, FR_PLANAR);
-    fr_plane *planes = calloc(3 * (size_t)B, sizeof(fr_plane));
-    for (int b = 0; b < B; ++b) {
-        memset(&tab[b], 0, sizeof(tab[b]));
-        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].format = format; tab[b].matrix = matrix;
-        for (int k = 0; k < 3; ++k) { /* plane 0 is w x h, planes 1 and 2 the format's chroma size */
-            const int pw = k && half_w ? (w[b] + 1) / 2 : w[b], ph = k && half_h ? (h[b] + 1) / 2 : h[b];
-            tab[b].plane[k] = src[k][b]; tab[b].pitch[k] = pitches[k] ? pitches[k][b] : pw;
-            planes[3 * b + k] = (fr_plane){src[k][b], (size_t)pw, (size_t)ph, (size_t)tab[b].pitch[k], &tab[b].plane[k]};
-        }
-    }
-    if (!frames_on_device) fr_stage_frames(net, planes, 3);
-    free(planes);
-    fr_finish(net);
-}
-
-void network_frames_packed_input_gpu(network *net, const uint8_t *const *frames, const int *w, const int *h, const int *pitch, int format,
-                                     int matrix, int frames_on_device)
-{
-    const int B = net->batch;
-    if (!frames || !w || !h) error("network_frames_packed_input_gpu: null frames / sizes");
-    if (format < MI355_PACKED_RGBA || format > MI355_PACKED_YVYU) error("network_frames_packed_input_gpu: unknown format (MI355_PACKED_RGBA .. _YVYU)");
-    if (matrix < MI355_YUV_BT601 || matrix > MI355_YUV_BT709_FULL) error("network_frames_packed_input_gpu: unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)");
-    const int rgb = format <= MI355_PACKED_ABGR;
-    if (rgb && matrix != 0) error("network_frames_packed_input_gpu: matrix must be 0 with MI355_PACKED_RGBA / _BGRA / _ARGB / _ABGR");
-    if (net->c != 3) error("network_frames_packed_input_gpu: packed frames feed 3-channel networks only");
-    for (int b = 0; b < B; ++b) {
-        if (!frames[b]) error("network_frames_packed_input_gpu: null frame");
-        if (w[b] < 1 || h[b] < 1 || w[b] > 32768 || h[b] > 32768) error("network_frames_packed_input_gpu: need 1 <= w, h <= 32768 for every frame");
-        if (pitch && pitch[b] < 4 * (rgb ? w[b] : (w[b] + 1) / 2))
-            error("network_frames_packed_input_gpu: need pitch >= 4 * w (RGB formats) or 4 * ((w + 1) / 2) (4:2:2 formats) for every frame");
-    }
-    mi355_frame_packed *tab = fr_begin(net, FR_PACKED);
-    fr_plane *planes = calloc((size_t)B, sizeof(fr_plane));
-    for (int b = 0; b < B; ++b) {
-        const int row = 4 * (rgb ? w[b] : (w[b] + 1) / 2); /* whole groups: a pixel, or a macropixel of two */
-        memset(&tab[b], 0, sizeof(tab[b]));
-        tab[b].data = frames[b];
-        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch = pitch ? pitch[b] : row; tab[b].format = format; tab[b].matrix = matrix;
-        planes[b] = (fr_plane){frames[b], (size_t)row, (size_t)h[b], (size_t)tab[b].pitch, &tab[b].data};
-    }
-    if (!frames_on_device) fr_stage_frames(net, planes, 1);
-    free(planes);
-    fr_finish(net);
-}
-
-void network_frames_p010_input_gpu(network *net, const uint8_t *const *y, const uint8_t *const *uv, const int *w, const int *h,
-                                   const int *pitch_y, const int *pitch_uv, int matrix, int frames_on_device)
-{
-    const int B = net->batch;
-    if (!y || !uv || !w || !h) error("network_frames_p010_input_gpu: null planes / sizes");
-    if (matrix < MI355_YUV_BT601 || matrix > MI355_YUV_BT709_FULL) error("network_frames_p010_input_gpu: unknown matrix (MI355_YUV_BT601 .. _BT709_FULL)");
-    if (net->c != 3) error("network_frames_p010_input_gpu: P010 frames feed 3-channel networks only");
-    for (int b = 0; b < B; ++b) {
-        if (!y[b] || !uv[b]) error("network_frames_p010_input_gpu: null plane");
-        if (w[b] < 1 || h[b] < 1 || w[b] > 32768 || h[b] > 32768) error("network_frames_p010_input_gpu: need 1 <= w, h <= 32768 for every frame");
-        if ((pitch_y && pitch_y[b] < 2 * w[b]) || (pitch_uv && pitch_uv[b] < 4 * ((w[b] + 1) / 2)))
-            error("network_frames_p010_input_gpu: need pitch_y >= 2 * w and pitch_uv >= 4 * ((w + 1) / 2) for every frame");
-    }
-    mi355_frame_p010 *tab = fr_begin(net, FR_P010);
-    fr_plane *planes = calloc(2 * (size_t)B, sizeof(fr_plane));
-    for (int b = 0; b < B; ++b) {
-        const int cw4 = 4 * ((w[b] + 1) / 2), ch = (h[b] + 1) / 2; /* bytes of a row of (U, V) pairs of 16-bit samples */
-        memset(&tab[b], 0, sizeof(tab[b]));
-        tab[b].y = y[b]; tab[b].uv = uv[b];
-        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch_y = pitch_y ? pitch_y[b] : 2 * w[b]; tab[b].pitch_uv = pitch_uv ? pitch_uv[b] : cw4;
-        tab[b].matrix = matrix;
-        planes[2 * b] = (fr_plane){y[b], 2 * (size_t)w[b], (size_t)h[b], (size_t)tab[b].pitch_y, &tab[b].y};
-        planes[2 * b + 1] = (fr_plane){uv[b], (size_t)cw4, (size_t)ch, (size_t)tab[b].pitch_uv, &tab[b].uv};
-    }
-    if (!frames_on_device) fr_stage_frames(net, planes, 2);
-    free(planes);
-    fr_finish(net);
-}
-
-/* the bytes of a tightly packed row of w raw samples, by layout */
-static int bayer_row_bytes(int sample, int w)
-{
-    return sample == MI355_RAW_U16 ? 2 * w : sample == MI355_RAW_MIPI10 ? 5 * ((w + 3) / 4) : sample == MI355_RAW_MIPI12 ? 3 * ((w + 1) / 2) : w;
-}
-
-void network_frames_bayer_input_gpu(network *net, const uint8_t *const *frames, const int *w, const int *h, const int *pitch, int pattern,
-                                    int sample, int shift, const uint8_t *const *tone, int frames_on_device)
-{
-    const int B = net->batch;
-    if (!frames || !w || !h) error("network_frames_bayer_input_gpu: null frames / sizes");
-    if (pattern < MI355_BAYER_RGGB || pattern > MI355_BAYER_MONO) error("network_frames_bayer_input_gpu: unknown pattern (MI355_BAYER_RGGB .. _MONO)");
-    if (sample < MI355_RAW_U8 || sample > MI355_RAW_MIPI12) error("network_frames_bayer_input_gpu: unknown sample layout (MI355_RAW_U8 .. _MIPI12)");
-    if (shift < 0 || shift > 8) error("network_frames_bayer_input_gpu: shift outside 0..8");
-    if (shift != 0 && sample != MI355_RAW_U16) error("network_frames_bayer_input_gpu: shift must be 0 without MI355_RAW_U16");
-    if (net->c != 3) error("network_frames_bayer_input_gpu: raw sensor frames feed 3-channel networks only");
-    for (int b = 0; b < B; ++b) {
-        if (!frames[b]) error("network_frames_bayer_input_gpu: null frame");
-        if (w[b] < 1 || h[b] < 1 || w[b] > 32768 || h[b] > 32768) error("network_frames_bayer_input_gpu: need 1 <= w, h <= 32768 for every frame");
-        if (pattern != MI355_BAYER_MONO && (w[b] < 2 || h[b] < 2)) error("network_frames_bayer_input_gpu: a Bayer frame needs w, h >= 2");
-        if (pitch && pitch[b] < bayer_row_bytes(sample, w[b]))
-            error("network_frames_bayer_input_gpu: need pitch >= w (U8), 2 * w (U16), 5 * ((w + 3) / 4) (MIPI10) or 3 * ((w + 1) / 2) (MIPI12) "
-                  "for every frame");
-    }
-    mi355_frame_bayer *tab = fr_begin(net, FR_BAYER);
-    fr_plane *planes = calloc((size_t)B, sizeof(fr_plane));
-    size_t tone_bytes = 0;
-    for (int b = 0; b < B; ++b) {
-        const int row = bayer_row_bytes(sample, w[b]);
-        memset(&tab[b], 0, sizeof(tab[b]));
-        tab[b].data = frames[b];
-        tab[b].tone = tone ? tone[b] : NULL;
-        tab[b].w = w[b]; tab[b].h = h[b]; tab[b].pitch = pitch ? pitch[b] : row;
-        tab[b].pattern = pattern; tab[b].sample = sample; tab[b].shift = shift;
-        planes[b] = (fr_plane){frames[b], (size_t)row, (size_t)h[b], (size_t)tab[b].pitch, &tab[b].data};
-        if (tab[b].tone) tone_bytes += fr_round(768);
-    }
-    if (!frames_on_device) { /* the tone tables go up behind the frames; a table several slots share goes up once */
-        size_t off = fr_stage_frames_and(net, planes, 1, tone_bytes);
-        for (int b = 0; b < B; ++b) {
-            if (!tone || !tone[b]) continue;
-            int same = -1;
-            for (int k = 0; k < b && same < 0; ++k)
-                if (tone[k] == tone[b]) same = k;
-            tab[b].tone = same >= 0 ? tab[same].tone : fr_stage(net, tone[b], 768, &off);
-        }
-    }
-    free(planes);
-    fr_finish(net);
-}
-
-/* ------------------------------------------------------------------------------------------------- JPEG input
- * The host decodes the entropy-coded streams (jpeg.c), the device does the rest (jpeg.hip): one staging block -- plane table, image
- * table, quantiser tables, coefficients, laid out exactly like its device copy -- goes up in one copy, then mi355_jpeg_idct over every
- * block of the batch and mi355_jpeg_to_rgb over every image.  The frames stay on the device for the 8-bit frame path. */
-static _Thread_local char jpg_err[320];
-const char *network_jpeg_last_error(void) { return jpg_err; }
-
-static int jpg_refuse(const char *why)
-{
-    snprintf(jpg_err, sizeof(jpg_err), "%s", why);
-    return MI355_EINVAL;
-}
-
-static void jpg_free(network *net)
-{
-    if (net->jpg_in_gpu) mi355_free(net->jpg_in_gpu);
-    if (net->jpg_planes_gpu) mi355_free(net->jpg_planes_gpu);
-    if (net->jpg_rgb_gpu) mi355_free(net->jpg_rgb_gpu);
-    if (net->jpg_coef_gpu) mi355_free(net->jpg_coef_gpu);
-    if (net->jpg_status_gpu) mi355_free(net->jpg_status_gpu);
-    free(net->jpg_stage_host);
-    free(net->jpg_status_host);
-    net->jpg_in_gpu = net->jpg_planes_gpu = net->jpg_rgb_gpu = net->jpg_stage_host = net->jpg_coef_gpu = net->jpg_status_gpu = NULL;
-    net->jpg_status_host = NULL;
-    net->jpg_in_bytes = net->jpg_planes_bytes = net->jpg_rgb_bytes = net->jpg_stage_bytes = net->jpg_coef_bytes = net->jpg_status_bytes = 0;
-    net->jpg_upload_pending = 0;
-}
-
-/* the device buffer holds at least `need` bytes; *waited: the stream has been waited for (nothing in flight reads what is freed) */
-static void jpg_reserve(network *net, void **buf, size_t *have, size_t need, int *waited, const char *what)
-{
-    if (need <= *have) return;
-    if (!*waited) { net_wait(net); *waited = 1; }
-    if (*buf) mi355_free(*buf);
-    *buf = NULL; *have = 0;
-    check_mi355(mi355_alloc(buf, need), what);
-    *have = need;
-}
-
-void set_jpeg_entropy_on_device(network *net, int on) { net->jpg_entropy_on_device = on != 0; }
-
-void set_jpeg_entropy_subseq_bits(network *net, int bits)
-{
-    if (bits < 32 || bits > 8192 || (bits & 31)) error("set_jpeg_entropy_subseq_bits: a multiple of 32 in 32 .. 8192");
-    net->jpg_subseq_bits = bits;
-}
-
-static const char *jpg_entropy_reason(int code)
-{
-    return code == MI355_JPEG_EHUFF ? "bad huffman code" : code == MI355_JPEG_EDC ? "bad DC category" :
-           code == MI355_JPEG_EINDEX ? "coefficient index past the end of the block" : "unknown status";
-}
-
-/* network_jpeg_decode_gpu with set_jpeg_entropy_on_device: the host only finds the scans (jpeg_scan.c).  One staging block -- plane
- * table, image table, quantiser tables, segment table, Huffman tables, the unstuffed bytes of every segment -- goes up in one copy;
- * the coefficient planes are zeroed on the device, mi355_jpeg_entropy fills them, the status words come back (the call's one wait),
- * and the two launches of the host-decode path follow on the same planes. */
-static int jpg_decode_entropy_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int n, uint8_t **rgb_dev, int *w, int *h, int *pitch)
-{
-    dnq_jpeg *im = calloc((size_t)n, sizeof(dnq_jpeg));
-    dnq_jpeg_scan_list *sl = calloc((size_t)n, sizeof(dnq_jpeg_scan_list));
-    int *first = calloc((size_t)n, sizeof(int)), *frame = calloc((size_t)n, sizeof(int));
-    int rc = MI355_OK, nu = 0, nplanes = 0, nsegs = 0, nhuff = 0;
-    size_t stream_bytes = 0;
-    for (int b = 0; b < n && rc == MI355_OK; ++b) {
-        first[b] = b;
-        for (int k = 0; k < b && first[b] == b; ++k)
-            if (data[k] == data[b] && bytes[k] == bytes[b]) first[b] = k;
-        if (first[b] != b) continue;
-        char why[256];
-        if (!data[b]) {
-            snprintf(jpg_err, sizeof(jpg_err), "jpeg slot %d: null data", b);
-            rc = MI355_EINVAL;
-        } else if (jpeg_scan_host(data[b], bytes[b], &im[b], &sl[b], why, sizeof(why))) {
-            snprintf(jpg_err, sizeof(jpg_err), "jpeg slot %d: %s", b, why);
-            rc = MI355_EINVAL;
-        } else {
-            frame[b] = nu++;
-            nplanes += im[b].ncomp;
-            nsegs += sl[b].nsegs;
-            nhuff += sl[b].nhuff;
-            stream_bytes += sl[b].nbytes;
-        }
-    }
-    if (rc != MI355_OK) { /* nothing has touched the device */
-        for (int b = 0; b < n; ++b) { jpeg_free(&im[b]); jpeg_scan_free(&sl[b]); }
-        free(im); free(sl); free(first); free(frame);
-        return rc;
-    }
-    const size_t off_images = fr_round(sizeof(mi355_jpeg_plane) * (size_t)nplanes);
-    const size_t off_quant = off_images + fr_round(sizeof(mi355_jpeg_image) * (size_t)nu);
-    const size_t off_segs = off_quant + fr_round(128 * (size_t)nplanes);
-    const size_t off_huff = off_segs + fr_round(sizeof(mi355_jpeg_segment) * (size_t)nsegs);
-    const size_t off_bits = off_huff + fr_round(sizeof(mi355_jpeg_huff) * (size_t)nhuff);
-    const size_t in_bytes = off_bits + fr_round(stream_bytes);
-    size_t coef_bytes = 0, planes_bytes = 0, rgb_bytes = 0;
-    for (int b = 0; b < n; ++b) {
-        if (first[b] != b) continue;
-        for (int k = 0; k < im[b].ncomp; ++k) {
-            const size_t blocks = (size_t)im[b].comp[k].blocks_w * im[b].comp[k].blocks_h;
-            coef_bytes += fr_round(128 * blocks);
-            planes_bytes += fr_round(64 * blocks);
-        }
-        rgb_bytes += fr_round((size_t)im[b].h * (((size_t)3 * im[b].w + 3) & ~(size_t)3));
-    }
-    check_mi355(mi355_init(net->gpu_index), "mi355_init");
-    if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
-    int waited = 0;
-    jpg_reserve(net, &net->jpg_in_gpu, &net->jpg_in_bytes, in_bytes, &waited, "alloc jpeg streams");
-    jpg_reserve(net, &net->jpg_coef_gpu, &net->jpg_coef_bytes, coef_bytes, &waited, "alloc jpeg coefficients");
-    jpg_reserve(net, &net->jpg_planes_gpu, &net->jpg_planes_bytes, planes_bytes, &waited, "alloc jpeg planes");
-    jpg_reserve(net, &net->jpg_rgb_gpu, &net->jpg_rgb_bytes, rgb_bytes, &waited, "alloc jpeg frames");
-    if (net->jpg_status_bytes < sizeof(int) * (size_t)nsegs) {
-        free(net->jpg_status_host);
-        net->jpg_status_host = malloc(sizeof(int) * (size_t)nsegs);
-        if (!net->jpg_status_host) error("network_jpeg_decode_gpu: out of memory");
-    }
-    jpg_reserve(net, &net->jpg_status_gpu, &net->jpg_status_bytes, sizeof(int) * (size_t)nsegs, &waited, "alloc jpeg status");
-    if (net->jpg_upload_pending && !waited) net_wait(net);
-    net->jpg_upload_pending = 0;
-    if (net->jpg_stage_bytes < in_bytes) {
-        free(net->jpg_stage_host);
-        net->jpg_stage_host = malloc(in_bytes);
-        if (!net->jpg_stage_host) error("network_jpeg_decode_gpu: out of memory");
-        net->jpg_stage_bytes = in_bytes;
-    }
-    uint8_t *stage = net->jpg_stage_host, *in_gpu = net->jpg_in_gpu, *coef_gpu = net->jpg_coef_gpu;
-    memset(stage, 0, off_huff);
-    mi355_jpeg_plane *planes = (mi355_jpeg_plane *)stage;
-    mi355_jpeg_image *images = (mi355_jpeg_image *)(stage + off_images);
-    mi355_jpeg_segment *segs = (mi355_jpeg_segment *)(stage + off_segs);
-    int *slot_of_seg = calloc((size_t)nsegs, sizeof(int));
-    size_t coef_at = 0, plane_at = 0, rgb_at = 0, bits_at = off_bits;
-    int pi = 0, si = 0, hi = 0, blocks_before = 0;
-    for (int b = 0; b < n; ++b) {
-        if (first[b] != b) continue;
-        mi355_jpeg_image *g = &images[frame[b]];
-        int16_t *coef_of[3] = {NULL, NULL, NULL};
-        g->rgb = (uint8_t *)net->jpg_rgb_gpu + rgb_at;
-        g->w = im[b].w; g->h = im[b].h; g->pitch = (3 * im[b].w + 3) & ~3; g->mode = im[b].mode;
-        rgb_at += fr_round((size_t)g->h * (size_t)g->pitch);
-        for (int k = 0; k < im[b].ncomp; ++k, ++pi) {
-            const dnq_jpeg_comp *c = &im[b].comp[k];
-            const size_t blocks = (size_t)c->blocks_w * c->blocks_h;
-            memcpy(stage + off_quant + 128 * (size_t)pi, c->quant, 128);
-            coef_of[k] = (int16_t *)(coef_gpu + coef_at);
-            planes[pi].coef = coef_of[k];
-            planes[pi].quant = (const uint16_t *)(in_gpu + off_quant + 128 * (size_t)pi);
-            planes[pi].out = (uint8_t *)net->jpg_planes_gpu + plane_at;
-            planes[pi].blocks_w = c->blocks_w; planes[pi].blocks_h = c->blocks_h; planes[pi].first_block = blocks_before;
-            g->comp[k].plane = planes[pi].out; g->comp[k].pitch = 8 * c->blocks_w; g->comp[k].rows = c->rows;
-            g->comp[k].hs = c->hs; g->comp[k].vs = c->vs;
-            blocks_before += (int)blocks;
-            coef_at += fr_round(128 * blocks);
-            plane_at += fr_round(64 * blocks);
-        }
-        memcpy(stage + off_huff + sizeof(mi355_jpeg_huff) * (size_t)hi, sl[b].huff, sizeof(mi355_jpeg_huff) * (size_t)sl[b].nhuff);
-        memcpy(stage + bits_at, sl[b].bytes, sl[b].nbytes);
-        for (int q = 0; q < sl[b].nsegs; ++q, ++si) {
-            const dnq_jpeg_scan_seg *z = &sl[b].segs[q];
-            mi355_jpeg_segment *t = &segs[si];
-            slot_of_seg[si] = b;
-            t->bits = (const uint32_t *)(in_gpu + bits_at + z->offset);
-            t->huff = (const mi355_jpeg_huff *)(in_gpu + off_huff);
-            t->nhuff = nhuff;
-            t->nbytes = z->nbytes;
-            t->ncomp = z->ncomp;
-            for (int c = 0; c < z->ncomp; ++c) {
-                const dnq_jpeg_comp *k = &im[b].comp[z->comp[c]];
-                t->coef[c] = coef_of[z->comp[c]];
-                t->bh[c] = z->bh[c]; t->bv[c] = z->bv[c];
-                t->blocks_w[c] = k->blocks_w; t->blocks_h[c] = k->blocks_h;
-                t->dc[c] = hi + z->dc[c]; t->ac[c] = hi + z->ac[c];
-            }
-            t->units_x = z->units_x; t->units_y = z->units_y; t->first_unit = z->first_unit; t->nunits = z->nunits;
-        }
-        hi += sl[b].nhuff;
-        bits_at += sl[b].nbytes; /* a multiple of 4: every segment is padded to one */
-    }
-    for (int b = 0; b < n; ++b) {
-        const mi355_jpeg_image *g = &images[frame[first[b]]];
-        rgb_dev[b] = g->rgb; w[b] = g->w; h[b] = g->h; pitch[b] = g->pitch;
-        jpeg_free(&im[b]);
-        jpeg_scan_free(&sl[b]);
-    }
-    free(im); free(sl); free(first); free(frame);
-    /* one copy, the entropy decode, the one wait of the call (for its status words), then the two launches of the host-decode path */
-    check_mi355(mi355_h2d(in_gpu, stage, in_bytes, net->stream), "upload jpeg streams");
-    check_mi355(mi355_memset(coef_gpu, 0, coef_bytes, net->stream), "zero jpeg coefficients");
-    check_mi355(mi355_jpeg_entropy((const mi355_jpeg_segment *)(in_gpu + off_segs), segs, nsegs, net->jpg_subseq_bits ? net->jpg_subseq_bits : 1024,
-                                   (int *)net->jpg_status_gpu, net->stream), "mi355_jpeg_entropy");
-    check_mi355(mi355_d2h(net->jpg_status_host, net->jpg_status_gpu, sizeof(int) * (size_t)nsegs, net->stream), "read jpeg status");
-    net_wait(net);
-    for (int q = 0; q < nsegs; ++q)
-        if (net->jpg_status_host[q]) {
-            snprintf(jpg_err, sizeof(jpg_err), "jpeg slot %d: %s (device)", slot_of_seg[q], jpg_entropy_reason(net->jpg_status_host[q]));
-            free(slot_of_seg);
-            return MI355_EINVAL;
-        }
-    free(slot_of_seg);
-    check_mi355(mi355_jpeg_idct((const mi355_jpeg_plane *)in_gpu, planes, nplanes, net->stream), "mi355_jpeg_idct");
-    check_mi355(mi355_jpeg_to_rgb((const mi355_jpeg_image *)(in_gpu + off_images), images, nu, net->stream), "mi355_jpeg_to_rgb");
-    return MI355_OK;
-}
-
-int network_jpeg_decode_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int n, uint8_t **rgb_dev, int *w, int *h, int *pitch)
-{
-    if (!net || !data || !bytes || !rgb_dev || !w || !h || !pitch || n < 1 || n > 65535)
-        return jpg_refuse("network_jpeg_decode_gpu: null argument / need 1 <= n <= 65535");
-    if (net->jpg_entropy_on_device) return jpg_decode_entropy_gpu(net, data, bytes, n, rgb_dev, w, h, pitch);
-    /* 1. the host half; a slot that names the bytes of an earlier slot (one image in every slot) shares its decode and its frame */
-    dnq_jpeg *im = calloc((size_t)n, sizeof(dnq_jpeg));
-    int *first = calloc((size_t)n, sizeof(int)), *frame = calloc((size_t)n, sizeof(int));
-    int rc = MI355_OK, nu = 0, nplanes = 0;
-    for (int b = 0; b < n && rc == MI355_OK; ++b) {
-        first[b] = b;
-        for (int k = 0; k < b && first[b] == b; ++k)
-            if (data[k] == data[b] && bytes[k] == bytes[b]) first[b] = k;
-        if (first[b] != b) continue;
-        char why[256];
-        if (!data[b]) {
-            snprintf(jpg_err, sizeof(jpg_err), "jpeg slot %d: null data", b);
-            rc = MI355_EINVAL;
-        } else if (jpeg_decode_host(data[b], bytes[b], &im[b], why, sizeof(why))) {
-            snprintf(jpg_err, sizeof(jpg_err), "jpeg slot %d: %s", b, why);
-            rc = MI355_EINVAL;
-        } else {
-            frame[b] = nu++;
-            nplanes += im[b].ncomp;
-        }
-    }
-    if (rc != MI355_OK) { /* nothing has touched the device */
-        for (int b = 0; b < n; ++b) jpeg_free(&im[b]);
-        free(im); free(first); free(frame);
-        return rc;
-    }
-    /* 2. the layout of the staging block (= of its device copy), of the component planes and of the frames */
-    const size_t off_images = fr_round(sizeof(mi355_jpeg_plane) * (size_t)nplanes);
-    const size_t off_quant = off_images + fr_round(sizeof(mi355_jpeg_image) * (size_t)nu);
-    const size_t off_coef = off_quant + fr_round(128 * (size_t)nplanes);
-    size_t in_bytes = off_coef, planes_bytes = 0, rgb_bytes = 0;
-    for (int b = 0; b < n; ++b) {
-        if (first[b] != b) continue;
-        for (int k = 0; k < im[b].ncomp; ++k) {
-            const size_t blocks = (size_t)im[b].comp[k].blocks_w * im[b].comp[k].blocks_h;
-            in_bytes += fr_round(128 * blocks);
-            planes_bytes += fr_round(64 * blocks);
-        }
-        rgb_bytes += fr_round((size_t)im[b].h * (((size_t)3 * im[b].w + 3) & ~(size_t)3));
-    }
-    check_mi355(mi355_init(net->gpu_index), "mi355_init");
-    if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
-    int waited = 0;
-    jpg_reserve(net, &net->jpg_in_gpu, &net->jpg_in_bytes, in_bytes, &waited, "alloc jpeg coefficients");
-    jpg_reserve(net, &net->jpg_planes_gpu, &net->jpg_planes_bytes, planes_bytes, &waited, "alloc jpeg planes");
-    jpg_reserve(net, &net->jpg_rgb_gpu, &net->jpg_rgb_bytes, rgb_bytes, &waited, "alloc jpeg frames");
-    /* 3. the staging block is rewritten only after the upload that read it last has completed */
-    if (net->jpg_upload_pending && !waited) net_wait(net);
-    net->jpg_upload_pending = 0;
-    if (net->jpg_stage_bytes < in_bytes) {
-        free(net->jpg_stage_host);
-        net->jpg_stage_host = malloc(in_bytes);
-        if (!net->jpg_stage_host) error("network_jpeg_decode_gpu: out of memory");
-        net->jpg_stage_bytes = in_bytes;
-    }
-    uint8_t *stage = net->jpg_stage_host, *in_gpu = net->jpg_in_gpu;
-    memset(stage, 0, off_coef);
-    mi355_jpeg_plane *planes = (mi355_jpeg_plane *)stage;
-    mi355_jpeg_image *images = (mi355_jpeg_image *)(stage + off_images);
-    size_t coef_at = off_coef, plane_at = 0, rgb_at = 0;
-    int pi = 0, blocks_before = 0;
-    for (int b = 0; b < n; ++b) {
-        if (first[b] != b) continue;
-        mi355_jpeg_image *g = &images[frame[b]];
-        g->rgb = (uint8_t *)net->jpg_rgb_gpu + rgb_at;
-        g->w = im[b].w; g->h = im[b].h; g->pitch = (3 * im[b].w + 3) & ~3; g->mode = im[b].mode;
-        rgb_at += fr_round((size_t)g->h * (size_t)g->pitch);
-        for (int k = 0; k < im[b].ncomp; ++k, ++pi) {
-            const dnq_jpeg_comp *c = &im[b].comp[k];
-            const size_t blocks = (size_t)c->blocks_w * c->blocks_h;
-            memcpy(stage + off_quant + 128 * (size_t)pi, c->quant, 128);
-            memcpy(stage + coef_at, c->coef, 128 * blocks);
-            planes[pi].coef = (const int16_t *)(in_gpu + coef_at);
-            planes[pi].quant = (const uint16_t *)(in_gpu + off_quant + 128 * (size_t)pi);
-            planes[pi].out = (uint8_t *)net->jpg_planes_gpu + plane_at;
-            planes[pi].blocks_w = c->blocks_w; planes[pi].blocks_h = c->blocks_h; planes[pi].first_block = blocks_before;
-            g->comp[k].plane = planes[pi].out; g->comp[k].pitch = 8 * c->blocks_w; g->comp[k].rows = c->rows;
-            g->comp[k].hs = c->hs; g->comp[k].vs = c->vs;
-            blocks_before += (int)blocks;
-            coef_at += fr_round(128 * blocks);
-            plane_at += fr_round(64 * blocks);
-        }
-    }
-    for (int b = 0; b < n; ++b) {
-        const mi355_jpeg_image *g = &images[frame[first[b]]];
-        rgb_dev[b] = g->rgb; w[b] = g->w; h[b] = g->h; pitch[b] = g->pitch;
-        jpeg_free(&im[b]);
-    }
-    free(im); free(first); free(frame);
-    /* 4. one copy, two launches */
-    check_mi355(mi355_h2d(in_gpu, stage, in_bytes, net->stream), "upload jpeg coefficients");
-    net->jpg_upload_pending = 1;
-    check_mi355(mi355_jpeg_idct((const mi355_jpeg_plane *)in_gpu, planes, nplanes, net->stream), "mi355_jpeg_idct");
-    check_mi355(mi355_jpeg_to_rgb((const mi355_jpeg_image *)(in_gpu + off_images), images, nu, net->stream), "mi355_jpeg_to_rgb");
-    return MI355_OK;
-}
-
-int network_frames_jpeg_input_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int *w, int *h)
-{
-    if (!net || !w || !h) return jpg_refuse("network_frames_jpeg_input_gpu: null argument");
-    if (net->c != 3) return jpg_refuse("network_frames_jpeg_input_gpu: JPEG images feed 3-channel networks only");
-    const int B = net->batch;
-    uint8_t **rgb = calloc((size_t)B, sizeof(uint8_t *));
-    int *pitch = calloc((size_t)B, sizeof(int));
-    const int rc = network_jpeg_decode_gpu(net, data, bytes, B, rgb, w, h, pitch);
-    if (rc == MI355_OK) network_frames_u8_input_gpu(net, (const uint8_t *const *)rgb, w, h, pitch, MI355_FRAME_RGB, 1);
-    free(rgb); free(pitch);
-    return rc;
-}
-
-/* ------------------------------------------------------------------------------------------------- PNG input
- * The host parses the chunks and inflates (png.c), the device does the rest (png.hip): one staging block -- segment table, image
- * table, palettes, filtered bytes, laid out exactly like its device copy -- goes up in one copy, then mi355_png_unfilter over every
- * pass of every image and mi355_png_to_rgb over every image.  The frames stay on the device for the 8-bit frame path. */
-static _Thread_local char png_err[320];
-const char *network_png_last_error(void) { return png_err; }
-
-static int png_refuse(const char *why)
-{
-    snprintf(png_err, sizeof(png_err), "%s", why);
-    return MI355_EINVAL;
-}
-
-static void pngin_free(network *net)
-{
-    if (net->png_in_gpu) mi355_free(net->png_in_gpu);
-    if (net->png_rows_gpu) mi355_free(net->png_rows_gpu);
-    if (net->png_rgb_gpu) mi355_free(net->png_rgb_gpu);
-    free(net->png_stage_host);
-    net->png_in_gpu = net->png_rows_gpu = net->png_rgb_gpu = net->png_stage_host = NULL;
-    net->png_in_bytes = net->png_rows_bytes = net->png_rgb_bytes = net->png_stage_bytes = 0;
-    net->png_upload_pending = 0;
-}
-
-int network_png_decode_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int n, uint8_t **rgb_dev, int *w, int *h, int *pitch)
-{
-    if (!net || !data || !bytes || !rgb_dev || !w || !h || !pitch || n < 1 || n > 65535)
-        return png_refuse("network_png_decode_gpu: null argument / need 1 <= n <= 65535");
-    /* 1. the host half; a slot that names the bytes of an earlier slot (one image in every slot) shares its decode and its frame */
-    dnq_png *im = calloc((size_t)n, sizeof(dnq_png));
-    int *first = calloc((size_t)n, sizeof(int)), *frame = calloc((size_t)n, sizeof(int));
-    if (!im || !first || !frame) error("network_png_decode_gpu: out of memory");
-    int rc = MI355_OK, nu = 0, nsegs = 0;
-    for (int b = 0; b < n && rc == MI355_OK; ++b) {
-        first[b] = b;
-        for (int k = 0; k < b && first[b] == b; ++k)
-            if (data[k] == data[b] && bytes[k] == bytes[b]) first[b] = k;
-        if (first[b] != b) continue;
-        char why[256];
-        if (!data[b]) {
-            snprintf(png_err, sizeof(png_err), "png slot %d: null data", b);
-            rc = MI355_EINVAL;
-        } else if (png_decode_host(data[b], bytes[b], &im[b], why, sizeof(why))) {
-            snprintf(png_err, sizeof(png_err), "png slot %d: %s", b, why);
-            rc = MI355_EINVAL;
-        } else {
-            frame[b] = nu++;
-            nsegs += im[b].npasses;
-        }
-    }
-    if (rc != MI355_OK) { /* nothing has touched the device */
-        for (int b = 0; b < n; ++b) png_free(&im[b]);
-        free(im); free(first); free(frame);
-        return rc;
-    }
-    /* 2. the layout of the staging block (= of its device copy), of the reconstructed passes and of the frames */
-    const size_t off_images = fr_round(sizeof(mi355_png_segment) * (size_t)nsegs);
-    const size_t off_pal = off_images + fr_round(sizeof(mi355_png_image) * (size_t)nu);
-    const size_t off_bytes = off_pal + 768 * (size_t)nu;
-    size_t in_bytes = fr_round(off_bytes), rows_bytes = 0, rgb_bytes = 0;
-    for (int b = 0; b < n; ++b) {
-        if (first[b] != b) continue;
-        in_bytes += fr_round(im[b].filtered_bytes);
-        for (int k = 0; k < im[b].npasses; ++k) rows_bytes += fr_round((size_t)im[b].pass[k].rows * (size_t)im[b].pass[k].row_bytes);
-        rgb_bytes += fr_round((size_t)im[b].h * (((size_t)3 * im[b].w + 3) & ~(size_t)3));
-    }
-    check_mi355(mi355_init(net->gpu_index), "mi355_init");
-    if (!net->stream && !net->on_default_stream) check_mi355(mi355_stream_acquire(&net->stream), "stream");
-    int waited = 0;
-    jpg_reserve(net, &net->png_in_gpu, &net->png_in_bytes, in_bytes, &waited, "alloc png scanlines");
-    jpg_reserve(net, &net->png_rows_gpu, &net->png_rows_bytes, rows_bytes, &waited, "alloc png passes");
-    jpg_reserve(net, &net->png_rgb_gpu, &net->png_rgb_bytes, rgb_bytes, &waited, "alloc png frames");
-    /* 3. the staging block is rewritten only after the upload that read it last has completed */
-    if (net->png_upload_pending && !waited) net_wait(net);
-    net->png_upload_pending = 0;
-    if (net->png_stage_bytes < in_bytes) {
-        free(net->png_stage_host);
-        net->png_stage_host = malloc(in_bytes);
-        if (!net->png_stage_host) error("network_png_decode_gpu: out of memory");
-        net->png_stage_bytes = in_bytes;
-    }
-    uint8_t *stage = net->png_stage_host, *in_gpu = net->png_in_gpu;
-    memset(stage, 0, fr_round(off_bytes));
-    mi355_png_segment *segs = (mi355_png_segment *)stage;
-    mi355_png_image *images = (mi355_png_image *)(stage + off_images);
-    size_t bytes_at = fr_round(off_bytes), rows_at = 0, rgb_at = 0;
-    int si = 0;
-    for (int b = 0; b < n; ++b) {
-        if (first[b] != b) continue;
-        const dnq_png *p = &im[b];
-        mi355_png_image *g = &images[frame[b]];
-        g->rgb = (uint8_t *)net->png_rgb_gpu + rgb_at;
-        g->w = p->w; g->h = p->h; g->pitch = (3 * p->w + 3) & ~3;
-        g->depth = p->depth; g->color = p->color; g->interlace = p->interlace; g->pal_len = p->pal_len;
-        rgb_at += fr_round((size_t)g->h * (size_t)g->pitch);
-        if (p->color == 3) {
-            memcpy(stage + off_pal + 768 * (size_t)frame[b], p->palette, 768);
-            g->palette = in_gpu + off_pal + 768 * (size_t)frame[b];
-        }
-        memcpy(stage + bytes_at, p->filtered, p->filtered_bytes);
-        for (int k = 0; k < p->npasses; ++k, ++si) {
-            const dnq_png_pass *q = &p->pass[k];
-            segs[si].filtered = in_gpu + bytes_at + q->offset;
-            segs[si].out = (uint8_t *)net->png_rows_gpu + rows_at;
-            segs[si].row_bytes = q->row_bytes; segs[si].rows = q->rows; segs[si].bpp = p->bpp;
-            g->pass[q->index] = segs[si].out;
-            rows_at += fr_round((size_t)q->rows * (size_t)q->row_bytes);
-        }
-        bytes_at += fr_round(p->filtered_bytes);
-    }
-    for (int b = 0; b < n; ++b) {
-        const mi355_png_image *g = &images[frame[first[b]]];
-        rgb_dev[b] = g->rgb; w[b] = g->w; h[b] = g->h; pitch[b] = g->pitch;
-        png_free(&im[b]);
-    }
-    free(im); free(first); free(frame);
-    /* 4. one copy, two launches */
-    check_mi355(mi355_h2d(in_gpu, stage, in_bytes, net->stream), "upload png scanlines");
-    net->png_upload_pending = 1;
-    check_mi355(mi355_png_unfilter((const mi355_png_segment *)in_gpu, segs, nsegs, net->stream), "mi355_png_unfilter");
-    check_mi355(mi355_png_to_rgb((const mi355_png_image *)(in_gpu + off_images), images, nu, net->stream), "mi355_png_to_rgb");
-    return MI355_OK;
-}
-
-int network_frames_png_input_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int *w, int *h)
-{
-    if (!net || !w || !h) return png_refuse("network_frames_png_input_gpu: null argument");
-    if (net->c != 3) return png_refuse("network_frames_png_input_gpu: PNG images feed 3-channel networks only");
-    const int B = net->batch;
-    uint8_t **rgb = calloc((size_t)B, sizeof(uint8_t *));
-    int *pitch = calloc((size_t)B, sizeof(int));
-    const int rc = network_png_decode_gpu(net, data, bytes, B, rgb, w, h, pitch);
-    if (rc == MI355_OK) network_frames_u8_input_gpu(net, (const uint8_t *const *)rgb, w, h, pitch, MI355_FRAME_RGB, 1);
-    free(rgb); free(pitch);
-    return rc;
 }
 
 void set_batch_network(network *net, int b)
@@ -2436,8 +1621,7 @@ void free_network(network *net)
     pi_free(net);
     od_free(net);
     fr_free(net);
-    jpg_free(net);
-    pngin_free(net);
+    coded_free(net);
     detb_free(net);
     if (net->selfcheck_gpu) mi355_free(net->selfcheck_gpu);
     if (net->stream) mi355_stream_release(net->stream);
