@@ -225,6 +225,14 @@ struct network {
     /* PNG input (network_png_decode_gpu).  The staging block holds segment table | image table | palettes | filtered bytes, the work
      * buffer the reconstructed passes mi355_png_unfilter writes.  A replica owns its own. */
     coded_bufs png;
+    /* set_png_inflate_on_device: the staging block then holds segment table | image table | palettes | stream table | compressed bytes,
+     * and the filtered bytes exist on the device only */
+    int png_inflate_on_device;
+    void *png_filt_gpu;         /* the filtered bytes mi355_png_inflate writes */
+    size_t png_filt_bytes;
+    void *png_status_gpu;       /* one status word per stream of the last call */
+    int *png_status_host;       /* their host copy */
+    size_t png_status_bytes;
     /* Batched box decode (network_yolo_detections_batch_gpu): lazily allocated, grown when needed, freed with the network and on
      * re-batch.  A replica owns its own. */
     int *detb_ints_gpu, *detb_ints_host; /* [2][batch] source sizes | counts [batch][nheads] | offsets [batch + 1] */
@@ -389,6 +397,18 @@ int network_png_decode_gpu(network *net, const uint8_t *const *data, const size_
                            int *pitch);
 int network_frames_png_input_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int *w, int *h);
 const char *network_png_last_error(void);
+/* set_png_inflate_on_device(net, 1): network_png_decode_gpu (and network_frames_png_input_gpu) only finds the deflate streams on the host
+ * (yolo_quantization_amd/host/png_scan.h: the same headers and the same refusals, which still launch nothing) and uploads the compressed
+ * bytes instead of the filtered ones; mi355_png_inflate inflates every image of the batch in one launch, one wave each, into a device
+ * buffer of the network, and the two launches follow unchanged.  The frames, and so the network's input, are byte for byte the ones
+ * of the host inflate.  A stream the device refuses returns MI355_EINVAL with "png slot <b>: <reason> (device)" -- the host decoder's
+ * reason -- after the inflate and before anything else is launched: the call waits once for the status words (network_host_waits()
+ * counts it), in this mode only.  An image with 2^31 or more filtered bytes, or more than 2^28 compressed ones, is refused in this
+ * mode; the host mode takes it.  Off by default; a replica inherits the mode. */
+void set_png_inflate_on_device(network *net, int on);
+struct dnq_png_scan;
+int png_scan_host(const uint8_t *data, size_t bytes, struct dnq_png_scan *out, char *err, size_t errlen);
+void png_scan_free(struct dnq_png_scan *s);
 /* The same step for raw sensor frames: one plane with one sample per pixel behind a Bayer colour filter (pattern: MI355_BAYER_RGGB,
  * _BGGR, _GRBG, _GBRG) or none (MI355_BAYER_MONO), as machine-vision cameras (BayerRG8 .., Mono8 .. Mono16) and MIPI CSI-2 sensors
  * without an ISP (RAW10, RAW12) deliver them.  sample: MI355_RAW_U8 (pitch[b] >= w[b]), MI355_RAW_U16 (little-endian, reduced to

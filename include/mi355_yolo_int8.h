@@ -709,6 +709,43 @@ typedef struct mi355_png_image {      /* 104 bytes */
 } mi355_png_image;
 int mi355_png_unfilter(const mi355_png_segment *table_dev, const mi355_png_segment *table_host, int nsegments, void *stream);
 int mi355_png_to_rgb(const mi355_png_image *table_dev, const mi355_png_image *table_host, int B, void *stream);
+/* Inflate of the IDAT streams on the device: the step in front of mi355_png_unfilter.  The host walks the chunks and gathers the
+ * IDAT payloads behind the two-byte zlib header into one buffer (yolo_quantization_amd/host/png_scan.h); a STREAM is that raw deflate
+ * data (RFC 1951) of one image.  mi355_png_inflate is one launch for every stream of a batch, one wave per stream: deflate has no
+ * block index, so a stream decodes front to back.  Lane 0 follows the symbols and fills a list of up to 64 tokens a round; all lanes
+ * build the blocks' Huffman tables, place the literals, copy the matches and the stored blocks inside a 64 KiB ring of the output in
+ * LDS and flush it to `out` in coalesced dword stores; see DESIGN.md.  The bytes are the host decoder's (png_decode_host's
+ * `filtered`), and the decode stops at `cap`, whatever the bits say: what a stream holds beyond the bytes the image needs is not read.
+ *
+ * `z`: nbytes bytes, 4-byte aligned, followed by zero bytes up to at least ((nbytes + 3) & ~3) + 8; nothing beyond them is read.
+ * `out`: cap bytes, 4-byte aligned; nothing outside out[0, cap) is written.  rows[k], row_bytes[k], k < npasses: the passes of the
+ * image in the order of their bytes, rows[k] rows of 1 + row_bytes[k] bytes; they add up to cap.  Behind the last byte the first byte
+ * of every row is checked against 4.  status_dev[s]: 0, or the first reason in the host decoder's order: what the stream raises
+ * (MI355_PNG_EBLOCK .. MI355_PNG_EPAST), then MI355_PNG_EPIXELS (the final block ended short of cap), then MI355_PNG_EFILTER.  These are
+ * defined returns of a bounded kernel: at most 8 * nbytes + 64 symbol steps and cap output bytes per stream, no wave waits for another.
+ *
+ * table_host mirrors table_dev and is validated before anything is launched (null or misaligned pointers, nbytes above 2^28, cap of 0
+ * or at least 2^31, npasses outside 1..7, passes that do not add up to cap, nstreams outside 1..65535): MI355_EINVAL with a message
+ * that starts "png_inflate:".  New struct and a new call: MI355_ABI_VERSION is unchanged. */
+#define MI355_PNG_EBLOCK     1        /* bad block type */
+#define MI355_PNG_ECORRUPT   2        /* zlib corrupt: a stored block's LEN / NLEN */
+#define MI355_PNG_ELENGTHS   3        /* bad codelengths */
+#define MI355_PNG_EHUFF      4        /* bad huffman code */
+#define MI355_PNG_EDIST      5        /* bad dist */
+#define MI355_PNG_EPREMATURE 6        /* premature end of the zlib data */
+#define MI355_PNG_EPAST      7        /* read past buffer: a stored block longer than the stream */
+#define MI355_PNG_EPIXELS    8        /* not enough pixels */
+#define MI355_PNG_EFILTER    9        /* invalid filter */
+typedef struct mi355_png_stream {     /* 88 bytes */
+    const uint32_t *z;                /* DEVICE: raw deflate data */
+    uint8_t *out;                     /* DEVICE: cap bytes */
+    uint32_t nbytes;
+    uint32_t cap;                     /* the image's filtered bytes: the stop mark */
+    int npasses;
+    int rows[7], row_bytes[7];
+    int reserved;                     /* zero */
+} mi355_png_stream;
+int mi355_png_inflate(const mi355_png_stream *table_dev, const mi355_png_stream *table_host, int nstreams, int *status_dev, void *stream);
 /* *sum_dev += an order-independent 64-bit checksum of `dwords` 32-bit words at buf (device pointers; zero *sum_dev first).  The
  * host's determinism self-check compares it between passes over the same input (network_selfcheck, darknet_q.h). */
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream);

@@ -45,10 +45,14 @@ clock, one thread), `upload_ms`, `idct_ms`, `to_rgb_ms` (HIP events around one c
 launch; medians of `iters`).  Before timing, the jpeg network's uint8 input, scales and zero points are compared with the u8 network's.
 
 --png times the PNG input path in the same way: batch 64 of 640 x 480 8-bit RGB files (the same pictures, filtered with Paeth and
-deflated by zlib at its default level before the clock starts), per scale mode two variants alternating within a repeat:
+deflated by zlib at its default level before the clock starts), per scale mode three variants alternating within a repeat:
   png     network_frames_png_input_gpu: host chunk parse + inflate of the batch, one upload of tables and filtered bytes,
           mi355_png_unfilter, mi355_png_to_rgb, then the u8 step on the frames where they lie
   u8      network_frames_u8_input_gpu on the decoded RGB frames in host memory
+  png_device  the same call with set_png_inflate_on_device: host chunk walk + gather of the IDAT payloads, one upload of tables and
+          compressed bytes, mi355_png_inflate, one wait for its status words, then the same two launches and the u8 step (its input,
+          scales and zero points are compared with the png network's first).  `stages_png_device`: host_scan_ms, upload_ms /
+          upload_bytes, inflate_ms (mi355_png_inflate between device events)
 and, once, the stages on their own: `host_inflate_ms` (png_decode_host over the batch, host clock, one thread), `upload_ms`,
 `unfilter_ms`, `to_rgb_ms` (HIP events around one copy of all filtered bytes and around each launch; medians of `iters`).  Before
 timing, the png network's uint8 input, scales and zero points are compared with the u8 network's.
@@ -392,22 +396,82 @@ def png_stages(files, ev, iters):
     return res, frames
 
 
+def inflate_stages(files, ev, iters):
+    """the stages of the png_device variant on their own, on the default stream: host scan (chunk walk + gather of the IDAT payloads),
+    one upload of the stream table and the compressed bytes, mi355_png_inflate between device events"""
+    S, H = binding.shim(), binding.host()
+    scan_ms = []
+    for _ in range(max(3, iters // 4)):
+        t0 = time.perf_counter()
+        for f in files:
+            sc = binding.DnqPngScan()
+            if H.png_scan_host(f, len(f), C.byref(sc), None, 0) != 0:
+                sys.exit("a generated file was refused")
+            H.png_scan_free(C.byref(sc))
+        scan_ms.append((time.perf_counter() - t0) * 1e3)
+    scans = [binding.png_scan(f) for f in files]
+    want = [binding.png_scanlines(f)["filtered"].tobytes() for f in files]
+    n = len(scans)
+    table = (binding.PngStream * n)()
+    zat, oat, ztot, otot = [], [], 0, 0
+    for sc in scans:
+        zat.append(ztot)
+        ztot += (((len(sc["z"]) + 3) & ~3) + 8 + 255) & ~255
+        oat.append(otot)
+        otot += (sc["filtered_bytes"] + 255) & ~255
+    stage = np.zeros(C.sizeof(table) + ztot, np.uint8)
+    for sc, at in zip(scans, zat):
+        stage[C.sizeof(table) + at:C.sizeof(table) + at + len(sc["z"])] = np.frombuffer(sc["z"], np.uint8)
+    dev, out, st = binding.DevBuf(stage.nbytes), binding.DevBuf(otot), binding.DevBuf(4 * n)
+    for i, sc in enumerate(scans):
+        t = table[i]
+        t.z, t.out, t.nbytes, t.cap = dev.ptr.value + C.sizeof(table) + zat[i], out.ptr.value + oat[i], len(sc["z"]), sc["filtered_bytes"]
+        t.npasses = len(sc["passes"])
+        for k, q in enumerate(sc["passes"]):
+            t.rows[k], t.row_bytes[k] = q["rows"], q["row_bytes"]
+    stage[:C.sizeof(table)] = np.frombuffer(bytes(table), np.uint8)
+    res = {"host_scan_ms": round(float(np.median(scan_ms)), 4), "upload_bytes": int(stage.nbytes), "stream_bytes": int(sum(len(sc["z"]) for sc in scans)),
+           "streams": n}
+    calls = {"upload_ms": lambda: S.mi355_h2d(dev.ptr, stage.ctypes.data, stage.nbytes, None),
+             "inflate_ms": lambda: S.mi355_png_inflate(dev.ptr, table, n, st.ptr, None)}
+    for name, call in calls.items():
+        ms = []
+        for _ in range(iters + 2):
+            binding.check(S.mi355_stream_sync(None), "sync")
+            binding.check(S.mi355_event_record(ev.a, None), "record")
+            binding.check(call(), name)
+            binding.check(S.mi355_event_record(ev.b, None), "record")
+            binding.check(S.mi355_stream_sync(None), "sync")
+            ms.append(ev.ms())
+        res[name] = round(float(np.median(ms[2:])), 4)
+    status = st.to_numpy(np.int32, n)
+    got = out.to_numpy(np.uint8, otot)
+    res["filtered_bytes_identical_to_png_decode_host"] = bool(not status.any() and all(
+        got[oat[i]:oat[i] + len(w)].tobytes() == w for i, w in enumerate(want)))
+    for b in (dev, out, st):
+        b.free()
+    return res
+
+
 def png_main(a, wts, ev):
     sw, sh = (int(v) for v in a.src.split("x"))
     files, pics = make_pngs(a.batch, sw, sh)
     res = {}
     res["stages"], frames = png_stages(files, ev, a.iters)
+    res["stages_png_device"] = inflate_stages(files, ev, a.iters)
     res["frames_identical_to_the_pictures"] = bool(all(np.array_equal(f, p) for f, p in zip(frames, pics)))
     for mode in ("shared", "per_image"):
-        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("png", "u8")}
+        nets = {k: binding.Net(CFG, wts, batch=a.batch) for k in ("png", "png_device", "u8")}
         for n in nets.values():
             n.set_input_per_image(mode == "per_image")
-        var = {"png": PngVariant(nets["png"], files), "u8": FramesVariant(nets["u8"], frames)}
+        nets["png_device"].set_png_inflate_on_device(True)
+        var = {"png": PngVariant(nets["png"], files), "png_device": PngVariant(nets["png_device"], files), "u8": FramesVariant(nets["u8"], frames)}
         for _ in range(a.warmup):
             for v in var.values():
                 v.step()
         out = {k: {"device_ms": [], "wall_ms": [], "call_ms": []} for k in var}
         same = same_input(nets["png"], nets["u8"])
+        out["png_device_identical_to_png"] = same_input(nets["png_device"], nets["png"])
         for _ in range(a.repeats):
             for k, v in var.items():  # alternating
                 for name, x in zip(("device_ms", "wall_ms", "call_ms"), timed(v, ev, a.iters)):

@@ -187,7 +187,20 @@ class DnqPng(C.Structure):
                 ("palette", C.c_uint8 * 768), ("filtered_bytes", C.c_size_t), ("filtered", C.POINTER(C.c_uint8))]
 
 
+class PngStream(C.Structure):
+    """mi355_png_stream: the deflate stream of one image of mi355_png_inflate's table (device pointers)."""
+    _fields_ = [("z", C.c_void_p), ("out", C.c_void_p), ("nbytes", C.c_uint32), ("cap", C.c_uint32), ("npasses", C.c_int),
+                ("rows", C.c_int * 7), ("row_bytes", C.c_int * 7), ("reserved", C.c_int)]
+
+
+class DnqPngScan(C.Structure):
+    """dnq_png_scan (yolo_quantization_amd/host/png_scan.h): what png_scan_host returns."""
+    _fields_ = [("im", DnqPng), ("z", C.POINTER(C.c_uint8)), ("nbytes", C.c_size_t), ("zcap", C.c_size_t)]
+
+
 PNG_MAX_DIM = 32768  # DNQ_PNG_MAX_DIM
+PNG_INFLATE_ERRORS = {1: "bad block type", 2: "zlib corrupt", 3: "bad codelengths", 4: "bad huffman code", 5: "bad dist",
+                      6: "premature end of the zlib data", 7: "read past buffer", 8: "not enough pixels", 9: "invalid filter"}
 JPEG_MODES = ("ycbcr", "rgb", "grey")
 JPEG_ENTROPY_ERRORS = {1: "bad huffman code", 2: "bad DC category", 3: "coefficient index past the end of the block"}
 
@@ -269,6 +282,8 @@ def shim():
             L.mi355_png_to_rgb.argtypes = [vp, C.POINTER(PngImage), ci, vp]
         if hasattr(L, "mi355_jpeg_entropy"):
             L.mi355_jpeg_entropy.argtypes = [vp, C.POINTER(JpegSegment), ci, ci, vp, vp]
+        if hasattr(L, "mi355_png_inflate"):
+            L.mi355_png_inflate.argtypes = [vp, C.POINTER(PngStream), ci, vp, vp]
         L.mi355_frames_u8_letterbox_minmax.argtypes = [vp, C.POINTER(FrameU8), ci, ci, ci, vp, vp]
         L.mi355_frames_u8_letterbox_quantize.argtypes = [vp, C.POINTER(FrameU8), ci, ci, ci, vp, vp, vp, vp]
         L.mi355_frames_yuv_letterbox_minmax.argtypes = [vp, C.POINTER(FrameYUV), ci, ci, ci, vp, vp]
@@ -551,6 +566,16 @@ def host():
             L.set_jpeg_entropy_on_device.restype = None
             L.set_jpeg_entropy_subseq_bits.argtypes = [vp, ci]
             L.set_jpeg_entropy_subseq_bits.restype = None
+        if hasattr(L, "png_scan_host"):
+            L.png_scan_host.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(DnqPngScan), C.c_char_p, C.c_size_t]
+            L.png_scan_free.argtypes = [C.POINTER(DnqPngScan)]
+            L.png_scan_free.restype = None
+            L.png_inflate_emulate_host.argtypes = [C.POINTER(PngStream), ci, C.POINTER(ci)]
+            L.png_inflate_emulate_why.restype = C.c_char_p
+            L.png_inflate_reason.argtypes = [ci]
+            L.png_inflate_reason.restype = C.c_char_p
+            L.set_png_inflate_on_device.argtypes = [vp, ci]
+            L.set_png_inflate_on_device.restype = None
         if hasattr(L, "network_frames_bayer_input_gpu"):  # as above
             L.network_frames_bayer_input_gpu.argtypes = [vp, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, ci, ci,
                                                          C.POINTER(vp), ci]
@@ -1005,14 +1030,120 @@ def png_scanlines(data):
         host().png_free(C.byref(p))
 
 
-def png_inflate(z, cap):
-    """png_inflate_host: the decoder's inflate on a zlib stream, at most cap bytes of output.  Host only."""
+def png_inflate(z, cap, passes=None):
+    """Two calls under one name.  png_inflate(z: bytes, cap: int): png_inflate_host, the host decoder's inflate on a ZLIB stream, at
+    most cap bytes of output; host only.  png_inflate(streams: list, caps: list, passes): mi355_png_inflate on built inputs, see
+    png_inflate_device."""
+    if not isinstance(z, (bytes, bytearray, memoryview)):
+        return png_inflate_device(z, cap, passes)
     out = np.empty(max(cap, 1), np.uint8)
     n = C.c_size_t(0)
     err = C.create_string_buffer(256)
     if host().png_inflate_host(bytes(z), len(z), out.ctypes.data, cap, C.byref(n), err, len(err)) != 0:
         raise PngError(err.value.decode())
     return out[:n.value].tobytes()
+
+
+def png_scan(data):
+    """png_scan_host on a PNG (bytes or a path): png_info's dict plus "z", the raw deflate data (the IDAT payloads behind the two-byte
+    zlib header).  Host only, nothing is inflated; raises PngError with the decoder's message."""
+    data = _jpeg_bytes(data)
+    sc = DnqPngScan()
+    err = C.create_string_buffer(256)
+    if host().png_scan_host(data, len(data), C.byref(sc), err, len(err)) != 0:
+        raise PngError(err.value.decode())
+    try:
+        d = _png_dict(sc.im)
+        raw = bytes(np.ctypeslib.as_array(sc.z, shape=(sc.zcap,)))
+        assert sc.zcap == ((sc.nbytes + 3) & ~3) + 8 and not any(raw[sc.nbytes:])
+        d["z"] = raw[:sc.nbytes]
+        return d
+    finally:
+        host().png_scan_free(C.byref(sc))
+
+
+PNG_INFLATE_GUARD = 256  # guard bytes around every output of png_inflate_device / png_inflate_emulate
+_STATUS_GUARD = 16       # guard words around the status words
+
+
+def _png_inflate_run(streams, caps, passes, emulate):
+    """One call of mi355_png_inflate (or of the emulation) for all streams.  Every output lies between guard bytes (0xA5), the status
+    words between guard words; MI355Error if a guard changed.  passes[i]: [(rows, row_bytes), ...] of stream i; None: one row of
+    caps[i] - 1 bytes.  Returns (outputs: bytes of caps[i] each, statuses)."""
+    n = len(streams)
+    assert n == len(caps) and n >= 1
+    passes = [None] * n if passes is None else list(passes)
+    G = PNG_INFLATE_GUARD
+    table = (PngStream * n)()
+    zat, oat, ztot, otot = [], [], 0, G
+    for z, cap in zip(streams, caps):
+        zat.append(ztot)
+        ztot += (((len(z) + 3) & ~3) + 8 + 255) & ~255
+        oat.append(otot)
+        otot += ((cap + 3) & ~3) + G
+    znp = np.zeros(max(ztot, 16), np.uint8)
+    for z, at in zip(streams, zat):
+        znp[at:at + len(z)] = np.frombuffer(bytes(z), np.uint8)
+    onp = np.full(otot, 0xA5, np.uint8)
+    snp = np.full(n + 2 * _STATUS_GUARD, 0x5A5A5A5A, np.int32)
+    if emulate:
+        zptr, optr, keep = znp.ctypes.data, onp.ctypes.data, []
+    else:
+        zb, ob, sb = DevBuf.from_numpy(znp), DevBuf.from_numpy(onp), DevBuf.from_numpy(snp)
+        zptr, optr, keep = zb.ptr.value, ob.ptr.value, [zb, ob, sb]
+    for i, (z, cap) in enumerate(zip(streams, caps)):
+        t = table[i]
+        t.z, t.out, t.nbytes, t.cap = zptr + zat[i], optr + oat[i], len(z), cap
+        ps = passes[i] if passes[i] is not None else [(1, cap - 1)]
+        t.npasses = len(ps)
+        for k, (rows, rb) in enumerate(ps[:7]):
+            t.rows[k], t.row_bytes[k] = rows, rb
+    try:
+        if emulate:
+            status = (C.c_int * n)()
+            if host().png_inflate_emulate_host(table, n, status) != 0:
+                raise MI355Error("png_inflate_emulate_host: " + host().png_inflate_emulate_why().decode())
+            snp[_STATUS_GUARD:_STATUS_GUARD + n] = list(status)
+        else:
+            tdev = DevBuf.from_numpy(np.frombuffer(bytes(table), np.uint8))
+            keep.append(tdev)
+            check(shim().mi355_png_inflate(tdev.ptr, table, n, sb.ptr.value + 4 * _STATUS_GUARD, None), "mi355_png_inflate")
+            check(shim().mi355_stream_sync(None), "sync")
+            onp = ob.to_numpy(np.uint8, otot)
+            snp = sb.to_numpy(np.int32, n + 2 * _STATUS_GUARD)
+    finally:
+        for b in keep:
+            b.free()
+    if not ((snp[:_STATUS_GUARD] == 0x5A5A5A5A).all() and (snp[_STATUS_GUARD + n:] == 0x5A5A5A5A).all()):
+        raise MI355Error("mi355_png_inflate wrote outside its status words")
+    outs, at = [], 0
+    for i, cap in enumerate(caps):
+        if not (onp[at:oat[i]] == 0xA5).all():
+            raise MI355Error(f"mi355_png_inflate wrote in front of stream {i}'s output")
+        outs.append(onp[oat[i]:oat[i] + cap].tobytes())
+        at = oat[i] + cap
+    if not (onp[at:] == 0xA5).all():
+        raise MI355Error("mi355_png_inflate wrote behind the last stream's output")
+    return outs, [int(v) for v in snp[_STATUS_GUARD:_STATUS_GUARD + n]]
+
+
+def png_inflate_device(streams, caps, passes=None):
+    """mi355_png_inflate on built inputs: streams[i] is raw deflate data (no zlib header), caps[i] its stop mark, passes[i] its
+    [(rows, row_bytes), ...] (None: one row of caps[i] - 1 bytes, so only the first byte is checked against 4); ONE launch for all of
+    them.  Returns (outputs, statuses): caps[i] bytes per stream (0xA5 where nothing was stored) and its status word (0, or a key of
+    PNG_INFLATE_ERRORS).  Guard bytes before, between and behind the outputs and guard words around the status words must come back
+    as they were.  A table the call refuses raises MI355Error with its message."""
+    return _png_inflate_run(list(streams), list(caps), passes, False)
+
+
+def png_inflate_emulate(streams, caps, passes=None):
+    """png_inflate_device's arguments and results from png_inflate_emulate_host: the kernel's rounds on the CPU, no device."""
+    return _png_inflate_run(list(streams), list(caps), passes, True)
+
+
+def png_stream_of(scan):
+    """(stream, cap, passes) of a png_scan dict, as png_inflate_device takes them"""
+    return scan["z"], scan["filtered_bytes"], [(q["rows"], q["row_bytes"]) for q in scan["passes"]]
 
 
 def png_unfilter(segments, src_offset=0, dst_offset=0):
@@ -1306,6 +1437,11 @@ class Net:
         self.H.set_jpeg_entropy_on_device(self.h, 1 if on else 0)
         if subseq_bits is not None:
             self.H.set_jpeg_entropy_subseq_bits(self.h, int(subseq_bits))
+
+    def set_png_inflate_on_device(self, on=True):
+        """PNG streams are inflated on the device (set_png_inflate_on_device): the input the network sees is unchanged; the PNG calls
+        then wait once, for the streams' status words."""
+        self.H.set_png_inflate_on_device(self.h, 1 if on else 0)
 
     def prepare_from_jpeg(self, items):
         """JPEG input path (network_frames_jpeg_input_gpu): every item (the bytes of a JPEG file, or a path) is entropy-decoded on the

@@ -269,6 +269,9 @@ int png_to_rgb_launch(const mi355_png_image *table_dev, const mi355_png_image *t
 // jpeg_entropy.hip: Huffman decoding of every segment of a batch, one workgroup each
 const char *jpeg_entropy_check(const mi355_jpeg_segment *host, int nsegments, int subseq_bits);
 int jpeg_entropy_launch(const mi355_jpeg_segment *table_dev, int nsegments, int subseq_bits, int *status_dev, hipStream_t st);
+// png_inflate.hip: inflate of every deflate stream of a batch, one wave each
+const char *png_inflate_check(const mi355_png_stream *host, int nstreams);
+int png_inflate_launch(const mi355_png_stream *table_dev, int nstreams, int *status_dev, hipStream_t st);
 int yolo_detections_sizes_launch(const float *out, int B, int n, int classes, int h, int w, const float *biases, const int *mask,
                                  int netw, int neth, const int *imw_dev, const int *imh_dev, float thresh, int relative, float *recs,
                                  int max_recs, int *counts, hipStream_t st);

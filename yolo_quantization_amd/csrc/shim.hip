@@ -1193,6 +1193,14 @@ int mi355_jpeg_entropy(const mi355_jpeg_segment *table_dev, const mi355_jpeg_seg
     return jpeg_entropy_launch(table_dev, nsegments, subseq_bits, status_dev, (hipStream_t)stream);
 }
 
+int mi355_png_inflate(const mi355_png_stream *table_dev, const mi355_png_stream *table_host, int nstreams, int *status_dev, void *stream)
+{
+    if (!table_dev || !status_dev) return einval("png_inflate: null");
+    const char *why = png_inflate_check(table_host, nstreams);
+    if (why) return einval(why);
+    return png_inflate_launch(table_dev, nstreams, status_dev, (hipStream_t)stream);
+}
+
 int mi355_frames_bayer_letterbox_minmax(const mi355_frame_bayer *table_dev, const mi355_frame_bayer *table_host, int B, int w, int h,
                                         float *minmax, void *stream)
 {

@@ -41,6 +41,7 @@
  * -input_device (detector test: the input scales and layer 0's constants are derived on the device, no copy back and no wait inside
  * the input step -- set_input_quantization_on_device; the output is unchanged).
  * -jpeg_device (JPEG sources: their scans are entropy-decoded on the device too -- set_jpeg_entropy_on_device; the output is unchanged).
+ * -png_device (PNG sources: their IDAT streams are inflated on the device too -- set_png_inflate_on_device; the output is unchanged).
  *
  * Image input: a baseline JPEG of ANY size -- any file that starts FF D8, whatever its name: entropy decode on the host, inverse DCT,
  * upsampling and colour conversion on the device (network_frames_jpeg_input_gpu), the pixels stb_image gives the reference, byte for
@@ -230,6 +231,7 @@ typedef struct {
     float thresh, hier_thresh;
     int batch, accum, store, use_graph, iters, gpu, boxes, quiet, inflight;
     int jpeg_device;       /* -jpeg_device: JPEG scans are entropy-decoded on the device (set_jpeg_entropy_on_device) */
+    int png_device;        /* -png_device: PNG streams are inflated on the device (set_png_inflate_on_device) */
     int input_device;      /* -input_device: scales and layer-0 constants are derived on the device (set_input_quantization_on_device) */
     int rank, nranks;      /* -gpus with -bcast: this replica's rank; rank 0 reads the weights file, the others receive blobs */
     const void *comm_id;   /* shared 128-byte RCCL unique id (NULL: every replica reads the file) */
@@ -507,6 +509,7 @@ static void test_detector(detect_job *job)
     }
 
     if (job->jpeg_device) set_jpeg_entropy_on_device(net, 1);
+    if (job->png_device) set_png_inflate_on_device(net, 1);
     if (job->input_device) {
         if (job->inflight > 1) error("-input_device does not go with -inflight: a replica's bank is filled by its own input step");
         if (set_input_quantization_on_device(net, 1)) error("-input_device: layer 0 cannot run on constants derived on the device");
@@ -601,7 +604,7 @@ int main(int argc, char **argv)
     if (argc < 2) {
         fprintf(stderr, "usage: %s detector test <data> <cfg> <weights> <image> [-thresh t] [-i gpu | -gpus a,b,..] [-batch B] "
                         "[-accum exact|ref-f32] [-parity wrap|saturate] [-dump dir] [-graph] [-n iters] [-boxes] "
-                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8|nv12|nv21|i420|yv12|i422|i444|rgba|bgra|argb|abgr|yuyv|uyvy|yvyu|p010|rggb|bggr|grbg|gbrg|mono] [-matrix bt601|bt601f|bt709|bt709f] [-raw u8|u16|mipi10|mipi12] [-raw_shift N] [-tone file] [-input_device] [-jpeg_device]\n", argv[0]);
+                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8|nv12|nv21|i420|yv12|i422|i444|rgba|bgra|argb|abgr|yuyv|uyvy|yvyu|p010|rggb|bggr|grbg|gbrg|mono] [-matrix bt601|bt601f|bt709|bt709f] [-raw u8|u16|mipi10|mipi12] [-raw_shift N] [-tone file] [-input_device] [-jpeg_device] [-png_device]\n", argv[0]);
         return 0;
     }
     detect_job job;
@@ -622,6 +625,7 @@ int main(int argc, char **argv)
     job.boxes = find_arg(argc, argv, "-boxes");
     job.input_device = find_arg(argc, argv, "-input_device");
     job.jpeg_device = find_arg(argc, argv, "-jpeg_device");
+    job.png_device = find_arg(argc, argv, "-png_device");
     const int bcast = find_arg(argc, argv, "-bcast");
     job.iters = atoi(find_char_arg(argc, argv, "-n", "1"));
     job.inflight = atoi(find_char_arg(argc, argv, "-inflight", "1"));

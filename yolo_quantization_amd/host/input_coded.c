@@ -16,6 +16,7 @@
 #include "jpeg.h"
 #include "jpeg_scan.h"
 #include "png.h"
+#include "png_scan.h"
 
 enum { CODED_ERR_LEN = 320 };
 
@@ -117,6 +118,12 @@ void coded_free(network *net)
     net->jpg_coef_gpu = net->jpg_status_gpu = NULL;
     net->jpg_status_host = NULL;
     net->jpg_coef_bytes = net->jpg_status_bytes = 0;
+    if (net->png_filt_gpu) mi355_free(net->png_filt_gpu);
+    if (net->png_status_gpu) mi355_free(net->png_status_gpu);
+    free(net->png_status_host);
+    net->png_filt_gpu = net->png_status_gpu = NULL;
+    net->png_status_host = NULL;
+    net->png_filt_bytes = net->png_status_bytes = 0;
 }
 
 typedef struct { void **buf; size_t *have, need; const char *what; } coded_want; /* a device buffer that holds at least `need` bytes */
@@ -361,40 +368,74 @@ int network_frames_jpeg_input_gpu(network *net, const uint8_t *const *data, cons
 
 /* ------------------------------------------------------------------------------------------------- PNG input
  * The host parses the chunks and inflates (png.c), the device does the rest (png.hip): the staging block -- segment table, image table,
- * palettes, filtered bytes -- goes up, then mi355_png_unfilter over every pass of every image and mi355_png_to_rgb over every image. */
+ * palettes, filtered bytes -- goes up, then mi355_png_unfilter over every pass of every image and mi355_png_to_rgb over every image.
+ *
+ * With set_png_inflate_on_device the host only finds the deflate streams (png_scan.c).  The staging block then holds segment table,
+ * image table, palettes, stream table and the compressed bytes; the filtered bytes get a device buffer of their own, which
+ * mi355_png_inflate fills; its status words come back (the call's one wait of its own), and the two launches follow on those bytes. */
 static _Thread_local char png_err[CODED_ERR_LEN];
 const char *network_png_last_error(void) { return png_err; }
 
-static int png_item_decode(const uint8_t *data, size_t bytes, void *item, char *why, size_t whylen) { return png_decode_host(data, bytes, item, why, whylen); }
-static void png_item_release(void *item) { png_free(item); }
+void set_png_inflate_on_device(network *net, int on) { net->png_inflate_on_device = on != 0; }
+
+typedef dnq_png_scan png_item; /* z: with the inflate on the device only */
+
+static int png_item_decode(const uint8_t *data, size_t bytes, void *item, char *why, size_t whylen)
+{
+    return png_decode_host(data, bytes, &((png_item *)item)->im, why, whylen);
+}
+
+static int png_item_scan(const uint8_t *data, size_t bytes, void *item, char *why, size_t whylen)
+{
+    png_item *it = item;
+    if (png_scan_host(data, bytes, it, why, whylen)) return -1;
+    const char *big = it->im.filtered_bytes >= ((size_t)1 << 31) ? "2^31 or more filtered bytes: inflate this image on the host" :
+                      it->nbytes > ((size_t)1 << 28) ? "more than 2^28 compressed bytes: inflate this image on the host" : NULL;
+    if (!big) return 0;
+    snprintf(why, whylen, "%s", big);
+    png_scan_free(it);
+    memset(it, 0, sizeof(*it));
+    return -1;
+}
+
+static void png_item_release(void *item)
+{
+    png_free(&((png_item *)item)->im);
+    png_scan_free(item);
+}
 
 typedef struct {
+    int inflate; /* the inflate runs on the device; without it the staging block has no stream table and filt is 0 */
     int nsegs;
-    size_t off_images, off_pal; /* into the staging block; the segment table is at 0 */
-    size_t in, work, rgb;       /* what the call needs of every buffer */
+    size_t off_images, off_pal, off_streams; /* into the staging block; the segment table is at 0 */
+    size_t in, filt, work, rgb;              /* what the call needs of every buffer */
 } png_layout;
 
-/* The layout of the staging block (= of its device copy), of the reconstructed passes and of the frames, in one walk that serves twice
- * like jpg_walk: with stage == NULL it only sizes, with the staging block it fills the segment table, the image table and the palettes
- * and copies the filtered bytes. */
-static void png_walk(const coded_slots *s, png_layout *L, uint8_t *stage, const coded_bufs *cb)
+/* The layout of the staging block (= of its device copy), of the filtered bytes on the device (inflate), of the reconstructed passes
+ * and of the frames, in one walk that serves twice like jpg_walk: with stage == NULL it only sizes, with the staging block it fills
+ * the segment table, the image table, the palettes and the stream table and copies the filtered bytes, or the compressed ones.
+ * slot_of_stream[i] (inflate): the slot stream i came with. */
+static void png_walk(const coded_slots *s, png_layout *L, uint8_t *stage, const coded_bufs *cb, uint8_t *filt_gpu, int *slot_of_stream)
 {
-    const dnq_png *items = (const dnq_png *)s->items;
-    size_t in = 0, work = 0, rgb = 0;
+    const png_item *items = (const png_item *)s->items;
+    size_t in = 0, filt = 0, work = 0, rgb = 0;
     take(&in, sizeof(mi355_png_segment) * (size_t)L->nsegs);
     L->off_images = take(&in, sizeof(mi355_png_image) * (size_t)s->nu);
     L->off_pal = take(&in, 768 * (size_t)s->nu);
+    L->off_streams = take(&in, L->inflate ? sizeof(mi355_png_stream) * (size_t)s->nu : 0);
     if (stage) memset(stage, 0, in); /* the tables */
     mi355_png_segment *segs = (mi355_png_segment *)stage;
     uint8_t *in_gpu = cb->in_gpu;
     int si = 0;
     for (int b = 0; b < s->n; ++b) {
         if (s->first[b] != b) continue;
-        const dnq_png *p = &items[b];
+        const dnq_png *p = &items[b].im;
         const int i = s->frame[b];
         mi355_png_image *g = stage ? (mi355_png_image *)(stage + L->off_images) + i : NULL;
         const coded_frame o = s->out[i] = coded_frame_take(&rgb, p->w, p->h);
-        const size_t bytes_at = take(&in, p->filtered_bytes);
+        const size_t bytes_at = L->inflate ? take(&in, items[b].zcap) : take(&in, p->filtered_bytes);
+        const size_t filt_at = L->inflate ? take(&filt, p->filtered_bytes) : 0;
+        const uint8_t *filtered = L->inflate ? filt_gpu + filt_at : in_gpu + bytes_at;
         if (stage) {
             g->rgb = (uint8_t *)cb->rgb_gpu + o.at; g->w = o.w; g->h = o.h; g->pitch = o.pitch;
             g->depth = p->depth; g->color = p->color; g->interlace = p->interlace; g->pal_len = p->pal_len;
@@ -402,19 +443,28 @@ static void png_walk(const coded_slots *s, png_layout *L, uint8_t *stage, const 
                 memcpy(stage + L->off_pal + 768 * (size_t)i, p->palette, 768);
                 g->palette = in_gpu + L->off_pal + 768 * (size_t)i;
             }
-            memcpy(stage + bytes_at, p->filtered, p->filtered_bytes);
+            if (L->inflate) {
+                mi355_png_stream *t = (mi355_png_stream *)(stage + L->off_streams) + i;
+                memcpy(stage + bytes_at, items[b].z, items[b].zcap); /* the zero bytes behind the stream included */
+                t->z = (const uint32_t *)(in_gpu + bytes_at); t->nbytes = (uint32_t)items[b].nbytes;
+                t->out = filt_gpu + filt_at; t->cap = (uint32_t)p->filtered_bytes;
+                t->npasses = p->npasses;
+                for (int k = 0; k < p->npasses; ++k) { t->rows[k] = p->pass[k].rows; t->row_bytes[k] = p->pass[k].row_bytes; }
+                slot_of_stream[i] = b;
+            } else
+                memcpy(stage + bytes_at, p->filtered, p->filtered_bytes);
         }
         for (int k = 0; k < p->npasses; ++k, ++si) {
             const dnq_png_pass *q = &p->pass[k];
             const size_t rows_at = take(&work, (size_t)q->rows * (size_t)q->row_bytes);
             if (!stage) continue;
-            segs[si].filtered = in_gpu + bytes_at + q->offset;
+            segs[si].filtered = filtered + q->offset;
             segs[si].out = (uint8_t *)cb->work_gpu + rows_at;
             segs[si].row_bytes = q->row_bytes; segs[si].rows = q->rows; segs[si].bpp = p->bpp;
             g->pass[q->index] = segs[si].out;
         }
     }
-    L->in = in; L->work = work; L->rgb = rgb;
+    L->in = in; L->filt = filt; L->work = work; L->rgb = rgb;
 }
 
 int network_png_decode_gpu(network *net, const uint8_t *const *data, const size_t *bytes, int n, uint8_t **rgb_dev, int *w, int *h, int *pitch)
@@ -422,22 +472,45 @@ int network_png_decode_gpu(network *net, const uint8_t *const *data, const size_
     static const char oom[] = "network_png_decode_gpu: out of memory";
     if (!net || !data || !bytes || !rgb_dev || !w || !h || !pitch || n < 1 || n > 65535)
         return coded_refuse(png_err, "network_png_decode_gpu: null argument / need 1 <= n <= 65535");
-    const coded_format f = {"png", png_err, sizeof(dnq_png), png_item_decode, png_item_release};
+    const int inflate = net->png_inflate_on_device;
+    const coded_format f = {"png", png_err, sizeof(png_item), inflate ? png_item_scan : png_item_decode, png_item_release};
     coded_slots s;
     if (coded_slots_decode(&f, data, bytes, n, &s, oom)) return MI355_EINVAL;
-    png_layout L = {0};
-    for (int b = 0; b < n; ++b) L.nsegs += ((const dnq_png *)s.items)[b].npasses; /* the items of the other slots are empty */
+    png_layout L = {.inflate = inflate};
+    for (int b = 0; b < n; ++b) L.nsegs += ((const png_item *)s.items)[b].im.npasses; /* the items of the other slots are empty */
     coded_bufs *cb = &net->png;
-    png_walk(&s, &L, NULL, cb);
-    const coded_want want[] = {{&cb->in_gpu, &cb->in_bytes, L.in, "alloc png scanlines"},
+    png_walk(&s, &L, NULL, cb, NULL, NULL);
+    const int nstreams = inflate ? s.nu : 0;
+    const size_t status_bytes = sizeof(int) * (size_t)nstreams;
+    if (net->png_status_bytes < status_bytes) {
+        free(net->png_status_host);
+        net->png_status_host = malloc(status_bytes);
+        if (!net->png_status_host) error(oom);
+    }
+    const coded_want want[] = {{&cb->in_gpu, &cb->in_bytes, L.in, inflate ? "alloc png streams" : "alloc png scanlines"},
+                               {&net->png_filt_gpu, &net->png_filt_bytes, L.filt, "alloc png scanlines"},
                                {&cb->work_gpu, &cb->work_bytes, L.work, "alloc png passes"},
-                               {&cb->rgb_gpu, &cb->rgb_bytes, L.rgb, "alloc png frames"}};
-    uint8_t *stage = coded_begin(net, cb, want, 3, L.in, oom), *in_gpu = cb->in_gpu;
-    png_walk(&s, &L, stage, cb);
+                               {&cb->rgb_gpu, &cb->rgb_bytes, L.rgb, "alloc png frames"},
+                               {&net->png_status_gpu, &net->png_status_bytes, status_bytes, "alloc png status"}};
+    uint8_t *stage = coded_begin(net, cb, want, 5, L.in, oom), *in_gpu = cb->in_gpu;
+    int *slot_of_stream = inflate ? calloc((size_t)nstreams, sizeof(int)) : NULL;
+    if (inflate && !slot_of_stream) error(oom);
+    png_walk(&s, &L, stage, cb, net->png_filt_gpu, slot_of_stream);
     coded_slots_finish(&f, &s, cb->rgb_gpu, rgb_dev, w, h, pitch);
-    /* one copy, two launches */
-    check_mi355(mi355_h2d(in_gpu, stage, L.in, net->stream), "upload png scanlines");
-    cb->upload_pending = 1;
+    /* one copy; then, for the inflate, its launch and the one wait of its own (for its status words); then two launches */
+    check_mi355(mi355_h2d(in_gpu, stage, L.in, net->stream), inflate ? "upload png streams" : "upload png scanlines");
+    if (inflate) {
+        check_mi355(mi355_png_inflate((const mi355_png_stream *)(in_gpu + L.off_streams), (const mi355_png_stream *)(stage + L.off_streams), nstreams,
+                                      (int *)net->png_status_gpu, net->stream), "mi355_png_inflate");
+        check_mi355(mi355_d2h(net->png_status_host, net->png_status_gpu, status_bytes, net->stream), "read png status");
+        net_wait(net); /* the upload has completed with it: nothing is left pending */
+        int bad = 0;
+        while (bad < nstreams && !net->png_status_host[bad]) ++bad;
+        if (bad < nstreams) snprintf(png_err, sizeof(png_err), "png slot %d: %s (device)", slot_of_stream[bad], png_inflate_reason(net->png_status_host[bad]));
+        free(slot_of_stream);
+        if (bad < nstreams) return MI355_EINVAL;
+    } else
+        cb->upload_pending = 1;
     check_mi355(mi355_png_unfilter((const mi355_png_segment *)in_gpu, (const mi355_png_segment *)stage, L.nsegs, net->stream), "mi355_png_unfilter");
     check_mi355(mi355_png_to_rgb((const mi355_png_image *)(in_gpu + L.off_images), (const mi355_png_image *)(stage + L.off_images), s.nu, net->stream),
                 "mi355_png_to_rgb");

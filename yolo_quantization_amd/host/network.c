@@ -1553,6 +1553,7 @@ network *network_replica_ex(network *parent, int default_stream)
     net->per_image = parent->per_image; /* its own bank (allocated by its first per-image batch); layer 0's raw weights are the parent's */
     net->input_on_device = parent->input_on_device; /* its own bank, pair and status arrays and copy of the constant table */
     net->jpg_entropy_on_device = parent->jpg_entropy_on_device; net->jpg_subseq_bits = parent->jpg_subseq_bits;
+    net->png_inflate_on_device = parent->png_inflate_on_device;
     net->dump_int32 = 0;
     if (parent->accum_mode == MI355_ACC_REF_F32) error("network_replica: MI355_ACC_REF_F32 reads raw weights, which a replica does not hold");
     net->replica_of = parent;
