@@ -263,7 +263,13 @@ int mi355_last_conv_kernel(void);
 int mi355_last_conv_launch(int *grid, int *threads, int *lds_bytes);
 
 /* ---- glue layers ---------------------------------------------------------------------------------------- */
-/* forward_maxpool_layer_quant (ref: src/maxpool_layer.c:109-172): window offset -pad/2, OOB taps = uint8 0 */
+/* forward_maxpool_layer_quant (ref: src/maxpool_layer.c:109-172): window offset -pad/2, OOB taps = uint8 0.  y must be
+ * (x.H + pad - size) / stride + 1 rows by (x.W + pad - size) / stride + 1 columns, C's truncating division (ref :31-32).
+ * Refused with MI355_EINVAL before anything is launched, mi355_last_error() then reads "invalid argument: " and one of:
+ *     "maxpool: null"                                          x, y or one of their data pointers is NULL
+ *     "maxpool: layout"                                        a cell size that is no multiple of 16 (the cs == 4 image), x.C != y.C, x.B != y.B
+ *     "maxpool: need size >= 1, stride >= 1 and pad >= 0"      checked before the division above
+ *     "maxpool: output dims"                                   y.H / y.W are not the sizes above, or those are below 1 */
 int mi355_maxpool_forward(const mi355_tensor *x, const mi355_tensor *y, int size, int stride, int pad, void *stream);
 /* forward_upsample_layer_quant (ref: src/upsample_layer.c:96-113, src/blas.c:781-803), nearest x stride */
 int mi355_upsample_forward(const mi355_tensor *x, const mi355_tensor *y, int stride, void *stream);
@@ -749,7 +755,10 @@ int mi355_png_inflate(const mi355_png_stream *table_dev, const mi355_png_stream 
 /* *sum_dev += an order-independent 64-bit checksum of `dwords` 32-bit words at buf (device pointers; zero *sum_dev first).  The
  * host's determinism self-check compares it between passes over the same input (network_selfcheck, darknet_q.h). */
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream);
-/* yolo head activations (ref: src/yolo_layer.c:132-146) on the float head tensor [B][n*(classes+5)][H*W] */
+/* yolo head activations (ref: src/yolo_layer.c:132-146) on the float head tensor [B][n*(classes+5)][H*W]: entries 2 and 3 of every
+ * anchor (w, h) are copied bit for bit, every other entry v becomes (float)(1 / (1 + exp(-(double)v))).  Refused with MI355_EINVAL
+ * before anything is launched, mi355_last_error() "invalid argument: " and "yolo: null" (in or out is NULL) or
+ * "yolo: need B, n, H, W >= 1 and classes >= 0". */
 int mi355_yolo_forward(const float *in, float *out, int B, int n, int classes, int H, int W, void *stream);
 
 /* get_yolo_detections + correct_yolo_boxes (ref: src/yolo_layer.c:246-277, 316-345) for a batch, on the device: only

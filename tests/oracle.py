@@ -139,8 +139,9 @@ def dequant(u8, zp_act, s_act):
 
 def maxpool_u8(x, size, stride, pad):
     c, h, w = x.shape
-    oh = (h + pad - size) // stride + 1
-    ow = (w + pad - size) // stride + 1
+    # C's truncating division, as orc_maxpool_u8 itself sizes its output (Python's // floors: one less where h + pad < size)
+    oh = int((h + pad - size) / stride) + 1
+    ow = int((w + pad - size) / stride) + 1
     out = np.empty((c, oh, ow), np.uint8)
     x = np.ascontiguousarray(x)
     lib().orc_maxpool_u8(_p(x), c, h, w, size, stride, pad, _p(out))

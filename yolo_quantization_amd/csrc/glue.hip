@@ -400,9 +400,10 @@ int letterbox_launch(const float *im, int imw, int imh, int c, float *out, int w
     else { new_h = h; new_w = (imw * h) / imh; }
     if (new_w < 2 || new_h < 2) return MI355_EINVAL;  // the reference divides by (w - 1), (h - 1)
     const float w_scale = (float)(imw - 1) / (new_w - 1), h_scale = (float)(imh - 1) / (new_h - 1);
-    // (int)(r * h_scale) must stay a row of the source image (the reference asserts it)
-    if ((int)((new_h - 1) * h_scale) > imh - 1 || (new_h > 1 && (int)((new_h - 2) * h_scale) + 1 > imh - 1) ||
-        (new_w > 1 && (int)((new_w - 2) * w_scale) + 1 > imw - 1))
+    // (int)(r * h_scale) must stay a row of the source image (the reference asserts it), and so must row iy + 1 and column ix + 1 where
+    // the kernel reads them: a one-row / one-column source never does (its imh == 1 / imw == 1 clauses, as the reference's)
+    if ((int)((new_h - 1) * h_scale) > imh - 1 || (imh > 1 && (int)((new_h - 2) * h_scale) + 1 > imh - 1) ||
+        (imw > 1 && (int)((new_w - 2) * w_scale) + 1 > imw - 1))
         return MI355_EINVAL;
     const long total = (long)c * h * w;
     hipLaunchKernelGGL(letterbox_kernel, dim3(nblk(total)), dim3(256), 0, st, im, imw, imh, c, out, w, h, new_w, new_h,

@@ -957,8 +957,9 @@ int mi355_maxpool_forward(const mi355_tensor *x, const mi355_tensor *y, int size
 {
     if (!x || !y || !x->data || !y->data) return einval("maxpool: null");
     if (x->cs % 16 || y->cs % 16 || x->C != y->C || x->B != y->B) return einval("maxpool: layout");
+    if (size < 1 || stride < 1 || pad < 0) return einval("maxpool: need size >= 1, stride >= 1 and pad >= 0");
     const int oh = (x->H + pad - size) / stride + 1, ow = (x->W + pad - size) / stride + 1;  // ref :31-32
-    if (oh != y->H || ow != y->W) return einval("maxpool: output dims");
+    if (oh < 1 || ow < 1 || oh != y->H || ow != y->W) return einval("maxpool: output dims");
     PoolArgs a{(const uint8_t *)x->data, (uint8_t *)y->data, x->B, x->H, x->W, oh, ow, x->cs, y->cs, x->lead, y->lead,
                (x->C + 15) / 16, size, stride, -pad / 2};
     return maxpool_launch(a, (hipStream_t)stream);
@@ -1223,6 +1224,7 @@ int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *st
 int mi355_yolo_forward(const float *in, float *out, int B, int n, int classes, int H, int W, void *stream)
 {
     if (!in || !out) return einval("yolo: null");
+    if (B < 1 || n < 1 || H < 1 || W < 1 || classes < 0) return einval("yolo: need B, n, H, W >= 1 and classes >= 0");
     return yolo_logistic_launch(in, out, B, n, classes, H * W, (hipStream_t)stream);
 }
 
