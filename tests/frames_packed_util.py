@@ -77,7 +77,9 @@ def geometry_accepts(imw, imh, w, h):
     if new_w < 2 or new_h < 2:
         return False
     ws, hs = f(imw - 1) / f(new_w - 1), f(imh - 1) / f(new_h - 1)
-    return not (int(f(new_h - 1) * hs) > imh - 1 or int(f(new_h - 2) * hs) + 1 > imh - 1 or int(f(new_w - 2) * ws) + 1 > imw - 1)
+    # row iy + 1 / column ix + 1 are never read from a frame of one row / one column
+    return not (int(f(new_h - 1) * hs) > imh - 1 or (imh > 1 and int(f(new_h - 2) * hs) + 1 > imh - 1) or
+                (imw > 1 and int(f(new_w - 2) * ws) + 1 > imw - 1))
 
 
 class Launch(frames_util._Launch):

@@ -19,8 +19,8 @@ JPEG_MIDDLE = ["444_48x32", "grey_51x37", "rgb_adobe0_48x32"]
 JPEG_LARGEST = ["444_q100_51x37", "440_24x64", "411_64x24"]
 PNG_MIDDLE = ["pal8_trns_23x19", "rgb16_trns_23x19", "rgb8_adam7_64x61"]
 PNG_SMALLEST = ["pal4_adam7_2x5", "grey16_plain_3x4", "rgb8_adam7_4x3"]
-# the letterbox refuses a source of one column or one row (it reads the pixel to the right and the one below): the 1 x 1 fixtures go
-# through the same buffers of the network by binding.png_decode(net=...), which stops at the RGB frames
+# the 1 x 1 fixtures go through the same buffers of the network by binding.png_decode(net=...), which stops at the RGB frames
+# (tests/test_gpu_frame_geometry.py sends them through prepare_from_png and prepare_from_jpeg, letterbox included)
 PNG_ONE_PIXEL = ["rgb8_adam7_1x1", "pal4_adam7_1x1", "grey16_plain_1x1"]
 B = 3
 

@@ -94,7 +94,8 @@ def _want(frames, netw, neth):
 
 def test_the_sizes_are_what_the_geometry_accepts():
     assert all(geometry_accepts(w, h, nw, nh) for w, h in SIZES + [(8, 5), (11, 5), (6, 5), (7, 5)] for nw, nh in NETS)
-    assert not geometry_accepts(1, 1, 12, 12) and not geometry_accepts(1, 5, 12, 12)  # no frame of one column is served, by any kind
+    # a frame of one column is served where both resized sides reach 2 (legal for MONO), refused where one does not
+    assert geometry_accepts(1, 1, 12, 12) and geometry_accepts(1, 5, 12, 12) and not geometry_accepts(1, 7, 12, 12)
 
 
 # ------------------------------------------------------------------------------------------------------------ C-ABI level
@@ -136,11 +137,15 @@ def test_patterns_differ_where_they_must():
 @pytest.mark.parametrize("size", [(1, 1), (1, 5)])
 def test_mono_frames_of_one_column_get_the_u8_calls_verdict(size):
     """MONO needs w, h >= 1 only, so the Bayer kind's own clauses pass a frame of one column; the letterbox geometry, which every kind
-    shares, serves no such frame: both kinds refuse it with the same words, and nothing is launched"""
+    shares, serves it where both resized sides reach 2: both kinds give the same bytes, scales and zero points.  Where a resized side
+    falls below 2 (1 x 7 into 12 x 12) both refuse it with the same words, and nothing is launched."""
     w, h = size
     f = Frame(_samples(w, h, 1), "mono", "u8")
     assert f.rgb.shape == (h, w, 3) and np.array_equal(f.rgb[:, :, 0], f.rgb[:, :, 2])
     good = _frame(5, 7, "mono", "u8", 2)
+    assert geometry_accepts(w, h, 12, 12)
+    assert_same(run(Launch, [good, f], 12, 12), run(_LaunchU8, [good.rgb, f.rgb], 12, 12), f"mono {w} x {h}")
+    f = Frame(_samples(1, 7, 1), "mono", "u8")
     for L, prefix in ((Launch([good, f], 12, 12), b"frames_bayer"), (_LaunchU8([good.rgb, f.rgb], 12, 12), b"frames_u8")):
         L.upload_table()
         assert L.minmax_rc() == EINVAL

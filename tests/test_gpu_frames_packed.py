@@ -41,7 +41,7 @@ def _dev():
 def test_the_sizes_are_what_the_geometry_accepts_and_refuses():
     assert all(geometry_accepts(w, h, NET, NET) for batch in BATCHES for w, h in batch)
     assert not any(geometry_accepts(w, h, NET, NET) for w, h in REFUSED_SIZES)
-    assert not geometry_accepts(1, 1, NET, NET) and not geometry_accepts(2, 13, NET, NET)  # nothing smaller than 2 x 2 is served
+    assert geometry_accepts(1, 1, NET, NET) and not geometry_accepts(2, 13, NET, NET)  # served: both resized sides reach 2; refused: one is 1
 
 
 def _sibling_packed(frames, fmt, matrix):

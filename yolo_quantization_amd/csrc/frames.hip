@@ -39,9 +39,10 @@ __host__ __device__ static inline bool frame_geometry(int imw, int imh, int w, i
     if (g.new_w < 2 || g.new_h < 2) return false;  // the reference divides by (w - 1), (h - 1)
     g.w_scale = (float)(imw - 1) / (g.new_w - 1);
     g.h_scale = (float)(imh - 1) / (g.new_h - 1);
-    // (int)(r * h_scale) must stay a row of the source image (the reference asserts it), ix + 1 a column
-    if ((int)((g.new_h - 1) * g.h_scale) > imh - 1 || (int)((g.new_h - 2) * g.h_scale) + 1 > imh - 1 ||
-        (int)((g.new_w - 2) * g.w_scale) + 1 > imw - 1)
+    // (int)(r * h_scale) must stay a row of the source image (the reference asserts it), and so must row iy + 1 and column ix + 1 where
+    // letterbox_px3 reads them: a one-row / one-column frame never does (its f.h == 1 / f.w == 1 clauses, letterbox_launch's guards)
+    if ((int)((g.new_h - 1) * g.h_scale) > imh - 1 || (imh > 1 && (int)((g.new_h - 2) * g.h_scale) + 1 > imh - 1) ||
+        (imw > 1 && (int)((g.new_w - 2) * g.w_scale) + 1 > imw - 1))
         return false;
     g.ox = (w - g.new_w) / 2;
     g.oy = (h - g.new_h) / 2;
