@@ -20,6 +20,12 @@ SIZES = (1, 1, 1, 1, 3, 3, 3, 3, 3, 5, 5, 5, 2, 4, 6, 7, 8, 9, 10, 11)
 POOLS = ((2, 2), (2, 2), (2, 1), (3, 2), (5, 1), (9, 1), (13, 1))
 
 
+def cdiv(a, b):
+    """C's truncating division (glue_edges.cdiv's equal): the reference sizes a pool's output with it, and Python's // floors"""
+    q = abs(a) // abs(b)
+    return q if (a < 0) == (b < 0) else -q
+
+
 # ----------------------------------------------------------------------------------------------- cfg text
 class Net:
     """cfg writer that tracks every layer's (type, channels, height, width)"""
@@ -50,11 +56,14 @@ class Net:
         t += f"activation={act}\nquantized=1\nquant_stop={qs}\n"
         return self._push(t, "conv", n, oh, ow)
 
-    def maxpool(self, size, stride, qs=0):
+    def maxpool(self, size, stride, qs=0, padding=None):
+        """padding: the cfg's `padding=` line (both sides together, as the reference counts it); None leaves the default, size - 1"""
         c, h, w = self.cur
-        pad = size - 1
-        return self._push(f"[maxpool]\nsize={size}\nstride={stride}\nquantized=1\nquant_stop={qs}\n", "maxpool", c,
-                          (h + pad - size) // stride + 1, (w + pad - size) // stride + 1)
+        pad = size - 1 if padding is None else padding
+        oh, ow = cdiv(h + pad - size, stride) + 1, cdiv(w + pad - size, stride) + 1  # C truncates (ref: src/maxpool_layer.c:31-32)
+        assert oh >= 1 and ow >= 1
+        t = f"[maxpool]\nsize={size}\nstride={stride}\n" + ("" if padding is None else f"padding={padding}\n")
+        return self._push(t + f"quantized=1\nquant_stop={qs}\n", "maxpool", c, oh, ow)
 
     def upsample(self, stride, qs=0):
         c, h, w = self.cur
@@ -334,6 +343,95 @@ def sweep():
     return nets
 
 
+# ---------------------------------------------------------------------------- the reference's view of the sweep
+# The reference has no integer [shortcut] (the op is this build's own: a quantized shortcut kills it with a segfault or an assert of
+# src/blas.c), so it runs the TWIN of a net: every [shortcut] replaced by a one-input route, a copy with the same shape, so that every
+# later index holds.  tests/golden/netgen_ref.json holds the reference's tensors of the twins.
+SHORTCUT_FEATURES = ("shortcut_from_convolutional", "shortcut_from_shortcut", "shortcut_from_route_input", "quant_stop_shortcut")
+REF_IMAGE_SEEDS = (5, 6)  # synth_image_u8 seeds of the two images every twin is recorded on
+
+
+def reference_twin(cfg_text):
+    """cfg text with a one-input `[route] layers = -1` in place of each [shortcut]; its quantized / quant_stop lines are kept and the
+    text is otherwise unchanged."""
+    out, lines, i = [], cfg_text.split("\n"), 0
+    while i < len(lines):
+        if lines[i].strip().replace(" ", "") == "[shortcut]":
+            out += ["[route]", "layers = -1"]
+            i += 1
+            while i < len(lines) and not lines[i].strip().startswith("["):
+                key = lines[i].strip().replace(" ", "").partition("=")[0]
+                if key in ("quantized", "quant_stop") or not lines[i].strip():
+                    out.append(lines[i])
+                i += 1
+        else:
+            out.append(lines[i])
+            i += 1
+    return "\n".join(out)
+
+
+def _ref_extra():
+    """aimed nets of the twin list only: what the sweep's own nets leave to one reading of the reference"""
+    E = {}
+    n = Net(24, 24)
+    n.conv(32, 3); n.conv(32, 3, act="relu6"); n.conv(16, 1, act="linear"); n.route([2, 1, 0], qs=1, absolute=True); n.conv(32, 3); n.head()
+    E["route_quant_stop_mixed_records"] = dict(
+        cfg=n.text("route_quant_stop_mixed_records: the float tail of route 3 dequantises each input with THAT input's scale and zero "
+                   "point (ref: src/route_layer.c:121-129); linear, relu6 and leaky producers, and a record of the route's own that "
+                   "differs from all three"), wseed=900, act_gain=1.0, glue_own_zp=True)
+    return E
+
+
+REF_EXTRA = _ref_extra()
+
+
+def ref_sweep():
+    """name -> dict like sweep() of the nets the reference runs: the twin of every net of the sweep with the sweep's own weight seeds and
+    gains, and REF_EXTRA.  AIMED_BIG stays out: its maps (72 and 74 cells wide) and work are above what the reference-pinned GPU tests allow themselves
+    (48 x 48, MAC_CAP), and what those two nets aim at, fusions of a whole round of the chip, is the planner's doing, not arithmetic."""
+    nets = {}
+    for name, spec in sweep().items():
+        if name not in AIMED_BIG:
+            nets[name] = dict(spec, cfg=reference_twin(spec["cfg"]), has_shortcut="[shortcut]" in spec["cfg"])
+    for name, spec in REF_EXTRA.items():
+        nets[name] = dict(spec, has_shortcut=False)
+    return nets
+
+
+POOL_MAPS = ((1, 1), (2, 3), (5, 6), (7, 4))
+
+
+def pool_nets():
+    """name -> (cfg text, (size, stride, padding, h, w)) of the one-pool nets: 1x1 conv, pool, head.  Sizes 1, 2, 3, 5, strides 1..4,
+    padding 0..size + 1 on POOL_MAPS; where h + padding < size (or w) the geometry is kept only if C's truncating division still gives
+    one output row (the reference's and the host's parsers then accept it; Python's floor would say 0)."""
+    nets = {}
+    for size in (1, 2, 3, 5):
+        for stride in (1, 2, 3, 4):
+            for padding in range(size + 2):
+                for h, w in POOL_MAPS:
+                    if cdiv(h + padding - size, stride) + 1 < 1 or cdiv(w + padding - size, stride) + 1 < 1:
+                        continue
+                    n = Net(h, w)
+                    n.conv(17, 1, act="leaky"); n.maxpool(size, stride, padding=padding); n.head()
+                    nets[f"pool_k{size}_s{stride}_p{padding}_{h}x{w}"] = (n.text(), (size, stride, padding, h, w))
+    return nets
+
+
+def upsample_nets():
+    """name -> (cfg text, (stride, h, w)) of the one-upsample nets: 1x1 conv, upsample, head; strides 1..4 on POOL_MAPS"""
+    nets = {}
+    for stride in (1, 2, 3, 4):
+        for h, w in POOL_MAPS:
+            n = Net(h, w)
+            n.conv(17, 1, act="leaky"); n.upsample(stride); n.head()
+            nets[f"up_s{stride}_{h}x{w}"] = (n.text(), (stride, h, w))
+    return nets
+
+
+ONE_LAYER_WSEED = 77
+
+
 # ------------------------------------------------------------------------------------- features from the text
 def parse(cfg_text):
     """[(section type, {key: value})] of the layers of a cfg text (the [net] section dropped)"""
@@ -361,7 +459,8 @@ def _map_sizes(cfg_text, secs):
             h, w = (h + 2 * p - size) // stride + 1, (w + 2 * p - size) // stride + 1
         elif t == "maxpool":
             size, stride = int(o["size"]), int(o["stride"])
-            h, w = (h + size - 1 - size) // stride + 1, (w + size - 1 - size) // stride + 1
+            pad = int(o.get("padding", size - 1))
+            h, w = cdiv(h + pad - size, stride) + 1, cdiv(w + pad - size, stride) + 1
         elif t == "upsample":
             h, w = h * int(o.get("stride", 2)), w * int(o.get("stride", 2))
         elif t == "route":
@@ -421,6 +520,8 @@ def features(cfg_text):
                     f.add("route_same_layer_twice")
             if qs:
                 f.add("quant_stop_route")
+                if len({secs[s][1].get("activation") for s in srcs_of[i] if secs[s][0] == "convolutional"}) > 1:
+                    f.add("quant_stop_route_mixed_records")  # (of the twin list: REF_EXTRA)
         elif t == "shortcut":
             frm = int(o["from"])
             frm = frm if frm >= 0 else i + frm

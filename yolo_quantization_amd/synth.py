@@ -91,8 +91,10 @@ def layer_shapes(sections: list[dict]) -> tuple[dict, list[LayerShape]]:
         elif t == "[maxpool]":
             stride = int(s.get("stride", 1)); size = int(s.get("size", stride))
             padding = int(s.get("padding", size - 1))
-            oh = (h + padding - size) // stride + 1
-            ow = (w + padding - size) // stride + 1
+            # C's truncating division, as the reference (src/maxpool_layer.c:31-32) and host/layers.c size it: where h + padding < size
+            # it gives one row more than Python's floor
+            oh = int((h + padding - size) / stride) + 1
+            ow = int((w + padding - size) / stride) + 1
             L = LayerShape("maxpool", c, h, w, c, oh, ow, 0, size, stride, padding, "", 0, q, qs)
         elif t == "[upsample]":
             stride = int(s.get("stride", 2))
