@@ -210,6 +210,8 @@ struct network {
     float *fr_mm_gpu, *fr_mm_host; /* [fr_cap][2] max, min */
     void *fr_pair_gpu, *fr_pair_host; /* shared-scale mode: [fr_cap] float scale | [fr_cap] uint8 zero point, image 0's in every slot */
     int fr_cap;
+    mi355_frame_view *fr_views; /* network_set_frame_views: [batch] views, the network's copy; NULL: every slot is its whole frame as stored.  Cleared on re-batch */
+    void *fr_views_gpu;         /* [fr_cap] mi355_frame_view, uploaded beside the frame table while views are set */
     /* JPEG input (network_jpeg_decode_gpu).  The staging block holds plane table | image table | quantiser tables | coefficients, the
      * work buffer the component planes the inverse DCT writes.  A replica owns its own. */
     coded_bufs jpg;
@@ -548,6 +550,40 @@ void detections_to_arrays(const detection *dets, int n, int classes, float *boxe
 void do_nms_sort(detection *dets, int total, int classes, float thresh); /* ref: src/box.c:58-89 */
 void do_nms_sort_arrays(const float *boxes, float *probs, const float *objectness, int n, int classes, float thresh);
 float box_iou(box a, box b);
+/* ---- frame views: a batch slot looks at a rectangle of its frame, mirrored or turned (mi355_frame_view, mi355_yolo_int8.h) ----------
+ * network_set_frame_views: views holds net->batch entries, which are copied; NULL clears.  While views are set, every
+ * network_frames_*_input_gpu call (and the JPEG and PNG inputs, which feed the u8 one) uploads the view table beside the frame table and
+ * letterboxes slot b's view of its frame: the result is, bit for bit, network_frames_u8_input_gpu's on the view materialised as an RGB
+ * frame.  w[b], h[b] of those calls stay the FRAME's sizes, and slots that name the same frame with different views upload it once.
+ * Both scale modes, set_input_quantization_on_device and graph replay are the shared tail's.  A view the shim refuses dies via error()
+ * as a frame the letterbox cannot serve does.  A replica owns its own views (none when made); re-batching clears them. */
+void network_set_frame_views(network *net, const mi355_frame_view *views);
+/* cols * rows views that cover a frame_w x frame_h frame, row by row (out[r * cols + c]), all with `orient`.  A tile is
+ * ceil((frame_w + (cols - 1) * overlap) / cols) wide, tile c starts at c * (tile_w - overlap), and the last one is moved left so that it
+ * ends on the frame's edge; rows likewise.  Returns cols * rows, or MI355_EINVAL (nothing written): a count or frame side below 1, a
+ * negative overlap, an orient outside 1..8, a tile larger than the frame, an overlap at or above the tile size.  Host only. */
+int network_tile_views(int frame_w, int frame_h, int cols, int rows, int overlap, int orient, mi355_frame_view *out);
+/* A box relative to the view -- what the decode returns with relative = 1 when imw[b], imh[b] are the view's ORIENTED size (h x w for
+ * orients 5..8) -- becomes a box relative to the frame.  In double: (u, t) = (b.x * vw, b.y * vh) and the sizes in view pixels; the
+ * orient undone on continuous coordinates (a mirrored axis is c - u, a transposing orient swaps the axes and the two sizes); plus
+ * (x0, y0); divided by the frame's size; stored as float.  Host only. */
+void network_view_box_to_frame(const mi355_frame_view *v, int frame_w, int frame_h, box *b);
+/* Detections of a batch of views, per FRAME.  frame_w[b], frame_h[b]: the size of the frame slot b looks at (the arrays given to the
+ * input call); frame_of_slot[b] in 0 .. batch - 1 names that frame.  Runs network_detections_batch with the views' oriented sizes,
+ * relative boxes and no NMS, maps every box to its frame (network_view_box_to_frame), concatenates the slots of a frame in slot order
+ * and applies do_nms_sort once per frame when nms > 0, so that an object two overlapping tiles report is kept once.  dets[f], num[f]
+ * (both [batch], the caller's; free_detections_batch frees them) are frame f's; a frame no slot names gets NULL, 0.  Without views set
+ * every slot is its whole frame.  Returns 0, or MI355_EINVAL (a frame_of_slot outside the batch, or network_detections_batch's). */
+int network_detections_views(network *net, const int *frame_w, const int *frame_h, const int *frame_of_slot, float thresh, float nms,
+                             int max_per_image, detection **dets, int *num);
+/* The device-free half: slot_dets[b] (slot_num[b] entries, relative to slot b's view) are consumed -- their boxes mapped, their entries
+ * moved into dets[frame_of_slot[b]], the arrays freed --, then the NMS.  views == NULL: whole frames. */
+int detections_views_merge(detection **slot_dets, int *slot_num, int B, const mi355_frame_view *views, const int *frame_w,
+                           const int *frame_h, const int *frame_of_slot, int classes, float nms, detection **dets, int *num);
+/* The EXIF orientation (IFD0 tag 0x0112, SHORT, count 1) of a JPEG file in memory: 1..8, and 1 for anything absent, malformed or out
+ * of range.  Never fails, never reads outside [data, data + bytes).  The decode path ignores EXIF, as the reference's stb_image does:
+ * the caller puts the value into a view.  Host only. */
+int jpeg_exif_orientation_host(const uint8_t *data, size_t bytes);
 char *data_cfg_find(const char *datacfg, const char *key); /* `key = value` of a .data file, or NULL */
 char **get_labels(char *filename, int *count);
 

@@ -573,6 +573,56 @@ int mi355_frames_bayer_letterbox_minmax(const mi355_frame_bayer *table_dev, cons
                                         float *minmax, void *stream);
 int mi355_frames_bayer_letterbox_quantize(const mi355_frame_bayer *table_dev, const mi355_frame_bayer *table_host, int B, int w, int h,
                                           const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
+/* Frame views: a batch slot looks at a rectangle of its frame, mirrored or turned.  For every kind above, the two calls with a table of
+ * views beside the table of frames, one view per slot (views_dev in device memory, views_host its host mirror).
+ *
+ * Let RGB(frame) be the interleaved RGB frame the kind's entry stands for: the bytes themselves (u8, packed and planar RGB), the int32
+ * formulas above with the kind's chroma rule (every YUV kind), D(frame) (Bayer and mono).  The view of a frame is
+ *     V = O_orient(a),  a = RGB(frame)[y0 : y0 + h, x0 : x0 + w]                    (a is [h][w][3])
+ * with O the EXIF orientations, the transforms that make a file carrying that value upright (numpy notation):
+ *     1  a                      2  a[:, ::-1]              3  a[::-1, ::-1]                       4  a[::-1]
+ *     5  a.transpose(1, 0, 2)   6  rot90(a, -1)            7  a[::-1, ::-1].transpose(1, 0, 2)    8  rot90(a, 1)
+ * Orients 5..8 give a view of h x w pixels.  The crop is a crop of the CONVERTED frame: the chroma of view pixel (x0 + i, y0 + j) is the
+ * full frame's sample at ((x0 + i) >> sx, (y0 + j) >> sy), so odd offsets are legal in every subsampled kind, 4:2:2 macropixels and MIPI
+ * groups may be cut anywhere, a Bayer site keeps the colour its frame coordinates give it, and Bayer neighbours outside the view but
+ * inside the frame are the real samples (reflection happens at the frame's border only).
+ *
+ * The claim, and the only one: min / max and the quantised bytes are, bit for bit, what the mi355_frames_u8_* calls give for V
+ * materialised as an interleaved RGB frame.
+ *
+ * Refusals (MI355_EINVAL, nothing launched or written), per slot in this order: the kind's own refusals of the FRAME, in their order and
+ * words; then behind the kind's prefix "view: orient outside 1..8", "view: reserved must be 0", "view: need w, h >= 1",
+ * "view: rectangle outside the frame" (x0 < 0, y0 < 0, x0 + w > the frame's w or y0 + h > the frame's h); then the letterbox geometry of
+ * the view's oriented size ("degenerate aspect (resized side < 2)").  New structs and new calls: MI355_ABI_VERSION is unchanged. */
+typedef struct mi355_frame_view {   /* 32 bytes */
+    int x0, y0, w, h;               /* the rectangle [x0, x0 + w) x [y0, y0 + h) of the stored frame */
+    int orient;                     /* 1..8, the EXIF numbering */
+    int reserved[3];                /* zero */
+} mi355_frame_view;
+int mi355_frames_u8_view_letterbox_minmax(const mi355_frame_u8 *table_dev, const mi355_frame_u8 *table_host, const mi355_frame_view *views_dev,
+    const mi355_frame_view *views_host, int B, int w, int h, float *minmax, void *stream);
+int mi355_frames_u8_view_letterbox_quantize(const mi355_frame_u8 *table_dev, const mi355_frame_u8 *table_host, const mi355_frame_view *views_dev,
+    const mi355_frame_view *views_host, int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
+int mi355_frames_yuv_view_letterbox_minmax(const mi355_frame_yuv *table_dev, const mi355_frame_yuv *table_host, const mi355_frame_view *views_dev,
+    const mi355_frame_view *views_host, int B, int w, int h, float *minmax, void *stream);
+int mi355_frames_yuv_view_letterbox_quantize(const mi355_frame_yuv *table_dev, const mi355_frame_yuv *table_host, const mi355_frame_view *views_dev,
+    const mi355_frame_view *views_host, int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
+int mi355_frames_planar_view_letterbox_minmax(const mi355_frame_planar *table_dev, const mi355_frame_planar *table_host, const mi355_frame_view *views_dev,
+    const mi355_frame_view *views_host, int B, int w, int h, float *minmax, void *stream);
+int mi355_frames_planar_view_letterbox_quantize(const mi355_frame_planar *table_dev, const mi355_frame_planar *table_host, const mi355_frame_view *views_dev,
+    const mi355_frame_view *views_host, int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
+int mi355_frames_packed_view_letterbox_minmax(const mi355_frame_packed *table_dev, const mi355_frame_packed *table_host, const mi355_frame_view *views_dev,
+    const mi355_frame_view *views_host, int B, int w, int h, float *minmax, void *stream);
+int mi355_frames_packed_view_letterbox_quantize(const mi355_frame_packed *table_dev, const mi355_frame_packed *table_host, const mi355_frame_view *views_dev,
+    const mi355_frame_view *views_host, int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
+int mi355_frames_p010_view_letterbox_minmax(const mi355_frame_p010 *table_dev, const mi355_frame_p010 *table_host, const mi355_frame_view *views_dev,
+    const mi355_frame_view *views_host, int B, int w, int h, float *minmax, void *stream);
+int mi355_frames_p010_view_letterbox_quantize(const mi355_frame_p010 *table_dev, const mi355_frame_p010 *table_host, const mi355_frame_view *views_dev,
+    const mi355_frame_view *views_host, int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
+int mi355_frames_bayer_view_letterbox_minmax(const mi355_frame_bayer *table_dev, const mi355_frame_bayer *table_host, const mi355_frame_view *views_dev,
+    const mi355_frame_view *views_host, int B, int w, int h, float *minmax, void *stream);
+int mi355_frames_bayer_view_letterbox_quantize(const mi355_frame_bayer *table_dev, const mi355_frame_bayer *table_host, const mi355_frame_view *views_dev,
+    const mi355_frame_view *views_host, int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out_u8, void *stream);
 /* The device half of a baseline JPEG decoder: everything after the entropy decode, for a whole batch in two launches, leaving interleaved
  * RGB frames in device memory that the u8 calls above take as they are.  The bytes are the ones stb_image v2.19 returns as the reference
  * compiles it (ref: src/stb_image.h; load_image_color -> stbi_load(.., 3), src/image.c:1293-1315): all of this is integer arithmetic in

@@ -56,6 +56,14 @@ deflated by zlib at its default level before the clock starts), per scale mode t
 and, once, the stages on their own: `host_inflate_ms` (png_decode_host over the batch, host clock, one thread), `upload_ms`,
 `unfilter_ms`, `to_rgb_ms` (HIP events around one copy of all filtered bytes and around each launch; medians of `iters`).  Before
 timing, the png network's uint8 input, scales and zero points are compared with the u8 network's.
+
+--views times frame views (network_set_frame_views): twelve tiles (4 x 3, overlap 64) of ONE 3840 x 2160 frame as the slots of a batch of
+12, per-image scales, five variants alternating within a repeat:
+  u8_view_orient1 / _orient6      the frame in every slot under twelve views (it goes up once), as stored and turned a quarter clockwise
+  nv12_view_orient1 / _orient6    the same frame as NV12 planes
+  u8_crops                        the twelve rectangles handed over as separate u8 frames by pointer and pitch (twelve uploads)
+with the bytes uploaded by each form.  Before timing, every view variant's input, scales and zero points are compared with the u8 step
+on the materialised tiles, and u8_view_orient1's with u8_crops'.  A record, not a claim: under orient 6 a wave reads a frame column.
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -588,6 +596,60 @@ def jpeg_main(a, wts, ev):
     print(json.dumps(res))
 
 
+class CropsVariant:
+    """the views' rectangles of one host frame handed over as separate u8 frames, by pointer and pitch (orient 1 only: a pointer cannot turn)"""
+
+    def __init__(self, net, frame, views):
+        B = len(views)
+        self.net, self.frame = net, frame
+        self.ptrs, self.w, self.h, self.pitch = (C.c_void_p * B)(), (C.c_int * B)(), (C.c_int * B)(), (C.c_int * B)()
+        for b, (x0, y0, w, h, _) in enumerate(views):
+            self.ptrs[b] = frame.ctypes.data + y0 * frame.strides[0] + 3 * x0
+            self.w[b], self.h[b], self.pitch[b] = w, h, frame.strides[0]
+        self.uploaded = sum((h - 1) * frame.strides[0] + 3 * w for _, _, w, h, _ in views)
+
+    def step(self):
+        self.net.H.network_frames_u8_input_gpu(self.net.h, self.ptrs, self.w, self.h, self.pitch, 0, 0)
+
+
+def views_main(a, wts, ev):
+    """--views: twelve tiles (4 x 3, overlap 64) of ONE 3840 x 2160 frame at the network's size, per-image scales: the frame under twelve views
+    (u8_view, nv12_view; uploaded once), at orient 1 and at orient 6, and the twelve crops as separate u8 frames by pointer and pitch."""
+    W, H, B = 3840, 2160, 12
+    frame = make_frames(1, W, H)[0]
+    y, uv = rgb_to_nv12(frame)
+    converted = nv12_to_rgb(y, uv)
+    tiles = {o: binding.tile_views(W, H, 4, 3, 64, o) for o in (1, 6)}
+    names = ["u8_view_orient1", "u8_view_orient6", "nv12_view_orient1", "nv12_view_orient6", "u8_crops"]
+    nets = {k: binding.Net(CFG, wts, batch=B) for k in names + ["check"]}
+    for n in nets.values():
+        n.set_input_per_image(True)
+    for o in (1, 6):
+        nets[f"u8_view_orient{o}"].set_frame_views(tiles[o])
+        nets[f"nv12_view_orient{o}"].set_frame_views(tiles[o])
+    var = {f"u8_view_orient{o}": FramesVariant(nets[f"u8_view_orient{o}"], [frame] * B) for o in (1, 6)}
+    var.update({f"nv12_view_orient{o}": NV12Variant(nets[f"nv12_view_orient{o}"], [(y, uv)] * B) for o in (1, 6)})
+    var["u8_crops"] = CropsVariant(nets["u8_crops"], frame, tiles[1])
+    for v in var.values():
+        for _ in range(a.warmup):
+            v.step()
+    same = {"u8_view_orient1_identical_to_crops": same_input(nets["u8_view_orient1"], nets["u8_crops"])}
+    for o in (1, 6):  # against the u8 path on the materialised tiles
+        for kind, rgb in (("u8", frame), ("nv12", converted)):
+            mat = [np.ascontiguousarray({1: lambda t: t, 6: lambda t: np.rot90(t, -1)}[o](rgb[y0:y0 + h, x0:x0 + w])) for x0, y0, w, h, _ in tiles[o]]
+            FramesVariant(nets["check"], mat).step()
+            same[f"{kind}_view_orient{o}_identical_to_u8_on_materialised_tiles"] = same_input(nets[f"{kind}_view_orient{o}"], nets["check"])
+    runs = {k: [] for k in names}
+    for _ in range(a.repeats):
+        for k in names:
+            d, wl, c = timed(var[k], ev, a.iters)
+            runs[k].append({"device_ms": round(d, 4), "wall_ms": round(wl, 4), "call_ms": round(c, 4)})
+    uploaded = {"u8_view": frame.nbytes, "nv12_view": y.nbytes + uv.nbytes, "u8_crops": var["u8_crops"].uploaded}
+    print(json.dumps({"views": {"frame": f"{W}x{H}", "tiles": "4x3, overlap 64", "tile": list(tiles[1][0][2:4]), "batch": B, "identical": same,
+                                "bytes_uploaded": uploaded, "runs": runs,
+                                "note": "median of --iters steps per entry, variants alternating within a repeat; a record, not a claim"}}))
+
+
 def same_input(a, b):
     same = np.array_equal(pull_input(a), pull_input(b))
     qa, qb = a.input_quantization(), b.input_quantization()
@@ -629,6 +691,7 @@ def main():
     ap.add_argument("--on-device", action="store_true", help="compare the synchronous step with the on-device one instead (see the module text)")
     ap.add_argument("--jpeg", action="store_true", help="time the JPEG input path beside the u8 path on the decoded frames instead (see the module text)")
     ap.add_argument("--png", action="store_true", help="time the PNG input path beside the u8 path on the decoded frames instead (see the module text)")
+    ap.add_argument("--views", action="store_true", help="time twelve tiles of one 3840 x 2160 frame as views and as separate crops instead (see views_main)")
     ap.add_argument("--subseq-bits", type=int, default=1024, help="--jpeg: bits a lane decodes per round in the jpeg_device variant")
     a = ap.parse_args()
     binding.init(0)  # raises without a gfx950: nothing is timed on a CPU
@@ -639,6 +702,9 @@ def main():
         return
     if a.png:
         png_main(a, wts, Events())
+        return
+    if a.views:
+        views_main(a, wts, Events())
         return
     sw, sh = (int(v) for v in a.src.split("x"))
     if sw % 2:

@@ -87,6 +87,17 @@ class FrameBayer(C.Structure):
                 ("sample", C.c_int), ("shift", C.c_int), ("reserved", C.c_int * 2)]
 
 
+class FrameView(C.Structure):
+    """mi355_frame_view: what a batch slot looks at -- the rectangle [x0, x0 + w) x [y0, y0 + h) of its frame under EXIF orientation
+    `orient` (1..8).  One per slot, beside the frame table, in the mi355_frames_<kind>_view_letterbox_minmax / _quantize calls."""
+    _fields_ = [("x0", C.c_int), ("y0", C.c_int), ("w", C.c_int), ("h", C.c_int), ("orient", C.c_int), ("reserved", C.c_int * 3)]
+
+
+class Box(C.Structure):
+    """box of darknet_q.h"""
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("w", C.c_float), ("h", C.c_float)]
+
+
 BAYER_PATTERN = {"rggb": 0, "bggr": 1, "grbg": 2, "gbrg": 3, "mono": 4}  # MI355_BAYER_RGGB .. MI355_BAYER_MONO
 RAW_SAMPLE = {"u8": 0, "u16": 1, "mipi10": 2, "mipi12": 3}  # MI355_RAW_U8 .. MI355_RAW_MIPI12
 
@@ -297,6 +308,11 @@ def shim():
         if hasattr(L, "mi355_frames_bayer_letterbox_minmax"):  # as above: an older build has no Bayer calls
             L.mi355_frames_bayer_letterbox_minmax.argtypes = [vp, C.POINTER(FrameBayer), ci, ci, ci, vp, vp]
             L.mi355_frames_bayer_letterbox_quantize.argtypes = [vp, C.POINTER(FrameBayer), ci, ci, ci, vp, vp, vp, vp]
+        for kind, struct in (("u8", FrameU8), ("yuv", FrameYUV), ("planar", FramePlanar), ("packed", FramePacked), ("p010", FrameP010),
+                             ("bayer", FrameBayer)):
+            pre = [vp, C.POINTER(struct), vp, C.POINTER(FrameView), ci, ci, ci]
+            getattr(L, f"mi355_frames_{kind}_view_letterbox_minmax").argtypes = pre + [vp, vp]
+            getattr(L, f"mi355_frames_{kind}_view_letterbox_quantize").argtypes = pre + [vp, vp, vp, vp]
         L.mi355_yolo_detections_sizes.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp, vp, C.c_float, ci, vp, ci, vp, vp]
         L.mi355_yolo_detections_batch_work_ints.restype = C.c_long
         L.mi355_yolo_detections_batch_work_ints.argtypes = [C.POINTER(YoloHead), ci, ci]
@@ -647,6 +663,15 @@ def host():
         L.detections_from_records.argtypes = [vp, vp, ci, ci, C.c_float, C.POINTER(vp), C.POINTER(ci)]
         L.detections_to_arrays.argtypes = [vp, ci, ci, vp, vp, vp]
         L.do_nms_sort_arrays.argtypes = [vp, vp, vp, ci, ci, C.c_float]
+        L.network_set_frame_views.argtypes = [vp, C.POINTER(FrameView)]
+        L.network_set_frame_views.restype = None
+        L.network_tile_views.argtypes = [ci, ci, ci, ci, ci, ci, C.POINTER(FrameView)]
+        L.network_view_box_to_frame.argtypes = [C.POINTER(FrameView), ci, ci, C.POINTER(Box)]
+        L.network_view_box_to_frame.restype = None
+        L.network_detections_views.argtypes = [vp, vp, vp, vp, C.c_float, C.c_float, ci, C.POINTER(vp), C.POINTER(ci)]
+        L.detections_views_merge.argtypes = [C.POINTER(vp), C.POINTER(ci), ci, C.POINTER(FrameView), vp, vp, vp, ci, C.c_float,
+                                             C.POINTER(vp), C.POINTER(ci)]
+        L.jpeg_exif_orientation_host.argtypes = [C.c_char_p, C.c_size_t]
         _host = L
     return _host
 
@@ -656,6 +681,39 @@ INFO_KEYS = ["type", "out_c", "out_h", "out_w", "c", "h", "w", "n", "size", "str
 PLAN_KEYS = ["route_elided", "out_view", "view_offset", "fuse_next_pool", "fuse_next_upsample", "fuse_next_shortcut", "fuse_next_yolo",
              "fuse_pool_keep"]
 T_CONV, T_MAXPOOL, T_ROUTE, T_SHORTCUT, T_YOLO, T_UPSAMPLE = 0, 3, 8, 13, 23, 26
+
+
+def frame_view(v, frame_w=None, frame_h=None):
+    """FrameView of `v`: a FrameView, an (x0, y0, w, h, orient) tuple, or None -- the whole frame_w x frame_h frame, orient 1"""
+    if isinstance(v, FrameView):
+        return v
+    if v is None:
+        v = (0, 0, frame_w, frame_h, 1)
+    x0, y0, w, h, orient = (int(t) for t in v)
+    return FrameView(x0, y0, w, h, orient, (C.c_int * 3)(0, 0, 0))
+
+
+def tile_views(frame_w, frame_h, cols, rows, overlap=0, orient=1):
+    """network_tile_views: cols * rows (x0, y0, w, h, orient) tuples that cover the frame, row by row"""
+    n = max(int(cols), 0) * max(int(rows), 0)
+    out = (FrameView * max(n, 1))()
+    rc = host().network_tile_views(int(frame_w), int(frame_h), int(cols), int(rows), int(overlap), int(orient), out)
+    if rc < 0:
+        raise ValueError(f"network_tile_views refuses {cols} x {rows} tiles with overlap {overlap}, orient {orient} of a {frame_w} x {frame_h} frame")
+    return [(v.x0, v.y0, v.w, v.h, v.orient) for v in out[:rc]]
+
+
+def view_box_to_frame(view, frame_w, frame_h, box):
+    """network_view_box_to_frame: (x, y, w, h) relative to the view (its oriented size) -> relative to the frame, float32 values"""
+    b = Box(*(float(t) for t in box))
+    host().network_view_box_to_frame(C.byref(frame_view(view, frame_w, frame_h)), int(frame_w), int(frame_h), C.byref(b))
+    return np.array([b.x, b.y, b.w, b.h], np.float32)
+
+
+def jpeg_exif_orientation(data):
+    """jpeg_exif_orientation_host: the EXIF orientation 1..8 of a JPEG file's bytes; 1 when there is none to be read"""
+    data = bytes(data)
+    return int(host().jpeg_exif_orientation_host(data, len(data)))
 
 
 def _as(ptr, n, dt):
@@ -1815,6 +1873,47 @@ class Net:
             if nms and nms > 0:  # rows keep their place, suppressed scores become 0
                 self.H.do_nms_sort_arrays(boxes.ctypes.data, probs.ctypes.data, obj.ctypes.data, k, classes, C.c_float(nms))
             out.append(dict(boxes=boxes, objectness=obj, probs=probs, found=int(counts[b].sum()), kept=int(k)))
+        self.H.free_detections_batch(dets, num, B)
+        return out
+
+    def set_frame_views(self, views, sizes=None):
+        """network_set_frame_views: one view per batch slot for the prepare_from_frames_* / _jpeg / _png calls that follow --
+        (x0, y0, w, h, orient) tuples or FrameView; None for a slot means its whole frame, orient 1, and needs sizes[b] = (w, h) of that
+        frame.  views = None clears: every slot is its whole frame as stored again."""
+        if views is None:
+            self.H.network_set_frame_views(self.h, None)
+            return
+        if len(views) != self.batch:
+            raise ValueError(f"set_frame_views: {len(views)} views for a batch of {self.batch}")
+        if any(v is None for v in views) and sizes is None:
+            raise ValueError("set_frame_views: a None view needs sizes, the (w, h) of every slot's frame")
+        table = (FrameView * self.batch)()
+        for b, v in enumerate(views):
+            table[b] = frame_view(v, *(sizes[b] if v is None else (None, None)))
+        self.H.network_set_frame_views(self.h, table)
+
+    def detect_views(self, frame_w, frame_h, frame_of_slot=None, thresh=.5, nms=.45, max_per_image=None):
+        """network_detections_views: the detections of a batch of views per FRAME.  frame_w, frame_h: the frame sizes per slot (or one
+        for all); frame_of_slot[b]: which frame slot b looks at (default: frame 0 for every slot).  Boxes are relative to the frame;
+        the slots of a frame are concatenated and go through one do_nms_sort.  Returns {frame: dict(boxes [k, 4], objectness [k],
+        probs [k, classes])} in the NMS's order, suppressed scores 0."""
+        classes = self.detections_shape()[1]
+        w, h = self._sizes(frame_w, frame_h)
+        B = self.batch
+        fos = np.ascontiguousarray(np.zeros(B, np.int32) if frame_of_slot is None else frame_of_slot, np.int32)
+        if fos.shape != (B,):
+            raise ValueError("detect_views: frame_of_slot needs one entry per slot")
+        dets, num = (C.c_void_p * B)(), (C.c_int * B)()
+        rc = self.H.network_detections_views(self.h, w.ctypes.data, h.ctypes.data, fos.ctypes.data, C.c_float(thresh), C.c_float(nms or 0.0),
+                                             0 if max_per_image is None else int(max_per_image), dets, num)
+        if rc != 0:
+            raise MI355Error(f"network_detections_views: code {rc} (refused: see stderr)")
+        out = {}
+        for f in sorted(set(fos.tolist())):
+            k = num[f]
+            boxes, obj, probs = np.zeros((k, 4), np.float32), np.zeros(k, np.float32), np.zeros((k, classes), np.float32)
+            self.H.detections_to_arrays(dets[f], k, classes, boxes.ctypes.data, obj.ctypes.data, probs.ctypes.data)
+            out[f] = dict(boxes=boxes, objectness=obj, probs=probs)
         self.H.free_detections_batch(dets, num, B)
         return out
 

@@ -23,6 +23,8 @@
 //                 the NV12 byte (truncation), loaded on its own;
 //   SourceBayer   one plane of raw sensor samples (mi355_frames_bayer_*: 8-bit, 16-bit, CSI-2 RAW10 / RAW12; RGGB, BGGR, GRBG, GBRG or
 //                 no mosaic): toned through the frame's optional tables and demosaiced bilinearly in registers at every tap.
+// A slot may look at its frame through a view (mi355_frame_view: a rectangle under an EXIF orientation): Viewed<Source> wraps any of the
+// six and is a Source itself (mi355_frames_*_view_*); its kernels, check and launchers are compiled from this file by frames_view.hip.
 #include "kargs.h"
 
 // letterbox_launch's geometry (glue.hip), shared by the host-side validation and the kernels: one function compiled for both sides, so
@@ -477,6 +479,69 @@ struct SourceBayer {
     }
 };
 
+#ifdef FRAMES_VIEW_TU
+// A view of a frame (mi355_frame_view): the rectangle [x0, x0 + w) x [y0, y0 + h) of the frame a Source stands for, turned or mirrored
+// by an EXIF orientation; itself a Source.  w and h are the view's (sides swapped by the transposing orients 5..8), so that
+// letterbox_px3's one-pixel clauses and frame_geometry see the view; the Source underneath is built from the whole frame, so chroma
+// addressing, MIPI groups, the Bayer colour of a site and its reflection stay in frame coordinates.  View tap (u, v) is crop pixel
+//   1 (u, v)   2 (cw-1-u, v)   3 (cw-1-u, ch-1-v)   4 (u, ch-1-v)   5 (v, u)   6 (v, ch-1-u)   7 (cw-1-v, ch-1-u)   8 (cw-1-v, u)
+// (cw, ch the crop's sides) plus (x0, y0).  The up to 2 x 2 view taps are always a 2 x 2, 1 x 2, 2 x 1 or 1 x 1 cell of the frame: the
+// Source's taps is called once, on the cell's low corner (two_x / two_y swapped by a transposing orient), so every kind keeps its shared
+// loads, and the cell is permuted into p.  The view is uniform over the workgroup (blockIdx.y is the slot): no branch on it diverges.
+template <class Source>
+struct Viewed {
+    using Frame = typename Source::Frame;
+    Source src;
+    int w, h;        // of the view
+    int x0, y0;      // crop pixel (0, 0) in frame coordinates
+    int ex, ey;      // the crop's last column and row: cw - 1, ch - 1
+    bool swap, mx, my;  // the view's axes are the crop's swapped; the crop's x / y axis runs against the view axis it serves
+    __device__ Viewed(const Frame &f, const mi355_frame_view &v)
+        : src(f), w(v.orient >= 5 ? v.h : v.w), h(v.orient >= 5 ? v.w : v.h), x0(v.x0), y0(v.y0), ex(v.w - 1), ey(v.h - 1),
+          swap(v.orient >= 5), mx(v.orient == 2 || v.orient == 3 || v.orient == 7 || v.orient == 8),
+          my(v.orient == 3 || v.orient == 4 || v.orient == 6 || v.orient == 7) {}
+    __device__ void taps(int ix, int iy, bool two_x, bool two_y, uint8_t p[2][2][3]) const
+    {
+        // along the crop's x axis runs view coordinate a, along its y axis view coordinate b
+        const int a = swap ? iy : ix, b = swap ? ix : iy;
+        const bool two_a = swap ? two_y : two_x, two_b = swap ? two_x : two_y;
+        // the cell's low corner: a mirrored axis counts down, so its second tap is the lower coordinate
+        const int cx = mx ? ex - a - (two_a ? 1 : 0) : a, cy = my ? ey - b - (two_b ? 1 : 0) : b;
+        uint8_t c[2][2][3];
+        src.taps(x0 + cx, y0 + cy, two_a, two_b, c);
+        // the cell into view order: mirror it along the axes that run backwards, then transpose it.  Exchanges and selects at constant
+        // indices only, so the cell stays in registers
+        if (mx && two_a) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                if (i == 1 && !two_b) break;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { const uint8_t t = c[i][0][k]; c[i][0][k] = c[i][1][k]; c[i][1][k] = t; }
+            }
+        }
+        if (my && two_b) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                if (j == 1 && !two_a) break;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { const uint8_t t = c[0][j][k]; c[0][j][k] = c[1][j][k]; c[1][j][k] = t; }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (r == 1 && !two_y) break;
+#pragma unroll
+            for (int d = 0; d < 2; ++d) {
+                if (d == 1 && !two_x) break;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) p[r][d][k] = swap ? c[d][r][k] : c[r][d][k];
+            }
+        }
+    }
+};
+
+#endif  // FRAMES_VIEW_TU
+
 // the three letterboxed floats (planes 0, 1, 2) of output pixel (x, y)
 template <class Source>
 __device__ static inline void letterbox_px3(const Source &f, const FrameGeo &g, const float *lut, int x, int y, float v[3])
@@ -512,9 +577,10 @@ __device__ static inline void letterbox_px3(const Source &f, const FrameGeo &g, 
 }
 
 // grid: (workgroups per image, B).  mm[2 b] = max(x, +0), mm[2 b + 1] = min(x, -0) as in image_minmax_batched_kernel (seeded before).
-// One body for every source; lut: the workgroup's 256-entry byte table.
-template <class Source, class Frame>
-__device__ static inline void letterbox_minmax_body(const Frame *table, int w, int h, uint32_t *mm, float *lut)
+// One body for every source; table[b]: what the Source of slot b is built from (a frame table, or ViewTable below); lut: the
+// workgroup's 256-entry byte table.
+template <class Source, class Table>
+__device__ static inline void letterbox_minmax_body(Table table, int w, int h, uint32_t *mm, float *lut)
 {
     fill_byte_lut(lut);
     const Source f(table[blockIdx.y]);
@@ -544,17 +610,19 @@ __device__ static inline void letterbox_minmax_body(const Frame *table, int w, i
     }
 }
 
+#ifndef FRAMES_VIEW_TU
 template <class Source>
 __global__ __launch_bounds__(256) void frames_letterbox_minmax_kernel(const typename Source::Frame *table, int w, int h, uint32_t *mm)
 {
     __shared__ float lut[256];
     letterbox_minmax_body<Source>(table, w, h, mm, lut);
 }
+#endif  // !FRAMES_VIEW_TU
 
 // grid: (workgroups per image, B); a thread serves four neighbouring x of one row in all three planes: one 4-byte store per plane
 // where the row position is 4-byte aligned, single bytes otherwise (w % 4 != 0: every other row, and the tail of each row)
-template <class Source, class Frame>
-__device__ static inline void letterbox_quantize_body(const Frame *table, int w, int h, const float *scale_dev, const uint8_t *zp_dev,
+template <class Source, class Table>
+__device__ static inline void letterbox_quantize_body(Table table, int w, int h, const float *scale_dev, const uint8_t *zp_dev,
                                                       uint8_t *out, float *lut)
 {
     fill_byte_lut(lut);
@@ -592,6 +660,7 @@ __device__ static inline void letterbox_quantize_body(const Frame *table, int w,
     }
 }
 
+#ifndef FRAMES_VIEW_TU
 template <class Source>
 __global__ __launch_bounds__(256) void frames_letterbox_quantize_kernel(const typename Source::Frame *table, int w, int h,
                                                                         const float *scale_dev, const uint8_t *zp_dev, uint8_t *out)
@@ -619,11 +688,75 @@ __global__ __launch_bounds__(256) void frames_letterbox_quantize_kernel<SourceBa
     letterbox_quantize_body<SourceBayer>(table, w, h, scale_dev, zp_dev, out, lut);
 }
 
+#else  // FRAMES_VIEW_TU
+// The kernels of a view of every kind: the same bodies over Viewed<Source>, built from the slot's frame and view.  They are compiled in
+// a translation unit of their own (frames_view.hip includes this file with FRAMES_VIEW_TU defined), so that the kernels above are
+// compiled exactly as without them: a second caller of a source's taps in the same unit changes how it is inlined into them.
+template <class Source>
+struct ViewTable {
+    const typename Source::Frame *frames;
+    const mi355_frame_view *views;
+    __device__ Viewed<Source> operator[](unsigned b) const { return Viewed<Source>(frames[b], views[b]); }
+};
+
+template <class Source>
+__global__ __launch_bounds__(256) void frames_view_letterbox_minmax_kernel(const typename Source::Frame *table, const mi355_frame_view *views,
+                                                                           int w, int h, uint32_t *mm)
+{
+    __shared__ float lut[256];
+    letterbox_minmax_body<Viewed<Source>>(ViewTable<Source>{table, views}, w, h, mm, lut);
+}
+
+template <class Source>
+__global__ __launch_bounds__(256) void frames_view_letterbox_quantize_kernel(const typename Source::Frame *table, const mi355_frame_view *views,
+                                                                             int w, int h, const float *scale_dev, const uint8_t *zp_dev,
+                                                                             uint8_t *out)
+{
+    __shared__ float lut[256];
+    letterbox_quantize_body<Viewed<Source>>(ViewTable<Source>{table, views}, w, h, scale_dev, zp_dev, out, lut);
+}
+
+template <>
+__global__ __launch_bounds__(256) void frames_view_letterbox_minmax_kernel<SourceBayer>(const mi355_frame_bayer *table,
+                                                                                        const mi355_frame_view *views, int w, int h,
+                                                                                        uint32_t *mm)
+{
+    __shared__ float lut[256];
+    bayer_stage_tone(table[blockIdx.y].tone);
+    letterbox_minmax_body<Viewed<SourceBayer>>(ViewTable<SourceBayer>{table, views}, w, h, mm, lut);
+}
+
+template <>
+__global__ __launch_bounds__(256) void frames_view_letterbox_quantize_kernel<SourceBayer>(const mi355_frame_bayer *table,
+                                                                                          const mi355_frame_view *views, int w, int h,
+                                                                                          const float *scale_dev, const uint8_t *zp_dev,
+                                                                                          uint8_t *out)
+{
+    __shared__ float lut[256];
+    bayer_stage_tone(table[blockIdx.y].tone);
+    letterbox_quantize_body<Viewed<SourceBayer>>(ViewTable<SourceBayer>{table, views}, w, h, scale_dev, zp_dev, out, lut);
+}
+
+#endif  // FRAMES_VIEW_TU
+
 // Host-side check of the table's host mirror, before anything is launched: NULL when every frame can be served, else what is wrong
 // ("<Source::name>: <reason>", in a buffer of the calling thread).  The conditions every kind shares are here, a kind's own in its
 // Source::check_pointers and Source::check.
+// The refusals that are a view's own, against the frame it looks at (already checked): NULL, or the reason.
+static const char *view_check(const mi355_frame_view &v, int frame_w, int frame_h)
+{
+    if (v.orient < 1 || v.orient > 8) return "view: orient outside 1..8";
+    if (v.reserved[0] != 0 || v.reserved[1] != 0 || v.reserved[2] != 0) return "view: reserved must be 0";
+    if (v.w < 1 || v.h < 1) return "view: need w, h >= 1";
+    // frame_w, frame_h <= 32768 and x0, y0 >= 0 where the differences are formed: no sum of the caller's numbers, no overflow
+    if (v.x0 < 0 || v.y0 < 0 || v.w > frame_w - v.x0 || v.h > frame_h - v.y0) return "view: rectangle outside the frame";
+    return nullptr;
+}
+
+// views: NULL (every slot is its whole frame as stored), or one view per slot: the frame is checked as ever, then the view, and the
+// geometry is that of the view's oriented size.
 template <class Source, class Frame>
-const char *frames_check(const Frame *host, int B, int w, int h)
+static const char *frames_check_views(const Frame *host, const mi355_frame_view *views, int B, int w, int h)
 {
     static thread_local char why[160];
     const char *bad = nullptr;
@@ -635,12 +768,32 @@ const char *frames_check(const Frame *host, int B, int w, int h)
         bad = Source::check_pointers(f);  // in the order the refusals have always had
         if (!bad && (f.w < 1 || f.h < 1 || f.w > 32768 || f.h > 32768)) bad = "need 1 <= w, h <= 32768 for every frame";
         if (!bad) bad = Source::check(f);
-        if (!bad && !frame_geometry(f.w, f.h, w, h, g)) bad = "degenerate aspect (resized side < 2)";
+        int vw = f.w, vh = f.h;
+        if (!bad && views) {
+            bad = view_check(views[b], f.w, f.h);
+            vw = views[b].orient >= 5 ? views[b].h : views[b].w;
+            vh = views[b].orient >= 5 ? views[b].w : views[b].h;
+        }
+        if (!bad && !frame_geometry(vw, vh, w, h, g)) bad = "degenerate aspect (resized side < 2)";
     }
     if (!bad) return nullptr;
     snprintf(why, sizeof(why), "%s: %s", Source::name, bad);
     return why;
 }
+
+#ifndef FRAMES_VIEW_TU
+template <class Source, class Frame>
+const char *frames_check(const Frame *host, int B, int w, int h)
+{
+    return frames_check_views<Source>(host, nullptr, B, w, h);
+}
+#else
+template <class Source, class Frame>
+const char *frames_view_check(const Frame *host, const mi355_frame_view *views_host, int B, int w, int h)
+{
+    return frames_check_views<Source>(host, views_host, B, w, h);
+}
+#endif
 
 // about 2048 workgroups in all, at least one per image (image_minmax_batched_launch's sizing)
 static int minmax_grid_x(int B, int w, int h)
@@ -656,6 +809,7 @@ static unsigned quantize_grid_x(int w, int h)
     return (unsigned)((threads + 255) / 256);
 }
 
+#ifndef FRAMES_VIEW_TU
 template <class Source, class Frame>
 int frames_letterbox_minmax_launch(const Frame *table_dev, int B, int w, int h, uint32_t *mm, hipStream_t st)
 {
@@ -673,12 +827,44 @@ int frames_letterbox_quantize_launch(const Frame *table_dev, int B, int w, int h
     return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
 }
 
+#else
+// the same two launches for views: the grids depend on the network input alone
+template <class Source, class Frame>
+int frames_view_letterbox_minmax_launch(const Frame *table_dev, const mi355_frame_view *views_dev, int B, int w, int h, uint32_t *mm,
+                                        hipStream_t st)
+{
+    if (image_minmax_seed_launch(mm, B, st) != MI355_OK) return MI355_EHIP;
+    hipLaunchKernelGGL(frames_view_letterbox_minmax_kernel<Source>, dim3(minmax_grid_x(B, w, h), B), dim3(256), 0, st, table_dev, views_dev,
+                       w, h, mm);
+    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
+}
+
+template <class Source, class Frame>
+int frames_view_letterbox_quantize_launch(const Frame *table_dev, const mi355_frame_view *views_dev, int B, int w, int h,
+                                          const float *scale_dev, const uint8_t *zp_dev, uint8_t *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(frames_view_letterbox_quantize_kernel<Source>, dim3(quantize_grid_x(w, h), B), dim3(256), 0, st, table_dev,
+                       views_dev, w, h, scale_dev, zp_dev, out);
+    return hipGetLastError() == hipSuccess ? MI355_OK : MI355_EHIP;
+}
+
+#endif
+
 // the six kinds behind the C-ABI (shim.hip)
+#ifdef FRAMES_VIEW_TU
+#define FRAMES_KIND(S)                                                                                                                \
+    template const char *frames_view_check<S, S::Frame>(const S::Frame *, const mi355_frame_view *, int, int, int);                             \
+    template int frames_view_letterbox_minmax_launch<S, S::Frame>(const S::Frame *, const mi355_frame_view *, int, int, int, uint32_t *,         \
+                                                                  hipStream_t);                                                                \
+    template int frames_view_letterbox_quantize_launch<S, S::Frame>(const S::Frame *, const mi355_frame_view *, int, int, int, const float *,   \
+                                                                    const uint8_t *, uint8_t *, hipStream_t);
+#else
 #define FRAMES_KIND(S)                                                                                                                \
     template const char *frames_check<S, S::Frame>(const S::Frame *, int, int, int);                                                            \
     template int frames_letterbox_minmax_launch<S, S::Frame>(const S::Frame *, int, int, int, uint32_t *, hipStream_t);                         \
     template int frames_letterbox_quantize_launch<S, S::Frame>(const S::Frame *, int, int, int, const float *, const uint8_t *, uint8_t *, \
                                                                hipStream_t);
+#endif
 FRAMES_KIND(SourceU8)
 FRAMES_KIND(SourceYUV)
 FRAMES_KIND(SourcePlanar)

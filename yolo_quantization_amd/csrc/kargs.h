@@ -255,6 +255,15 @@ template <class Source, class Frame> int frames_letterbox_minmax_launch(const Fr
 template <class Source, class Frame>
 int frames_letterbox_quantize_launch(const Frame *table_dev, int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev, uint8_t *out,
                                      hipStream_t st);
+// the same three for a batch whose slots look at their frames through views (one mi355_frame_view per slot)
+template <class Source, class Frame>
+const char *frames_view_check(const Frame *host, const mi355_frame_view *views_host, int B, int w, int h);
+template <class Source, class Frame>
+int frames_view_letterbox_minmax_launch(const Frame *table_dev, const mi355_frame_view *views_dev, int B, int w, int h, uint32_t *mm,
+                                        hipStream_t st);
+template <class Source, class Frame>
+int frames_view_letterbox_quantize_launch(const Frame *table_dev, const mi355_frame_view *views_dev, int B, int w, int h,
+                                          const float *scale_dev, const uint8_t *zp_dev, uint8_t *out, hipStream_t st);
 // jpeg.hip: dequantise + inverse DCT of every block of a batch, then upsampling + colour into RGB frames.  The checks read the host
 // mirror of the table and return NULL or why it is refused; the launchers take the grid from it.
 const char *jpeg_idct_check(const mi355_jpeg_plane *host, int nplanes);

@@ -49,6 +49,47 @@ static int frames_quantize(const char *null_msg, const Frame *table_dev, const F
     return frames_letterbox_quantize_launch<Source>(table_dev, B, w, h, scale_dev, zp_dev, out_u8, (hipStream_t)stream);
 }
 
+// The same two calls for a batch of views: the two view tables are arguments like the frame table's.
+template <class Source, class Frame>
+static int frames_view_minmax(const char *null_msg, const Frame *table_dev, const Frame *table_host, const mi355_frame_view *views_dev,
+                              const mi355_frame_view *views_host, int B, int w, int h, float *minmax, void *stream)
+{
+    if (!table_dev || !views_dev || !views_host || !minmax) return einval(null_msg);
+    const char *why = frames_view_check<Source>(table_host, views_host, B, w, h);
+    if (why) return einval(why);
+    return frames_view_letterbox_minmax_launch<Source>(table_dev, views_dev, B, w, h, reinterpret_cast<uint32_t *>(minmax),
+                                                       (hipStream_t)stream);
+}
+
+template <class Source, class Frame>
+static int frames_view_quantize(const char *null_msg, const Frame *table_dev, const Frame *table_host, const mi355_frame_view *views_dev,
+                                const mi355_frame_view *views_host, int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev,
+                                uint8_t *out_u8, void *stream)
+{
+    if (!table_dev || !views_dev || !views_host || !scale_dev || !zp_dev || !out_u8) return einval(null_msg);
+    const char *why = frames_view_check<Source>(table_host, views_host, B, w, h);
+    if (why) return einval(why);
+    return frames_view_letterbox_quantize_launch<Source>(table_dev, views_dev, B, w, h, scale_dev, zp_dev, out_u8, (hipStream_t)stream);
+}
+
+// the pair of view calls of one kind
+#define FRAMES_VIEW_CALLS(kind, S)                                                                                                                    \
+    int mi355_frames_##kind##_view_letterbox_minmax(const mi355_frame_##kind *table_dev, const mi355_frame_##kind *table_host,                        \
+                                                               const mi355_frame_view *views_dev, const mi355_frame_view *views_host,                 \
+                                                               int B, int w, int h, float *minmax, void *stream)                                      \
+    {                                                                                                                                                 \
+        return frames_view_minmax<S>("frames_" #kind ": view_letterbox_minmax: null", table_dev, table_host, views_dev, views_host, B, w,             \
+                                     h, minmax, stream);                                                                                              \
+    }                                                                                                                                                 \
+    int mi355_frames_##kind##_view_letterbox_quantize(const mi355_frame_##kind *table_dev, const mi355_frame_##kind *table_host,                      \
+                                                                 const mi355_frame_view *views_dev, const mi355_frame_view *views_host,               \
+                                                                 int B, int w, int h, const float *scale_dev, const uint8_t *zp_dev,                  \
+                                                                 uint8_t *out_u8, void *stream)                                                       \
+    {                                                                                                                                                 \
+        return frames_view_quantize<S>("frames_" #kind ": view_letterbox_quantize: null", table_dev, table_host, views_dev, views_host, B,            \
+                                       w, h, scale_dev, zp_dev, out_u8, stream);                                                                      \
+    }
+
 extern "C" {
 
 const char *mi355_last_error(void) { return g_err; }
@@ -1214,6 +1255,13 @@ int mi355_frames_bayer_letterbox_quantize(const mi355_frame_bayer *table_dev, co
     return frames_quantize<SourceBayer>("frames_bayer: letterbox_quantize: null", table_dev, table_host, B, w, h, scale_dev, zp_dev, out_u8,
                                         stream);
 }
+
+FRAMES_VIEW_CALLS(u8, SourceU8)
+FRAMES_VIEW_CALLS(yuv, SourceYUV)
+FRAMES_VIEW_CALLS(planar, SourcePlanar)
+FRAMES_VIEW_CALLS(packed, SourcePacked)
+FRAMES_VIEW_CALLS(p010, SourceP010)
+FRAMES_VIEW_CALLS(bayer, SourceBayer)
 
 int mi355_checksum_u32(const void *buf, long dwords, uint64_t *sum_dev, void *stream)
 {

@@ -52,6 +52,10 @@
  * device (network_frames_png_input_gpu), stb_image's pixels again, `-frames u8` implied like for a JPEG.  A -list may mix PNG, JPEG
  * and PPM files of different sizes.  Progressive and CMYK JPEGs, BMP, GIF and the other formats of the reference's stb_image are not
  * built and are refused with a message (which still lists PNG: a file with the PNG signature but no IHDR behind it gets it).
+ * -view x,y,w,h | -orient N | -orient exif | -tiles CxR[,overlap] (with -frames, one image, one device: every slot looks at a
+ * rectangle of the frame under an EXIF orientation -- network_set_frame_views --; `exif` reads a JPEG file's own, other files get 1;
+ * -tiles fills C * R slots with network_tile_views' tiles and prints ONE block, network_detections_views' boxes in the image's
+ * coordinates after one NMS).
  */
 #include <math.h>
 #include <pthread.h>
@@ -232,6 +236,9 @@ typedef struct {
     int batch, accum, store, use_graph, iters, gpu, boxes, quiet, inflight;
     int jpeg_device;       /* -jpeg_device: JPEG scans are entropy-decoded on the device (set_jpeg_entropy_on_device) */
     int png_device;        /* -png_device: PNG streams are inflated on the device (set_png_inflate_on_device) */
+    int view_set, view[4]; /* -view x,y,w,h: the rectangle of the frame every slot looks at */
+    int orient;            /* -orient N: 1..8; -orient exif: -1, the file's EXIF orientation (JPEG files; other files 1); 0: not given */
+    int tiles, tile_cols, tile_rows, tile_overlap; /* -tiles CxR[,overlap]: the image's tiles fill the batch's C * R slots */
     int input_device;      /* -input_device: scales and layer-0 constants are derived on the device (set_input_quantization_on_device) */
     int rank, nranks;      /* -gpus with -bcast: this replica's rank; rank 0 reads the weights file, the others receive blobs */
     const void *comm_id;   /* shared 128-byte RCCL unique id (NULL: every replica reads the file) */
@@ -250,6 +257,38 @@ static int batch_detections(const detect_job *job, network *net, const int *imw,
     const float nms = .45f; /* ref :892 */
     if (network_detections_batch(net, imw, imh, job->thresh, 1, nms, 0, dets, num)) error("detector: the network's yolo layers cannot be decoded together");
     return classes;
+}
+
+/* -orient exif: the EXIF orientation of a JPEG file, 1 for every other file */
+static int file_orientation(const char *path)
+{
+    if (!is_jpeg_file(path)) return 1;
+    FILE *f = fopen(path, "rb");
+    if (!f) file_error(path);
+    static uint8_t head[1 << 16]; /* APP1 lies in front of the tables and the scan */
+    const size_t n = fread(head, 1, sizeof(head), f);
+    fclose(f);
+    return jpeg_exif_orientation_host(head, n);
+}
+
+/* -view, -orient, -tiles: the views of the batch's slots on the one fw x fh frame they all hold */
+static void set_job_views(const detect_job *job, network *net, int fw, int fh)
+{
+    const int B = net->batch;
+    const int orient = job->orient < 0 ? file_orientation(job->filename) : job->orient ? job->orient : 1;
+    mi355_frame_view *views = calloc((size_t)B, sizeof(mi355_frame_view));
+    if (job->tiles) {
+        if (network_tile_views(fw, fh, job->tile_cols, job->tile_rows, job->tile_overlap, orient, views) != B)
+            error("-tiles: the tiles do not fit the image (a tile larger than the image, or an overlap at or above the tile size)");
+    } else {
+        for (int b = 0; b < B; ++b) {
+            views[b].x0 = job->view_set ? job->view[0] : 0; views[b].y0 = job->view_set ? job->view[1] : 0;
+            views[b].w = job->view_set ? job->view[2] : fw; views[b].h = job->view_set ? job->view[3] : fh;
+            views[b].orient = orient;
+        }
+    }
+    network_set_frame_views(net, views);
+    free(views);
 }
 
 /* draw_detections' console output for one slot of batch_detections' result */
@@ -531,6 +570,10 @@ static void test_detector(detect_job *job)
         for (int b = 0; b < job->batch; ++b) slot[b] = (char *)job->filename;
         feed_frames(job, net, slot, fw, fh);
         im.w = fw[0]; im.h = fh[0];
+        if (job->view_set || job->orient || job->tiles) { /* the first pass told the frame's size: once more, through the views */
+            set_job_views(job, net, im.w, im.h);
+            feed_frames(job, net, slot, fw, fh);
+        }
         free(slot); free(fw); free(fh);
     } else {
         im = load_image_any(job->filename, net->c, net->h, net->w);
@@ -580,8 +623,18 @@ static void test_detector(detect_job *job)
         int *imw = calloc((size_t)B, sizeof(int)), *imh = calloc((size_t)B, sizeof(int)), *num = calloc((size_t)B, sizeof(int));
         detection **dets = calloc((size_t)B, sizeof(detection *));
         for (int b = 0; b < B; ++b) { imw[b] = im.w; imh[b] = im.h; }
-        const int classes = batch_detections(job, net, imw, imh, dets, num);
-        print_detections(job, classes, dets[0], num[0], names, nnames);
+        if (net->fr_views) { /* one block for the image: every slot's boxes in the frame's coordinates, one NMS over them */
+            int classes = 0, *frame_of_slot = calloc((size_t)B, sizeof(int)); /* every slot looks at frame 0 */
+            for (int i = 0; i < net->n; ++i)
+                if (net->layers[i].type == YOLO) classes = net->layers[i].classes;
+            if (classes && network_detections_views(net, imw, imh, frame_of_slot, job->thresh, .45f, 0, dets, num))
+                error("detector: the network's yolo layers cannot be decoded together");
+            print_detections(job, classes, dets[0], num[0], names, nnames);
+            free(frame_of_slot);
+        } else {
+            const int classes = batch_detections(job, net, imw, imh, dets, num);
+            print_detections(job, classes, dets[0], num[0], names, nnames);
+        }
         free_detections_batch(dets, num, B);
         free(imw); free(imh); free(num); free(dets);
     }
@@ -604,7 +657,7 @@ int main(int argc, char **argv)
     if (argc < 2) {
         fprintf(stderr, "usage: %s detector test <data> <cfg> <weights> <image> [-thresh t] [-i gpu | -gpus a,b,..] [-batch B] "
                         "[-accum exact|ref-f32] [-parity wrap|saturate] [-dump dir] [-graph] [-n iters] [-boxes] "
-                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8|nv12|nv21|i420|yv12|i422|i444|rgba|bgra|argb|abgr|yuyv|uyvy|yvyu|p010|rggb|bggr|grbg|gbrg|mono] [-matrix bt601|bt601f|bt709|bt709f] [-raw u8|u16|mipi10|mipi12] [-raw_shift N] [-tone file] [-input_device] [-jpeg_device] [-png_device]\n", argv[0]);
+                        "[-save_packed file] [-packed file] [-bcast] [-inflight N] [-list file] [-frames u8|nv12|nv21|i420|yv12|i422|i444|rgba|bgra|argb|abgr|yuyv|uyvy|yvyu|p010|rggb|bggr|grbg|gbrg|mono] [-matrix bt601|bt601f|bt709|bt709f] [-raw u8|u16|mipi10|mipi12] [-raw_shift N] [-tone file] [-view x,y,w,h] [-orient 1..8|exif] [-tiles CxR[,overlap]] [-input_device] [-jpeg_device] [-png_device]\n", argv[0]);
         return 0;
     }
     detect_job job;
@@ -692,6 +745,30 @@ int main(int argc, char **argv)
     }
     if (job.iters < 1) job.iters = 1;
     if (job.batch < 1) job.batch = 1;
+    const char *view_s = find_char_arg(argc, argv, "-view", NULL), *orient_s = find_char_arg(argc, argv, "-orient", NULL);
+    const char *tiles_s = find_char_arg(argc, argv, "-tiles", NULL);
+    job.view_set = job.orient = job.tiles = job.tile_overlap = 0;
+    if (view_s) {
+        char tail;
+        if (sscanf(view_s, "%d,%d,%d,%d%c", &job.view[0], &job.view[1], &job.view[2], &job.view[3], &tail) != 4) error("-view: x,y,w,h");
+        job.view_set = 1;
+    }
+    if (orient_s) {
+        if (0 == strcmp(orient_s, "exif")) job.orient = -1;
+        else if (strlen(orient_s) == 1 && orient_s[0] >= '1' && orient_s[0] <= '8') job.orient = orient_s[0] - '0';
+        else error("-orient: 1 .. 8 (the EXIF numbering) or `exif` (a JPEG file's own; other files 1)");
+    }
+    if (tiles_s) {
+        char tail;
+        const int got = sscanf(tiles_s, "%dx%d,%d%c", &job.tile_cols, &job.tile_rows, &job.tile_overlap, &tail);
+        if ((got != 2 && got != 3) || job.tile_cols < 1 || job.tile_rows < 1 || job.tile_cols * (long)job.tile_rows > 4096 || job.tile_overlap < 0)
+            error("-tiles: CxR[,overlap]");
+        if (view_s) error("-tiles does not go with -view: the tiles are the views");
+        job.tiles = 1;
+        job.batch = job.tile_cols * job.tile_rows; /* one image fills the batch */
+    }
+    if ((view_s || orient_s || tiles_s) && (job.listfile || gpu_list || job.inflight > 1))
+        error("-view, -orient and -tiles run one image on one device, without -list, -gpus and -inflight");
     job.accum = 0 == strcmp(accum_s, "ref-f32") ? MI355_ACC_REF_F32 : MI355_ACC_EXACT;
     job.store = 0 == strcmp(parity_s, "saturate") ? MI355_STORE_SATURATE : MI355_STORE_WRAP;
     if (strcmp(argv[1], "detector")) {
@@ -715,6 +792,7 @@ int main(int argc, char **argv)
             error(is_jpeg_file(job.filename) ? "a JPEG image does not go with raw -frames formats" : "a PNG image does not go with raw -frames formats");
         job.frames = FRAMES_U8;
     }
+    if ((job.view_set || job.orient || job.tiles) && !job.frames) error("-view, -orient and -tiles go with -frames (a JPEG or PNG file implies -frames u8)");
     if (!gpu_list) {
         test_detector(&job);
         return 0;

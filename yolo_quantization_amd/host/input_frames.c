@@ -21,10 +21,12 @@ void fr_free(network *net)
     if (net->fr_table_gpu) mi355_free(net->fr_table_gpu);
     if (net->fr_mm_gpu) mi355_free(net->fr_mm_gpu);
     if (net->fr_pair_gpu) mi355_free(net->fr_pair_gpu);
+    if (net->fr_views_gpu) mi355_free(net->fr_views_gpu);
     free(net->fr_table_host); free(net->fr_mm_host); free(net->fr_pair_host);
     net->fr_arena_gpu = NULL; net->fr_table_gpu = NULL; net->fr_table_host = NULL;
     net->fr_mm_gpu = net->fr_mm_host = NULL;
     net->fr_pair_gpu = net->fr_pair_host = NULL;
+    net->fr_views_gpu = NULL;
     net->fr_arena_bytes = 0;
     net->fr_cap = 0;
 }
@@ -38,6 +40,7 @@ static void fr_alloc(network *net)
     check_mi355(mi355_alloc((void **)&net->fr_mm_gpu, 2 * sizeof(float) * B), "alloc minmax");
     check_mi355(mi355_alloc(&net->fr_pair_gpu, 5 * B), "alloc input pairs");
     check_mi355(mi355_alloc(&net->fr_table_gpu, sizeof(mi355_frame_planar) * B), "alloc frame table");
+    check_mi355(mi355_alloc(&net->fr_views_gpu, sizeof(mi355_frame_view) * B), "alloc view table");
     net->fr_mm_host = calloc(2 * B, sizeof(float));
     net->fr_pair_host = calloc(5, B);
     net->fr_table_host = calloc(B, sizeof(mi355_frame_planar));
@@ -111,20 +114,66 @@ static size_t fr_stage_frames_and(network *net, const fr_plane *planes, int np, 
 
 static void fr_stage_frames(network *net, const fr_plane *planes, int np) { (void)fr_stage_frames_and(net, planes, np, 0); }
 
+/* The two launches of the table's kind; with views set (network_set_frame_views) the view pair of the same kind, which takes the view
+ * table beside the frame table. */
+static void fr_minmax(network *net)
+{
+    const int B = net->batch, kind = net->fr_kind, w = net->w, h = net->h;
+    const void *tg = net->fr_table_gpu, *th = net->fr_table_host;
+    const mi355_frame_view *vg = net->fr_views_gpu, *vh = net->fr_views;
+    float *mm = net->fr_mm_gpu;
+    void *st = net->stream;
+    if (vh) {
+        if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_view_letterbox_minmax(tg, th, vg, vh, B, w, h, mm, st), "mi355_frames_planar_view_letterbox_minmax");
+        else if (kind == FR_PACKED) check_mi355(mi355_frames_packed_view_letterbox_minmax(tg, th, vg, vh, B, w, h, mm, st), "mi355_frames_packed_view_letterbox_minmax");
+        else if (kind == FR_P010) check_mi355(mi355_frames_p010_view_letterbox_minmax(tg, th, vg, vh, B, w, h, mm, st), "mi355_frames_p010_view_letterbox_minmax");
+        else if (kind == FR_BAYER) check_mi355(mi355_frames_bayer_view_letterbox_minmax(tg, th, vg, vh, B, w, h, mm, st), "mi355_frames_bayer_view_letterbox_minmax");
+        else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_view_letterbox_minmax(tg, th, vg, vh, B, w, h, mm, st), "mi355_frames_yuv_view_letterbox_minmax");
+        else check_mi355(mi355_frames_u8_view_letterbox_minmax(tg, th, vg, vh, B, w, h, mm, st), "mi355_frames_u8_view_letterbox_minmax");
+        return;
+    }
+    if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_letterbox_minmax(tg, th, B, w, h, mm, st), "mi355_frames_planar_letterbox_minmax");
+    else if (kind == FR_PACKED) check_mi355(mi355_frames_packed_letterbox_minmax(tg, th, B, w, h, mm, st), "mi355_frames_packed_letterbox_minmax");
+    else if (kind == FR_P010) check_mi355(mi355_frames_p010_letterbox_minmax(tg, th, B, w, h, mm, st), "mi355_frames_p010_letterbox_minmax");
+    else if (kind == FR_BAYER) check_mi355(mi355_frames_bayer_letterbox_minmax(tg, th, B, w, h, mm, st), "mi355_frames_bayer_letterbox_minmax");
+    else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_letterbox_minmax(tg, th, B, w, h, mm, st), "mi355_frames_yuv_letterbox_minmax");
+    else check_mi355(mi355_frames_u8_letterbox_minmax(tg, th, B, w, h, mm, st), "mi355_frames_u8_letterbox_minmax");
+}
+
+static void fr_quantize(network *net, const float *scale_dev, const uint8_t *zp_dev)
+{
+    const int B = net->batch, kind = net->fr_kind, w = net->w, h = net->h;
+    const void *tg = net->fr_table_gpu, *th = net->fr_table_host;
+    const mi355_frame_view *vg = net->fr_views_gpu, *vh = net->fr_views;
+    uint8_t *out = net->input_uint8_gpu;
+    void *st = net->stream;
+    if (vh) {
+        if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_view_letterbox_quantize(tg, th, vg, vh, B, w, h, scale_dev, zp_dev, out, st), "mi355_frames_planar_view_letterbox_quantize");
+        else if (kind == FR_PACKED) check_mi355(mi355_frames_packed_view_letterbox_quantize(tg, th, vg, vh, B, w, h, scale_dev, zp_dev, out, st), "mi355_frames_packed_view_letterbox_quantize");
+        else if (kind == FR_P010) check_mi355(mi355_frames_p010_view_letterbox_quantize(tg, th, vg, vh, B, w, h, scale_dev, zp_dev, out, st), "mi355_frames_p010_view_letterbox_quantize");
+        else if (kind == FR_BAYER) check_mi355(mi355_frames_bayer_view_letterbox_quantize(tg, th, vg, vh, B, w, h, scale_dev, zp_dev, out, st), "mi355_frames_bayer_view_letterbox_quantize");
+        else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_view_letterbox_quantize(tg, th, vg, vh, B, w, h, scale_dev, zp_dev, out, st), "mi355_frames_yuv_view_letterbox_quantize");
+        else check_mi355(mi355_frames_u8_view_letterbox_quantize(tg, th, vg, vh, B, w, h, scale_dev, zp_dev, out, st), "mi355_frames_u8_view_letterbox_quantize");
+        return;
+    }
+    if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, st), "mi355_frames_planar_letterbox_quantize");
+    else if (kind == FR_PACKED) check_mi355(mi355_frames_packed_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, st), "mi355_frames_packed_letterbox_quantize");
+    else if (kind == FR_P010) check_mi355(mi355_frames_p010_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, st), "mi355_frames_p010_letterbox_quantize");
+    else if (kind == FR_BAYER) check_mi355(mi355_frames_bayer_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, st), "mi355_frames_bayer_letterbox_quantize");
+    else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, st), "mi355_frames_yuv_letterbox_quantize");
+    else check_mi355(mi355_frames_u8_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, st), "mi355_frames_u8_letterbox_quantize");
+}
+
 /* The common tail, the host mirror of the table filled with device pointers: table upload, min / max launch, the batch's one host
  * sync, the (scale, zero point) branch, quantiser launch, with the calls of the frames' kind. */
 static void fr_finish(network *net)
 {
-    const int B = net->batch, kind = net->fr_kind, w = net->w, h = net->h;
-    const void *tg = net->fr_table_gpu, *th = net->fr_table_host;
+    const int B = net->batch, kind = net->fr_kind;
+    const void *th = net->fr_table_host;
     if (net->input_on_device) od_alloc(net);
     check_mi355(mi355_h2d(net->fr_table_gpu, th, fr_entry_bytes[kind] * (size_t)B, net->stream), "upload frame table");
-    if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_planar_letterbox_minmax");
-    else if (kind == FR_PACKED) check_mi355(mi355_frames_packed_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_packed_letterbox_minmax");
-    else if (kind == FR_P010) check_mi355(mi355_frames_p010_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_p010_letterbox_minmax");
-    else if (kind == FR_BAYER) check_mi355(mi355_frames_bayer_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_bayer_letterbox_minmax");
-    else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_yuv_letterbox_minmax");
-    else check_mi355(mi355_frames_u8_letterbox_minmax(tg, th, B, w, h, net->fr_mm_gpu, net->stream), "mi355_frames_u8_letterbox_minmax");
+    if (net->fr_views) check_mi355(mi355_h2d(net->fr_views_gpu, net->fr_views, sizeof(mi355_frame_view) * (size_t)B, net->stream), "upload view table");
+    fr_minmax(net);
     const float *scale_dev;
     const uint8_t *zp_dev;
     if (net->input_on_device) { /* pairs and layer 0 follow on the stream: nothing comes back, nothing is waited for */
@@ -150,13 +199,7 @@ static void fr_finish(network *net)
         scale_dev = (const float *)net->fr_pair_gpu;
         zp_dev = (const uint8_t *)net->fr_pair_gpu + 4 * (size_t)B;
     }
-    uint8_t *out = net->input_uint8_gpu;
-    if (kind == FR_PLANAR) check_mi355(mi355_frames_planar_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_planar_letterbox_quantize");
-    else if (kind == FR_PACKED) check_mi355(mi355_frames_packed_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_packed_letterbox_quantize");
-    else if (kind == FR_P010) check_mi355(mi355_frames_p010_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_p010_letterbox_quantize");
-    else if (kind == FR_BAYER) check_mi355(mi355_frames_bayer_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_bayer_letterbox_quantize");
-    else if (kind == FR_YUV) check_mi355(mi355_frames_yuv_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_yuv_letterbox_quantize");
-    else check_mi355(mi355_frames_u8_letterbox_quantize(tg, th, B, w, h, scale_dev, zp_dev, out, net->stream), "mi355_frames_u8_letterbox_quantize");
+    fr_quantize(net, scale_dev, zp_dev);
 }
 
 /* Every entry point: refuse what it must before the device is touched, fill its table entries with the caller's pointers, describe the

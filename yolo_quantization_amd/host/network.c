@@ -919,6 +919,7 @@ void set_batch_network(network *net, int b)
     pi_free(net); /* the per-image bank and index arrays are sized by the batch */
     od_free(net); /* and the device-derived bank, its pair, status and min / max arrays */
     fr_free(net); /* so are the frame table, its min / max and the staging arena */
+    network_set_frame_views(net, NULL); /* views are per slot: a new batch has none */
     detb_free(net); /* and the batched box decode's buffers */
     free(net->input); free(net->input_uint8);
     net->input = calloc((size_t)net->inputs * b, sizeof(float));
@@ -1622,6 +1623,7 @@ void free_network(network *net)
     pi_free(net);
     od_free(net);
     fr_free(net);
+    network_set_frame_views(net, NULL);
     coded_free(net);
     detb_free(net);
     if (net->selfcheck_gpu) mi355_free(net->selfcheck_gpu);
