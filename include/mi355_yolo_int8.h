@@ -238,6 +238,29 @@ int mi355_conv_pool_forward_per_image(const mi355_conv_desc *desc, const mi355_t
                                       const int32_t *entry_of_image, const uint8_t *zp_in_of_image, const mi355_tensor *y,
                                       const mi355_tensor *ypool, void *stream);
 
+/* Depthwise convolution, `[convolutional] groups = c` with filters = c (MobileNet-style backbones): filter j sees channel j alone.  The
+ * reference's quantised forward loops over groups (ref: src/convolutional_layer.c:697-716) but its prep does not (src/blas.c:290-311
+ * indexes c*size*size weights per filter), so the layer is builder-specified: the reference's forward with
+ * groups = c and its prep with c read as c / groups = 1.  With K = ksize * ksize, per filter j
+ *     acc[j][p] = sum_taps (weights_uint8[j][tap] - zp_w[j]) * x_u8[j][tap(p)]          exact int32, out-of-image taps = desc.zp_in
+ * and biases_int32 / M_value / shift_value are the caller's, from src/blas.c:313-333 with that K; the epilogue (both stores, every
+ * activation, y_f32) is mi355_conv_forward's.  Channel j equals the dense one-channel, one-filter convolution, and the layer equals
+ * the dense c -> c layer whose off-diagonal weights are zp_w[j].  Both accumulation modes give the same integers (K * 255 * 255 < 2^24:
+ * the reference's fp32 accumulation is exact) and run the same kernel.
+ *   mi355_conv_dw_pack_size   bytes of the blob, a function of (c, ksize) only; 0 outside c >= 1, 1 <= ksize <= 11
+ *   mi355_conv_dw_pack        weights_uint8: [c][ksize*ksize]; position independent like mi355_conv_pack's blob, same conditions on
+ *                             M_value / shift_value
+ *   mi355_conv_dw_forward     desc.n == desc.c, size 1..11, stride >= 1, pad >= 0; x.cs % 16 == 0 (not the 3-channel image), x.data and
+ *                             blob 16-byte aligned.  The tensor's pad cells are never read.  y (nullable), acc_out, y_f32 as in
+ *                             mi355_conv_forward; channels >= n of y's cells keep their bytes.  No fused form.  Anything else returns
+ *                             MI355_EINVAL with a message that starts "conv_dw_forward:", nothing launched.
+ * New calls, no struct change: MI355_ABI_VERSION is unchanged. */
+size_t mi355_conv_dw_pack_size(int c, int ksize);
+int mi355_conv_dw_pack(int c, int ksize, const uint8_t *weights_uint8, const uint8_t *zp_w, const int32_t *biases_int32,
+                       const double *M_value, const double *shift_value, void *blob);
+int mi355_conv_dw_forward(const mi355_conv_desc *desc, const mi355_tensor *x, const void *blob, const mi355_tensor *y,
+                          int32_t *acc_out, float *y_f32, void *stream);
+
 /* Tile configuration override for benchmarking (0 = auto). */
 int mi355_conv_set_tile(int bm, int bn);
 /* Development switches.  Bits 0..8 are timing ablations of the K loop (no DMA / no s_barrier / no MFMA / ...), compiled
@@ -253,7 +276,8 @@ int mi355_debug_flags(int flags);
 /* Which kernel family served the calling thread's most recent mi355_conv_*forward call (tests assert that a shape reaches
  * the kernel it is meant to exercise): 0 none yet, 1 first layer (conv_aux.hip), 2 conv_small.hip (few-channel / 64-channel
  * conv + maxpool), 3 conv1x1.hip, 4 conv_ws3.hip, 5 conv_igemm.hip / conv_rows.hip / conv_rows16.hip, 6 fp32-accumulate emulation,
- * 7 conv_pool16.hip (16 -> 32 + maxpool with the packed epilogue table), 8 conv_small32.hip (32 -> 64 + maxpool). */
+ * 7 conv_pool16.hip (16 -> 32 + maxpool with the packed epilogue table), 8 conv_small32.hip (32 -> 64 + maxpool), 9 conv_kxk.hip (the
+ * general shapes), 10 conv_dw.hip (mi355_conv_dw_forward). */
 int mi355_last_conv_kernel(void);
 /* Geometry of the calling thread's most recent convolution kernel launch (any mi355_conv_*forward call): workgroups in the grid,
  * threads per workgroup, bytes of dynamic LDS, as the launcher chose them for the plan, batch and tile count.  Each pointer may be

@@ -4,6 +4,7 @@
 
   python tools/conv_microbench.py [--c 256 --n 256 --hw 52 --batch 32 --k 3] [--iters 20] [--tile BM BN] [--mode flat|patch]
   python tools/conv_microbench.py --net       # every conv shape of yolov3-tiny at batch 64
+  python tools/conv_microbench.py --dw [--out FILE]   # depthwise 3x3 (conv_dw.hip) against its dense twin and the HBM floor
 """
 import argparse
 import ctypes as C
@@ -68,8 +69,73 @@ def run(c, n, hw, k, batch, iters, tile=None, mode=None, check=False, nt=0):
             "frac_mfma_peak": round(ops / t / 1e12 / PEAK, 4), "gbs": round(byt / t / 1e9, 1), "tile": tile, "mode": mode, "nt": nt}
 
 
+def _time_us(launch, st, iters):
+    """device events around `iters` launches on stream st, after a warm-up"""
+    S = binding.shim()
+    e0 = C.c_void_p(); e1 = C.c_void_p()
+    S.mi355_event_create(C.byref(e0)); S.mi355_event_create(C.byref(e1))
+    for _ in range(3):
+        launch()
+    S.mi355_stream_sync(st)
+    S.mi355_event_record(e0, st)
+    for _ in range(iters):
+        launch()
+    S.mi355_event_record(e1, st)
+    ms = C.c_float()
+    binding.check(S.mi355_event_elapsed_ms(e0, e1, C.byref(ms)), "elapsed")
+    S.mi355_event_destroy(e0); S.mi355_event_destroy(e1)
+    return ms.value / iters * 1e3
+
+
+def run_dw(iters, repeats):
+    """The depthwise kernel on 3x3 stride 1 | 2, 64 x 208 x 208 and 256 x 52 x 52 at batch 32, each against two baselines: its dense
+    twin (off-diagonal weights = the filter's zero point: the same bytes out) on the dense kernels, and the HBM floor, tensor bytes in
+    + out over the bandwidth a device-to-device copy of 256 MiB reaches in this process.  The two kernels alternate, `repeats` rounds;
+    medians and ranges in microseconds."""
+    S = binding.shim()
+    st = C.c_void_p(); binding.check(S.mi355_stream_create(C.byref(st)))
+    nb = 256 << 20
+    src, dst = binding.DevBuf(nb), binding.DevBuf(nb)
+    copy_us = [_time_us(lambda: binding.check(S.mi355_d2d(dst.ptr, src.ptr, nb, st), "d2d"), st, 10) for _ in range(repeats)]
+    bw = 2.0 * nb / (np.median(copy_us) * 1e-6)  # bytes read + written per second
+    src.free(); dst.free()
+    out = {"copy_256MiB_us": copy_us, "copy_bytes_per_s": bw, "iters": iters, "cases": []}
+    for c, hw in ((64, 208), (256, 52)):
+        for stride in (1, 2):
+            rng = np.random.default_rng(c + stride)
+            B, k = 32, 3
+            x = rng.integers(0, 256, (B, c, hw, hw), dtype=np.uint8)
+            wq = rng.integers(0, 256, (c, k * k), dtype=np.uint8)
+            zp_w = rng.integers(100, 157, c, dtype=np.uint8)
+            bias = np.zeros(c, np.int32); mv = np.full(c, 0.75); sv = np.full(c, 2.0 ** -7)
+            wd = np.repeat(zp_w[:, None], c * k * k, axis=1).reshape(c, c, k * k)
+            wd[np.arange(c), np.arange(c)] = wq
+            ohw = (hw + 2 - k) // stride + 1
+            xt = binding.DevTensor.from_nchw(x, 0)
+            y, yd = binding.DevTensor(B, ohw, ohw, c, 23), binding.DevTensor(B, ohw, ohw, c, 23)
+            blob = binding.DevBuf.from_numpy(binding.conv_dw_pack(wq, zp_w, k, bias, mv, sv))
+            blobd = binding.DevBuf.from_numpy(binding.conv_pack(wd.reshape(c, -1), zp_w, c, k, bias, mv, sv))
+            d = binding.ConvDesc(c, c, k, stride, 1, binding.ACT["leaky"], 0, 0, 0, 23, 1.0)
+            dw = lambda: binding.check(S.mi355_conv_dw_forward(C.byref(d), xt.ref(), blob.ptr, y.ref(), None, None, st), "dw")
+            dense = lambda: binding.check(S.mi355_conv_forward(C.byref(d), xt.ref(), blobd.ptr, None, None, yd.ref(), None, None, st), "dense")
+            t_dw, t_dense = [], []
+            for _ in range(repeats):
+                t_dw.append(_time_us(dw, st, iters)); t_dense.append(_time_us(dense, st, iters))
+            S.mi355_stream_sync(st)
+            same = bool(np.array_equal(y.to_nchw(), yd.to_nchw()))
+            floor_us = (B * c * (hw * hw + ohw * ohw)) / bw * 1e6
+            out["cases"].append({"c": c, "hw": hw, "stride": stride, "batch": B, "dw_us": t_dw, "dense_twin_us": t_dense,
+                                 "dense_kernel": binding.last_conv_kernel(), "bytes_equal": same, "hbm_floor_us": floor_us,
+                                 "dw_over_dense": float(np.median(t_dw) / np.median(t_dense)),
+                                 "dw_over_floor": float(np.median(t_dw) / floor_us)})
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dw", action="store_true", help="depthwise 3x3 against its dense twin and the HBM floor")
+    ap.add_argument("--out", default="", help="--dw: also write the JSON here")
+    ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--c", type=int, default=256); ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--hw", type=int, default=52); ap.add_argument("--k", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32); ap.add_argument("--iters", type=int, default=20)
@@ -86,7 +152,13 @@ if __name__ == "__main__":
     binding.init(0)
     if a.dbg:
         binding.shim().mi355_debug_flags(a.dbg)
-    if a.ablate:
+    if a.dw:
+        r = run_dw(a.iters, a.repeats)
+        print(json.dumps(r))
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(r, f, indent=1)
+    elif a.ablate:
         S = binding.shim()
         for flags, name in [(0, "full"), (1, "no-dma"), (2, "no-barrier"), (4, "no-mfma"), (16, "no-cellsum"), (3, "no-dma,no-barrier"), (5, "no-dma,no-mfma"), (7, "only-lds-reads"), (15, "nothing-in-loop"), (32, "no-epilogue"), (47, "empty-kernel"), (63, "empty-kernel-no-cellsum"), (11, "only-mfma"), (9, "mfma+barrier"), (3, "lds+mfma"), (15 + 64, "epi-no-requant"), (15 + 128, "epi-no-copyout"), (15 + 64 + 128, "epi-neither")]:
             S.mi355_debug_flags(flags)

@@ -10,15 +10,17 @@ accepts: /root/reference/src/parser.c:170-204 (convolutional), 411-431 (maxpool)
   cfg/yolov3_quant.cfg             full YOLOv3 @608 (75 convs, 23 quantized [shortcut]s, 3 heads) -- BASELINE config[4]
   cfg/res_unit.cfg                 16x16 unit net for the quantized residual add and the glue layers' quant_stop tails
   cfg/s2_unit.cfg                  24x24 chain of stride-2 3x3 convolutions (the downsampling layers of full YOLOv3)
+  cfg/dw_unit.cfg                  24x24 depthwise-separable unit net (groups = channels layers between 1x1 convolutions)
 """
 import os, sys
 
 def net(w, h, c=3, batch=1):
     return f"[net]\nbatch={batch}\nsubdivisions=1\nwidth={w}\nheight={h}\nchannels={c}\n\n"
 
-def conv(filters, size, act, bn=1, stop=0, stride=1):
+def conv(filters, size, act, bn=1, stop=0, stride=1, groups=1):
     s = "[convolutional]\n"
     if bn: s += "batch_normalize=1\n"
+    if groups != 1: s += f"groups={groups}\n"   # groups = channels = filters: depthwise
     s += f"filters={filters}\nsize={size}\nstride={stride}\npad=1\nactivation={act}\nquantized=1\nquant_stop={stop}\n\n"
     return s
 
@@ -76,6 +78,20 @@ def s2_unit(act="leaky"):
     s += conv(128, 3, act, stride=2)      # 6   2x2   (odd input map)
     s += conv(30, 1, "linear", bn=0, stop=1)  # 7
     s += yolo("0,1,2")                    # 8
+    return s
+
+def dw_unit(act="leaky"):
+    # 24x24x3 input, MobileNet-style depthwise + pointwise pairs: 3x3 depthwise at stride 1 and 2, a 5x5 depthwise with a
+    # quant_stop float tail behind a maxpool, 1x1 convolutions between them
+    s = net(24, 24, c=3)
+    s += conv(16, 3, act)                             # 0   24x24
+    s += conv(16, 3, act, groups=16)                  # 1   depthwise
+    s += conv(32, 1, act)                             # 2   pointwise
+    s += conv(32, 3, "relu6", stride=2, groups=32)    # 3   12x12
+    s += maxpool(2, 2)                                # 4   6x6
+    s += conv(32, 5, act, stop=1, groups=32)          # 5   5x5 depthwise, float tail
+    s += conv(30, 1, "linear", bn=0, stop=1)          # 6
+    s += yolo("0,1,2")                                # 7
     return s
 
 def shortcut(frm=-3):
@@ -149,4 +165,5 @@ if __name__ == "__main__":
     open(os.path.join(out, "yolov3_chain_quant.cfg"), "w").write(yolov3_chain())
     open(os.path.join(out, "yolov3_quant.cfg"), "w").write(yolov3())
     open(os.path.join(out, "res_unit.cfg"), "w").write(res_unit())
+    open(os.path.join(out, "dw_unit.cfg"), "w").write(dw_unit())
     print("wrote cfgs to", os.path.normpath(out))

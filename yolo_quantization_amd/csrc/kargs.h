@@ -186,6 +186,59 @@ inline KxkGeom kxk_geom(int n, int c, int ksize)
     return g;
 }
 
+// conv_dw.hip: the depthwise convolution (groups == c == n).  Its blob (mi355_conv_dw_pack) is a header and per-channel arrays padded to
+// whole 64-channel chunks, offsets a function of (c, ksize) only:
+//     wd      int16 [c64 / 64][ksize * ksize][64]   w_u8 - zp_w of (chunk, tap, channel in the chunk); 0 for channels >= c
+//     bias    int32 [c64]      mval, sval, mprime   f64 [c64]   (mprime = M_value * shift_value, common.h requant_q_exact)
+#define MI355_DW_MAGIC 0x4D494457u /* "MIDW" */
+struct DwBlobHeader {
+    uint32_t magic;
+    int32_t c, ksize, c64;
+    int32_t pow2;        // 1: every shift_value is an exact power of two (ConvBlobHeader.pow2)
+    int32_t pad_[3];
+    uint64_t off_wd, off_bias, off_mval, off_sval, off_mprime, total;
+};
+inline bool dw_blob_layout(int c, int ksize, DwBlobHeader *h)
+{
+    if (c < 1 || ksize < 1 || ksize > 11) return false;
+    *h = DwBlobHeader{};
+    h->magic = MI355_DW_MAGIC; h->c = c; h->ksize = ksize; h->c64 = (c + 63) / 64 * 64;
+    uint64_t off = (sizeof(DwBlobHeader) + 15) & ~(uint64_t)15;
+    h->off_wd = off;     off += (uint64_t)h->c64 * ksize * ksize * 2;
+    off = (off + 15) & ~(uint64_t)15;
+    h->off_bias = off;   off += (uint64_t)h->c64 * 4;
+    h->off_mval = off;   off += (uint64_t)h->c64 * 8;
+    h->off_sval = off;   off += (uint64_t)h->c64 * 8;
+    h->off_mprime = off; off += (uint64_t)h->c64 * 8;
+    h->total = off;
+    return true;
+}
+struct DwArgs {
+    const uint8_t *x;        // input tensor, biased PHWC (cs % 16 == 0, data 16-byte aligned)
+    int in_cs, in_lead;
+    int B, H, W, c;          // input map; channels == filters
+    int ksize, stride, pad, OH, OW;
+    const int16_t *wd;
+    const int32_t *bias;
+    const double *mval, *sval, *mprime;
+    const DwBlobHeader *hdr; // device copy (pow2 flag)
+    uint8_t *y;
+    int out_cs, out_lead;
+    int32_t *acc_out;
+    float *y_f32;
+    int zp_in, zp_act, act, store_mode;
+    float s_act;
+    int plan;
+    // tile geometry (set by the launcher)
+    int ry_sh;               // the 16 pixel runs of a workgroup are 2^ry_sh rows by 16 >> ry_sh runs
+    int tiles_x, tiles_y, nchunks;
+    int ph, pw, pitch;       // staged patch: rows, cells per row, LDS cells between rows (odd)
+    int pieces16;            // 16-byte pieces of a cell that hold channels: ceil(c / 16)
+    FastDiv fd_pw;
+};
+constexpr int DW_RUN = 8;    // output pixels along x per lane; the tile is 2^ry_sh rows by (16 >> ry_sh) * DW_RUN columns
+int conv_dw_launch(DwArgs &a, hipStream_t st);  // MI355_EINVAL when no tile fits LDS (nothing launched)
+
 int yolo_detections_launch(const float *out, int B, int n, int classes, int h, int w, const float *biases, const int *mask,
                            int netw, int neth, int imw, int imh, float thresh, int relative, float *recs, int max_recs,
                            int *counts, hipStream_t st);

@@ -942,6 +942,84 @@ int mi355_conv_forward(const mi355_conv_desc *d, const mi355_tensor *x, const vo
     return conv_forward_impl(d, x, blob, w_u8, zp_w, y, nullptr, acc_out, y_f32, stream);
 }
 
+// ------------------------------------------------------------------------------------- depthwise convolution (conv_dw.hip)
+size_t mi355_conv_dw_pack_size(int c, int ksize)
+{
+    DwBlobHeader h;
+    return dw_blob_layout(c, ksize, &h) ? (size_t)h.total : 0;
+}
+
+int mi355_conv_dw_pack(int c, int ksize, const uint8_t *wq, const uint8_t *zp_w, const int32_t *biases_int32, const double *M_value,
+                       const double *shift_value, void *blob)
+{
+    DwBlobHeader h;
+    if (!dw_blob_layout(c, ksize, &h)) return einval("conv_dw_pack: need c >= 1 and 1 <= ksize <= 11");
+    if (!wq || !zp_w || !biases_int32 || !M_value || !shift_value || !blob) return einval("conv_dw_pack: null");
+    h.pow2 = 1;
+    for (int j = 0; j < c; ++j) {
+        if (!(M_value[j] > 0.0 && M_value[j] < 1.0) || !(shift_value[j] > 0.0 && shift_value[j] <= 1.0))
+            return einval("conv_dw_pack: need 0 < M_value < 1 and 0 < shift_value <= 1 (ref asserts 0<M<1, src/blas.c:391-392)");
+        int e = 0;
+        if (frexp(shift_value[j], &e) != 0.5 || e > 1 || e < -30) h.pow2 = 0;  // as mi355_conv_pack: 2^-s, 0 <= s <= 31
+    }
+    char *base = (char *)blob;
+    memset(base, 0, (size_t)h.total);
+    memcpy(base, &h, sizeof(h));
+    const int kk = ksize * ksize;
+    int16_t *wd = (int16_t *)(base + h.off_wd);
+    for (int j = 0; j < c; ++j) {
+        for (int t = 0; t < kk; ++t) wd[((size_t)(j / 64) * kk + t) * 64 + j % 64] = (int16_t)((int)wq[(size_t)j * kk + t] - (int)zp_w[j]);
+        ((int32_t *)(base + h.off_bias))[j] = biases_int32[j];
+        ((double *)(base + h.off_mval))[j] = M_value[j];
+        ((double *)(base + h.off_sval))[j] = shift_value[j];
+        ((double *)(base + h.off_mprime))[j] = M_value[j] * shift_value[j];
+    }
+    return MI355_OK;
+}
+
+int mi355_conv_dw_forward(const mi355_conv_desc *d, const mi355_tensor *x, const void *blob, const mi355_tensor *y, int32_t *acc_out,
+                          float *y_f32, void *stream)
+{
+    if (!d || !x || !x->data || !blob) return einval("conv_dw_forward: null");
+    if (d->n != d->c) return einval("conv_dw_forward: depthwise means desc.n == desc.c (channel multipliers are not served)");
+    if (d->ksize < 1 || d->ksize > 11) return einval("conv_dw_forward: size must be 1..11");
+    if (d->stride < 1 || d->pad < 0) return einval("conv_dw_forward: need stride >= 1 and pad >= 0");
+    if (x->cs % 16 || x->cs < (d->c + 15) / 16 * 16)
+        return einval("conv_dw_forward: x.cs must be a multiple of 16 that holds the channels (the 3-channel image's 4-byte cells are not served)");
+    if (x->C != d->c) return einval("conv_dw_forward: x.C != desc.c");
+    const long OHl = ((long)x->H + 2L * d->pad - d->ksize) / d->stride + 1, OWl = ((long)x->W + 2L * d->pad - d->ksize) / d->stride + 1;
+    if (x->H + 2L * d->pad < d->ksize || x->W + 2L * d->pad < d->ksize || OHl < 1 || OWl < 1)
+        return einval("conv_dw_forward: the padded map is smaller than the kernel");
+    if (y && (y->C != d->n || y->B != x->B || y->H != OHl || y->W != OWl || !y->data || y->cs % 16 || y->cs < d->n))
+        return einval("conv_dw_forward: y shape");
+    if (((uintptr_t)x->data & 15) || ((uintptr_t)blob & 15) || (y && ((uintptr_t)y->data & 3)))
+        return einval("conv_dw_forward: x.data and blob must be aligned to 16 bytes, y.data to 4");
+    DwBlobHeader h;
+    dw_blob_layout(d->c, d->ksize, &h);
+    const char *base = (const char *)blob;
+    DwArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = (const uint8_t *)x->data; a.in_cs = x->cs; a.in_lead = x->lead;
+    a.B = x->B; a.H = x->H; a.W = x->W; a.c = d->c;
+    a.ksize = d->ksize; a.stride = d->stride; a.pad = d->pad; a.OH = (int)OHl; a.OW = (int)OWl;
+    a.wd = (const int16_t *)(base + h.off_wd); a.bias = (const int32_t *)(base + h.off_bias);
+    a.mval = (const double *)(base + h.off_mval); a.sval = (const double *)(base + h.off_sval);
+    a.mprime = (const double *)(base + h.off_mprime);
+    a.hdr = (const DwBlobHeader *)base;
+    a.y = y ? (uint8_t *)y->data : nullptr; a.out_cs = y ? y->cs : 0; a.out_lead = y ? y->lead : 0;
+    a.acc_out = acc_out; a.y_f32 = y_f32;
+    a.zp_in = d->zp_in; a.zp_act = d->zp_act; a.act = d->activation; a.store_mode = d->store_mode; a.s_act = d->s_act;
+    a.plan = d->plan;
+    // desc.accum_mode: MI355_ACC_REF_F32 needs no kernel of its own here.  The reference accumulates a filter's K = size * size products in
+    // fp32, one by one (src/gemm.c:279-299): every product is an integer below 2^16, every partial sum of either pass is bounded by
+    // K * 255 * 255 <= 121 * 65025 = 7 868 025 < 2^24, so every fp32 addition is exact and both modes define the same integers.
+    const int rc = conv_dw_launch(a, (hipStream_t)stream);
+    if (rc == MI355_EINVAL) return einval("conv_dw_forward: no tile of the depthwise kernel fits this stride and size in LDS");
+    if (rc != MI355_OK) return hip_fail(hipGetLastError(), "conv_dw launch");
+    g_last_kernel = 10;
+    return rc;
+}
+
 int mi355_conv_yolo_forward(const mi355_conv_desc *d, const mi355_tensor *x, const void *blob, const mi355_tensor *y,
                             float *y_f32, float *yolo_out, int classes, void *stream)
 {

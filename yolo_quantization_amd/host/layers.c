@@ -41,6 +41,7 @@ static int conv_plain(const layer *l, const network *net, const mi355_conv_desc 
     const uint8_t *w = full ? l->weights_uint8_gpu : NULL, *zp_w = full ? l->weight_zero_point_gpu : NULL;
     int32_t *acc = full && net->dump_int32 ? l->output_int32_gpu : NULL;
     float *f32 = full && l->quant_stop_flag ? l->output_gpu : NULL;
+    if (l->groups > 1) return mi355_conv_dw_forward(d, net->cur_t, l->blob_gpu, &l->out_t, acc, f32, net->stream); /* depthwise: one kernel for both accumulation modes */
     if (!pi) return mi355_conv_forward(d, net->cur_t, l->blob_gpu, w, zp_w, &l->out_t, acc, f32, net->stream);
     const void *idx = bank_index(net);
     return mi355_conv_forward_per_image(d, net->cur_t, bank_of(net), net->pi_entry_bytes, (const int32_t *)idx,

@@ -141,7 +141,7 @@ static void prep_conv_layer(network *net, int i)
         l->input_data_uint8_scales[0] = net->layers[i - 1].activ_data_uint8_scales[0];
         l->input_data_uint8_zero_point[0] = net->layers[i - 1].activ_data_uint8_zero_point[0];
     }
-    const int K = l->c * l->size * l->size; /* ref :306 */
+    const int K = l->c / l->groups * l->size * l->size; /* ref :306, with l->c read as l->c / l->groups for the depthwise layer */
     const float s_in = l->input_data_uint8_scales[0];
     const int zp_in = l->input_data_uint8_zero_point[0];
     if (s_in == 0 || l->activ_data_uint8_scales[0] == 0) error("zero quantisation scale (ref: src/blas.c:312,332 asserts)");
@@ -159,6 +159,12 @@ static void prep_conv_layer(network *net, int i)
         float t = b / (s_in * l->weight_data_uint8_scales[ii]) + (float)l->weights_sum_int[ii]; /* ref :333 */
         l->biases_int32[ii] = (int32_t)t;
     }
+}
+
+/* bytes of a conv layer's packed blob: a function of the cfg alone */
+static size_t conv_blob_size(const layer *l)
+{
+    return l->groups > 1 ? mi355_conv_dw_pack_size(l->c, l->size) : mi355_conv_pack_size(l->n, l->c, l->size);
 }
 
 static void alloc_layer_device(network *net, int i)
@@ -335,7 +341,7 @@ void quantization_prep_host(network *net, float in_scale, uint8_t in_zp)
             fprintf(stderr, "layer %d: a 3-filter convolution can only feed another convolution\n", i);
             error("unsupported layer after a 3-filter convolution");
         }
-        size_t sz = mi355_conv_pack_size(l->n, l->c, l->size);
+        size_t sz = conv_blob_size(l);
         if (!sz) {
             fprintf(stderr, "layer %d: conv %dx%d, %d->%d channels is not supported by the gfx950 kernels "
                             "(sizes above 11 are refused)\n", i, l->size, l->size, l->c, l->n);
@@ -344,6 +350,11 @@ void quantization_prep_host(network *net, float in_scale, uint8_t in_zp)
         free(l->blob_host);
         l->blob_host = malloc(sz);
         l->blob_bytes = sz;
+        if (l->groups > 1) { /* depthwise: its own blob, no epilogue table (the planner offers it to no fusion) */
+            check_mi355(mi355_conv_dw_pack(l->c, l->size, l->weights_uint8, l->weight_data_uint8_zero_point, l->biases_int32, l->M_value,
+                                           l->M0_right_shift_value, l->blob_host), "mi355_conv_dw_pack");
+            continue;
+        }
         check_mi355(mi355_conv_pack(l->n, l->c, l->size, l->weights_uint8, l->weight_data_uint8_zero_point,
                                     l->biases_int32, l->M_value, l->M0_right_shift_value, l->blob_host),
                     "mi355_conv_pack");
@@ -366,7 +377,7 @@ static void plan_fusion(network *net)
     for (int i = 0; i < net->n; ++i) net->layers[i].fuse_next = net->layers[i].fuse_pool_keep = 0;
     for (int i = 0; i + 1 < net->n; ++i) {
         layer *c = &net->layers[i], *p = &net->layers[i + 1];
-        if (c->type != CONVOLUTIONAL) continue;
+        if (c->type != CONVOLUTIONAL || c->groups > 1) continue; /* a depthwise layer runs unfused: the layer after it on its own */
         switch (p->type) {
         case SHORTCUT:
             if (c->stride == 1 && !c->quant_stop_flag && !p->quant_stop_flag && c->c % 16 == 0 && p->index != i && !output_read_elsewhere(net, i))
@@ -1337,7 +1348,7 @@ size_t network_packed_size(network *net) /* a function of the cfg alone: every r
     for (int i = 0; i < net->n; ++i) {
         layer *l = &net->layers[i];
         if (l->type != CONVOLUTIONAL) continue;
-        const size_t b = mi355_conv_pack_size(l->n, l->c, l->size);
+        const size_t b = conv_blob_size(l);
         if (!b) error("network_packed_size: unsupported convolution shape");
         sz += (b + 15) & ~(size_t)15;
     }
@@ -1402,7 +1413,7 @@ void network_import_packed_host(network *net, const void *buf, size_t bytes)
         if (l->activ_data_uint8_scales) { l->activ_data_uint8_scales[0] = r.s_act; l->activ_data_uint8_zero_point[0] = (uint8_t)r.zp_act; }
         if (l->type == CONVOLUTIONAL) {
             l->input_data_uint8_scales[0] = r.s_in; l->input_data_uint8_zero_point[0] = (uint8_t)r.zp_in;
-            if (r.blob_bytes != mi355_conv_pack_size(l->n, l->c, l->size)) error("network_import_packed: blob size mismatch");
+            if (r.blob_bytes != conv_blob_size(l)) error("network_import_packed: blob size mismatch");
             free(l->blob_host);
             l->blob_host = malloc(r.blob_bytes);
             l->blob_bytes = r.blob_bytes;

@@ -130,7 +130,14 @@ static layer parse_convolutional(section *o, size_params p, int count)
     int bn = option_find_int(o, "batch_normalize", 0);
     int q = option_find_int(o, "quantized", 0);
     int qs = option_find_int(o, "quant_stop", 0);
-    if (groups != 1) error("grouped convolution is outside the INT8 path of the reference (prep ignores groups, src/blas.c:306)");
+    /* groups == c == n is the depthwise layer (conv_dw.hip); the reference's prep ignores groups (src/blas.c:306), so no
+     * other grouping has integer semantics to follow */
+    if (groups < 1) error("[convolutional] groups must be >= 1");
+    if (groups != 1) {
+        if (groups != p.c) error("[convolutional] 1 < groups < channels: general grouped convolution is not built, only depthwise (groups = channels)");
+        if (n != p.c) error("[convolutional] groups = channels with filters != channels: depthwise channel multipliers are not built");
+        if (p.index == 0) error("[convolutional] a depthwise first layer on the image is not built (its 4-byte cells are not served)");
+    }
     layer l = make_convolutional_layer(p.batch, p.h, p.w, p.c, n, groups, size, stride, padding, act, bn, qs,
                                        p.close_quantization, q, count);
     l.fisrt_time_train_fag = option_find_int(o, "first_time", 0);
@@ -329,7 +336,7 @@ static void load_convolutional_weights(layer l, FILE *fp) /* ref :1124-1159 */
     xread(l.activ_data_uint8_zero_point, 1, 1, fp, "act zp");
     xread(l.weight_data_uint8_scales, sizeof(float), l.n, fp, "w scales");
     xread(l.weight_data_uint8_zero_point, 1, l.n, fp, "w zp");
-    xread(l.weights_uint8, 1, (size_t)l.c * l.n * l.size * l.size, fp, "weights_uint8");
+    xread(l.weights_uint8, 1, num, fp, "weights_uint8");
     /* float weights follow; the integer path never reads them (only BN-folds them in place upstream) */
     if (fseek(fp, (long)(num * sizeof(float)), SEEK_CUR)) error("load_weights: seek");
 }

@@ -67,6 +67,7 @@ class LayerShape:
     quantized: int = 0
     quant_stop: int = 0
     inputs: list[int] = field(default_factory=list)  # route sources (absolute indices)
+    groups: int = 1  # conv: groups == c == n is the depthwise layer, c / groups weights per filter per tap
 
 
 def layer_shapes(sections: list[dict]) -> tuple[dict, list[LayerShape]]:
@@ -87,7 +88,7 @@ def layer_shapes(sections: list[dict]) -> tuple[dict, list[LayerShape]]:
             oh = (h + 2 * padding - size) // stride + 1
             ow = (w + 2 * padding - size) // stride + 1
             L = LayerShape("conv", c, h, w, n, oh, ow, n, size, stride, padding, s.get("activation", "logistic"),
-                           int(s.get("batch_normalize", 0)), q, qs)
+                           int(s.get("batch_normalize", 0)), q, qs, groups=int(s.get("groups", 1)))
         elif t == "[maxpool]":
             stride = int(s.get("stride", 1)); size = int(s.get("size", stride))
             padding = int(s.get("padding", size - 1))
@@ -142,7 +143,7 @@ def _glue_record(a, i: int, own_zp: bool):
 
 
 def synth_weights(cfg_path: str, out_path: str, seed: int = 1234, act_gain: float = 1.0, small_m_channels: int = 0,
-                  glue_own_zp: bool = False) -> dict:
+                  glue_own_zp: bool = False, dense_twin: bool = False) -> dict:
     """Write a seeded synthetic `.weights` file for `cfg_path`. Returns {'sha256': ..., 'layers': [...]}.
     act_gain > 1 divides every activation scale by that factor so that requantised values overflow 0..255 and
     exercise the reference's wrap-on-store behaviour (src/convolutional_layer.c:737-749).
@@ -151,7 +152,10 @@ def synth_weights(cfg_path: str, out_path: str, seed: int = 1234, act_gain: floa
     integer requantisation accepts (common.h intrq_make): the 'unfriendly model' of bench.py --small-m-channels.
     glue_own_zp (off: every byte of the file as before) gives the records of [maxpool], multi-input [route] and quantized [upsample] layers
     a zero point that DIFFERS from their input's: the layer after such a glue layer takes its input zero point -- its pad value -- from
-    that record (src/blas.c:301-305), so a host that inherited it from the wrong layer no longer passes."""
+    that record (src/blas.c:301-305), so a host that inherited it from the wrong layer no longer passes.
+    dense_twin writes the file for the same cfg with its `groups=` keys removed: every depthwise layer as the dense c -> c layer whose
+    weight of filter j on channel i is the depthwise one for i == j and the filter's zero point elsewhere (same accumulators
+    and prep constants), every other byte as without it."""
     rng = np.random.default_rng(seed)
     _, layers = layer_shapes(read_cfg(cfg_path))
     act_q: list[tuple[np.float32, int]] = []
@@ -160,7 +164,7 @@ def synth_weights(cfg_path: str, out_path: str, seed: int = 1234, act_gain: floa
     info = []
     for i, L in enumerate(layers):
         if L.type == "conv":
-            K = L.c * L.size * L.size
+            K = L.c // L.groups * L.size * L.size
             w = (rng.standard_normal((L.n, K)) * np.sqrt(2.0 / K)).astype(np.float32)
             if small_m_channels > 0:
                 w[:min(small_m_channels, L.n)] *= np.float32(1.0 / 64.0)
@@ -179,6 +183,11 @@ def synth_weights(cfg_path: str, out_path: str, seed: int = 1234, act_gain: floa
             a_s = np.float32(a_s / np.float32(act_gain))
             in_s, in_zp = act_q[i - 1] if i > 0 else (np.float32(1.0 / 255.0), 0)
             blob += struct.pack("<fBfB", float(in_s), int(in_zp), float(a_s), int(a_zp))
+            if dense_twin and L.groups > 1:
+                kk = L.size * L.size
+                qd = np.repeat(wzp[:, None], L.c * kk, axis=1).reshape(L.n, L.c, kk)
+                qd[np.arange(L.n), np.arange(L.n)] = q
+                q, w = qd.reshape(L.n, -1), np.zeros((L.n, L.c * kk), np.float32)
             blob += wscale.tobytes() + wzp.tobytes() + q.tobytes() + w.tobytes()
             act_q.append((a_s, a_zp))
             info.append({"i": i, "type": "conv", "K": K, "n": L.n})
