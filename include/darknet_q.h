@@ -111,6 +111,10 @@ struct layer {
                            also does the quantized residual add of the [shortcut].  YOLO: this quant_stop head conv also writes the yolo
                            layer's activations */
     int fuse_pool_keep; /* FUSE_POOL which also stores the conv's own tensor: a route reads it */
+    int spp;            /* [maxpool]: 0, or its part in a fused SPP group (plan_fusion): 1 = the leader, whose turn runs mi355_spp_forward
+                           for every pool of the group, 2 = a member, which does nothing when its turn comes.  A refusal of the
+                           launcher clears the whole group */
+    int spp_n, spp_pool[3]; /* leader: pools of the group and their layer indices, itself first */
     int conv_kernel;    /* kernel family that served this conv's last forward (mi355_last_conv_kernel) */
     int prepared;
 };
@@ -619,6 +623,9 @@ void network_load_packed(network *net, char *filename);
  * out_view, byte offset of the layer's tensor inside the buffer that owns it, fuse_next_pool, fuse_next_upsample, fuse_next_shortcut,
  * fuse_next_yolo, fuse_pool_keep.  Returns 0, or -1 for a bad index.  Read-only: tests and tools look at the plan through it. */
 int dnq_layer_plan(network *net, int i, int *out);
+
+/* layer i's part in a fused SPP group as the run mode honours it (none under dump_int32): 0 none, 1 leader, 2 member */
+int dnq_layer_spp(network *net, int i);
 
 /* misc */
 void error(const char *s);

@@ -295,6 +295,15 @@ int mi355_last_conv_launch(int *grid, int *threads, int *lds_bytes);
  *     "maxpool: need size >= 1, stride >= 1 and pad >= 0"      checked before the division above
  *     "maxpool: output dims"                                   y.H / y.W are not the sizes above, or those are below 1 */
 int mi355_maxpool_forward(const mi355_tensor *x, const mi355_tensor *y, int size, int stride, int pad, void *stream);
+/* The SPP block's pools in one launch (spp.hip): n = 1..3 stride-1 "same" max pools of one tensor, each into its
+ * own tensor.  ys[i] receives exactly the bytes mi355_maxpool_forward(x, ys[i], sizes[i], 1, sizes[i] - 1, stream) stores, whole 16-byte
+ * groups of in-image cells only; x's pad cells are never read.  sizes are odd and strictly increasing, 3 <= sizes[0], sizes[n - 1] <= 13.
+ * Every ys[i] has x's B, H, W and C; x.cs and ys[i].cs are multiples of 16 that hold the channels, every data pointer is 16-byte
+ * aligned.  The outputs may be channel windows of the buffer that holds x (the concat of the block), but they must not overlap x's
+ * bytes or one another: workgroups read x while others store (an output whose window starts inside x's or another output's is refused,
+ * other overlaps are the caller's to avoid).  Anything else returns MI355_EINVAL with a message that starts "spp:", nothing launched.
+ * A new call, no struct change: MI355_ABI_VERSION is unchanged. */
+int mi355_spp_forward(const mi355_tensor *x, int n, const int *sizes, const mi355_tensor *const *ys, void *stream);
 /* forward_upsample_layer_quant (ref: src/upsample_layer.c:96-113, src/blas.c:781-803), nearest x stride */
 int mi355_upsample_forward(const mi355_tensor *x, const mi355_tensor *y, int stride, void *stream);
 /* forward_route_layer_quant (ref: src/route_layer.c:107-130): channel concat of n inputs, no rescale */

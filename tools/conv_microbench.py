@@ -5,6 +5,7 @@
   python tools/conv_microbench.py [--c 256 --n 256 --hw 52 --batch 32 --k 3] [--iters 20] [--tile BM BN] [--mode flat|patch]
   python tools/conv_microbench.py --net       # every conv shape of yolov3-tiny at batch 64
   python tools/conv_microbench.py --dw [--out FILE]   # depthwise 3x3 (conv_dw.hip) against its dense twin and the HBM floor
+  python tools/conv_microbench.py --spp [--out FILE]  # the fused SPP pools (spp.hip) against the three plain pools and the HBM floor
 """
 import argparse
 import ctypes as C
@@ -131,10 +132,57 @@ def run_dw(iters, repeats):
     return out
 
 
+def run_spp(iters, repeats):
+    """mi355_spp_forward (5, 9, 13) on 512 x 13 x 13 and 512 x 19 x 19 at batch 32 and 64 against the three mi355_maxpool_forward launches
+    it replaces, both writing into the windows of one concat buffer (p13, p9, p5, x), and against the HBM floor: x in plus three outputs
+    out over the bandwidth a device-to-device copy of 256 MiB reaches in this process.  The two alternate, `repeats` rounds; medians and
+    ranges in microseconds.  The bytes of the two are compared in the run."""
+    S = binding.shim()
+    st = C.c_void_p(); binding.check(S.mi355_stream_create(C.byref(st)))
+    nb = 256 << 20
+    src, dst = binding.DevBuf(nb), binding.DevBuf(nb)
+    copy_us = [_time_us(lambda: binding.check(S.mi355_d2d(dst.ptr, src.ptr, nb, st), "d2d"), st, 10) for _ in range(repeats)]
+    bw = 2.0 * nb / (np.median(copy_us) * 1e-6)  # bytes read + written per second
+    src.free(); dst.free()
+    out = {"copy_256MiB_us": copy_us, "copy_bytes_per_s": bw, "iters": iters, "sizes": [5, 9, 13], "cases": []}
+    sizes, c = (5, 9, 13), 512
+    for hw in (13, 19):
+        for B in (32, 64):
+            rng = np.random.default_rng(hw + B)
+            full = np.zeros((B, 4 * c, hw, hw), np.uint8)
+            full[:, 3 * c:] = rng.integers(0, 256, (B, c, hw, hw), dtype=np.uint8)
+            cats = []
+            for _ in range(2):  # one concat buffer for the fused launch, one for the plain ones: the same x in both
+                cat = binding.DevTensor.from_nchw(full, 0)
+                win = []
+                for k in range(4):
+                    t = binding.Tensor.from_buffer_copy(cat.t)
+                    t.data, t.C = cat.buf.ptr.value + k * c, c
+                    win.append(t)
+                cats.append((cat, win[3], win[2::-1]))  # x is the last window, the pools in front of it, largest first
+            (fcat, fx, fys), (pcat, px, pys) = cats
+            fused = lambda: binding.check(binding.spp_forward(fx, sizes, fys, st), "spp")
+
+            def plain():
+                for k, y in zip(sizes, pys):
+                    binding.check(S.mi355_maxpool_forward(px, y, k, 1, k - 1, st), "maxpool")
+            t_f, t_p = [], []
+            for _ in range(repeats):
+                t_f.append(_time_us(fused, st, iters)); t_p.append(_time_us(plain, st, iters))
+            S.mi355_stream_sync(st)
+            same = bool(np.array_equal(fcat.to_nchw(), pcat.to_nchw()))
+            floor_us = 4.0 * B * c * hw * hw / bw * 1e6
+            out["cases"].append({"c": c, "hw": hw, "batch": B, "spp_us": t_f, "three_maxpools_us": t_p, "bytes_equal": same,
+                                 "hbm_floor_us": floor_us, "spp_over_plain": float(np.median(t_f) / np.median(t_p)),
+                                 "spp_over_floor": float(np.median(t_f) / floor_us)})
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--dw", action="store_true", help="depthwise 3x3 against its dense twin and the HBM floor")
-    ap.add_argument("--out", default="", help="--dw: also write the JSON here")
+    ap.add_argument("--spp", action="store_true", help="the fused SPP pools against the three plain pools and the HBM floor")
+    ap.add_argument("--out", default="", help="--dw, --spp: also write the JSON here")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--c", type=int, default=256); ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--hw", type=int, default=52); ap.add_argument("--k", type=int, default=3)
@@ -152,8 +200,8 @@ if __name__ == "__main__":
     binding.init(0)
     if a.dbg:
         binding.shim().mi355_debug_flags(a.dbg)
-    if a.dw:
-        r = run_dw(a.iters, a.repeats)
+    if a.dw or a.spp:
+        r = run_spp(a.iters, a.repeats) if a.spp else run_dw(a.iters, a.repeats)
         print(json.dumps(r))
         if a.out:
             with open(a.out, "w") as f:

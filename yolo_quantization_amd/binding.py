@@ -263,6 +263,8 @@ def shim():
             L.mi355_conv_dw_pack_size.restype = C.c_size_t
             L.mi355_conv_dw_pack.argtypes = [ci, ci, vp, vp, vp, vp, vp, vp]
             L.mi355_conv_dw_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.POINTER(Tensor), vp, vp, vp]
+        if hasattr(L, "mi355_spp_forward"):  # (MI355_LIB_DIR may name an older build)
+            L.mi355_spp_forward.argtypes = [C.POINTER(Tensor), ci, vp, vp, vp]
         L.mi355_last_conv_kernel.argtypes = []
         L.mi355_last_conv_kernel.restype = ci
         if hasattr(L, "mi355_last_conv_launch"):  # (absent from older A/B builds under build_ab/)
@@ -522,6 +524,15 @@ def conv_dw_forward(x: DevTensor, wq, zp_w, ksize, biases_int32, M_value, shift_
     return out
 
 
+def spp_forward(x, sizes, ys, stream=None):
+    """mi355_spp_forward: the stride-1 "same" max pools `sizes` of x (a DevTensor or a Tensor view) into ys, one launch; returns the
+    shim's code (0, or MI355_EINVAL with mi355_last_error() starting "spp:").  A None stands for a null pointer."""
+    ref = lambda t: None if t is None else C.addressof(t.t if isinstance(t, DevTensor) else t)
+    sz = (C.c_int * max(len(sizes), 1))(*sizes)
+    yp = (C.c_void_p * max(len(ys), 1))(*[ref(y) for y in ys])
+    return int(shim().mi355_spp_forward(C.cast(ref(x), C.POINTER(Tensor)), len(sizes), sz, yp, stream))
+
+
 FUSED = ("pool2", "pool1", "upsample", "yolo", "shortcut")
 
 
@@ -683,6 +694,9 @@ def host():
         L.network_load_packed.argtypes = [vp, C.c_char_p]
         L.dnq_layer_conv_kernel.argtypes = [vp, ci]
         L.dnq_layer_conv_kernel.restype = ci
+        if hasattr(L, "dnq_layer_spp"):
+            L.dnq_layer_spp.argtypes = [vp, ci]
+            L.dnq_layer_spp.restype = ci
         L.set_input_quantization_per_image.argtypes = [vp, ci]
         L.set_input_quantization_per_image.restype = ci
         L.network_input_quantization.argtypes = [vp, vp, vp]
@@ -1825,6 +1839,10 @@ class Net:
     def conv_kernel(self, i):
         """mi355_last_conv_kernel code of the kernel that served conv layer i in the last forward pass (5 = conv_rows / conv_igemm)"""
         return int(self.H.dnq_layer_conv_kernel(self.h, i))
+
+    def spp(self, i):
+        """dnq_layer_spp: 0, 1 for the leading [maxpool] of a fused SPP group (it runs mi355_spp_forward for the group), 2 for a member"""
+        return int(self.H.dnq_layer_spp(self.h, i))
 
     def is_fused(self, i):
         """conv i runs fused with the layer after it and its own uint8 tensor is not stored."""

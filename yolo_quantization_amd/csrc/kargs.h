@@ -239,6 +239,28 @@ struct DwArgs {
 constexpr int DW_RUN = 8;    // output pixels along x per lane; the tile is 2^ry_sh rows by (16 >> ry_sh) * DW_RUN columns
 int conv_dw_launch(DwArgs &a, hipStream_t st);  // MI355_EINVAL when no tile fits LDS (nothing launched)
 
+// spp.hip: up to three stride-1 "same" max pools of one tensor in one launch (the SPP block of yolov3-spp / yolov4), computed as a
+// cascade: level i is the box max of size d[i] of level i - 1, level 0 being x, so that level i is x's pool of size sizes[i].
+constexpr int SPP_MAX = 3;       // levels
+constexpr int SPP_RUN = 8;       // outputs along the pass direction per lane; also the smallest tile side
+constexpr int SPP_TILE = 20;     // largest tile side: (20 + 12) rows of 33 cells of 32 bytes, twice, is 67 584 bytes of LDS
+struct SppArgs {
+    const uint8_t *x;            // input tensor, biased PHWC (cs % 16 == 0, data 16-byte aligned)
+    int in_cs, in_lead;
+    int B, H, W;
+    int pieces16;                // 16-byte pieces of a cell that hold channels: ceil(C / 16); read and stored whole, as maxpool_u8_kernel does
+    int n;                       // levels, 1..SPP_MAX
+    int d[SPP_MAX];              // window of level i over level i - 1: sizes[i] - sizes[i - 1] + 1 (sizes[0] for level 0)
+    uint8_t *y[SPP_MAX];         // each level's own tensor (x's B, H, W; data 16-byte aligned)
+    int out_cs[SPP_MAX], out_lead[SPP_MAX];
+    // tile geometry (set by the launcher)
+    int R;                       // halo of the staged patch: (sizes[n - 1] - 1) / 2
+    int TH, TW, tiles_x, tiles_y, nchunks;
+    int ph, pw, pitch;           // staged patch: rows, cells per row, LDS cells between rows (odd)
+    FastDiv fd_pw, fd_tw;
+};
+int spp_launch(SppArgs &a, hipStream_t st);
+
 int yolo_detections_launch(const float *out, int B, int n, int classes, int h, int w, const float *biases, const int *mask,
                            int netw, int neth, int imw, int imh, float thresh, int relative, float *recs, int max_recs,
                            int *counts, hipStream_t st);

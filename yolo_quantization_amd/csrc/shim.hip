@@ -1084,6 +1084,40 @@ int mi355_maxpool_forward(const mi355_tensor *x, const mi355_tensor *y, int size
     return maxpool_launch(a, (hipStream_t)stream);
 }
 
+int mi355_spp_forward(const mi355_tensor *x, int n, const int *sizes, const mi355_tensor *const *ys, void *stream)
+{
+    if (!x || !x->data || !sizes || !ys) return einval("spp: null");
+    if (n < 1 || n > SPP_MAX) return einval("spp: n must be 1..3");
+    const int cp = (x->C + 15) / 16 * 16;  // bytes of a cell that are read and stored: whole 16-byte groups, as the plain kernel
+    if (x->C < 1 || x->cs % 16 || x->cs < cp) return einval("spp: x.cs must be a multiple of 16 that holds the channels");
+    if ((uintptr_t)x->data & 15) return einval("spp: x.data must be aligned to 16 bytes");
+    SppArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < n; ++i) {
+        const int prev = i ? sizes[i - 1] : 1;
+        if (!(sizes[i] & 1) || sizes[i] < 3 || sizes[i] > 13 || sizes[i] <= prev)
+            return einval("spp: sizes must be odd, strictly increasing, 3 <= sizes[0] and sizes[n - 1] <= 13");
+        const mi355_tensor *y = ys[i];
+        if (!y || !y->data) return einval("spp: null");
+        if (y->B != x->B || y->H != x->H || y->W != x->W || y->C != x->C) return einval("spp: every output has x's B, H, W and C");
+        if (y->cs % 16 || y->cs < cp) return einval("spp: y.cs must be a multiple of 16 that holds the channels");
+        if ((uintptr_t)y->data & 15) return einval("spp: y.data must be aligned to 16 bytes");
+        for (int j = -1; j < i; ++j) {  // windows that start inside one another (the caller answers for every other overlap)
+            const char *o = (const char *)(j < 0 ? x->data : ys[j]->data), *p = (const char *)y->data;
+            if ((p >= o ? p - o : o - p) < cp) return einval("spp: an output overlaps x or another output");
+        }
+        a.d[i] = sizes[i] - prev + 1;
+        a.y[i] = (uint8_t *)y->data; a.out_cs[i] = y->cs; a.out_lead[i] = y->lead;
+    }
+    a.x = (const uint8_t *)x->data; a.in_cs = x->cs; a.in_lead = x->lead;
+    a.B = x->B; a.H = x->H; a.W = x->W; a.pieces16 = cp / 16; a.n = n;
+    if (a.B < 1 || a.H < 1 || a.W < 1) return einval("spp: empty tensor");
+    const int rc = spp_launch(a, (hipStream_t)stream);
+    if (rc == MI355_EINVAL) return einval("spp: the grid does not fit a launch");
+    if (rc != MI355_OK) return hip_fail(hipGetLastError(), "spp launch");
+    return rc;
+}
+
 int mi355_upsample_forward(const mi355_tensor *x, const mi355_tensor *y, int stride, void *stream)
 {
     if (!x || !y || !x->data || !y->data) return einval("upsample: null");

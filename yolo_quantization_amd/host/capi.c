@@ -120,6 +120,13 @@ int dnq_layer_plan(network *net, int i, int *out)
     return 0;
 }
 
+/* layer i's part in a fused SPP group (layer.spp), 0 where the run mode keeps the plain pools */
+int dnq_layer_spp(network *net, int i)
+{
+    if (i < 0 || i >= net->n) return 0;
+    return spp_on(net) ? net->layers[i].spp : 0;
+}
+
 /* k[0..2] = Ka, Kb, `from` index of shortcut layer i */
 int dnq_layer_shortcut(network *net, int i, int32_t *k)
 {

@@ -23,6 +23,9 @@ void coded_free(network *net); /* the buffers of the JPEG and PNG input paths */
 /* Does this run mode honour the planner's fused forms (layer.fuse_next)?  Parity dumps (fuse_maxpool = 0, dump_int32) and the ref-f32
  * twin run every layer on its own. */
 static inline int fusion_on(const network *net) { return net->fuse_maxpool && !net->dump_int32 && net->accum_mode == MI355_ACC_EXACT; }
+/* ... and the fused SPP groups (layer.spp)?  They store every pool's own tensor, bytes the plain kernel's, so only the parity dumps keep
+ * the plain path: that makes the dumps the expectation the fused runs are held against. */
+static inline int spp_on(const network *net) { return !net->dump_int32; }
 
 layer make_convolutional_layer(int batch, int h, int w, int c, int n, int groups, int size, int stride, int padding,
                                ACTIVATION activation, int batch_normalize, int quant_stop_flag,

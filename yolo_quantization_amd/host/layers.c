@@ -133,6 +133,22 @@ static void dequant_tail(layer l, network net)
 /* ref: forward_maxpool_layer_quant, src/maxpool_layer.c:109-172 */
 static void forward_maxpool_layer_quant_gpu(layer l, network net)
 {
+    /* A fused SPP group (plan_fusion): the leader's turn computes every pool of the group from the tensor they all read; a member's
+     * turn finds its tensor written.  MI355_EINVAL means nothing was launched: the group is cleared in the network's layer array and
+     * every pool of it, this one first, runs the plain kernel.  (A guard: on the tensors this host allocates -- 16-byte cells, aligned,
+     * one shape per group -- spp_group refuses everything the launcher refuses.) */
+    if (l.spp && spp_on(&net)) {
+        if (l.spp == 2) return;
+        int sizes[3];
+        const mi355_tensor *ys[3];
+        for (int k = 0; k < l.spp_n; ++k) {
+            sizes[k] = net.layers[l.spp_pool[k]].size;
+            ys[k] = &net.layers[l.spp_pool[k]].out_t;
+        }
+        const int rc = mi355_spp_forward(net.cur_t, l.spp_n, sizes, ys, net.stream);
+        if (rc != MI355_EINVAL) { check_mi355(rc, "mi355_spp_forward"); return; }
+        for (int k = 0; k < l.spp_n; ++k) net.layers[l.spp_pool[k]].spp = 0;
+    }
     check_mi355(mi355_maxpool_forward(net.cur_t, &l.out_t, l.size, l.stride, l.pad, net.stream), "mi355_maxpool_forward");
     if (l.quant_stop_flag) dequant_tail(l, net);
 }

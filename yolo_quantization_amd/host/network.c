@@ -365,16 +365,61 @@ void quantization_prep_host(network *net, float in_scale, uint8_t in_zp)
     plan_fusion(net); /* pure host logic: the candidates are readable (dnq_layer_plan) without a device */
 }
 
+/* the layer whose tensor [maxpool] i reads: the one before it, through any one-input [route]s */
+static int pool_source(const network *net, int i)
+{
+    int j = i - 1;
+    while (j >= 0 && net->layers[j].type == ROUTE && net->layers[j].n == 1 && net->layers[j].input_layers[0] < j) j = net->layers[j].input_layers[0];
+    return j;
+}
+
+/* a pool the SPP kernel serves: stride 1, an odd size, the "same" padding, no float tail, not written by a fused conv + pool */
+static int spp_pool_ok(const network *net, int i)
+{
+    const layer *p = &net->layers[i];
+    return p->type == MAXPOOL && p->stride == 1 && (p->size & 1) && p->size >= 3 && p->pad == p->size - 1 && !p->quant_stop_flag &&
+           !(i > 0 && net->layers[i - 1].type == CONVOLUTIONAL && net->layers[i - 1].fuse_next == FUSE_POOL);
+}
+
+/* SPP: the pools that read one tensor -- each follows it or a one-input route to it, with nothing but those routes between them -- run as
+ * one launch of spp_u8_kernel when the first of them has its turn (mi355_spp_forward).  The group is all of them or none: two or three,
+ * every one served (spp_pool_ok), sizes strictly increasing in layer order, the largest 7..13.  13 is the kernel's halo limit; below 7
+ * the plain kernel's 9 + 25 taps are few, and every net that predates the clause (pools of 1, 2, 3, 5) keeps its plan.
+ * Returns the layer behind the run of pools that starts at [maxpool] i. */
+static int spp_group(network *net, int i)
+{
+    const int src = pool_source(net, i);
+    int n = 0, ok = 1, pool[3] = { 0, 0, 0 }, j = i;
+    for (; j < net->n; ++j) {
+        const layer *q = &net->layers[j];
+        if (q->type == ROUTE && q->n == 1) continue;
+        if (q->type != MAXPOOL || pool_source(net, j) != src) break;
+        ok &= n < 3 && spp_pool_ok(net, j) && (!n || q->size > net->layers[pool[n - 1]].size);
+        if (n < 3) pool[n] = j;
+        ++n;
+    }
+    if (!ok || n < 2 || net->layers[pool[n - 1]].size < 7 || net->layers[pool[n - 1]].size > 13) return j;
+    layer *lead = &net->layers[i];
+    lead->spp = 1;
+    lead->spp_n = n;
+    for (int k = 0; k < n; ++k) {
+        lead->spp_pool[k] = pool[k];
+        if (k) net->layers[pool[k]].spp = 2;
+    }
+    return j;
+}
+
 /* The fusion candidates: conv i can run the layer after it in its own kernel, in the one way that layer's type allows
  * (layer.fuse_next).  The planner judges by shape; the launchers have the last word at run time (layers.c).
  *   maxpool:  the reference's size-2 window, stride 2 on an even map (or stride 1 behind a 128 / 256-channel conv), behind a 3x3
  *             stride-1 conv; the conv's own tensor has no other reader, or (128 / 256 channels) is stored as well (fuse_pool_keep)
  *   upsample: the conv stores every pixel stride x stride times; its own tensor has no other reader
  *   shortcut: the conv's epilogue does the quantized residual add; its own tensor has no other reader and is not the `from`
- *   yolo:     a quant_stop head conv whose kernel writes both float tensors */
+ *   yolo:     a quant_stop head conv whose kernel writes both float tensors
+ * and the one fused form without a conv (layer.spp): the SPP block's pools, which all read one tensor, in one launch (spp_group). */
 static void plan_fusion(network *net)
 {
-    for (int i = 0; i < net->n; ++i) net->layers[i].fuse_next = net->layers[i].fuse_pool_keep = 0;
+    for (int i = 0; i < net->n; ++i) net->layers[i].fuse_next = net->layers[i].fuse_pool_keep = net->layers[i].spp = 0;
     for (int i = 0; i + 1 < net->n; ++i) {
         layer *c = &net->layers[i], *p = &net->layers[i + 1];
         if (c->type != CONVOLUTIONAL || c->groups > 1) continue; /* a depthwise layer runs unfused: the layer after it on its own */
@@ -413,6 +458,7 @@ static void plan_fusion(network *net)
             break;
         }
     }
+    for (int i = 1; i < net->n;) i = net->layers[i].type == MAXPOOL ? spp_group(net, i) : i + 1;
 }
 
 void quantization_weights_and_activations_fixed_input(network *net, float in_scale, uint8_t in_zp)
@@ -1003,6 +1049,11 @@ static void run_layers(network *netp)
             const int stored = !(fusion_on(netp) && pl->fuse_next != FUSE_NONE && !(pl->fuse_next == FUSE_POOL && pl->fuse_pool_keep));
             if (!stored) error("forward_network_gpu: layer range starts behind a conv whose own tensor is not stored (fused with the layer after it)");
         }
+        /* a member of a fused SPP group does nothing on its turn: its leader, which writes its tensor, must run in the range too */
+        for (int i = 0; i < netp->range_lo && spp_on(netp); ++i)
+            for (int k = 1; netp->layers[i].spp == 1 && k < netp->layers[i].spp_n; ++k)
+                if (netp->layers[i].spp_pool[k] >= netp->range_lo && netp->layers[i].spp_pool[k] < netp->range_hi)
+                    error("forward_network_gpu: layer range holds a pool of a fused SPP group without the group's first pool");
     }
     if (netp->prof_ev && netp->prof_used < netp->prof_cap && !netp->use_graph && netp->prof_calls++ % netp->prof_stride == netp->prof_phase % netp->prof_stride)
         ev = netp->prof_ev + (size_t)(netp->prof_used++) * (net.n + 2);
