@@ -33,7 +33,7 @@ extern "C" {
 
 /* same enumerator values as the reference (include/darknet.h:87-89, 99-130) */
 typedef enum { LOGISTIC = 0, RELU = 1, LINEAR = 3, RELU6 = 8, LEAKY = 9 } ACTIVATION;
-typedef enum { CONVOLUTIONAL = 0, MAXPOOL = 3, ROUTE = 8, SHORTCUT = 13, YOLO = 23, UPSAMPLE = 26 } LAYER_TYPE;
+typedef enum { CONVOLUTIONAL = 0, DECONVOLUTIONAL = 1, MAXPOOL = 3, ROUTE = 8, SHORTCUT = 13, YOLO = 23, UPSAMPLE = 26 } LAYER_TYPE;
 
 /* layer.fuse_next: the layer after a conv that runs inside the conv's kernel.  The type of that layer decides the kind */
 enum { FUSE_NONE = 0, FUSE_POOL, FUSE_UPSAMPLE, FUSE_SHORTCUT, FUSE_YOLO };

@@ -261,6 +261,32 @@ int mi355_conv_dw_pack(int c, int ksize, const uint8_t *weights_uint8, const uin
 int mi355_conv_dw_forward(const mi355_conv_desc *desc, const mi355_tensor *x, const void *blob, const mi355_tensor *y,
                           int32_t *acc_out, float *y_f32, void *stream);
 
+/* Transposed convolution, `[deconvolutional]` (learned upsampling).  The reference has the float layer only (src/deconvolutional_layer.c,
+ * GEMM + col2im), so the integer layer is builder-specified as its STUFFED TWIN: with x^ the
+ * ((H - 1) s + 1) x ((W - 1) s + 1) map that holds x[ci][iy][ix] at (iy s, ix s) and desc.zp_in everywhere else, and
+ * w^[f][ci][a][b] = weights_uint8[ci][f][k - 1 - a][k - 1 - b], the layer is the dense convolution of x^ with w^ at stride 1 and
+ * padding k - 1 - pad: exact int32 accumulators with K = c k k, out-of-map taps = desc.zp_in, biases_int32 / M_value / shift_value
+ * the caller's (src/blas.c:313-333 on w^ with that K), the epilogue (both stores, leaky / relu / relu6 / linear, y_f32)
+ * mi355_conv_forward's.  Output map: OH = (H - 1) stride + ksize - 2 pad, OW likewise.  The kernel (conv_tr.hip) neither builds x^
+ * nor multiplies by its fill: each of the stride^2 output phases is a stride-1 implicit GEMM over its own taps.
+ *   mi355_conv_tr_pack_size   bytes of the blob, a function of (n, c, ksize, stride) only; 0 outside n >= 1, c >= 1, 1 <= ksize <= 11,
+ *                             1 <= stride <= 8
+ *   mi355_conv_tr_pack        weights_uint8: the reference's record [c][n][ksize][ksize]; zp_w, biases_int32, M_value, shift_value per
+ *                             filter; position independent like mi355_conv_pack's blob, same conditions on M_value / shift_value
+ *   mi355_conv_tr_forward     desc.stride = s, desc.pad = p with 0 <= p <= ksize - 1, MI355_ACC_EXACT only; x.cs % 16 == 0 (not the
+ *                             3-channel image), x.data and blob 16-byte aligned.  The tensor's pad cells are never read.  y (nullable),
+ *                             acc_out ([B][n][OH * OW]) and y_f32 as in mi355_conv_forward; channels >= n of y's cells keep their bytes.
+ *                             No fused form.  Anything else returns MI355_EINVAL with a message that starts "conv_tr_forward:", nothing
+ *                             launched.
+ *                             The blob is device memory, so its header is not read back: the caller guarantees that it was packed for
+ *                             desc's (n, c, ksize, stride) -- mi355_conv_tr_pack_size of those four is its size -- as for every blob here.
+ * New calls, no struct change: MI355_ABI_VERSION is unchanged. */
+size_t mi355_conv_tr_pack_size(int n, int c, int ksize, int stride);
+int mi355_conv_tr_pack(int n, int c, int ksize, int stride, const uint8_t *weights_uint8, const uint8_t *zp_w, const int32_t *biases_int32,
+                       const double *M_value, const double *shift_value, void *blob);
+int mi355_conv_tr_forward(const mi355_conv_desc *desc, const mi355_tensor *x, const void *blob, const mi355_tensor *y,
+                          int32_t *acc_out, float *y_f32, void *stream);
+
 /* Tile configuration override for benchmarking (0 = auto). */
 int mi355_conv_set_tile(int bm, int bn);
 /* Development switches.  Bits 0..8 are timing ablations of the K loop (no DMA / no s_barrier / no MFMA / ...), compiled
@@ -277,7 +303,7 @@ int mi355_debug_flags(int flags);
  * the kernel it is meant to exercise): 0 none yet, 1 first layer (conv_aux.hip), 2 conv_small.hip (few-channel / 64-channel
  * conv + maxpool), 3 conv1x1.hip, 4 conv_ws3.hip, 5 conv_igemm.hip / conv_rows.hip / conv_rows16.hip, 6 fp32-accumulate emulation,
  * 7 conv_pool16.hip (16 -> 32 + maxpool with the packed epilogue table), 8 conv_small32.hip (32 -> 64 + maxpool), 9 conv_kxk.hip (the
- * general shapes), 10 conv_dw.hip (mi355_conv_dw_forward). */
+ * general shapes), 10 conv_dw.hip (mi355_conv_dw_forward), 11 conv_tr.hip (mi355_conv_tr_forward). */
 int mi355_last_conv_kernel(void);
 /* Geometry of the calling thread's most recent convolution kernel launch (any mi355_conv_*forward call): workgroups in the grid,
  * threads per workgroup, bytes of dynamic LDS, as the launcher chose them for the plan, batch and tile count.  Each pointer may be

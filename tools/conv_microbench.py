@@ -6,6 +6,7 @@
   python tools/conv_microbench.py --net       # every conv shape of yolov3-tiny at batch 64
   python tools/conv_microbench.py --dw [--out FILE]   # depthwise 3x3 (conv_dw.hip) against its dense twin and the HBM floor
   python tools/conv_microbench.py --spp [--out FILE]  # the fused SPP pools (spp.hip) against the three plain pools and the HBM floor
+  python tools/conv_microbench.py --tr [--out FILE]   # transposed k4 s2 / k2 s2 (conv_tr.hip) against its stuffed dense twin and the HBM floor
 """
 import argparse
 import ctypes as C
@@ -178,11 +179,58 @@ def run_spp(iters, repeats):
     return out
 
 
+def run_tr(iters, repeats):
+    """The transposed kernel (conv_tr.hip) on k4 s2 p1 and k2 s2 p0, 256 x 26 x 26 -> 128 and 128 x 52 x 52 -> 64 at batch 32, each
+    against two baselines: its stuffed dense twin (the zero-point-stuffed map, built before the clock, through the dense
+    kernels with the flipped weights: the same bytes out) and the HBM floor, tensor bytes in + out over the bandwidth a device-to-device
+    copy of 256 MiB reaches in this process.  The two kernels alternate, `repeats` rounds; medians and ranges in microseconds."""
+    S = binding.shim()
+    st = C.c_void_p(); binding.check(S.mi355_stream_create(C.byref(st)))
+    nb = 256 << 20
+    src, dst = binding.DevBuf(nb), binding.DevBuf(nb)
+    copy_us = [_time_us(lambda: binding.check(S.mi355_d2d(dst.ptr, src.ptr, nb, st), "d2d"), st, 10) for _ in range(repeats)]
+    bw = 2.0 * nb / (np.median(copy_us) * 1e-6)  # bytes read + written per second
+    src.free(); dst.free()
+    out = {"copy_256MiB_us": copy_us, "copy_bytes_per_s": bw, "iters": iters, "cases": []}
+    for c, hw, n in ((256, 26, 128), (128, 52, 64)):
+        for k, s, p in ((4, 2, 1), (2, 2, 0)):
+            rng = np.random.default_rng(c + k)
+            B, zp_in = 32, 5
+            x = rng.integers(0, 256, (B, c, hw, hw), dtype=np.uint8)
+            w = rng.integers(0, 256, (c, n, k, k), dtype=np.uint8)
+            zp_w = rng.integers(100, 157, n, dtype=np.uint8)
+            bias = np.zeros(n, np.int32); mv = np.full(n, 0.75); sv = np.full(n, 2.0 ** -12)
+            ohw, shw = (hw - 1) * s + k - 2 * p, (hw - 1) * s + 1
+            xh = np.full((B, c, shw, shw), zp_in, np.uint8)
+            xh[:, :, ::s, ::s] = x
+            wh = np.ascontiguousarray(w.transpose(1, 0, 2, 3)[:, :, ::-1, ::-1]).reshape(n, -1)
+            xt, xht = binding.DevTensor.from_nchw(x, zp_in), binding.DevTensor.from_nchw(xh, zp_in)
+            y, yd = binding.DevTensor(B, ohw, ohw, n, 23), binding.DevTensor(B, ohw, ohw, n, 23)
+            blob = binding.DevBuf.from_numpy(binding.conv_tr_pack(w, zp_w, k, s, bias, mv, sv))
+            blobd = binding.DevBuf.from_numpy(binding.conv_pack(wh, zp_w, c, k, bias, mv, sv))
+            d = binding.ConvDesc(n, c, k, s, p, binding.ACT["leaky"], 0, 0, zp_in, 23, 1.0)
+            dd = binding.ConvDesc(n, c, k, 1, k - 1 - p, binding.ACT["leaky"], 0, 0, zp_in, 23, 1.0)
+            tr = lambda: binding.check(S.mi355_conv_tr_forward(C.byref(d), xt.ref(), blob.ptr, y.ref(), None, None, st), "tr")
+            dense = lambda: binding.check(S.mi355_conv_forward(C.byref(dd), xht.ref(), blobd.ptr, None, None, yd.ref(), None, None, st), "dense")
+            t_tr, t_dense = [], []
+            for _ in range(repeats):
+                t_tr.append(_time_us(tr, st, iters)); t_dense.append(_time_us(dense, st, iters))
+            S.mi355_stream_sync(st)
+            same = bool(np.array_equal(y.to_nchw(), yd.to_nchw()))
+            floor_us = (B * (c * hw * hw + n * ohw * ohw)) / bw * 1e6
+            out["cases"].append({"c": c, "hw": hw, "n": n, "k": k, "stride": s, "pad": p, "batch": B, "tr_us": t_tr, "dense_twin_us": t_dense,
+                                 "dense_kernel": binding.last_conv_kernel(), "bytes_equal": same, "hbm_floor_us": floor_us,
+                                 "tr_over_dense": float(np.median(t_tr) / np.median(t_dense)),
+                                 "tr_over_floor": float(np.median(t_tr) / floor_us)})
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--tr", action="store_true", help="transposed k4 s2 / k2 s2 against the stuffed dense twin and the HBM floor")
     ap.add_argument("--dw", action="store_true", help="depthwise 3x3 against its dense twin and the HBM floor")
     ap.add_argument("--spp", action="store_true", help="the fused SPP pools against the three plain pools and the HBM floor")
-    ap.add_argument("--out", default="", help="--dw, --spp: also write the JSON here")
+    ap.add_argument("--out", default="", help="--dw, --spp, --tr: also write the JSON here")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--c", type=int, default=256); ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--hw", type=int, default=52); ap.add_argument("--k", type=int, default=3)
@@ -200,8 +248,8 @@ if __name__ == "__main__":
     binding.init(0)
     if a.dbg:
         binding.shim().mi355_debug_flags(a.dbg)
-    if a.dw or a.spp:
-        r = run_spp(a.iters, a.repeats) if a.spp else run_dw(a.iters, a.repeats)
+    if a.dw or a.spp or a.tr:
+        r = run_tr(a.iters, a.repeats) if a.tr else (run_spp(a.iters, a.repeats) if a.spp else run_dw(a.iters, a.repeats))
         print(json.dumps(r))
         if a.out:
             with open(a.out, "w") as f:

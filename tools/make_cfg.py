@@ -11,6 +11,7 @@ accepts: /root/reference/src/parser.c:170-204 (convolutional), 411-431 (maxpool)
   cfg/res_unit.cfg                 16x16 unit net for the quantized residual add and the glue layers' quant_stop tails
   cfg/s2_unit.cfg                  24x24 chain of stride-2 3x3 convolutions (the downsampling layers of full YOLOv3)
   cfg/dw_unit.cfg                  24x24 depthwise-separable unit net (groups = channels layers between 1x1 convolutions)
+  cfg/tr_unit.cfg                  24x24 unit net with two [deconvolutional] layers (k4 s2 p1, k2 s2 p0) and a route over one of them
 """
 import os, sys
 
@@ -94,6 +95,25 @@ def dw_unit(act="leaky"):
     s += yolo("0,1,2")                                # 7
     return s
 
+def deconv(filters, size, stride, padding, act, bn=1, stop=0):
+    s = "[deconvolutional]\n"
+    if bn: s += "batch_normalize=1\n"
+    s += f"filters={filters}\nsize={size}\nstride={stride}\npadding={padding}\nactivation={act}\nquantized=1\nquant_stop={stop}\n\n"
+    return s
+
+def tr_unit(act="leaky"):
+    # 24x24x3 input: stride-2 convolutions down to 12x12, transposed layers back up (the usual k4 s2 p1 and the one-tap k2 s2 p0),
+    # a route that concatenates the second with the first, a 1x1 head
+    s = net(24, 24, c=3)
+    s += conv(16, 3, act, stride=2)                   # 0   12x12
+    s += deconv(16, 4, 2, 1, act)                     # 1   24x24
+    s += conv(32, 3, act, stride=2)                   # 2   12x12
+    s += deconv(16, 2, 2, 0, "relu6")                 # 3   24x24
+    s += route("-1,1")                                # 4   32 channels
+    s += conv(30, 1, "linear", bn=0, stop=1)          # 5
+    s += yolo("0,1,2")                                # 6
+    return s
+
 def shortcut(frm=-3):
     return f"[shortcut]\nfrom={frm}\nactivation=linear\nquantized=1\nquant_stop=0\n\n"
 
@@ -166,4 +186,5 @@ if __name__ == "__main__":
     open(os.path.join(out, "yolov3_quant.cfg"), "w").write(yolov3())
     open(os.path.join(out, "res_unit.cfg"), "w").write(res_unit())
     open(os.path.join(out, "dw_unit.cfg"), "w").write(dw_unit())
+    open(os.path.join(out, "tr_unit.cfg"), "w").write(tr_unit())
     print("wrote cfgs to", os.path.normpath(out))

@@ -265,6 +265,11 @@ def shim():
             L.mi355_conv_dw_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.POINTER(Tensor), vp, vp, vp]
         if hasattr(L, "mi355_spp_forward"):  # (MI355_LIB_DIR may name an older build)
             L.mi355_spp_forward.argtypes = [C.POINTER(Tensor), ci, vp, vp, vp]
+        if hasattr(L, "mi355_conv_tr_forward"):  # (MI355_LIB_DIR may name an older build)
+            L.mi355_conv_tr_pack_size.argtypes = [ci, ci, ci, ci]
+            L.mi355_conv_tr_pack_size.restype = C.c_size_t
+            L.mi355_conv_tr_pack.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+            L.mi355_conv_tr_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.POINTER(Tensor), vp, vp, vp]
         L.mi355_last_conv_kernel.argtypes = []
         L.mi355_last_conv_kernel.restype = ci
         if hasattr(L, "mi355_last_conv_launch"):  # (absent from older A/B builds under build_ab/)
@@ -533,6 +538,47 @@ def spp_forward(x, sizes, ys, stream=None):
     return int(shim().mi355_spp_forward(C.cast(ref(x), C.POINTER(Tensor)), len(sizes), sz, yp, stream))
 
 
+def conv_tr_pack(wq, zp_w, ksize, stride, biases_int32, M_value, shift_value):
+    """mi355_conv_tr_pack -> numpy uint8 blob of a transposed layer; wq: the reference's record [c, n, ksize, ksize]"""
+    wq = np.ascontiguousarray(wq, np.uint8)
+    c, n = wq.shape[0], wq.shape[1]
+    sz = shim().mi355_conv_tr_pack_size(n, c, ksize, stride)
+    if not sz:
+        raise MI355Error(f"unsupported transposed shape n={n} c={c} k={ksize} s={stride}")
+    blob = np.zeros(sz, np.uint8)
+    zp_w = np.ascontiguousarray(zp_w, np.uint8)
+    b = np.ascontiguousarray(biases_int32, np.int32)
+    mv = np.ascontiguousarray(M_value, np.float64)
+    sv = np.ascontiguousarray(shift_value, np.float64)
+    check(shim().mi355_conv_tr_pack(n, c, ksize, stride, wq.ctypes.data, zp_w.ctypes.data, b.ctypes.data, mv.ctypes.data, sv.ctypes.data,
+                                    blob.ctypes.data), "conv_tr_pack")
+    return blob
+
+
+def conv_tr_forward(x: DevTensor, wq, zp_w, ksize, stride, pad, biases_int32, M_value, shift_value, zp_in, zp_act, s_act, activation,
+                    store=STORE_WRAP, accum=ACC_EXACT, want_acc=True, want_f32=False, plan=0, y=None):
+    """One transposed layer ([deconvolutional]) through mi355_conv_tr_forward; wq: [c, n, ksize, ksize]; result as conv_forward.
+    y: the output DevTensor to write into (default: a fresh one filled with zp_act)."""
+    n = np.shape(wq)[1]
+    blob = DevBuf.from_numpy(conv_tr_pack(wq, zp_w, ksize, stride, biases_int32, M_value, shift_value))
+    OH, OW = (x.t.H - 1) * stride + ksize - 2 * pad, (x.t.W - 1) * stride + ksize - 2 * pad
+    if y is None:
+        y = DevTensor(x.t.B, OH, OW, n, zp_act)
+    cnt = x.t.B * n * OH * OW
+    acc = DevBuf(cnt * 4) if want_acc else None
+    f32 = DevBuf(cnt * 4) if want_f32 else None
+    d = ConvDesc(n, x.t.C, ksize, stride, pad, activation, store, accum, zp_in, zp_act, float(s_act), int(plan), 0)
+    check(shim().mi355_conv_tr_forward(C.byref(d), x.ref(), blob.ptr, y.ref(), acc.ptr if acc else None,
+                                       f32.ptr if f32 else None, None), "conv_tr_forward")
+    check(shim().mi355_stream_sync(None), "sync")
+    out = {"u8": y.to_nchw(), "tensor": y}
+    if acc:
+        out["int32"] = acc.to_numpy(np.int32, cnt).reshape(x.t.B, n, OH * OW)
+    if f32:
+        out["f32"] = f32.to_numpy(np.float32, cnt).reshape(x.t.B, n, OH * OW)
+    return out
+
+
 FUSED = ("pool2", "pool1", "upsample", "yolo", "shortcut")
 
 
@@ -743,6 +789,7 @@ INFO_KEYS = ["type", "out_c", "out_h", "out_w", "c", "h", "w", "n", "size", "str
 PLAN_KEYS = ["route_elided", "out_view", "view_offset", "fuse_next_pool", "fuse_next_upsample", "fuse_next_shortcut", "fuse_next_yolo",
              "fuse_pool_keep"]
 T_CONV, T_MAXPOOL, T_ROUTE, T_SHORTCUT, T_YOLO, T_UPSAMPLE = 0, 3, 8, 13, 23, 26
+T_DECONV = 1  # [deconvolutional]: a weight record, a prep and int32 accumulators like T_CONV
 
 
 def frame_view(v, frame_w=None, frame_h=None):
@@ -1830,7 +1877,7 @@ class Net:
         ty = self.info[i]["type"]
         if ty != T_YOLO:
             out["u8"] = _as(self.H.dnq_layer_u8(self.h, i), cnt, C.c_uint8).copy()
-        if ty == T_CONV:
+        if ty in (T_CONV, T_DECONV):
             out["int32"] = _as(self.H.dnq_layer_int32(self.h, i), cnt, C.c_int32).copy()
         if ty == T_YOLO or (self.info[i]["quant_stop"] and (self.keep_head_float or ty != T_CONV or not self.fuses_next(i))):
             out["f32"] = _as(self.H.dnq_layer_f32(self.h, i), cnt, C.c_float).copy()

@@ -239,6 +239,72 @@ struct DwArgs {
 constexpr int DW_RUN = 8;    // output pixels along x per lane; the tile is 2^ry_sh rows by (16 >> ry_sh) * DW_RUN columns
 int conv_dw_launch(DwArgs &a, hipStream_t st);  // MI355_EINVAL when no tile fits LDS (nothing launched)
 
+// conv_tr.hip: the transposed convolution ([deconvolutional]), split into its stride x stride output phases.  Phase
+// (ty, tx) owns the taps ky = ty + s jy, kx = tx + s jx, numbered t = jy * tr_taps(k, s, tx) + jx.  With nu = ceil(c / 16) channel
+// units, a phase's K-steps (32 bytes: two lane halves of one unit of one tap) are dense: first (unit pair up, tap t) -> step
+// up * taps + t with half kh on unit 2 up + kh; then, for an odd nu, the last unit's taps in pairs -> half kh on tap 2 tp + kh.
+// The blob (mi355_conv_tr_pack) is a header, the A fragments [phase][mpad / 32][steps of the phase][64 lanes][16 B], per-filter
+// arrays and two int32 per (phase, filter): cw = 128 sum w' + 128 d K_phase over the phase's own taps, and sw = sum (w - zp_w) over
+// every other tap, which the kernel multiplies by the input zero point (the stuffed cells of the dense twin).
+#define MI355_TR_MAGIC 0x4D495452u /* "MITR" */
+constexpr int TR_MAX_STRIDE = 8;
+constexpr int TR_MAX_TAPS = 128;   // tap slots of the kernel's offset table (11 x 11 at stride 1: 121)
+__host__ __device__ inline int tr_taps(int k, int s, int t) { return t < k ? (k - t + s - 1) / s : 0; }
+__host__ __device__ inline int tr_steps(int nu, int taps) { return (nu / 2) * taps + ((nu & 1) ? (taps + 1) / 2 : 0); }
+struct TrBlobHeader {
+    uint32_t magic;
+    int32_t n, c, ksize, stride, mpad, nu;
+    int32_t step0[TR_MAX_STRIDE * TR_MAX_STRIDE + 1];  // K-steps of the phases before phase ty * s + tx (per 32-row M tile)
+    uint64_t off_wk, off_cw, off_sw, off_dzp, off_bias, off_mval, off_sval, total;
+};
+inline bool tr_blob_layout(int n, int c, int ksize, int stride, TrBlobHeader *h)
+{
+    if (n < 1 || c < 1 || ksize < 1 || ksize > 11 || stride < 1 || stride > TR_MAX_STRIDE) return false;
+    *h = TrBlobHeader{};
+    h->magic = MI355_TR_MAGIC; h->n = n; h->c = c; h->ksize = ksize; h->stride = stride;
+    h->mpad = (n + 127) / 128 * 128;  // rows padded to the largest M tile
+    h->nu = (c + 15) / 16;
+    int steps = 0;
+    for (int ph = 0; ph < stride * stride; ++ph) {
+        h->step0[ph] = steps;
+        steps += tr_steps(h->nu, tr_taps(ksize, stride, ph / stride) * tr_taps(ksize, stride, ph % stride));
+    }
+    h->step0[stride * stride] = steps;
+    uint64_t off = (sizeof(TrBlobHeader) + 15) & ~(uint64_t)15;
+    h->off_wk = off;   off += (uint64_t)(h->mpad / 32) * steps * 64 * 16;
+    h->off_cw = off;   off += (uint64_t)stride * stride * h->mpad * 4;
+    h->off_sw = off;   off += (uint64_t)stride * stride * h->mpad * 4;
+    h->off_dzp = off;  off += (uint64_t)h->mpad * 4;
+    h->off_bias = off; off += (uint64_t)h->mpad * 4;
+    h->off_mval = off; off += (uint64_t)h->mpad * 8;
+    h->off_sval = off; off += (uint64_t)h->mpad * 8;
+    h->total = off;
+    return true;
+}
+struct TrArgs {
+    const uint8_t *x;        // input tensor, biased PHWC (cs % 16 == 0, data 16-byte aligned)
+    int in_cs, in_lead;
+    int B, H, W, c;
+    int n, ksize, stride, pad, OH, OW;
+    const int8_t *wk;
+    const int32_t *cw, *sw, *dzp, *bias;
+    const double *mval, *sval;
+    const TrBlobHeader *hdr; // device copy (step0)
+    uint8_t *y;
+    int out_cs, out_lead;
+    int32_t *acc_out;
+    float *y_f32;
+    int zp_in, zp_act, act, store_mode;
+    float s_act;
+    int plan;
+    // tile geometry (set by the launcher).  A tile is 2^tw_sh columns of quotient space: output (oy, ox) of phase (ty, tx) sits at
+    // (qy, qx) = ((oy + pad) / s, (ox + pad) / s), and tap (jy, jx) reads input (qy - jy, qx - jx)
+    int nu, mpad, halo;      // halo = ceil(k / s) - 1 input rows / columns before the tile
+    int tw_sh, tiles_x, tiles_y, mgroups, ph, pw;
+    int cu, nchunks;         // channel units staged at a time (all of them when nchunks == 1; else even)
+};
+int conv_tr_launch(TrArgs &a, hipStream_t st);  // MI355_EINVAL when the grid does not fit (nothing launched)
+
 // spp.hip: up to three stride-1 "same" max pools of one tensor in one launch (the SPP block of yolov3-spp / yolov4), computed as a
 // cascade: level i is the box max of size d[i] of level i - 1, level 0 being x, so that level i is x's pool of size sizes[i].
 constexpr int SPP_MAX = 3;       // levels

@@ -1020,6 +1020,115 @@ int mi355_conv_dw_forward(const mi355_conv_desc *d, const mi355_tensor *x, const
     return rc;
 }
 
+// ------------------------------------------------------------------------------------- transposed convolution (conv_tr.hip)
+size_t mi355_conv_tr_pack_size(int n, int c, int ksize, int stride)
+{
+    TrBlobHeader h;
+    return tr_blob_layout(n, c, ksize, stride, &h) ? (size_t)h.total : 0;
+}
+
+int mi355_conv_tr_pack(int n, int c, int ksize, int stride, const uint8_t *wq, const uint8_t *zp_w, const int32_t *biases_int32,
+                       const double *M_value, const double *shift_value, void *blob)
+{
+    TrBlobHeader h;
+    if (!tr_blob_layout(n, c, ksize, stride, &h)) return einval("conv_tr_pack: need n >= 1, c >= 1, 1 <= ksize <= 11 and 1 <= stride <= 8");
+    if (!wq || !zp_w || !biases_int32 || !M_value || !shift_value || !blob) return einval("conv_tr_pack: null");
+    for (int oc = 0; oc < n; ++oc)
+        if (!(M_value[oc] > 0.0 && M_value[oc] < 1.0) || !(shift_value[oc] > 0.0 && shift_value[oc] <= 1.0))
+            return einval("conv_tr_pack: need 0 < M_value < 1 and 0 < shift_value <= 1 (ref asserts 0<M<1, src/blas.c:391-392)");
+    char *base = (char *)blob;
+    memset(base, 0, (size_t)h.total);
+    memcpy(base, &h, sizeof(h));
+    const int k = ksize, s = stride, kk = k * k, nu = h.nu, mtiles = h.mpad / 32;
+    auto w_at = [&](int ci, int oc, int ky, int kx) { return (int)wq[((size_t)ci * n + oc) * kk + ky * k + kx]; };  // the reference's [c][n][k][k]
+    int32_t *cw = (int32_t *)(base + h.off_cw), *sw = (int32_t *)(base + h.off_sw);
+    for (int oc = 0; oc < n; ++oc) {
+        ((int32_t *)(base + h.off_dzp))[oc] = 128 - (int)zp_w[oc];
+        ((int32_t *)(base + h.off_bias))[oc] = biases_int32[oc];
+        ((double *)(base + h.off_mval))[oc] = M_value[oc];
+        ((double *)(base + h.off_sval))[oc] = shift_value[oc];
+        // per tap: sum over the channels of w; then per phase the own taps' 128 sum w' + 128 K d and the other taps' sum (w - zp_w)
+        long tapsum[121], all = 0;
+        for (int t = 0; t < kk; ++t) {
+            long v = 0;
+            for (int ci = 0; ci < c; ++ci) v += w_at(ci, oc, t / k, t % k);
+            tapsum[t] = v;
+            all += v - (long)c * zp_w[oc];
+        }
+        for (int ph = 0; ph < s * s; ++ph) {
+            long own_w = 0, own_n = 0;
+            for (int ky = ph / s; ky < k; ky += s)
+                for (int kx = ph % s; kx < k; kx += s) { own_w += tapsum[ky * k + kx]; ++own_n; }
+            const long Kp = own_n * c, d = 128 - (long)zp_w[oc];
+            cw[(size_t)ph * h.mpad + oc] = (int32_t)(uint32_t)(128 * (own_w - 128 * Kp) + 128 * Kp * d);  // modulo 2^32, like the accumulators
+            sw[(size_t)ph * h.mpad + oc] = (int32_t)(uint32_t)(all - (own_w - Kp * (long)zp_w[oc]));
+        }
+    }
+    // A fragments: lane (row lane % 32, half kh = lane / 32) of K-step g of a phase; byte e = channel 16 unit + e of the half's tap (kargs.h)
+    int8_t *wk = (int8_t *)(base + h.off_wk);
+    for (int ph = 0; ph < s * s; ++ph) {
+        const int ty = ph / s, tx = ph % s, jxn = tr_taps(k, s, tx), taps = tr_taps(k, s, ty) * jxn, G = tr_steps(nu, taps);
+        for (int mt = 0; mt < mtiles; ++mt)
+            for (int g = 0; g < G; ++g)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int oc = 32 * mt + (lane & 31), kh = lane >> 5;
+                    const bool paired = g < (nu / 2) * taps;
+                    const int t = paired ? g % taps : 2 * (g - (nu / 2) * taps) + kh, unit = paired ? 2 * (g / taps) + kh : nu - 1;
+                    if (oc >= n || t >= taps) continue;
+                    const int ky = ty + s * (t / jxn), kx = tx + s * (t % jxn);
+                    int8_t *dst = wk + (((size_t)h.step0[ph] * mtiles + (size_t)mt * G + g) * 64 + lane) * 16;
+                    for (int e = 0; e < 16 && 16 * unit + e < c; ++e) dst[e] = (int8_t)(w_at(16 * unit + e, oc, ky, kx) ^ 0x80);
+                }
+    }
+    return MI355_OK;
+}
+
+int mi355_conv_tr_forward(const mi355_conv_desc *d, const mi355_tensor *x, const void *blob, const mi355_tensor *y, int32_t *acc_out,
+                          float *y_f32, void *stream)
+{
+    if (!d || !x || !x->data || !blob) return einval("conv_tr_forward: null");
+    if (d->n < 1 || d->c < 1) return einval("conv_tr_forward: need n >= 1 and c >= 1");
+    if (d->ksize < 1 || d->ksize > 11) return einval("conv_tr_forward: size must be 1..11");
+    if (d->stride < 1 || d->stride > TR_MAX_STRIDE) return einval("conv_tr_forward: stride must be 1..8");
+    if (d->pad < 0 || d->pad > d->ksize - 1) return einval("conv_tr_forward: need 0 <= pad <= size - 1 (the dense twin's padding size - 1 - pad)");
+    if (d->accum_mode != MI355_ACC_EXACT)
+        return einval("conv_tr_forward: MI355_ACC_EXACT only (the reference has no integer transposed forward whose fp32 order could be followed)");
+    if (d->activation != MI355_ACT_LEAKY && d->activation != MI355_ACT_RELU && d->activation != MI355_ACT_RELU6 && d->activation != MI355_ACT_LINEAR)
+        return einval("conv_tr_forward: activation must be leaky, relu, relu6 or linear");
+    if (x->cs % 16 || x->cs < (d->c + 15) / 16 * 16)
+        return einval("conv_tr_forward: x.cs must be a multiple of 16 that holds the channels (the 3-channel image's 4-byte cells are not served)");
+    if (x->C != d->c) return einval("conv_tr_forward: x.C != desc.c");
+    const long OHl = ((long)x->H - 1) * d->stride + d->ksize - 2L * d->pad, OWl = ((long)x->W - 1) * d->stride + d->ksize - 2L * d->pad;
+    if (x->H < 1 || x->W < 1 || OHl < 1 || OWl < 1) return einval("conv_tr_forward: the output map (H - 1) stride + size - 2 pad is empty");
+    if (y && (y->C != d->n || y->B != x->B || y->H != OHl || y->W != OWl || !y->data || y->cs < d->n || (y->cs != 4 && y->cs % 16)))
+        return einval("conv_tr_forward: y shape");
+    if (((uintptr_t)x->data & 15) || ((uintptr_t)blob & 15) || (y && ((uintptr_t)y->data & 3)))
+        return einval("conv_tr_forward: x.data and blob must be aligned to 16 bytes, y.data to 4");
+    TrBlobHeader h;
+    tr_blob_layout(d->n, d->c, d->ksize, d->stride, &h);
+    const char *base = (const char *)blob;
+    TrArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = (const uint8_t *)x->data; a.in_cs = x->cs; a.in_lead = x->lead;
+    a.B = x->B; a.H = x->H; a.W = x->W; a.c = d->c;
+    a.n = d->n; a.ksize = d->ksize; a.stride = d->stride; a.pad = d->pad; a.OH = (int)OHl; a.OW = (int)OWl;
+    a.wk = (const int8_t *)(base + h.off_wk);
+    a.cw = (const int32_t *)(base + h.off_cw); a.sw = (const int32_t *)(base + h.off_sw);
+    a.dzp = (const int32_t *)(base + h.off_dzp); a.bias = (const int32_t *)(base + h.off_bias);
+    a.mval = (const double *)(base + h.off_mval); a.sval = (const double *)(base + h.off_sval);
+    a.hdr = (const TrBlobHeader *)base;
+    a.y = y ? (uint8_t *)y->data : nullptr; a.out_cs = y ? y->cs : 0; a.out_lead = y ? y->lead : 0;
+    a.acc_out = acc_out; a.y_f32 = y_f32;
+    a.zp_in = d->zp_in; a.zp_act = d->zp_act; a.act = d->activation; a.store_mode = d->store_mode; a.s_act = d->s_act;
+    a.plan = d->plan;
+    a.nu = h.nu; a.mpad = h.mpad;
+    const int rc = conv_tr_launch(a, (hipStream_t)stream);
+    if (rc == MI355_EINVAL) return einval("conv_tr_forward: the grid of the transposed kernel does not fit this shape");
+    if (rc != MI355_OK) return hip_fail(hipGetLastError(), "conv_tr launch");
+    g_last_kernel = 11;
+    return rc;
+}
+
 int mi355_conv_yolo_forward(const mi355_conv_desc *d, const mi355_tensor *x, const void *blob, const mi355_tensor *y,
                             float *y_f32, float *yolo_out, int classes, void *stream)
 {

@@ -58,9 +58,9 @@ int dnq_layer_prep(network *net, int i, int32_t *biases_int32, double *M_value, 
     if (q && l->activ_data_uint8_scales) {
         q[2] = l->activ_data_uint8_scales[0];
         q[3] = l->activ_data_uint8_zero_point[0];
-        if (l->type == CONVOLUTIONAL) { q[0] = l->input_data_uint8_scales[0]; q[1] = l->input_data_uint8_zero_point[0]; }
+        if (conv_like(l)) { q[0] = l->input_data_uint8_scales[0]; q[1] = l->input_data_uint8_zero_point[0]; }
     }
-    if (l->type != CONVOLUTIONAL) return 1;
+    if (!conv_like(l)) return 1;
     for (int k = 0; k < l->n; ++k) {
         if (biases_int32) biases_int32[k] = l->biases_int32[k];
         if (M_value) M_value[k] = l->M_value[k];

@@ -122,6 +122,24 @@ static void forward_convolutional_layer_quant_gpu(layer l, network net)
     check_mi355(conv_plain(&l, &net, &d, pi, 1), fused_name[FUSE_NONE]);
 }
 
+/* The transposed convolution: the dense layer on the zero-point-stuffed input, on conv_tr.hip.  Unfused, exact mode only. */
+static void forward_deconvolutional_layer_quant_gpu(layer l, network net)
+{
+    if (!l.prepared) error("forward_gpu before quantization_weights_and_activations");
+    mi355_conv_desc d;
+    memset(&d, 0, sizeof(d));
+    d.n = l.n; d.c = l.c; d.ksize = l.size; d.stride = l.stride; d.pad = l.pad;
+    d.activation = l.activation;
+    d.plan = net.plan;
+    d.store_mode = net.store_mode;
+    d.accum_mode = net.accum_mode;
+    d.zp_in = l.input_data_uint8_zero_point[0];
+    d.zp_act = l.activ_data_uint8_zero_point[0];
+    d.s_act = l.activ_data_uint8_scales[0];
+    check_mi355(mi355_conv_tr_forward(&d, net.cur_t, l.blob_gpu, &l.out_t, net.dump_int32 ? l.output_int32_gpu : NULL,
+                                      l.quant_stop_flag ? l.output_gpu : NULL, net.stream), "mi355_conv_tr_forward");
+}
+
 /* quant_stop tail shared by the glue layers: l.output = (u8 - zp) * scale (ref: src/maxpool_layer.c:163-171,
  * src/upsample_layer.c:104-112) */
 static void dequant_tail(layer l, network net)
@@ -249,6 +267,20 @@ layer make_convolutional_layer(int batch, int h, int w, int c, int n, int groups
     }
     l.forward = forward_cpu_not_built;
     l.forward_gpu = forward_convolutional_layer_quant_gpu;
+    return l;
+}
+
+/* [deconvolutional], DESIGN.md 7d: the convolution's record and prep fields, the transposed output map (ref: src/deconvolutional_layer.c:68-69) */
+layer make_deconvolutional_layer(int batch, int h, int w, int c, int n, int size, int stride, int padding, ACTIVATION activation,
+                                 int batch_normalize, int quant_stop_flag, int close_quantization, int layer_quantization, int count)
+{
+    layer l = make_convolutional_layer(batch, h, w, c, n, 1, size, stride, padding, activation, batch_normalize, quant_stop_flag,
+                                       close_quantization, layer_quantization, count);
+    l.type = DECONVOLUTIONAL;
+    l.out_h = (h - 1) * stride + size - 2 * padding;
+    l.out_w = (w - 1) * stride + size - 2 * padding;
+    l.outputs = l.out_h * l.out_w * l.out_c;
+    l.forward_gpu = forward_deconvolutional_layer_quant_gpu;
     return l;
 }
 

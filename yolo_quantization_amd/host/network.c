@@ -46,6 +46,7 @@ const char *get_layer_string(LAYER_TYPE t)
 {
     switch (t) {
     case CONVOLUTIONAL: return "CONV";
+    case DECONVOLUTIONAL: return "DECONV";
     case MAXPOOL: return "MAX";
     case ROUTE: return "ROUTE";
     case UPSAMPLE: return "UPSAMPLE";
@@ -150,7 +151,12 @@ static void prep_conv_layer(network *net, int i)
         if (l->weight_data_uint8_scales[ii] == 0) error("zero weight scale (ref: src/blas.c:293 assert)");
         l->mult_zero_point[ii] = (uint32_t)(K * zp_in * (int)l->weight_data_uint8_zero_point[ii]);
         int32_t wsum = 0;
-        for (int jj = 0; jj < K; ++jj) wsum += l->weights_uint8[(size_t)ii * K + jj];
+        if (l->type == DECONVOLUTIONAL) { /* the record is [c][n][k][k]: filter ii's weights, the rows of the flipped w^ */
+            const int kk = l->size * l->size;
+            for (int ci = 0; ci < l->c; ++ci)
+                for (int t = 0; t < kk; ++t) wsum += l->weights_uint8[((size_t)ci * l->n + ii) * kk + t];
+        } else
+            for (int jj = 0; jj < K; ++jj) wsum += l->weights_uint8[(size_t)ii * K + jj];
         l->weights_sum_int[ii] = (int32_t)(l->mult_zero_point[ii] - (uint32_t)(wsum * zp_in));
         l->M[ii] = s_in * l->weight_data_uint8_scales[ii] / l->activ_data_uint8_scales[0];
         quant_multi_smaller_than_one_to_scale_and_shift(l->M[ii], &l->M0[ii], &l->M0_right_shift[ii]);
@@ -164,6 +170,7 @@ static void prep_conv_layer(network *net, int i)
 /* bytes of a conv layer's packed blob: a function of the cfg alone */
 static size_t conv_blob_size(const layer *l)
 {
+    if (l->type == DECONVOLUTIONAL) return mi355_conv_tr_pack_size(l->n, l->c, l->size, l->stride);
     return l->groups > 1 ? mi355_conv_dw_pack_size(l->c, l->size) : mi355_conv_pack_size(l->n, l->c, l->size);
 }
 
@@ -184,11 +191,11 @@ static void alloc_layer_device(network *net, int i)
     }
     if (l->type == YOLO || l->quant_stop_flag)
         check_mi355(mi355_alloc((void **)&l->output_gpu, (size_t)B * l->outputs * sizeof(float)), "alloc float out");
-    if (l->type == CONVOLUTIONAL && net->dump_int32)
+    if (conv_like(l) && net->dump_int32)
         check_mi355(mi355_alloc((void **)&l->output_int32_gpu, (size_t)B * l->outputs * sizeof(int32_t)), "alloc int32 out");
     free(l->output); free(l->output_int32); free(l->output_uint8_final);
     l->output = calloc((size_t)B * l->outputs, sizeof(float));
-    l->output_int32 = l->type == CONVOLUTIONAL ? calloc((size_t)B * l->outputs, sizeof(int32_t)) : NULL;
+    l->output_int32 = conv_like(l) ? calloc((size_t)B * l->outputs, sizeof(int32_t)) : NULL;
     l->output_uint8_final = calloc((size_t)B * l->outputs, sizeof(uint8_t));
 }
 
@@ -333,9 +340,17 @@ void quantization_prep_host(network *net, float in_scale, uint8_t in_zp)
     l0->input_data_uint8_zero_point[0] = in_zp;
     for (int i = 0; i < net->n; ++i) {
         layer *l = &net->layers[i];
-        if (l->type != CONVOLUTIONAL) continue;
+        if (!conv_like(l)) continue;
         prep_conv_layer(net, i);
         /* a 3-filter conv stores 4-byte cells of plain bytes (the image's layout); only a convolution reads those */
+        if (l->type == DECONVOLUTIONAL) {
+            if (net->accum_mode == MI355_ACC_REF_F32)
+                error("[deconvolutional] runs in MI355_ACC_EXACT only: the reference has no integer transposed forward whose fp32 order could be followed");
+            if (l->n == 3 && i + 1 < net->n && net->layers[i + 1].type != CONVOLUTIONAL) {
+                fprintf(stderr, "layer %d: a 3-filter [deconvolutional] can only feed a convolution\n", i);
+                error("unsupported layer after a 3-filter [deconvolutional]");
+            }
+        }
         if (l->n == 3 && ((i + 1 < net->n && net->layers[i + 1].type != CONVOLUTIONAL && net->layers[i + 1].type != ROUTE) ||
                           output_read_elsewhere(net, i))) {
             fprintf(stderr, "layer %d: a 3-filter convolution can only feed another convolution\n", i);
@@ -350,6 +365,11 @@ void quantization_prep_host(network *net, float in_scale, uint8_t in_zp)
         free(l->blob_host);
         l->blob_host = malloc(sz);
         l->blob_bytes = sz;
+        if (l->type == DECONVOLUTIONAL) { /* transposed: its own blob, no epilogue table (the planner offers it to no fusion) */
+            check_mi355(mi355_conv_tr_pack(l->n, l->c, l->size, l->stride, l->weights_uint8, l->weight_data_uint8_zero_point, l->biases_int32,
+                                           l->M_value, l->M0_right_shift_value, l->blob_host), "mi355_conv_tr_pack");
+            continue;
+        }
         if (l->groups > 1) { /* depthwise: its own blob, no epilogue table (the planner offers it to no fusion) */
             check_mi355(mi355_conv_dw_pack(l->c, l->size, l->weights_uint8, l->weight_data_uint8_zero_point, l->biases_int32, l->M_value,
                                            l->M0_right_shift_value, l->blob_host), "mi355_conv_dw_pack");
@@ -467,7 +487,7 @@ void quantization_weights_and_activations_fixed_input(network *net, float in_sca
     quantization_prep_host(net, in_scale, in_zp);
     alloc_network_device(net);
     for (int i = 0; i < net->n; ++i)
-        if (net->layers[i].type == CONVOLUTIONAL) upload_conv(net, i, net->has_host_weights);
+        if (conv_like(&net->layers[i])) upload_conv(net, i, net->has_host_weights);
     net_wait(net);
     net->prepared = 1;
 }
@@ -990,7 +1010,7 @@ void set_batch_network(network *net, int b)
         plan_fusion(net); /* launcher acceptance depends on the batch: flags an earlier EINVAL fallback cleared are re-derived */
         alloc_network_device(net);
         for (int i = 0; i < net->n; ++i)
-            if (net->layers[i].type == CONVOLUTIONAL) upload_conv(net, i, net->has_host_weights);
+            if (conv_like(&net->layers[i])) upload_conv(net, i, net->has_host_weights);
         net_wait(net);
     }
 }
@@ -1073,7 +1093,7 @@ static void run_layers(network *netp)
         layer l = net.layers[i];
         const int asked = fusion_on(&net) ? l.fuse_next : FUSE_NONE;
         l.forward_gpu(l, net);
-        if (l.type == CONVOLUTIONAL) netp->layers[i].conv_kernel = mi355_last_conv_kernel();
+        if (conv_like(&l)) netp->layers[i].conv_kernel = mi355_last_conv_kernel();
         if (ev) check_mi355(mi355_event_record(ev[i + 2], net.stream), "event");
         /* plan_fusion marks candidates by shape; the launchers have the last word.  A fused call they refuse
          * (MI355_EINVAL) was re-run unfused by the conv's forward_gpu, which also cleared fuse_next for good: the layer
@@ -1398,7 +1418,7 @@ size_t network_packed_size(network *net) /* a function of the cfg alone: every r
     sz = (sz + 15) & ~(size_t)15;
     for (int i = 0; i < net->n; ++i) {
         layer *l = &net->layers[i];
-        if (l->type != CONVOLUTIONAL) continue;
+        if (!conv_like(l)) continue;
         const size_t b = conv_blob_size(l);
         if (!b) error("network_packed_size: unsupported convolution shape");
         sz += (b + 15) & ~(size_t)15;
@@ -1421,7 +1441,7 @@ void network_export_packed(network *net, void *buf)
         pack_rec r;
         memset(&r, 0, sizeof(r));
         if (l->activ_data_uint8_scales) { r.s_act = l->activ_data_uint8_scales[0]; r.zp_act = l->activ_data_uint8_zero_point[0]; }
-        if (l->type == CONVOLUTIONAL) { r.s_in = l->input_data_uint8_scales[0]; r.zp_in = l->input_data_uint8_zero_point[0]; }
+        if (conv_like(l)) { r.s_in = l->input_data_uint8_scales[0]; r.zp_in = l->input_data_uint8_zero_point[0]; }
         r.blob_bytes = l->blob_bytes;
         memcpy(p, &r, sizeof(r)); p += sizeof(r);
     }
@@ -1462,7 +1482,7 @@ void network_import_packed_host(network *net, const void *buf, size_t bytes)
         pack_rec r;
         memcpy(&r, &recs[i], sizeof(r));
         if (l->activ_data_uint8_scales) { l->activ_data_uint8_scales[0] = r.s_act; l->activ_data_uint8_zero_point[0] = (uint8_t)r.zp_act; }
-        if (l->type == CONVOLUTIONAL) {
+        if (conv_like(l)) {
             l->input_data_uint8_scales[0] = r.s_in; l->input_data_uint8_zero_point[0] = (uint8_t)r.zp_in;
             if (r.blob_bytes != conv_blob_size(l)) error("network_import_packed: blob size mismatch");
             free(l->blob_host);
@@ -1536,7 +1556,7 @@ void network_import_packed(network *net, const void *buf, size_t bytes)
     plan_fusion(net);
     alloc_network_device(net);
     for (int i = 0; i < net->n; ++i)
-        if (net->layers[i].type == CONVOLUTIONAL) upload_conv(net, i, 0);
+        if (conv_like(&net->layers[i])) upload_conv(net, i, 0);
     net_wait(net);
     net->prepared = 1;
 }
@@ -1639,7 +1659,7 @@ network *network_replica_ex(network *parent, int default_stream)
             l->activ_data_uint8_scales[0] = p->activ_data_uint8_scales[0];
             l->activ_data_uint8_zero_point[0] = p->activ_data_uint8_zero_point[0];
         }
-        if (l->type == CONVOLUTIONAL) {
+        if (conv_like(l)) {
             l->input_data_uint8_scales[0] = p->input_data_uint8_scales[0];
             l->input_data_uint8_zero_point[0] = p->input_data_uint8_zero_point[0];
             l->blob_gpu = p->blob_gpu;

@@ -144,6 +144,31 @@ static layer parse_convolutional(section *o, size_params p, int count)
     return l;
 }
 
+/* [deconvolutional] / [deconv]: the keys of parse_convolutional, read the same way */
+static layer parse_deconvolutional(section *o, size_params p, int count)
+{
+    int n = option_find_int(o, "filters", 1);
+    int size = option_find_int(o, "size", 1);
+    int stride = option_find_int(o, "stride", 1);
+    int pad = option_find_int(o, "pad", 0);
+    int padding = option_find_int(o, "padding", 0);
+    if (pad) padding = size / 2;
+    ACTIVATION act = get_activation(option_find_str(o, "activation", "logistic"));
+    if (act == LOGISTIC) error("[deconvolutional] activation=logistic (or no activation key): the quantized epilogue stores nothing for it; use leaky, relu6, relu or linear");
+    if (!(p.h && p.w && p.c)) error("Layer before deconvolutional layer must output image.");
+    if (p.index == 0) error("[deconvolutional] as the first layer on the image is not built (its 4-byte cells are not served)");
+    if (size < 1 || size > 11) error("[deconvolutional] size must be 1..11");
+    if (stride < 1 || stride > 8) error("[deconvolutional] stride must be 1..8");
+    if (padding < 0 || padding > size - 1) error("[deconvolutional] padding must be 0..size-1 (the dense twin's padding is size - 1 - padding)");
+    if ((p.h - 1) * stride + size - 2 * padding < 1 || (p.w - 1) * stride + size - 2 * padding < 1) error("[deconvolutional] the output map is empty");
+    int bn = option_find_int(o, "batch_normalize", 0);
+    int q = option_find_int(o, "quantized", 0);
+    int qs = option_find_int(o, "quant_stop", 0);
+    layer l = make_deconvolutional_layer(p.batch, p.h, p.w, p.c, n, size, stride, padding, act, bn, qs, p.close_quantization, q, count);
+    l.fisrt_time_train_fag = option_find_int(o, "first_time", 0);
+    return l;
+}
+
 static layer parse_maxpool(section *o, size_params p, int count)
 {
     int stride = option_find_int(o, "stride", 1);
@@ -285,6 +310,7 @@ network *parse_network_cfg(char *filename, int close_quantization)
         p.index = i;
         layer l;
         if (!strcmp(s->type, "[convolutional]") || !strcmp(s->type, "[conv]")) l = parse_convolutional(s, p, i);
+        else if (!strcmp(s->type, "[deconvolutional]") || !strcmp(s->type, "[deconv]")) l = parse_deconvolutional(s, p, i);
         else if (!strcmp(s->type, "[maxpool]") || !strcmp(s->type, "[max]")) l = parse_maxpool(s, p, i);
         else if (!strcmp(s->type, "[upsample]")) l = parse_upsample(s, p, i);
         else if (!strcmp(s->type, "[route]")) l = parse_route(s, p, net, i);
@@ -364,7 +390,7 @@ void load_weights(network *net, char *filename)
     }
     for (int i = 0; i < net->n; ++i) {
         layer l = net->layers[i];
-        if (l.type == CONVOLUTIONAL) load_convolutional_weights(l, fp);
+        if (conv_like(&l)) load_convolutional_weights(l, fp); /* the transposed layer loads the convolution's record (ref :1232) */
         if (l.type == MAXPOOL) load_act_record(l, fp); /* always, ref :1244-1246 */
         if (l.type == ROUTE && l.layer_quant_flag) {   /* ref :1174-1183 */
             if (l.n > 1 && !l.fisrt_time_train_fag) load_act_record(l, fp);

@@ -89,6 +89,11 @@ def layer_shapes(sections: list[dict]) -> tuple[dict, list[LayerShape]]:
             ow = (w + 2 * padding - size) // stride + 1
             L = LayerShape("conv", c, h, w, n, oh, ow, n, size, stride, padding, s.get("activation", "logistic"),
                            int(s.get("batch_normalize", 0)), q, qs, groups=int(s.get("groups", 1)))
+        elif t in ("[deconvolutional]", "[deconv]"):  # the convolution's keys, the transposed output map
+            n = int(s.get("filters", 1)); size = int(s.get("size", 1)); stride = int(s.get("stride", 1))
+            padding = size // 2 if int(s.get("pad", 0)) else int(s.get("padding", 0))
+            L = LayerShape("deconv", c, h, w, n, (h - 1) * stride + size - 2 * padding, (w - 1) * stride + size - 2 * padding, n, size,
+                           stride, padding, s.get("activation", "logistic"), int(s.get("batch_normalize", 0)), q, qs)
         elif t == "[maxpool]":
             stride = int(s.get("stride", 1)); size = int(s.get("size", stride))
             padding = int(s.get("padding", size - 1))
@@ -163,7 +168,7 @@ def synth_weights(cfg_path: str, out_path: str, seed: int = 1234, act_gain: floa
     blob += struct.pack("<iiiQ", 0, 2, 0, 0)
     info = []
     for i, L in enumerate(layers):
-        if L.type == "conv":
+        if L.type in ("conv", "deconv"):
             K = L.c // L.groups * L.size * L.size
             w = (rng.standard_normal((L.n, K)) * np.sqrt(2.0 / K)).astype(np.float32)
             if small_m_channels > 0:
@@ -188,9 +193,16 @@ def synth_weights(cfg_path: str, out_path: str, seed: int = 1234, act_gain: floa
                 qd = np.repeat(wzp[:, None], L.c * kk, axis=1).reshape(L.n, L.c, kk)
                 qd[np.arange(L.n), np.arange(L.n)] = q
                 q, w = qd.reshape(L.n, -1), np.zeros((L.n, L.c * kk), np.float32)
+            rec = {"i": i, "type": L.type, "K": K, "n": L.n}
+            if L.type == "deconv":
+                # the rows drawn above are the filters of the flipped w^; the file holds the reference's [c][n][k][k]
+                unflip = lambda a: np.ascontiguousarray(a.reshape(L.n, L.c, L.size, L.size)[:, :, ::-1, ::-1].transpose(1, 0, 2, 3))
+                rec.update(w_hat=q.copy(), weights_uint8=unflip(q), zp_w=wzp, s_w=wscale, biases=bias,
+                           bn=(sc, mean, var) if L.batch_normalize else (None, None, None))
+                q, w = unflip(q), unflip(w)
             blob += wscale.tobytes() + wzp.tobytes() + q.tobytes() + w.tobytes()
             act_q.append((a_s, a_zp))
-            info.append({"i": i, "type": "conv", "K": K, "n": L.n})
+            info.append(rec)
         elif L.type == "maxpool":
             a = _glue_record(act_q[i - 1], i, glue_own_zp)
             blob += struct.pack("<fB", float(a[0]), int(a[1]))
