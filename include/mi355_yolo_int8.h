@@ -287,6 +287,35 @@ int mi355_conv_tr_pack(int n, int c, int ksize, int stride, const uint8_t *weigh
 int mi355_conv_tr_forward(const mi355_conv_desc *desc, const mi355_tensor *x, const void *blob, const mi355_tensor *y,
                           int32_t *acc_out, float *y_f32, void *stream);
 
+/* Grouped convolution, `[convolutional] groups=g` with any g that divides both the channels and the filters (the ResNeXt / ShuffleNet
+ * blocks; g = 1 is the dense layer, g = c = n the depthwise one, cg = 1 with ng > 1 a channel multiplier).  The reference's prep overruns
+ * for groups != 1 (src/blas.c:290-311), so the integer layer is builder-specified: the reference's forward loop over
+ * groups (src/convolutional_layer.c:697-722) in exact int32.  With cg = c / g, ng = n / g, K = cg ksize^2, filter j reads the input
+ * channels [(j / ng) cg, (j / ng + 1) cg):  acc[j][p] = sum_{ci < cg, taps} (w[j][ci][tap] - zp_w[j]) x[(j / ng) cg + ci][tap(p)], modulo
+ * 2^32, out-of-image taps = desc.zp_in; biases_int32 / M_value / shift_value the caller's (src/blas.c:313-333 with that K); the epilogue
+ * (both stores, leaky / relu / relu6 / linear, acc_out, y_f32) mi355_conv_forward's.  It equals the dense c -> n layer whose weight of
+ * filter j on a channel outside its group is zp_w[j].  The kernel (conv_group.hip) is a block-diagonal GEMM: it multiplies and reads the
+ * weights of the groups only.
+ *   mi355_conv_group_pack_size   bytes of the blob, a function of (n, c, groups, ksize) only; 0 outside n, c, groups >= 1,
+ *                                c % groups == n % groups == 0, 1 <= ksize <= 11
+ *   mi355_conv_group_pack        weights_uint8: the reference's record [n][cg ksize ksize] in (ci, ky, kx) order; zp_w, biases_int32,
+ *                                M_value, shift_value per filter; position independent like mi355_conv_pack's blob, same conditions on
+ *                                M_value / shift_value
+ *   mi355_conv_group_forward     `groups` is an argument of the call: mi355_conv_desc is unchanged.  desc.stride >= 1, desc.pad >= 0,
+ *                                ksize 1 only at stride 1 and pad 0, a non-empty output map, MI355_ACC_EXACT only; x.C == desc.c,
+ *                                x.cs % 16 == 0 and y.cs % 16 == 0, x.data and blob 16-byte aligned.  The tensor's pad cells are never read.
+ *                                y (nullable), acc_out ([B][n][OH * OW]) and y_f32 as in mi355_conv_forward; channels >= n of y's cells keep
+ *                                their bytes.  No fused form.  Anything else returns MI355_EINVAL with a message that starts
+ *                                "conv_group_forward:", nothing launched or written; a group whose pieces do not fit in LDS at 64 pixels
+ *                                (from cg = 512 at ksize 11, stride 1) says "no tile fits".
+ *                                The caller guarantees that the blob was packed for (desc.n, desc.c, groups, desc.ksize), as for every blob.
+ * New calls, no struct change: MI355_ABI_VERSION is unchanged. */
+size_t mi355_conv_group_pack_size(int n, int c, int groups, int ksize);
+int mi355_conv_group_pack(int n, int c, int groups, int ksize, const uint8_t *weights_uint8, const uint8_t *zp_w, const int32_t *biases_int32,
+                          const double *M_value, const double *shift_value, void *blob);
+int mi355_conv_group_forward(const mi355_conv_desc *desc, const mi355_tensor *x, const void *blob, int groups, const mi355_tensor *y,
+                             int32_t *acc_out, float *y_f32, void *stream);
+
 /* Tile configuration override for benchmarking (0 = auto). */
 int mi355_conv_set_tile(int bm, int bn);
 /* Development switches.  Bits 0..8 are timing ablations of the K loop (no DMA / no s_barrier / no MFMA / ...), compiled
@@ -303,7 +332,8 @@ int mi355_debug_flags(int flags);
  * the kernel it is meant to exercise): 0 none yet, 1 first layer (conv_aux.hip), 2 conv_small.hip (few-channel / 64-channel
  * conv + maxpool), 3 conv1x1.hip, 4 conv_ws3.hip, 5 conv_igemm.hip / conv_rows.hip / conv_rows16.hip, 6 fp32-accumulate emulation,
  * 7 conv_pool16.hip (16 -> 32 + maxpool with the packed epilogue table), 8 conv_small32.hip (32 -> 64 + maxpool), 9 conv_kxk.hip (the
- * general shapes), 10 conv_dw.hip (mi355_conv_dw_forward), 11 conv_tr.hip (mi355_conv_tr_forward). */
+ * general shapes), 10 conv_dw.hip (mi355_conv_dw_forward), 11 conv_tr.hip (mi355_conv_tr_forward),
+ * 12 conv_group.hip (mi355_conv_group_forward). */
 int mi355_last_conv_kernel(void);
 /* Geometry of the calling thread's most recent convolution kernel launch (any mi355_conv_*forward call): workgroups in the grid,
  * threads per workgroup, bytes of dynamic LDS, as the launcher chose them for the plan, batch and tile count.  Each pointer may be

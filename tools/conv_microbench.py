@@ -7,6 +7,7 @@
   python tools/conv_microbench.py --dw [--out FILE]   # depthwise 3x3 (conv_dw.hip) against its dense twin and the HBM floor
   python tools/conv_microbench.py --spp [--out FILE]  # the fused SPP pools (spp.hip) against the three plain pools and the HBM floor
   python tools/conv_microbench.py --tr [--out FILE]   # transposed k4 s2 / k2 s2 (conv_tr.hip) against its stuffed dense twin and the HBM floor
+  python tools/conv_microbench.py --group [--out FILE]  # grouped 3x3 (conv_group.hip) against its dense twin and the HBM floor
 """
 import argparse
 import ctypes as C
@@ -225,12 +226,58 @@ def run_tr(iters, repeats):
     return out
 
 
+def run_group(iters, repeats):
+    """The grouped kernel (conv_group.hip) on 3x3 layers of cardinality 32 -- 128 x 52 x 52, 256 x 26 x 26 at stride 1 and 2,
+    512 x 13 x 13 -- and on 256 x 26 x 26 with two groups, n = c, batch 32, each against two baselines: its dense twin (DESIGN.md 7e:
+    weights outside a filter's group = the filter's zero point: the same bytes out) on the dense kernels, and the HBM floor, tensor
+    bytes in + out over the bandwidth a device-to-device copy of 256 MiB reaches in this process.  The two kernels alternate,
+    `repeats` rounds; medians and ranges in microseconds."""
+    S = binding.shim()
+    st = C.c_void_p(); binding.check(S.mi355_stream_create(C.byref(st)))
+    nb = 256 << 20
+    src, dst = binding.DevBuf(nb), binding.DevBuf(nb)
+    copy_us = [_time_us(lambda: binding.check(S.mi355_d2d(dst.ptr, src.ptr, nb, st), "d2d"), st, 10) for _ in range(repeats)]
+    bw = 2.0 * nb / (np.median(copy_us) * 1e-6)  # bytes read + written per second
+    src.free(); dst.free()
+    out = {"copy_256MiB_us": copy_us, "copy_bytes_per_s": bw, "iters": iters, "cases": []}
+    for c, hw, g, stride in ((128, 52, 32, 1), (256, 26, 32, 1), (256, 26, 32, 2), (512, 13, 32, 1), (256, 26, 2, 1)):
+        rng = np.random.default_rng(c + g + stride)
+        B, k, n, cg = 32, 3, c, c // g
+        x = rng.integers(0, 256, (B, c, hw, hw), dtype=np.uint8)
+        wq = rng.integers(0, 256, (n, cg * k * k), dtype=np.uint8)
+        zp_w = rng.integers(100, 157, n, dtype=np.uint8)
+        bias = np.zeros(n, np.int32); mv = np.full(n, 0.75); sv = np.full(n, 2.0 ** -(7 + int(np.log2(cg))))
+        wd = np.repeat(zp_w[:, None], c * k * k, axis=1).reshape(n, c, k * k)
+        for j in range(n):
+            wd[j, j // cg * cg:(j // cg + 1) * cg] = wq[j].reshape(cg, k * k)  # (n == c: ng == cg)
+        ohw = (hw + 2 - k) // stride + 1
+        xt = binding.DevTensor.from_nchw(x, 0)
+        y, yd = binding.DevTensor(B, ohw, ohw, n, 23), binding.DevTensor(B, ohw, ohw, n, 23)
+        blob = binding.DevBuf.from_numpy(binding.conv_group_pack(wq, zp_w, g, c, k, bias, mv, sv))
+        blobd = binding.DevBuf.from_numpy(binding.conv_pack(wd.reshape(n, -1), zp_w, c, k, bias, mv, sv))
+        d = binding.ConvDesc(n, c, k, stride, 1, binding.ACT["leaky"], 0, 0, 0, 23, 1.0)
+        grp = lambda: binding.check(S.mi355_conv_group_forward(C.byref(d), xt.ref(), blob.ptr, g, y.ref(), None, None, st), "group")
+        dense = lambda: binding.check(S.mi355_conv_forward(C.byref(d), xt.ref(), blobd.ptr, None, None, yd.ref(), None, None, st), "dense")
+        t_grp, t_dense = [], []
+        for _ in range(repeats):
+            t_grp.append(_time_us(grp, st, iters)); t_dense.append(_time_us(dense, st, iters))
+        S.mi355_stream_sync(st)
+        same = bool(np.array_equal(y.to_nchw(), yd.to_nchw()))
+        floor_us = (B * (c * hw * hw + n * ohw * ohw)) / bw * 1e6
+        out["cases"].append({"c": c, "hw": hw, "n": n, "groups": g, "k": k, "stride": stride, "batch": B, "group_us": t_grp,
+                             "dense_twin_us": t_dense, "dense_kernel": binding.last_conv_kernel(), "bytes_equal": same,
+                             "hbm_floor_us": floor_us, "group_over_dense": float(np.median(t_grp) / np.median(t_dense)),
+                             "group_over_floor": float(np.median(t_grp) / floor_us)})
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--group", action="store_true", help="grouped 3x3 against its dense twin and the HBM floor")
     ap.add_argument("--tr", action="store_true", help="transposed k4 s2 / k2 s2 against the stuffed dense twin and the HBM floor")
     ap.add_argument("--dw", action="store_true", help="depthwise 3x3 against its dense twin and the HBM floor")
     ap.add_argument("--spp", action="store_true", help="the fused SPP pools against the three plain pools and the HBM floor")
-    ap.add_argument("--out", default="", help="--dw, --spp, --tr: also write the JSON here")
+    ap.add_argument("--out", default="", help="--dw, --spp, --tr, --group: also write the JSON here")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--c", type=int, default=256); ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--hw", type=int, default=52); ap.add_argument("--k", type=int, default=3)
@@ -248,8 +295,9 @@ if __name__ == "__main__":
     binding.init(0)
     if a.dbg:
         binding.shim().mi355_debug_flags(a.dbg)
-    if a.dw or a.spp or a.tr:
-        r = run_tr(a.iters, a.repeats) if a.tr else (run_spp(a.iters, a.repeats) if a.spp else run_dw(a.iters, a.repeats))
+    if a.dw or a.spp or a.tr or a.group:
+        fn = run_group if a.group else (run_tr if a.tr else (run_spp if a.spp else run_dw))
+        r = fn(a.iters, a.repeats)
         print(json.dumps(r))
         if a.out:
             with open(a.out, "w") as f:

@@ -270,6 +270,11 @@ def shim():
             L.mi355_conv_tr_pack_size.restype = C.c_size_t
             L.mi355_conv_tr_pack.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
             L.mi355_conv_tr_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.POINTER(Tensor), vp, vp, vp]
+        if hasattr(L, "mi355_conv_group_forward"):  # (MI355_LIB_DIR may name an older build)
+            L.mi355_conv_group_pack_size.argtypes = [ci, ci, ci, ci]
+            L.mi355_conv_group_pack_size.restype = C.c_size_t
+            L.mi355_conv_group_pack.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+            L.mi355_conv_group_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, ci, C.POINTER(Tensor), vp, vp, vp]
         L.mi355_last_conv_kernel.argtypes = []
         L.mi355_last_conv_kernel.restype = ci
         if hasattr(L, "mi355_last_conv_launch"):  # (absent from older A/B builds under build_ab/)
@@ -570,6 +575,49 @@ def conv_tr_forward(x: DevTensor, wq, zp_w, ksize, stride, pad, biases_int32, M_
     d = ConvDesc(n, x.t.C, ksize, stride, pad, activation, store, accum, zp_in, zp_act, float(s_act), int(plan), 0)
     check(shim().mi355_conv_tr_forward(C.byref(d), x.ref(), blob.ptr, y.ref(), acc.ptr if acc else None,
                                        f32.ptr if f32 else None, None), "conv_tr_forward")
+    check(shim().mi355_stream_sync(None), "sync")
+    out = {"u8": y.to_nchw(), "tensor": y}
+    if acc:
+        out["int32"] = acc.to_numpy(np.int32, cnt).reshape(x.t.B, n, OH * OW)
+    if f32:
+        out["f32"] = f32.to_numpy(np.float32, cnt).reshape(x.t.B, n, OH * OW)
+    return out
+
+
+def conv_group_pack(wq, zp_w, groups, c, ksize, biases_int32, M_value, shift_value):
+    """mi355_conv_group_pack -> numpy uint8 blob of a grouped layer; wq: the reference's record [n, c / groups * ksize * ksize]"""
+    wq = np.ascontiguousarray(wq, np.uint8)
+    n = wq.shape[0]
+    sz = shim().mi355_conv_group_pack_size(n, c, groups, ksize)
+    if not sz:
+        raise MI355Error(f"unsupported grouped shape n={n} c={c} groups={groups} k={ksize}")
+    blob = np.zeros(sz, np.uint8)
+    zp_w = np.ascontiguousarray(zp_w, np.uint8)
+    b = np.ascontiguousarray(biases_int32, np.int32)
+    mv = np.ascontiguousarray(M_value, np.float64)
+    sv = np.ascontiguousarray(shift_value, np.float64)
+    check(shim().mi355_conv_group_pack(n, c, groups, ksize, wq.ctypes.data, zp_w.ctypes.data, b.ctypes.data, mv.ctypes.data, sv.ctypes.data,
+                                       blob.ctypes.data), "conv_group_pack")
+    return blob
+
+
+def conv_group_forward(x: DevTensor, wq, zp_w, groups, ksize, biases_int32, M_value, shift_value, zp_in, zp_act, s_act, activation,
+                       store=STORE_WRAP, accum=ACC_EXACT, want_acc=True, want_f32=False, stride=1, pad=None, plan=0, y=None):
+    """One grouped layer (filter j reads the channels of group j // (n // groups)) through mi355_conv_group_forward; wq: [n, c / groups *
+    ksize * ksize]; result as conv_tr_forward.  y: the output DevTensor to write into (default: a fresh one filled with zp_act)."""
+    n, c = np.shape(wq)[0], x.t.C
+    blob = DevBuf.from_numpy(conv_group_pack(wq, zp_w, groups, c, ksize, biases_int32, M_value, shift_value))
+    if pad is None:
+        pad = ksize // 2
+    OH, OW = (x.t.H + 2 * pad - ksize) // stride + 1, (x.t.W + 2 * pad - ksize) // stride + 1
+    if y is None:
+        y = DevTensor(x.t.B, OH, OW, n, zp_act)
+    cnt = x.t.B * n * OH * OW
+    acc = DevBuf(cnt * 4) if want_acc else None
+    f32 = DevBuf(cnt * 4) if want_f32 else None
+    d = ConvDesc(n, c, ksize, stride, pad, activation, store, accum, zp_in, zp_act, float(s_act), int(plan), 0)
+    check(shim().mi355_conv_group_forward(C.byref(d), x.ref(), blob.ptr, int(groups), y.ref(), acc.ptr if acc else None,
+                                          f32.ptr if f32 else None, None), "conv_group_forward")
     check(shim().mi355_stream_sync(None), "sync")
     out = {"u8": y.to_nchw(), "tensor": y}
     if acc:

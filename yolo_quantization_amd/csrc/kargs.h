@@ -305,6 +305,103 @@ struct TrArgs {
 };
 int conv_tr_launch(TrArgs &a, hipStream_t st);  // MI355_EINVAL when the grid does not fit (nothing launched)
 
+// conv_group.hip: the grouped convolution (1 <= groups) as a block-diagonal GEMM on V_MFMA_I32_16X16X64_I8.  M tile t
+// holds filters 16 t .. 16 t + 15; filter j belongs to group j / ng and reads channels [(j / ng) cg, (j / ng + 1) cg).  A PIECE is
+// one 16-byte run of 16 channels of a cell; a SLOT is (piece, tap), one 16-lane group of a K-step.  A tile's K is cut into SEGMENTS
+// at group boundaries: groups join a segment while its piece range stays within GRP_SEG_PIECES, a larger group is a segment alone.
+// A segment's slots are (piece p0 + i, tap t) -> slot i k k + t, padded to whole K-steps with slots that point at (p0, tap 0)
+// against zero weights.  Rows whose group lies outside the segment are zero in it, so a piece shared by two segments counts once.
+// The blob (mi355_conv_group_pack) is a function of (n, c, groups, ksize) alone:
+//     tseg    int32 [mtiles + 1]   first segment of each tile
+//     seg     GrpSeg [nsegs]
+//     frag    per segment: slot table int32 [4 nsteps] (piece - p0) << 8 | tap, then per K-step the weight fragment and the
+//             indicator fragment (1 where the row's weight is live), each [64 lanes][16 B] in MFMA lane order
+//     rows    GrpRow [16 mtiles]   per filter: d = 128 - zp_w, cst = 128 sum w' + 128 K d, the bias and the epilogue's multipliers
+#define MI355_GRP_MAGIC 0x4D494752u /* "MIGR" */
+constexpr int GRP_SEG_PIECES = 16;
+constexpr int GRP_MAX_TAPS = 128;  // tap slots of the kernel's offset table (11 x 11: 121)
+struct GrpSeg {
+    int32_t tile, p0, npieces, nsteps;
+    int32_t first, last;     // first / last segment of its tile: clear the accumulators / run the epilogue
+    uint32_t off16;          // slot table, then fragments: 16-byte units from off_frag
+    int32_t qa;              // first group of the segment (the last follows from the walk in grp_tile_segs)
+};
+struct GrpRow {
+    int32_t d, cst, bias, pad_;
+    double mval, sval, mprime;  // mprime = M_value * shift_value (common.h requant_q_exact)
+};
+struct GrpBlobHeader {
+    uint32_t magic;
+    int32_t n, c, groups, ksize, mtiles, nsegs;
+    int32_t pow2;            // 1: every shift_value is an exact power of two (ConvBlobHeader.pow2)
+    uint64_t off_tseg, off_seg, off_frag, off_rows, total;
+};
+inline bool grp_domain(int n, int c, int g, int ksize) { return n >= 1 && c >= 1 && g >= 1 && c % g == 0 && n % g == 0 && ksize >= 1 && ksize <= 11; }
+// the segments of M tile t: piece range [p0, p0 + np) and group range [qa, qb] each; returns their number (at most 16)
+inline int grp_tile_segs(int n, int c, int g, int t, int *p0, int *np, int *qa, int *qb)
+{
+    const int cg = c / g, ng = n / g;
+    const int ga = 16 * t / ng, gb = (16 * t + 15 < n ? 16 * t + 15 : n - 1) / ng;
+    int cnt = 0;
+    for (int a = ga; a <= gb; ++cnt) {
+        const int first = (int)((long)a * cg / 16);
+        int b = a;
+        while (b + 1 <= gb && (int)(((long)(b + 2) * cg - 1) / 16) - first + 1 <= GRP_SEG_PIECES) ++b;
+        p0[cnt] = first; np[cnt] = (int)(((long)(b + 1) * cg - 1) / 16) - first + 1; qa[cnt] = a; qb[cnt] = b;
+        a = b + 1;
+    }
+    return cnt;
+}
+inline bool grp_blob_layout(int n, int c, int g, int ksize, GrpBlobHeader *h)
+{
+    if (!grp_domain(n, c, g, ksize)) return false;
+    *h = GrpBlobHeader{};
+    h->magic = MI355_GRP_MAGIC; h->n = n; h->c = c; h->groups = g; h->ksize = ksize; h->mtiles = (n + 15) / 16;
+    uint64_t frag = 0;
+    int p0[16], np[16], qa[16], qb[16];
+    for (int t = 0; t < h->mtiles; ++t) {
+        const int ns = grp_tile_segs(n, c, g, t, p0, np, qa, qb);
+        h->nsegs += ns;
+        for (int i = 0; i < ns; ++i) {
+            const uint64_t nsteps = ((uint64_t)np[i] * ksize * ksize + 3) / 4;
+            frag += nsteps * (16 + 2048);
+        }
+    }
+    if (frag / 16 > 0xFFFFFFFFull) return false;
+    const uint64_t rows = (uint64_t)h->mtiles * 16;
+    uint64_t off = (sizeof(GrpBlobHeader) + 15) & ~(uint64_t)15;
+    h->off_tseg = off;   off = (off + ((uint64_t)h->mtiles + 1) * 4 + 15) & ~(uint64_t)15;
+    h->off_seg = off;    off += (uint64_t)h->nsegs * sizeof(GrpSeg);
+    h->off_frag = off;   off += frag;
+    h->off_rows = off;   off += rows * sizeof(GrpRow);
+    h->total = off;
+    return true;
+}
+struct GrpArgs {
+    const uint8_t *x;        // input tensor, biased PHWC (cs % 16 == 0, data 16-byte aligned)
+    int in_cs, in_lead;
+    int B, H, W, c;
+    int n, groups, ksize, stride, pad, OH, OW;
+    const int32_t *tseg;
+    const GrpSeg *seg;
+    const char *frag;
+    const GrpRow *rows;
+    const GrpBlobHeader *hdr; // device copy (pow2 flag)
+    uint8_t *y;
+    int out_cs, out_lead;
+    int32_t *acc_out;
+    float *y_f32;
+    int zp_in, zp_act, act, store_mode;
+    float s_act;
+    int plan;
+    // tile geometry (set by the launcher)
+    int mtiles, mb, fblocks; // M tiles, M tiles per filter block, filter blocks
+    int tw_sh, tiles_x, tiles_y, ph, pw;
+    int plane;               // LDS cells between the planes of two pieces (odd)
+    int restage;             // 1: a segment's pieces are staged when it is walked (the block's pieces do not fit together)
+};
+int conv_group_launch(GrpArgs &a, hipStream_t st);  // MI355_EINVAL when no tile fits LDS (nothing launched)
+
 // spp.hip: up to three stride-1 "same" max pools of one tensor in one launch (the SPP block of yolov3-spp / yolov4), computed as a
 // cascade: level i is the box max of size d[i] of level i - 1, level 0 being x, so that level i is x's pool of size sizes[i].
 constexpr int SPP_MAX = 3;       // levels

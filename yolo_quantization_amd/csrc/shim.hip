@@ -1129,6 +1129,120 @@ int mi355_conv_tr_forward(const mi355_conv_desc *d, const mi355_tensor *x, const
     return rc;
 }
 
+// ------------------------------------------------------------------------------------- grouped convolution (conv_group.hip)
+size_t mi355_conv_group_pack_size(int n, int c, int groups, int ksize)
+{
+    GrpBlobHeader h;
+    return grp_blob_layout(n, c, groups, ksize, &h) ? (size_t)h.total : 0;
+}
+
+int mi355_conv_group_pack(int n, int c, int groups, int ksize, const uint8_t *wq, const uint8_t *zp_w, const int32_t *biases_int32,
+                          const double *M_value, const double *shift_value, void *blob)
+{
+    GrpBlobHeader h;
+    if (!grp_blob_layout(n, c, groups, ksize, &h))
+        return einval("conv_group_pack: need n >= 1, c >= 1, groups >= 1 that divides both, and 1 <= ksize <= 11");
+    if (!wq || !zp_w || !biases_int32 || !M_value || !shift_value || !blob) return einval("conv_group_pack: null");
+    h.pow2 = 1;
+    for (int j = 0; j < n; ++j) {
+        if (!(M_value[j] > 0.0 && M_value[j] < 1.0) || !(shift_value[j] > 0.0 && shift_value[j] <= 1.0))
+            return einval("conv_group_pack: need 0 < M_value < 1 and 0 < shift_value <= 1 (ref asserts 0<M<1, src/blas.c:391-392)");
+        int e = 0;
+        if (frexp(shift_value[j], &e) != 0.5 || e > 1 || e < -30) h.pow2 = 0;  // as mi355_conv_pack: 2^-s, 0 <= s <= 31
+    }
+    char *base = (char *)blob;
+    memset(base, 0, (size_t)h.total);
+    memcpy(base, &h, sizeof(h));
+    const int kk = ksize * ksize, cg = c / groups, ng = n / groups, K = cg * kk;
+    for (int j = 0; j < n; ++j) {
+        long sw = 0;
+        for (int i = 0; i < K; ++i) sw += (int)wq[(size_t)j * K + i] - 128;
+        const long d = 128 - (long)zp_w[j];
+        // (cst modulo 2^32, like the accumulators)
+        ((GrpRow *)(base + h.off_rows))[j] = GrpRow{(int32_t)d, (int32_t)(uint32_t)(128 * sw + 128 * (long)K * d), biases_int32[j], 0,
+                                                   M_value[j], shift_value[j], M_value[j] * shift_value[j]};
+    }
+    int32_t *tseg = (int32_t *)(base + h.off_tseg);
+    GrpSeg *seg = (GrpSeg *)(base + h.off_seg);
+    uint64_t off = 0;
+    int nseg = 0, p0[16], np[16], qa[16], qb[16];
+    for (int t = 0; t < h.mtiles; ++t) {
+        tseg[t] = nseg;
+        const int ns = grp_tile_segs(n, c, groups, t, p0, np, qa, qb);
+        for (int i = 0; i < ns; ++i, ++nseg) {
+            const int nslots = np[i] * kk, nsteps = (nslots + 3) / 4;
+            seg[nseg] = GrpSeg{t, p0[i], np[i], nsteps, i == 0, i == ns - 1, (uint32_t)(off / 16), qa[i]};
+            int32_t *slots = (int32_t *)(base + h.off_frag + off);
+            int8_t *fr = (int8_t *)(slots + 4 * nsteps);
+            for (int sl = 0; sl < nslots; ++sl) slots[sl] = (sl / kk) << 8 | (sl % kk);
+            // lane (row lane % 16, slot 4 step + lane / 16) of a K-step: byte e = channel 16 piece + e, live inside the row's own group
+            for (int st = 0; st < nsteps; ++st)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int j = 16 * t + (lane & 15), sl = 4 * st + (lane >> 4);
+                    if (j >= n || sl >= nslots || j / ng < qa[i] || j / ng > qb[i]) continue;
+                    const int q = j / ng, tap = sl % kk;
+                    int8_t *wf = fr + ((size_t)st * 128 + lane) * 16, *jf = wf + 1024;
+                    for (int e = 0; e < 16; ++e) {
+                        const int ci = 16 * (p0[i] + sl / kk) + e - q * cg;
+                        if (ci < 0 || ci >= cg) continue;
+                        wf[e] = (int8_t)(wq[(size_t)j * K + (size_t)ci * kk + tap] ^ 0x80);
+                        jf[e] = 1;
+                    }
+                }
+            off += (uint64_t)nsteps * (16 + 2048);
+        }
+    }
+    tseg[h.mtiles] = nseg;
+    return MI355_OK;
+}
+
+int mi355_conv_group_forward(const mi355_conv_desc *d, const mi355_tensor *x, const void *blob, int groups, const mi355_tensor *y,
+                             int32_t *acc_out, float *y_f32, void *stream)
+{
+    if (!d || !x || !x->data || !blob) return einval("conv_group_forward: null");
+    if (d->n < 1 || d->c < 1 || groups < 1) return einval("conv_group_forward: need n >= 1, c >= 1 and groups >= 1");
+    if (d->c % groups) return einval("conv_group_forward: groups must divide the channels (desc.c)");
+    if (d->n % groups) return einval("conv_group_forward: groups must divide the filters (desc.n)");
+    if (d->ksize < 1 || d->ksize > 11) return einval("conv_group_forward: size must be 1..11");
+    if (d->stride < 1 || d->pad < 0) return einval("conv_group_forward: need stride >= 1 and pad >= 0");
+    if (d->ksize == 1 && (d->stride != 1 || d->pad != 0))
+        return einval("conv_group_forward: a 1x1 layer needs stride 1 and pad 0, as for the dense call");
+    if (d->accum_mode != MI355_ACC_EXACT)
+        return einval("conv_group_forward: MI355_ACC_EXACT only (there is no reference fp32 order to follow once K 255^2 >= 2^24)");
+    if (d->activation != MI355_ACT_LEAKY && d->activation != MI355_ACT_RELU && d->activation != MI355_ACT_RELU6 && d->activation != MI355_ACT_LINEAR)
+        return einval("conv_group_forward: activation must be leaky, relu, relu6 or linear");
+    if (x->cs % 16 || x->cs < (d->c + 15) / 16 * 16)
+        return einval("conv_group_forward: x.cs must be a multiple of 16 that holds the channels (the 3-channel image's 4-byte cells are not served)");
+    if (x->C != d->c) return einval("conv_group_forward: x.C != desc.c");
+    const long OHl = ((long)x->H + 2L * d->pad - d->ksize) / d->stride + 1, OWl = ((long)x->W + 2L * d->pad - d->ksize) / d->stride + 1;
+    if (x->H < 1 || x->W < 1 || x->H + 2L * d->pad < d->ksize || x->W + 2L * d->pad < d->ksize || OHl < 1 || OWl < 1)
+        return einval("conv_group_forward: the output map is empty (the padded map is smaller than the kernel)");
+    if (y && (y->C != d->n || y->B != x->B || y->H != OHl || y->W != OWl || !y->data || y->cs % 16 || y->cs < d->n))
+        return einval("conv_group_forward: y shape (y.cs must be a multiple of 16 that holds the filters)");
+    if (((uintptr_t)x->data & 15) || ((uintptr_t)blob & 15) || (y && ((uintptr_t)y->data & 3)))
+        return einval("conv_group_forward: x.data and blob must be aligned to 16 bytes, y.data to 4");
+    GrpBlobHeader h;
+    if (!grp_blob_layout(d->n, d->c, groups, d->ksize, &h)) return einval("conv_group_forward: the blob of this shape is too large");
+    const char *base = (const char *)blob;
+    GrpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = (const uint8_t *)x->data; a.in_cs = x->cs; a.in_lead = x->lead;
+    a.B = x->B; a.H = x->H; a.W = x->W; a.c = d->c;
+    a.n = d->n; a.groups = groups; a.ksize = d->ksize; a.stride = d->stride; a.pad = d->pad; a.OH = (int)OHl; a.OW = (int)OWl;
+    a.tseg = (const int32_t *)(base + h.off_tseg); a.seg = (const GrpSeg *)(base + h.off_seg); a.frag = base + h.off_frag;
+    a.rows = (const GrpRow *)(base + h.off_rows);
+    a.hdr = (const GrpBlobHeader *)base;
+    a.y = y ? (uint8_t *)y->data : nullptr; a.out_cs = y ? y->cs : 0; a.out_lead = y ? y->lead : 0;
+    a.acc_out = acc_out; a.y_f32 = y_f32;
+    a.zp_in = d->zp_in; a.zp_act = d->zp_act; a.act = d->activation; a.store_mode = d->store_mode; a.s_act = d->s_act;
+    a.plan = d->plan;
+    const int rc = conv_group_launch(a, (hipStream_t)stream);
+    if (rc == MI355_EINVAL) return einval("conv_group_forward: no tile fits: the pieces of one group at this size and stride exceed LDS");
+    if (rc != MI355_OK) return hip_fail(hipGetLastError(), "conv_group launch");
+    g_last_kernel = 12;
+    return rc;
+}
+
 int mi355_conv_yolo_forward(const mi355_conv_desc *d, const mi355_tensor *x, const void *blob, const mi355_tensor *y,
                             float *y_f32, float *yolo_out, int classes, void *stream)
 {
