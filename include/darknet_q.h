@@ -117,6 +117,7 @@ struct layer {
     int spp_n, spp_pool[3]; /* leader: pools of the group and their layer indices, itself first */
     int conv_kernel;    /* kernel family that served this conv's last forward (mi355_last_conv_kernel) */
     int prepared;
+    int dilation;       /* [convolutional] dilation=: 1 = the dense layer; above 1 the layer runs on conv_dil.hip, unfused */
 };
 
 /* The buffers of one coded-image input path (JPEG, PNG): lazily allocated, grown when needed, freed with the network. */

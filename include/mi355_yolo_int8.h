@@ -316,6 +316,25 @@ int mi355_conv_group_pack(int n, int c, int groups, int ksize, const uint8_t *we
 int mi355_conv_group_forward(const mi355_conv_desc *desc, const mi355_tensor *x, const void *blob, int groups, const mi355_tensor *y,
                              int32_t *acc_out, float *y_f32, void *stream);
 
+/* Dilated (atrous) convolution ([convolutional] dilation=d; DeepLab's ASPP, RFB, TridentNet, ENet / ERFNet bodies).  The reference has
+ * no such layer; the definition is this library's.  With D = dilation (ksize - 1) + 1, OH = H + 2 pad - D + 1 and OW likewise, stride 1:
+ *     acc[j][oy][ox] = sum_{ci, ky, kx} (w[j][ci][ky][kx] - zp_w[j]) x[ci][oy - pad + ky dilation][ox - pad + kx dilation]
+ * modulo 2^32, out-of-image taps = desc.zp_in.  Weights, biases_int32, M_value and shift_value are exactly the dense c -> n, ksize x
+ * ksize layer's (K = c ksize ksize), and so is the blob: pack with mi355_conv_pack, there is no packer of its own.  The epilogue (both
+ * stores, leaky / relu / relu6 / linear, acc_out, y_f32) is mi355_conv_forward's.  At dilation 1 the layer is the dense layer; for
+ * D <= 11 it is the dense D x D layer whose weight off the tap lattice is zp_w[j].  The kernel (conv_dil.hip) runs the layer as
+ * dilation x dilation dense convolutions on the phase-subsampled maps, gathered and scattered in place.
+ *   mi355_conv_dil_forward   `dilation` is an argument of the call: mi355_conv_desc is unchanged.  dilation >= 1, ksize 2..11,
+ *                            desc.stride == 1, desc.pad >= 0, a non-empty output map, MI355_ACC_EXACT only; x.C == desc.c, y.C == desc.n,
+ *                            x.cs % 16 == 0 and y.cs % 16 == 0 (not the image's 4-byte cells), x.data, y.data and blob 16-byte aligned; a
+ *                            blob of mi355_conv_pack(desc.n, desc.c, desc.ksize), which carries the general-kernel fragments for every
+ *                            ksize >= 2.  The tensor's pad cells are never read.  y (nullable), acc_out ([B][n][OH * OW]) and y_f32 as in
+ *                            mi355_conv_forward; channels >= n of y's cells keep their bytes.  No fused form.  Anything else returns
+ *                            MI355_EINVAL with a message that starts "conv_dil_forward:", nothing launched or written.
+ * A new call, no struct change: MI355_ABI_VERSION is unchanged. */
+int mi355_conv_dil_forward(const mi355_conv_desc *desc, const mi355_tensor *x, const void *blob, int dilation, const mi355_tensor *y,
+                           int32_t *acc_out, float *y_f32, void *stream);
+
 /* Tile configuration override for benchmarking (0 = auto). */
 int mi355_conv_set_tile(int bm, int bn);
 /* Development switches.  Bits 0..8 are timing ablations of the K loop (no DMA / no s_barrier / no MFMA / ...), compiled
@@ -333,7 +352,7 @@ int mi355_debug_flags(int flags);
  * conv + maxpool), 3 conv1x1.hip, 4 conv_ws3.hip, 5 conv_igemm.hip / conv_rows.hip / conv_rows16.hip, 6 fp32-accumulate emulation,
  * 7 conv_pool16.hip (16 -> 32 + maxpool with the packed epilogue table), 8 conv_small32.hip (32 -> 64 + maxpool), 9 conv_kxk.hip (the
  * general shapes), 10 conv_dw.hip (mi355_conv_dw_forward), 11 conv_tr.hip (mi355_conv_tr_forward),
- * 12 conv_group.hip (mi355_conv_group_forward). */
+ * 12 conv_group.hip (mi355_conv_group_forward), 13 conv_dil.hip (mi355_conv_dil_forward). */
 int mi355_last_conv_kernel(void);
 /* Geometry of the calling thread's most recent convolution kernel launch (any mi355_conv_*forward call): workgroups in the grid,
  * threads per workgroup, bytes of dynamic LDS, as the launcher chose them for the plan, batch and tile count.  Each pointer may be

@@ -8,6 +8,7 @@
   python tools/conv_microbench.py --spp [--out FILE]  # the fused SPP pools (spp.hip) against the three plain pools and the HBM floor
   python tools/conv_microbench.py --tr [--out FILE]   # transposed k4 s2 / k2 s2 (conv_tr.hip) against its stuffed dense twin and the HBM floor
   python tools/conv_microbench.py --group [--out FILE]  # grouped 3x3 (conv_group.hip) against its dense twin and the HBM floor
+  python tools/conv_microbench.py --dil [--out FILE]  # dilated 3x3 (conv_dil.hip) against the same layer at d = 1, its stuffed twin and the HBM floor
 """
 import argparse
 import ctypes as C
@@ -271,13 +272,62 @@ def run_group(iters, repeats):
     return out
 
 
+def run_dil(iters, repeats):
+    """The dilated kernel (conv_dil.hip) on 3x3 "same" layers, n = c, batch 32 -- 256 x 33 x 33 at d = 6, 12, 18 (ASPP) and 128 x 65 x 65
+    at d = 2, 4 -- each against: the same layer at d = 1, pad 1 on whichever dense kernel serves it (equal MACs and bytes); where
+    D = 2 d + 1 <= 11 its stuffed dense twin (weights off the tap lattice = the filter's zero point, the same bytes out)
+    on conv_kxk.hip; and the HBM floor, tensor bytes in + out over the bandwidth a device-to-device copy of 256 MiB reaches in this
+    process.  The kernels of a case alternate, `repeats` rounds; medians and ranges in microseconds."""
+    S = binding.shim()
+    st = C.c_void_p(); binding.check(S.mi355_stream_create(C.byref(st)))
+    nb = 256 << 20
+    src, dst = binding.DevBuf(nb), binding.DevBuf(nb)
+    copy_us = [_time_us(lambda: binding.check(S.mi355_d2d(dst.ptr, src.ptr, nb, st), "d2d"), st, 10) for _ in range(repeats)]
+    bw = 2.0 * nb / (np.median(copy_us) * 1e-6)  # bytes read + written per second
+    src.free(); dst.free()
+    out = {"copy_256MiB_us": copy_us, "copy_bytes_per_s": bw, "iters": iters, "cases": []}
+    for c, hw, dil in ((256, 33, 6), (256, 33, 12), (256, 33, 18), (128, 65, 2), (128, 65, 4)):
+        rng = np.random.default_rng(c + dil)
+        B, k, n, D = 32, 3, c, 2 * dil + 1
+        x = rng.integers(0, 256, (B, c, hw, hw), dtype=np.uint8)
+        wq = rng.integers(0, 256, (n, c * k * k), dtype=np.uint8)
+        zp_w = rng.integers(100, 157, n, dtype=np.uint8)
+        bias = np.zeros(n, np.int32); mv = np.full(n, 0.75); sv = np.full(n, 2.0 ** -(7 + int(np.log2(c))))
+        xt = binding.DevTensor.from_nchw(x, 0)
+        y, y1, yt = (binding.DevTensor(B, hw, hw, n, 23) for _ in range(3))
+        blob = binding.DevBuf.from_numpy(binding.conv_pack(wq, zp_w, c, k, bias, mv, sv))
+        desc = lambda kk, pad: binding.ConvDesc(n, c, kk, 1, pad, binding.ACT["leaky"], 0, 0, 0, 23, 1.0)
+        dd, d1, dt = desc(k, dil), desc(k, 1), desc(D, dil)
+        runs = {"dil": lambda: binding.check(S.mi355_conv_dil_forward(C.byref(dd), xt.ref(), blob.ptr, dil, y.ref(), None, None, st), "dil"),
+                "dense_d1": lambda: binding.check(S.mi355_conv_forward(C.byref(d1), xt.ref(), blob.ptr, None, None, y1.ref(), None, None, st), "d1")}
+        if D <= 11:
+            wt = np.repeat(zp_w[:, None], c * D * D, axis=1).reshape(n, c, D, D)
+            wt[:, :, ::dil, ::dil] = wq.reshape(n, c, k, k)
+            blobt = binding.DevBuf.from_numpy(binding.conv_pack(wt.reshape(n, -1), zp_w, c, D, bias, mv, sv))
+            runs["stuffed_twin"] = lambda: binding.check(S.mi355_conv_forward(C.byref(dt), xt.ref(), blobt.ptr, None, None, yt.ref(), None, None, st), "twin")
+        times, kern = {key: [] for key in runs}, {}
+        for _ in range(repeats):
+            for key, fn in runs.items():
+                times[key].append(_time_us(fn, st, iters)); kern[key] = binding.last_conv_kernel()
+        S.mi355_stream_sync(st)
+        floor_us = (B * (c + n) * hw * hw) / bw * 1e6
+        med = {key: float(np.median(v)) for key, v in times.items()}
+        case = {"c": c, "hw": hw, "n": n, "k": k, "dilation": dil, "batch": B, "us": times, "kernel": kern, "hbm_floor_us": floor_us,
+                "dil_over_dense_d1": med["dil"] / med["dense_d1"], "dil_over_floor": med["dil"] / floor_us}
+        if D <= 11:
+            case.update(bytes_equal=bool(np.array_equal(y.to_nchw(), yt.to_nchw())), dil_over_stuffed_twin=med["dil"] / med["stuffed_twin"])
+        out["cases"].append(case)
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dil", action="store_true", help="dilated 3x3 against the same layer at d = 1, its stuffed twin and the HBM floor")
     ap.add_argument("--group", action="store_true", help="grouped 3x3 against its dense twin and the HBM floor")
     ap.add_argument("--tr", action="store_true", help="transposed k4 s2 / k2 s2 against the stuffed dense twin and the HBM floor")
     ap.add_argument("--dw", action="store_true", help="depthwise 3x3 against its dense twin and the HBM floor")
     ap.add_argument("--spp", action="store_true", help="the fused SPP pools against the three plain pools and the HBM floor")
-    ap.add_argument("--out", default="", help="--dw, --spp, --tr, --group: also write the JSON here")
+    ap.add_argument("--out", default="", help="--dw, --spp, --tr, --group, --dil: also write the JSON here")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--c", type=int, default=256); ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--hw", type=int, default=52); ap.add_argument("--k", type=int, default=3)
@@ -295,8 +345,8 @@ if __name__ == "__main__":
     binding.init(0)
     if a.dbg:
         binding.shim().mi355_debug_flags(a.dbg)
-    if a.dw or a.spp or a.tr or a.group:
-        fn = run_group if a.group else (run_tr if a.tr else (run_spp if a.spp else run_dw))
+    if a.dw or a.spp or a.tr or a.group or a.dil:
+        fn = run_dil if a.dil else (run_group if a.group else (run_tr if a.tr else (run_spp if a.spp else run_dw)))
         r = fn(a.iters, a.repeats)
         print(json.dumps(r))
         if a.out:

@@ -12,6 +12,7 @@ accepts: /root/reference/src/parser.c:170-204 (convolutional), 411-431 (maxpool)
   cfg/s2_unit.cfg                  24x24 chain of stride-2 3x3 convolutions (the downsampling layers of full YOLOv3)
   cfg/dw_unit.cfg                  24x24 depthwise-separable unit net (groups = channels layers between 1x1 convolutions)
   cfg/tr_unit.cfg                  24x24 unit net with two [deconvolutional] layers (k4 s2 p1, k2 s2 p0) and a route over one of them
+  cfg/dil_unit.cfg                 20x20 small ASPP: three parallel dilated 3x3 branches (dilation 2, 3, 5) on one tensor, a route, a 1x1
 """
 import os, sys
 
@@ -114,6 +115,24 @@ def tr_unit(act="leaky"):
     s += yolo("0,1,2")                                # 6
     return s
 
+def dilated(filters, size, dilation, act, src=None):
+    # [convolutional] dilation=d, pad=1: the "same" padding d * (size // 2); src: a one-input route in front of it
+    s = route(str(src)) if src is not None else ""
+    return s + (f"[convolutional]\nbatch_normalize=1\nfilters={filters}\nsize={size}\nstride=1\npad=1\ndilation={dilation}\n"
+                f"activation={act}\nquantized=1\nquant_stop=0\n\n")
+
+def dil_unit(act="leaky"):
+    # a small ASPP on a 20x20x3 input: a dense stem, three parallel dilated 3x3 branches on its tensor, their concatenation, a 1x1 head
+    s = net(20, 20, c=3)
+    s += conv(16, 3, act)                             # 0   20x20
+    s += dilated(16, 3, 2, act)                       # 1
+    s += dilated(16, 3, 3, "relu6", src=0)            # 2, 3
+    s += dilated(16, 3, 5, act, src=0)                # 4, 5
+    s += route("1,3,5")                               # 6   48 channels
+    s += conv(30, 1, "linear", bn=0, stop=1)          # 7
+    s += yolo("0,1,2")                                # 8
+    return s
+
 def shortcut(frm=-3):
     return f"[shortcut]\nfrom={frm}\nactivation=linear\nquantized=1\nquant_stop=0\n\n"
 
@@ -187,4 +206,5 @@ if __name__ == "__main__":
     open(os.path.join(out, "res_unit.cfg"), "w").write(res_unit())
     open(os.path.join(out, "dw_unit.cfg"), "w").write(dw_unit())
     open(os.path.join(out, "tr_unit.cfg"), "w").write(tr_unit())
+    open(os.path.join(out, "dil_unit.cfg"), "w").write(dil_unit())
     print("wrote cfgs to", os.path.normpath(out))

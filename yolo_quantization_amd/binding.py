@@ -275,6 +275,8 @@ def shim():
             L.mi355_conv_group_pack_size.restype = C.c_size_t
             L.mi355_conv_group_pack.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
             L.mi355_conv_group_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, ci, C.POINTER(Tensor), vp, vp, vp]
+        if hasattr(L, "mi355_conv_dil_forward"):  # (MI355_LIB_DIR may name an older build)
+            L.mi355_conv_dil_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, ci, C.POINTER(Tensor), vp, vp, vp]
         L.mi355_last_conv_kernel.argtypes = []
         L.mi355_last_conv_kernel.restype = ci
         if hasattr(L, "mi355_last_conv_launch"):  # (absent from older A/B builds under build_ab/)
@@ -627,6 +629,33 @@ def conv_group_forward(x: DevTensor, wq, zp_w, groups, ksize, biases_int32, M_va
     return out
 
 
+def conv_dil_forward(x: DevTensor, wq, zp_w, dilation, ksize, biases_int32, M_value, shift_value, zp_in, zp_act, s_act, activation,
+                     store=STORE_WRAP, accum=ACC_EXACT, want_acc=True, want_f32=False, pad=None, plan=0, y=None):
+    """One dilated layer (stride 1; tap (ky, kx) reads input (oy - pad + ky dilation, ox - pad + kx dilation)) through
+    mi355_conv_dil_forward on the dense layer's blob (conv_pack); wq: [n, c * ksize * ksize]; result as conv_tr_forward.  pad=None:
+    dilation * (ksize // 2).  y: the output DevTensor to write into (default: a fresh one filled with zp_act)."""
+    n, c = np.shape(wq)[0], x.t.C
+    blob = _pack_blob(wq, zp_w, c, ksize, biases_int32, M_value, shift_value, activation, zp_act, False)
+    if pad is None:
+        pad = dilation * (ksize // 2)
+    OH, OW = x.t.H + 2 * pad - dilation * (ksize - 1), x.t.W + 2 * pad - dilation * (ksize - 1)
+    if y is None:
+        y = DevTensor(x.t.B, OH, OW, n, zp_act)
+    cnt = x.t.B * n * OH * OW
+    acc = DevBuf(cnt * 4) if want_acc else None
+    f32 = DevBuf(cnt * 4) if want_f32 else None
+    d = ConvDesc(n, c, ksize, 1, pad, activation, store, accum, zp_in, zp_act, float(s_act), int(plan), 0)
+    check(shim().mi355_conv_dil_forward(C.byref(d), x.ref(), blob.ptr, int(dilation), y.ref(), acc.ptr if acc else None,
+                                        f32.ptr if f32 else None, None), "conv_dil_forward")
+    check(shim().mi355_stream_sync(None), "sync")
+    out = {"u8": y.to_nchw(), "tensor": y}
+    if acc:
+        out["int32"] = acc.to_numpy(np.int32, cnt).reshape(x.t.B, n, OH * OW)
+    if f32:
+        out["f32"] = f32.to_numpy(np.float32, cnt).reshape(x.t.B, n, OH * OW)
+    return out
+
+
 FUSED = ("pool2", "pool1", "upsample", "yolo", "shortcut")
 
 
@@ -788,6 +817,9 @@ def host():
         L.network_load_packed.argtypes = [vp, C.c_char_p]
         L.dnq_layer_conv_kernel.argtypes = [vp, ci]
         L.dnq_layer_conv_kernel.restype = ci
+        if hasattr(L, "dnq_layer_dilation"):
+            L.dnq_layer_dilation.argtypes = [vp, ci]
+            L.dnq_layer_dilation.restype = ci
         if hasattr(L, "dnq_layer_spp"):
             L.dnq_layer_spp.argtypes = [vp, ci]
             L.dnq_layer_spp.restype = ci
@@ -1501,6 +1533,8 @@ class Net:
             a = (C.c_int * 16)()
             H.dnq_layer_info(self.h, i, a)
             self.info.append(dict(zip(INFO_KEYS, list(a))))
+            # 1 for a dense [convolutional], 0 for other layers (MI355_LIB_DIR may name an older build, which knows dense layers only)
+            self.info[-1]["dilation"] = int(H.dnq_layer_dilation(self.h, i)) if hasattr(H, "dnq_layer_dilation") else int(a[0] == 0)
 
     def set(self, key, val):
         assert self.H.dnq_net_set(self.h, key.encode(), int(val)) == 0

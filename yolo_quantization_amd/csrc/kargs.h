@@ -402,6 +402,36 @@ struct GrpArgs {
 };
 int conv_group_launch(GrpArgs &a, hipStream_t st);  // MI355_EINVAL when no tile fits LDS (nothing launched)
 
+// conv_dil.hip: the dilated (atrous) stride-1 convolution as d x d dense convolutions on the phase-subsampled maps.
+// Output (oy, ox) has phase (oy % d, ox % d) and phase index (oy / d, ox / d); tap (ky, kx) of it reads input
+// (oy - pad + ky d, ox - pad + kx d), which is cell (jy + ky, jx + kx) of a patch gathered at cell stride d.  The A operand is the
+// dense layer's: the general-kernel fragments of mi355_conv_pack (ConvBlobHeader.off_gen, K layout kxk_geom).
+struct DilArgs {
+    const uint8_t *x;        // input tensor, biased PHWC (cs % 16 == 0, data 16-byte aligned)
+    int in_cs, in_lead;
+    int B, H, W, c;
+    int n, ksize, dil, pad, OH, OW;
+    const int8_t *wk;        // packed A fragments [mpad / 32][ksteps][64 lanes][16 B]
+    int unit, nchunks, spc, ksteps;
+    const int32_t *cw, *dzp, *bias;
+    const double *mval, *sval, *mprime;
+    const ConvBlobHeader *hdr;  // device copy (pow2 flag)
+    uint8_t *y;
+    int out_cs, out_lead;
+    int32_t *acc_out;
+    float *y_f32;
+    int zp_in, zp_act, act, store_mode;
+    float s_act;
+    // tile geometry (set by the launcher).  A phase tile is 2^th_sh x 2^tw_sh phase indices; a workgroup owns `slots` consecutive
+    // tiles of the image's list [phase (qy, qx)][tile (ty, tx)], each with its own staged patch of ph x pw cells
+    int th_sh, tw_sh, slots;
+    int nqx, tiles_x, tpp, ntiles;  // phases along x: min(d, OW); tiles of a phase along x; tiles of a phase; tiles of an image
+    int wpi, mgroups;           // workgroups per image and M group: ceil(ntiles / slots)
+    int ph, pw;
+    FastDiv fd_pc, fd_pw, fd_tpp, fd_tx, fd_nqx;  // patch cells, patch width, tiles per phase, tiles_x, nqx
+};
+int conv_dil_launch(DilArgs &a, hipStream_t st);  // MI355_EINVAL when no tile fits LDS (nothing launched)
+
 // spp.hip: up to three stride-1 "same" max pools of one tensor in one launch (the SPP block of yolov3-spp / yolov4), computed as a
 // cascade: level i is the box max of size d[i] of level i - 1, level 0 being x, so that level i is x's pool of size sizes[i].
 constexpr int SPP_MAX = 3;       // levels

@@ -1243,6 +1243,60 @@ int mi355_conv_group_forward(const mi355_conv_desc *d, const mi355_tensor *x, co
     return rc;
 }
 
+// ------------------------------------------------------------------------------------- dilated convolution (conv_dil.hip)
+int mi355_conv_dil_forward(const mi355_conv_desc *d, const mi355_tensor *x, const void *blob, int dilation, const mi355_tensor *y,
+                           int32_t *acc_out, float *y_f32, void *stream)
+{
+    if (!d || !x || !x->data || !blob) return einval("conv_dil_forward: null");
+    if (d->n < 1 || d->c < 1) return einval("conv_dil_forward: need n >= 1 and c >= 1");
+    if (dilation < 1) return einval("conv_dil_forward: need dilation >= 1");
+    if (d->ksize < 2 || d->ksize > 11) return einval("conv_dil_forward: size must be 2..11 (a 1x1 layer has nothing to dilate)");
+    if (d->stride != 1) return einval("conv_dil_forward: stride must be 1 (a strided dilated layer is not d x d dense layers)");
+    if (d->pad < 0) return einval("conv_dil_forward: need pad >= 0");
+    if (d->accum_mode != MI355_ACC_EXACT)
+        return einval("conv_dil_forward: MI355_ACC_EXACT only (the reference has no dilated forward whose fp32 order could be followed)");
+    if (d->activation != MI355_ACT_LEAKY && d->activation != MI355_ACT_RELU && d->activation != MI355_ACT_RELU6 && d->activation != MI355_ACT_LINEAR)
+        return einval("conv_dil_forward: activation must be leaky, relu, relu6 or linear");
+    if (x->cs % 16 || x->cs < (d->c + 15) / 16 * 16)
+        return einval("conv_dil_forward: x.cs must be a multiple of 16 that holds the channels (the 3-channel image's 4-byte cells are not served)");
+    if (x->C != d->c) return einval("conv_dil_forward: x.C != desc.c");
+    const long D = (long)dilation * (d->ksize - 1) + 1;
+    const long OHl = (long)x->H + 2L * d->pad - D + 1, OWl = (long)x->W + 2L * d->pad - D + 1;
+    if (x->H < 1 || x->W < 1 || OHl < 1 || OWl < 1)
+        return einval("conv_dil_forward: the output map is empty (the padded map is smaller than the dilated kernel, dilation (size - 1) + 1)");
+    if ((long)x->H + 2L * d->pad > (1L << 28) || (long)x->W + 2L * d->pad > (1L << 28))
+        return einval("conv_dil_forward: the padded map must stay below 2^28 cells a side");
+    if (y && (y->C != d->n || y->B != x->B || y->H != OHl || y->W != OWl || !y->data || y->cs % 16 || y->cs < d->n))
+        return einval("conv_dil_forward: y shape (y.cs must be a multiple of 16 that holds the filters)");
+    if (((uintptr_t)x->data & 15) || ((uintptr_t)blob & 15) || (y && ((uintptr_t)y->data & 15)))
+        return einval("conv_dil_forward: x.data, y.data and blob must be aligned to 16 bytes");
+    ConvBlobHeader h;
+    if (blob_layout(d->n, d->c, d->ksize, &h) != MI355_OK || !h.off_gen)
+        return einval("conv_dil_forward: the blob of this shape carries no general-kernel fragments");
+    const char *base = (const char *)blob;
+    const KxkGeom kg = kxk_geom(d->n, d->c, d->ksize);
+    DilArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = (const uint8_t *)x->data; a.in_cs = x->cs; a.in_lead = x->lead;
+    a.B = x->B; a.H = x->H; a.W = x->W; a.c = d->c;
+    a.n = d->n; a.ksize = d->ksize; a.dil = dilation; a.pad = d->pad; a.OH = (int)OHl; a.OW = (int)OWl;
+    a.wk = (const int8_t *)(base + h.off_gen);
+    a.unit = kg.unit; a.nchunks = kg.nchunks; a.spc = kg.spc; a.ksteps = kg.ksteps;
+    a.cw = (const int32_t *)(base + h.off_cw); a.dzp = (const int32_t *)(base + h.off_dzp);
+    a.bias = (const int32_t *)(base + h.off_bias);
+    a.mval = (const double *)(base + h.off_mval); a.sval = (const double *)(base + h.off_sval);
+    a.mprime = (const double *)(base + h.off_mprime);
+    a.hdr = (const ConvBlobHeader *)base;
+    a.y = y ? (uint8_t *)y->data : nullptr; a.out_cs = y ? y->cs : 0; a.out_lead = y ? y->lead : 0;
+    a.acc_out = acc_out; a.y_f32 = y_f32;
+    a.zp_in = d->zp_in; a.zp_act = d->zp_act; a.act = d->activation; a.store_mode = d->store_mode; a.s_act = d->s_act;
+    const int rc = conv_dil_launch(a, (hipStream_t)stream);
+    if (rc == MI355_EINVAL) return einval("conv_dil_forward: no tile fits: the grid of this shape is too large");
+    if (rc != MI355_OK) return hip_fail(hipGetLastError(), "conv_dil launch");
+    g_last_kernel = 13;
+    return rc;
+}
+
 int mi355_conv_yolo_forward(const mi355_conv_desc *d, const mi355_tensor *x, const void *blob, const mi355_tensor *y,
                             float *y_f32, float *yolo_out, int classes, void *stream)
 {

@@ -71,11 +71,19 @@ int dnq_layer_prep(network *net, int i, int32_t *biases_int32, double *M_value, 
     return 0;
 }
 
-/* kernel family (mi355_last_conv_kernel codes) that served conv layer i in the last forward pass, 0 for other layers */
+/* kernel family (mi355_last_conv_kernel codes) that served conv layer i in the last forward pass, 0 for other layers and before the
+ * first pass -- except a dilated layer, whose kernel (13) the cfg alone decides: it reads 13 from load_network on */
 int dnq_layer_conv_kernel(network *net, int i)
 {
     if (i < 0 || i >= net->n) return 0;
     return net->layers[i].conv_kernel;
+}
+
+/* dilation of [convolutional] layer i, 1 for a dense one, 0 for other layers */
+int dnq_layer_dilation(network *net, int i)
+{
+    if (i < 0 || i >= net->n || net->layers[i].type != CONVOLUTIONAL) return 0;
+    return net->layers[i].dilation;
 }
 
 /* layer i + 1 runs inside layer i's kernel and layer i's own tensor is NOT stored */

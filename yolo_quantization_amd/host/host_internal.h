@@ -31,6 +31,9 @@ static inline int spp_on(const network *net) { return !net->dump_int32; }
 static inline int conv_like(const layer *l) { return l->type == CONVOLUTIONAL || l->type == DECONVOLUTIONAL; }
 layer make_deconvolutional_layer(int batch, int h, int w, int c, int n, int size, int stride, int padding, ACTIVATION activation,
                                  int batch_normalize, int quant_stop_flag, int close_quantization, int layer_quantization, int count);
+/* [convolutional] dilation=d > 1: the dense layer's record, prep and blob; its own output map, kernel and forward */
+static inline int conv_dilated(const layer *l) { return l->type == CONVOLUTIONAL && l->dilation > 1; }
+void set_convolutional_dilation(layer *l, int dilation);
 layer make_convolutional_layer(int batch, int h, int w, int c, int n, int groups, int size, int stride, int padding,
                                ACTIVATION activation, int batch_normalize, int quant_stop_flag,
                                int close_quantization, int layer_quantization, int count);

@@ -140,6 +140,24 @@ static void forward_deconvolutional_layer_quant_gpu(layer l, network net)
                                       l.quant_stop_flag ? l.output_gpu : NULL, net.stream), "mi355_conv_tr_forward");
 }
 
+/* The dilated convolution: the dense layer's blob on conv_dil.hip.  Unfused, exact mode only (refused at prep otherwise). */
+static void forward_dilated_layer_quant_gpu(layer l, network net)
+{
+    if (!l.prepared) error("forward_gpu before quantization_weights_and_activations");
+    mi355_conv_desc d;
+    memset(&d, 0, sizeof(d));
+    d.n = l.n; d.c = l.c; d.ksize = l.size; d.stride = l.stride; d.pad = l.pad;
+    d.activation = l.activation;
+    d.plan = net.plan;
+    d.store_mode = net.store_mode;
+    d.accum_mode = net.accum_mode;
+    d.zp_in = l.input_data_uint8_zero_point[0];
+    d.zp_act = l.activ_data_uint8_zero_point[0];
+    d.s_act = l.activ_data_uint8_scales[0];
+    check_mi355(mi355_conv_dil_forward(&d, net.cur_t, l.blob_gpu, l.dilation, &l.out_t, net.dump_int32 ? l.output_int32_gpu : NULL,
+                                       l.quant_stop_flag ? l.output_gpu : NULL, net.stream), "mi355_conv_dil_forward");
+}
+
 /* quant_stop tail shared by the glue layers: l.output = (u8 - zp) * scale (ref: src/maxpool_layer.c:163-171,
  * src/upsample_layer.c:104-112) */
 static void dequant_tail(layer l, network net)
@@ -267,7 +285,20 @@ layer make_convolutional_layer(int batch, int h, int w, int c, int n, int groups
     }
     l.forward = forward_cpu_not_built;
     l.forward_gpu = forward_convolutional_layer_quant_gpu;
+    l.dilation = 1;
     return l;
+}
+
+/* dilation=d > 1 on a stride-1 [convolutional]: the output map of the dilated kernel d (size - 1) + 1; the kernel is a
+ * function of the cfg alone, so conv_kernel says 13 from here on */
+void set_convolutional_dilation(layer *l, int dilation)
+{
+    l->dilation = dilation;
+    l->out_h = l->h + 2 * l->pad - dilation * (l->size - 1);
+    l->out_w = l->w + 2 * l->pad - dilation * (l->size - 1);
+    l->outputs = l->out_h * l->out_w * l->out_c;
+    l->conv_kernel = 13;
+    l->forward_gpu = forward_dilated_layer_quant_gpu;
 }
 
 /* [deconvolutional], DESIGN.md 7d: the convolution's record and prep fields, the transposed output map (ref: src/deconvolutional_layer.c:68-69) */

@@ -226,6 +226,7 @@ static int view_producer_ok(network *net, int j, int r)
     layer *p = &net->layers[j];
     if (j >= r || p->out_view || p->out_c % 16) return 0;
     if (p->type != CONVOLUTIONAL && p->type != UPSAMPLE && p->type != MAXPOOL) return 0;
+    if (conv_dilated(p)) return 0; /* a route over a dilated layer copies, as over [deconvolutional] */
     if (p->type == CONVOLUTIONAL && p->fuse_next == FUSE_POOL && !p->fuse_pool_keep && net->fuse_maxpool) return 0;
     if (j > 0 && net->layers[j - 1].fuse_next == FUSE_POOL && net->fuse_maxpool && p->type == MAXPOOL) return 0; /* written by the fused conv */
     const int zp_differs = p->activ_data_uint8_zero_point[0] != net->layers[r].activ_data_uint8_zero_point[0];
@@ -351,6 +352,8 @@ void quantization_prep_host(network *net, float in_scale, uint8_t in_zp)
                 error("unsupported layer after a 3-filter [deconvolutional]");
             }
         }
+        if (conv_dilated(l) && net->accum_mode == MI355_ACC_REF_F32)
+            error("[convolutional] dilation > 1 runs in MI355_ACC_EXACT only: the reference has no dilated forward whose fp32 order could be followed");
         if (l->n == 3 && ((i + 1 < net->n && net->layers[i + 1].type != CONVOLUTIONAL && net->layers[i + 1].type != ROUTE) ||
                           output_read_elsewhere(net, i))) {
             fprintf(stderr, "layer %d: a 3-filter convolution can only feed another convolution\n", i);
@@ -442,7 +445,7 @@ static void plan_fusion(network *net)
     for (int i = 0; i < net->n; ++i) net->layers[i].fuse_next = net->layers[i].fuse_pool_keep = net->layers[i].spp = 0;
     for (int i = 0; i + 1 < net->n; ++i) {
         layer *c = &net->layers[i], *p = &net->layers[i + 1];
-        if (c->type != CONVOLUTIONAL || c->groups > 1) continue; /* a depthwise layer runs unfused: the layer after it on its own */
+        if (c->type != CONVOLUTIONAL || c->groups > 1 || c->dilation > 1) continue; /* a depthwise or dilated layer runs unfused: the layer after it on its own */
         switch (p->type) {
         case SHORTCUT:
             if (c->stride == 1 && !c->quant_stop_flag && !p->quant_stop_flag && c->c % 16 == 0 && p->index != i && !output_read_elsewhere(net, i))

@@ -121,6 +121,7 @@ static layer parse_convolutional(section *o, size_params p, int count)
     int pad = option_find_int(o, "pad", 0);
     int padding = option_find_int(o, "padding", 0);
     int groups = option_find_int(o, "groups", 1);
+    int dilation = option_find_int(o, "dilation", 1); /* not a key of the reference */
     if (pad) padding = size / 2; /* ref :178 */
     ACTIVATION act = get_activation(option_find_str(o, "activation", "logistic"));
     if (act == LOGISTIC) /* also the default when the key is missing (ref: src/parser.c:180) */
@@ -138,8 +139,21 @@ static layer parse_convolutional(section *o, size_params p, int count)
         if (n != p.c) error("[convolutional] groups = channels with filters != channels: depthwise channel multipliers are not built");
         if (p.index == 0) error("[convolutional] a depthwise first layer on the image is not built (its 4-byte cells are not served)");
     }
+    /* dilation=d: taps d cells apart at stride 1; pad=1 is the "same" padding of an odd size, d (size / 2) */
+    if (dilation < 1) error("[convolutional] dilation must be >= 1");
+    if (dilation > 1) {
+        if (stride != 1) error("[convolutional] dilation > 1 needs stride=1 (a strided dilated layer is not d x d dense layers)");
+        if (size < 2) error("[convolutional] dilation > 1 needs size >= 2 (a 1x1 layer has nothing to dilate)");
+        if (groups != 1) error("[convolutional] dilation > 1 needs groups=1 (the dilated depthwise layer is not built)");
+        if (p.index == 0) error("[convolutional] a dilated first layer on the image is not built (its 4-byte cells are not served)");
+        if (p.c == 3 || n == 3) error("[convolutional] dilation > 1 on 3 channels or with 3 filters is not built (tensors of 3 channels have 4-byte cells, which conv_dil.hip does not serve)");
+        if (pad) padding = dilation * (size / 2);
+        if (p.h + 2 * padding - dilation * (size - 1) < 1 || p.w + 2 * padding - dilation * (size - 1) < 1)
+            error("[convolutional] dilation: the output map is empty (the padded map is smaller than dilation (size - 1) + 1)");
+    }
     layer l = make_convolutional_layer(p.batch, p.h, p.w, p.c, n, groups, size, stride, padding, act, bn, qs,
                                        p.close_quantization, q, count);
+    if (dilation > 1) set_convolutional_dilation(&l, dilation);
     l.fisrt_time_train_fag = option_find_int(o, "first_time", 0);
     return l;
 }

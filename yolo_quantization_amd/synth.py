@@ -68,6 +68,7 @@ class LayerShape:
     quant_stop: int = 0
     inputs: list[int] = field(default_factory=list)  # route sources (absolute indices)
     groups: int = 1  # conv: groups == c == n is the depthwise layer, c / groups weights per filter per tap
+    dilation: int = 1  # conv: cells between taps
 
 
 def layer_shapes(sections: list[dict]) -> tuple[dict, list[LayerShape]]:
@@ -83,12 +84,13 @@ def layer_shapes(sections: list[dict]) -> tuple[dict, list[LayerShape]]:
         if t == "[convolutional]":
             n = int(s.get("filters", 1)); size = int(s.get("size", 1)); stride = int(s.get("stride", 1))
             pad = int(s.get("pad", 0)); padding = int(s.get("padding", 0))
+            dil = int(s.get("dilation", 1))  # stride 1; pad=1 is the "same" padding dil * (size // 2)
             if pad:
-                padding = size // 2
-            oh = (h + 2 * padding - size) // stride + 1
-            ow = (w + 2 * padding - size) // stride + 1
+                padding = dil * (size // 2)
+            oh = (h + 2 * padding - dil * (size - 1) - 1) // stride + 1
+            ow = (w + 2 * padding - dil * (size - 1) - 1) // stride + 1
             L = LayerShape("conv", c, h, w, n, oh, ow, n, size, stride, padding, s.get("activation", "logistic"),
-                           int(s.get("batch_normalize", 0)), q, qs, groups=int(s.get("groups", 1)))
+                           int(s.get("batch_normalize", 0)), q, qs, groups=int(s.get("groups", 1)), dilation=dil)
         elif t in ("[deconvolutional]", "[deconv]"):  # the convolution's keys, the transposed output map
             n = int(s.get("filters", 1)); size = int(s.get("size", 1)); stride = int(s.get("stride", 1))
             padding = size // 2 if int(s.get("pad", 0)) else int(s.get("padding", 0))
@@ -200,6 +202,8 @@ def synth_weights(cfg_path: str, out_path: str, seed: int = 1234, act_gain: floa
                 rec.update(w_hat=q.copy(), weights_uint8=unflip(q), zp_w=wzp, s_w=wscale, biases=bias,
                            bn=(sc, mean, var) if L.batch_normalize else (None, None, None))
                 q, w = unflip(q), unflip(w)
+            if L.dilation > 1:  # the dense layer's record; what a check of the layer needs beside the host's prep
+                rec.update(weights_uint8=q.copy(), zp_w=wzp)
             blob += wscale.tobytes() + wzp.tobytes() + q.tobytes() + w.tobytes()
             act_q.append((a_s, a_zp))
             info.append(rec)
