@@ -33,7 +33,7 @@ extern "C" {
 
 /* same enumerator values as the reference (include/darknet.h:87-89, 99-130) */
 typedef enum { LOGISTIC = 0, RELU = 1, LINEAR = 3, RELU6 = 8, LEAKY = 9 } ACTIVATION;
-typedef enum { CONVOLUTIONAL = 0, DECONVOLUTIONAL = 1, MAXPOOL = 3, ROUTE = 8, SHORTCUT = 13, YOLO = 23, UPSAMPLE = 26 } LAYER_TYPE;
+typedef enum { CONVOLUTIONAL = 0, DECONVOLUTIONAL = 1, CONNECTED = 2, MAXPOOL = 3, ROUTE = 8, AVGPOOL = 11, SHORTCUT = 13, YOLO = 23, UPSAMPLE = 26 } LAYER_TYPE;
 
 /* layer.fuse_next: the layer after a conv that runs inside the conv's kernel.  The type of that layer decides the kind */
 enum { FUSE_NONE = 0, FUSE_POOL, FUSE_UPSAMPLE, FUSE_SHORTCUT, FUSE_YOLO };
@@ -118,6 +118,8 @@ struct layer {
     int conv_kernel;    /* kernel family that served this conv's last forward (mi355_last_conv_kernel) */
     int prepared;
     int dilation;       /* [convolutional] dilation=: 1 = the dense layer; above 1 the layer runs on conv_dil.hip, unfused */
+    int fc_c, fc_h, fc_w; /* [connected]: the input map it flattens; c = fc_c fc_h fc_w, h = w = size = 1 are the record's convolution */
+    void *workspace_gpu;  /* [connected]: the split-K workspace of mi355_connected_forward (NULL when the launcher does not split this shape) */
 };
 
 /* The buffers of one coded-image input path (JPEG, PNG): lazily allocated, grown when needed, freed with the network. */

@@ -335,6 +335,42 @@ int mi355_conv_group_forward(const mi355_conv_desc *desc, const mi355_tensor *x,
 int mi355_conv_dil_forward(const mi355_conv_desc *desc, const mi355_tensor *x, const void *blob, int dilation, const mi355_tensor *y,
                            int32_t *acc_out, float *y_f32, void *stream);
 
+/* The classifier tail (classify.hip): the fully connected layer `[connected] output=n` and the global average pool
+ * `[avgpool]`.  The reference has no integer path for either; the definitions are this library's.
+ * Connected: with K = x.C x.H x.W and the input flattened in the reference's (c, y, x) order, the layer is the dense 1x1 convolution of
+ * a K-channel 1 x 1 map:  acc[b][j] = sum_k (w[j][k] - zp_w[j]) x[b][k]  (no padding, so no zero point of the input enters), and
+ * biases_int32 / M_value / shift_value, the epilogue (both stores, leaky / relu / relu6 / linear), acc_out [B][n] and y_f32 [B][n] are
+ * mi355_conv_forward's for c = K, ksize = 1.  The kernel is a skinny GEMM on V_MFMA_I32_16X16X64_I8 whose N dimension is the images; it
+ * reads every weight byte once per launch (per 64 images) and splits K over workgroups when the filters alone cannot fill the chip.
+ *   mi355_connected_pack_size       bytes of the blob, a function of (n, C, H, W, cs) only; 0 outside n, C, H, W >= 1, cs % 16 == 0,
+ *                                   cs >= C, C H W <= 33024 (K 255^2 stays below 2^31)
+ *   mi355_connected_pack            weights_uint8: the reference's record [n][C H W] in (c, y, x) order, permuted to the tensor's cell
+ *                                   order (y, x, channel) with zero weights on the spare channels of every cell's 16-byte pieces that
+ *                                   hold channels; cs is a cell size of the input tensor the layer will read.  The kernel skips the
+ *                                   bytes of a cell past those pieces, so the bytes of the blob are the same for every valid cs and the
+ *                                   blob serves a tensor of any cell size that holds C (a channel window of a wider buffer).
+ *                                   Position independent; M_value / shift_value as for mi355_conv_pack
+ *   mi355_connected_workspace_size  bytes of the split-K workspace for (n, K, B), 0 when the launcher does not split this shape
+ *   mi355_connected_forward         desc is an unchanged mi355_conv_desc with c = K, ksize = 1, stride = 1, pad = 0; MI355_ACC_EXACT only;
+ *                                   x.cs % 16 == 0; y (nullable) a B x n x 1 x 1 tensor, channels >= n of its cells keep their bytes;
+ *                                   x.data, blob and workspace 16-byte aligned; workspace may be NULL when its size is 0.  Both plans
+ *                                   give the same bytes.  x's pad cells and the bytes at or beyond C of a cell are never used.
+ *                                   The blob lives in device memory, so the call cannot read it: the kernel itself compares the blob's
+ *                                   header with (desc.n, x.C, x.H, x.W) and, when they differ, reads nothing past the header and
+ *                                   writes nothing (the call still returns MI355_OK: the caller answers for the blob, as for every blob).
+ *   mi355_avgpool_forward           y[b][c] = floor((2 S + HW) / (2 HW)), S the sum of the H W unsigned bytes of channel c of image b:
+ *                                   round-half-up of the mean, in exact integers; y a B x C x 1 x 1 tensor of the same record (scale,
+ *                                   zero point) as x; H W <= 2^22; x.cs % 16 == 0 and y.cs % 16 == 0, both data pointers 16-byte aligned
+ * Anything else returns MI355_EINVAL with a message that starts "connected_forward:" / "avgpool_forward:", nothing launched or written.
+ * New calls, no struct change: MI355_ABI_VERSION is unchanged. */
+size_t mi355_connected_pack_size(int n, int C, int H, int W, int cs);
+int mi355_connected_pack(int n, int C, int H, int W, int cs, const uint8_t *weights_uint8, const uint8_t *zp_w, const int32_t *biases_int32,
+                         const double *M_value, const double *shift_value, void *blob);
+size_t mi355_connected_workspace_size(int n, int K, int B);
+int mi355_connected_forward(const mi355_conv_desc *desc, const mi355_tensor *x, const void *blob, const mi355_tensor *y, int32_t *acc_out,
+                            float *y_f32, void *workspace, void *stream);
+int mi355_avgpool_forward(const mi355_tensor *x, const mi355_tensor *y, void *stream);
+
 /* Tile configuration override for benchmarking (0 = auto). */
 int mi355_conv_set_tile(int bm, int bn);
 /* Development switches.  Bits 0..8 are timing ablations of the K loop (no DMA / no s_barrier / no MFMA / ...), compiled
@@ -352,7 +388,8 @@ int mi355_debug_flags(int flags);
  * conv + maxpool), 3 conv1x1.hip, 4 conv_ws3.hip, 5 conv_igemm.hip / conv_rows.hip / conv_rows16.hip, 6 fp32-accumulate emulation,
  * 7 conv_pool16.hip (16 -> 32 + maxpool with the packed epilogue table), 8 conv_small32.hip (32 -> 64 + maxpool), 9 conv_kxk.hip (the
  * general shapes), 10 conv_dw.hip (mi355_conv_dw_forward), 11 conv_tr.hip (mi355_conv_tr_forward),
- * 12 conv_group.hip (mi355_conv_group_forward), 13 conv_dil.hip (mi355_conv_dil_forward). */
+ * 12 conv_group.hip (mi355_conv_group_forward), 13 conv_dil.hip (mi355_conv_dil_forward),
+ * 14 classify.hip (mi355_connected_forward). */
 int mi355_last_conv_kernel(void);
 /* Geometry of the calling thread's most recent convolution kernel launch (any mi355_conv_*forward call): workgroups in the grid,
  * threads per workgroup, bytes of dynamic LDS, as the launcher chose them for the plan, batch and tile count.  Each pointer may be

@@ -9,6 +9,7 @@
   python tools/conv_microbench.py --tr [--out FILE]   # transposed k4 s2 / k2 s2 (conv_tr.hip) against its stuffed dense twin and the HBM floor
   python tools/conv_microbench.py --group [--out FILE]  # grouped 3x3 (conv_group.hip) against its dense twin and the HBM floor
   python tools/conv_microbench.py --dil [--out FILE]  # dilated 3x3 (conv_dil.hip) against the same layer at d = 1, its stuffed twin and the HBM floor
+  python tools/conv_microbench.py --fc [--out FILE]   # connected / avgpool (classify.hip) against the layer spelled as a convolution and the HBM floor
 """
 import argparse
 import ctypes as C
@@ -320,14 +321,70 @@ def run_dil(iters, repeats):
     return out
 
 
+def run_fc(iters, repeats):
+    """The classifier tail (classify.hip).  Connected: 1024 -> 1000, 2048 -> 1000 on a 1 x 1 map and 512 x 7 x 7 -> 4096,
+    at batch 32 and 64, each against the same layer through mi355_conv_forward (a 1x1 layer on the 1 x 1 map; the 7 x 7 layer on the
+    7 x 7 map, pad 0) and the HBM floor: blob + input + output bytes over the bandwidth a device-to-device copy of 256 MiB reaches in
+    this process.  Average pool: 1024 x 7 x 7 and 1280 x 13 x 13 against its floor.  The kernels of a case alternate, `repeats` rounds;
+    medians and ranges in microseconds."""
+    S = binding.shim()
+    st = C.c_void_p(); binding.check(S.mi355_stream_create(C.byref(st)))
+    nb = 256 << 20
+    src, dst = binding.DevBuf(nb), binding.DevBuf(nb)
+    copy_us = [_time_us(lambda: binding.check(S.mi355_d2d(dst.ptr, src.ptr, nb, st), "d2d"), st, 10) for _ in range(repeats)]
+    bw = 2.0 * nb / (np.median(copy_us) * 1e-6)  # bytes read + written per second
+    src.free(); dst.free()
+    out = {"copy_256MiB_us": copy_us, "copy_bytes_per_s": bw, "iters": iters, "connected": [], "avgpool": []}
+    for c, hw, n in ((1024, 1, 1000), (2048, 1, 1000), (512, 7, 4096)):
+        rng = np.random.default_rng(c + n)
+        K = c * hw * hw
+        wq = rng.integers(0, 256, (n, K), dtype=np.uint8)
+        zp_w = rng.integers(100, 157, n, dtype=np.uint8)
+        bias = np.zeros(n, np.int32); mv = np.full(n, 0.75); sv = np.full(n, 2.0 ** -(7 + int(np.log2(K))))
+        pack = binding.connected_pack(wq, zp_w, c, hw, hw, c, bias, mv, sv)
+        blob, blobc = binding.DevBuf.from_numpy(pack), binding.DevBuf.from_numpy(binding.conv_pack(wq, zp_w, c, hw, bias, mv, sv))
+        for B in (32, 64):
+            xt = binding.DevTensor.from_nchw(rng.integers(0, 256, (B, c, hw, hw), dtype=np.uint8), 0)
+            y, yc = binding.DevTensor(B, 1, 1, n, 23), binding.DevTensor(B, 1, 1, n, 23)
+            wsz = S.mi355_connected_workspace_size(n, K, B)
+            ws = binding.DevBuf(wsz) if wsz else None
+            df = binding.ConvDesc(n, K, 1, 1, 0, binding.ACT["leaky"], 0, 0, 0, 23, 1.0)
+            dc = binding.ConvDesc(n, c, hw, 1, 0, binding.ACT["leaky"], 0, 0, 0, 23, 1.0)
+            runs = {"connected": lambda: binding.check(S.mi355_connected_forward(C.byref(df), xt.ref(), blob.ptr, y.ref(), None, None,
+                                                                                  ws.ptr if ws else None, st), "fc"),
+                    "conv_forward": lambda: binding.check(S.mi355_conv_forward(C.byref(dc), xt.ref(), blobc.ptr, None, None, yc.ref(), None, None, st), "conv")}
+            times, kern, grid = {key: [] for key in runs}, {}, {}
+            for _ in range(repeats):
+                for key, fn in runs.items():
+                    times[key].append(_time_us(fn, st, iters)); kern[key] = binding.last_conv_kernel(); grid[key] = binding.last_conv_launch()
+            S.mi355_stream_sync(st)
+            floor_us = (pack.size + B * (K + n)) / bw * 1e6
+            med = {key: float(np.median(v)) for key, v in times.items()}
+            out["connected"].append({"c": c, "hw": hw, "n": n, "batch": B, "blob_bytes": int(pack.size), "us": times, "kernel": kern, "launch": grid,
+                                     "hbm_floor_us": floor_us, "bytes_equal": bool(np.array_equal(y.to_nchw(), yc.to_nchw())),
+                                     "connected_over_conv_forward": med["connected"] / med["conv_forward"],
+                                     "connected_over_floor": med["connected"] / floor_us})
+    for c, hw in ((1024, 7), (1280, 13)):
+        B = 32
+        xt = binding.DevTensor.from_nchw(np.random.default_rng(c).integers(0, 256, (B, c, hw, hw), dtype=np.uint8), 0)
+        y = binding.DevTensor(B, 1, 1, c, 0)
+        fn = lambda: binding.check(S.mi355_avgpool_forward(xt.ref(), y.ref(), st), "avgpool")
+        times = [_time_us(fn, st, iters) for _ in range(repeats)]
+        S.mi355_stream_sync(st)
+        floor_us = B * c * (hw * hw + 1) / bw * 1e6
+        out["avgpool"].append({"c": c, "hw": hw, "batch": B, "us": times, "hbm_floor_us": floor_us, "avgpool_over_floor": float(np.median(times)) / floor_us})
+    return out
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fc", action="store_true", help="connected / avgpool against the layer spelled as a convolution and the HBM floor")
     ap.add_argument("--dil", action="store_true", help="dilated 3x3 against the same layer at d = 1, its stuffed twin and the HBM floor")
     ap.add_argument("--group", action="store_true", help="grouped 3x3 against its dense twin and the HBM floor")
     ap.add_argument("--tr", action="store_true", help="transposed k4 s2 / k2 s2 against the stuffed dense twin and the HBM floor")
     ap.add_argument("--dw", action="store_true", help="depthwise 3x3 against its dense twin and the HBM floor")
     ap.add_argument("--spp", action="store_true", help="the fused SPP pools against the three plain pools and the HBM floor")
-    ap.add_argument("--out", default="", help="--dw, --spp, --tr, --group, --dil: also write the JSON here")
+    ap.add_argument("--out", default="", help="--dw, --spp, --tr, --group, --dil, --fc: also write the JSON here")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--c", type=int, default=256); ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--hw", type=int, default=52); ap.add_argument("--k", type=int, default=3)
@@ -345,8 +402,8 @@ if __name__ == "__main__":
     binding.init(0)
     if a.dbg:
         binding.shim().mi355_debug_flags(a.dbg)
-    if a.dw or a.spp or a.tr or a.group or a.dil:
-        fn = run_dil if a.dil else (run_group if a.group else (run_tr if a.tr else (run_spp if a.spp else run_dw)))
+    if a.dw or a.spp or a.tr or a.group or a.dil or a.fc:
+        fn = run_fc if a.fc else run_dil if a.dil else (run_group if a.group else (run_tr if a.tr else (run_spp if a.spp else run_dw)))
         r = fn(a.iters, a.repeats)
         print(json.dumps(r))
         if a.out:

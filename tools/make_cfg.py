@@ -13,6 +13,8 @@ accepts: /root/reference/src/parser.c:170-204 (convolutional), 411-431 (maxpool)
   cfg/dw_unit.cfg                  24x24 depthwise-separable unit net (groups = channels layers between 1x1 convolutions)
   cfg/tr_unit.cfg                  24x24 unit net with two [deconvolutional] layers (k4 s2 p1, k2 s2 p0) and a route over one of them
   cfg/dil_unit.cfg                 20x20 small ASPP: three parallel dilated 3x3 branches (dilation 2, 3, 5) on one tensor, a route, a 1x1
+  cfg/cls_unit.cfg                 24x20 small classifier: three convolutions, the global [avgpool], two [connected] layers
+  cfg/cls_route_unit.cfg           6x5 classifier tail among routes: a [connected] on a tensor that is a window of a concat's buffer, routes over both layers
 """
 import os, sys
 
@@ -133,6 +135,35 @@ def dil_unit(act="leaky"):
     s += yolo("0,1,2")                                # 8
     return s
 
+def connected(output, act, bn=0, stop=0):
+    # [connected] output=n: the 1x1 convolution of the flattened input
+    return f"[connected]\n{'batch_normalize=1' + chr(10) if bn else ''}output={output}\nactivation={act}\nquantized=1\nquant_stop={stop}\n\n"
+
+def cls_unit(act="leaky"):
+    # a small classifier on a 24 wide, 20 high input: 40 channels (spare bytes in every cell) into the global pool, float logits out
+    s = net(24, 20, c=3)
+    s += conv(16, 3, act) + maxpool(2, 2)              # 0, 1   12x10
+    s += conv(32, 3, act)                              # 2
+    s += conv(40, 1, "relu6")                          # 3      40 channels in cells of 48 bytes
+    s += "[avgpool]\nquantized=1\nquant_stop=0\n\n"    # 4      1x1x40
+    s += connected(24, act, bn=1)                      # 5
+    s += connected(10, "linear", stop=1)               # 6      the logits
+    return s
+
+def cls_route_unit(act="leaky"):
+    # the tail among routes: layer 1 feeds a [connected] AND the concat 3, so its tensor is a window of the concat's 32-byte cells
+    s = net(6, 5, c=3)
+    s += conv(16, 3, act)                              # 0   6x5x16
+    s += conv(16, 1, "relu6")                          # 1
+    s += connected(12, act)                            # 2   reads 1 through the window
+    s += route("1,0")                                  # 3   32 channels
+    s += "[avgpool]\nquantized=1\nquant_stop=0\n\n"    # 4
+    s += route("4")                                    # 5   a route over the pool copies
+    s += connected(10, "relu")                         # 6
+    s += route("2")                                    # 7   a route over a [connected] copies
+    s += connected(7, "linear", stop=1)                # 8
+    return s
+
 def shortcut(frm=-3):
     return f"[shortcut]\nfrom={frm}\nactivation=linear\nquantized=1\nquant_stop=0\n\n"
 
@@ -207,4 +238,6 @@ if __name__ == "__main__":
     open(os.path.join(out, "dw_unit.cfg"), "w").write(dw_unit())
     open(os.path.join(out, "tr_unit.cfg"), "w").write(tr_unit())
     open(os.path.join(out, "dil_unit.cfg"), "w").write(dil_unit())
+    open(os.path.join(out, "cls_unit.cfg"), "w").write(cls_unit())
+    open(os.path.join(out, "cls_route_unit.cfg"), "w").write(cls_route_unit())
     print("wrote cfgs to", os.path.normpath(out))

@@ -277,6 +277,14 @@ def shim():
             L.mi355_conv_group_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, ci, C.POINTER(Tensor), vp, vp, vp]
         if hasattr(L, "mi355_conv_dil_forward"):  # (MI355_LIB_DIR may name an older build)
             L.mi355_conv_dil_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, ci, C.POINTER(Tensor), vp, vp, vp]
+        if hasattr(L, "mi355_connected_forward"):  # (MI355_LIB_DIR may name an older build)
+            L.mi355_connected_pack_size.argtypes = [ci, ci, ci, ci, ci]
+            L.mi355_connected_pack_size.restype = C.c_size_t
+            L.mi355_connected_pack.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+            L.mi355_connected_workspace_size.argtypes = [ci, ci, ci]
+            L.mi355_connected_workspace_size.restype = C.c_size_t
+            L.mi355_connected_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.POINTER(Tensor), vp, vp, vp, vp]
+            L.mi355_avgpool_forward.argtypes = [C.POINTER(Tensor), C.POINTER(Tensor), vp]
         L.mi355_last_conv_kernel.argtypes = []
         L.mi355_last_conv_kernel.restype = ci
         if hasattr(L, "mi355_last_conv_launch"):  # (absent from older A/B builds under build_ab/)
@@ -656,6 +664,60 @@ def conv_dil_forward(x: DevTensor, wq, zp_w, dilation, ksize, biases_int32, M_va
     return out
 
 
+def avgpool_forward(x: DevTensor, y=None):
+    """The global average pool through mi355_avgpool_forward: round-half-up of each channel's mean over the map, into
+    y (default: a fresh B x C x 1 x 1 DevTensor).  Returns dict(u8 [B, C, 1, 1], tensor)."""
+    if y is None:
+        y = DevTensor(x.t.B, 1, 1, x.t.C, 0)
+    check(shim().mi355_avgpool_forward(x.ref(), y.ref(), None), "avgpool_forward")
+    check(shim().mi355_stream_sync(None), "sync")
+    return {"u8": y.to_nchw(), "tensor": y}
+
+
+def connected_pack(wq, zp_w, C_, H, W, cs, biases_int32, M_value, shift_value):
+    """mi355_connected_pack -> numpy uint8 blob of a fully connected layer on a C_ x H x W input whose tensor has cells of cs bytes;
+    wq: the reference's record [n, C_ * H * W] in (c, y, x) order"""
+    wq = np.ascontiguousarray(wq, np.uint8)
+    n = wq.shape[0]
+    sz = shim().mi355_connected_pack_size(n, C_, H, W, cs)
+    if not sz:
+        raise MI355Error(f"unsupported connected shape n={n} C={C_} H={H} W={W} cs={cs}")
+    blob = np.zeros(sz, np.uint8)
+    zp_w = np.ascontiguousarray(zp_w, np.uint8)
+    b = np.ascontiguousarray(biases_int32, np.int32)
+    mv = np.ascontiguousarray(M_value, np.float64)
+    sv = np.ascontiguousarray(shift_value, np.float64)
+    check(shim().mi355_connected_pack(n, C_, H, W, cs, wq.ctypes.data, zp_w.ctypes.data, b.ctypes.data, mv.ctypes.data, sv.ctypes.data,
+                                      blob.ctypes.data), "connected_pack")
+    return blob
+
+
+def connected_forward(x: DevTensor, wq, zp_w, biases_int32, M_value, shift_value, zp_in, zp_act, s_act, activation, store=STORE_WRAP,
+                      want_acc=True, want_f32=False, plan=0, y=None, workspace=True):
+    """One fully connected layer on the flattened x (K = C H W, the reference's (c, y, x) order) through mi355_connected_forward;
+    wq: [n, K].  Returns dict(u8 [B, n, 1, 1], tensor, int32 [B, n], f32 [B, n]).  y: the output DevTensor to write into (default: a
+    fresh one filled with zp_act).  workspace=None passes NULL, which only shapes that the launcher does not split accept."""
+    n, K = np.shape(wq)[0], x.t.C * x.t.H * x.t.W
+    blob = DevBuf.from_numpy(connected_pack(wq, zp_w, x.t.C, x.t.H, x.t.W, x.t.cs, biases_int32, M_value, shift_value))
+    if y is None:
+        y = DevTensor(x.t.B, 1, 1, n, zp_act)
+    cnt = x.t.B * n
+    acc = DevBuf(cnt * 4) if want_acc else None
+    f32 = DevBuf(cnt * 4) if want_f32 else None
+    wsz = shim().mi355_connected_workspace_size(n, K, x.t.B)
+    ws = DevBuf(wsz) if workspace and wsz else None
+    d = ConvDesc(n, K, 1, 1, 0, activation, store, ACC_EXACT, zp_in, zp_act, float(s_act), int(plan), 0)
+    check(shim().mi355_connected_forward(C.byref(d), x.ref(), blob.ptr, y.ref(), acc.ptr if acc else None, f32.ptr if f32 else None,
+                                         ws.ptr if ws else None, None), "connected_forward")
+    check(shim().mi355_stream_sync(None), "sync")
+    out = {"u8": y.to_nchw(), "tensor": y}
+    if acc:
+        out["int32"] = acc.to_numpy(np.int32, cnt).reshape(x.t.B, n)
+    if f32:
+        out["f32"] = f32.to_numpy(np.float32, cnt).reshape(x.t.B, n)
+    return out
+
+
 FUSED = ("pool2", "pool1", "upsample", "yolo", "shortcut")
 
 
@@ -870,6 +932,7 @@ PLAN_KEYS = ["route_elided", "out_view", "view_offset", "fuse_next_pool", "fuse_
              "fuse_pool_keep"]
 T_CONV, T_MAXPOOL, T_ROUTE, T_SHORTCUT, T_YOLO, T_UPSAMPLE = 0, 3, 8, 13, 23, 26
 T_DECONV = 1  # [deconvolutional]: a weight record, a prep and int32 accumulators like T_CONV
+T_CONNECTED, T_AVGPOOL = 2, 11  # [connected]: the same, on its flattened input; [avgpool]: the global pool
 
 
 def frame_view(v, frame_w=None, frame_h=None):
@@ -1959,7 +2022,7 @@ class Net:
         ty = self.info[i]["type"]
         if ty != T_YOLO:
             out["u8"] = _as(self.H.dnq_layer_u8(self.h, i), cnt, C.c_uint8).copy()
-        if ty in (T_CONV, T_DECONV):
+        if ty in (T_CONV, T_DECONV, T_CONNECTED):
             out["int32"] = _as(self.H.dnq_layer_int32(self.h, i), cnt, C.c_int32).copy()
         if ty == T_YOLO or (self.info[i]["quant_stop"] and (self.keep_head_float or ty != T_CONV or not self.fuses_next(i))):
             out["f32"] = _as(self.H.dnq_layer_f32(self.h, i), cnt, C.c_float).copy()

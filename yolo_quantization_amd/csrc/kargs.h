@@ -432,6 +432,81 @@ struct DilArgs {
 };
 int conv_dil_launch(DilArgs &a, hipStream_t st);  // MI355_EINVAL when no tile fits LDS (nothing launched)
 
+// classify.hip: the fully connected layer as a skinny GEMM on V_MFMA_I32_16X16X64_I8 whose N dimension is the images.
+// The K axis is "packed K": the input tensor's cell order, cell (y, x) after cell, cp = round_up(C, 16) bytes a cell (the 16-byte
+// pieces of a cell that hold channels), Kp = H W cp, cut into K-steps of 64 bytes.  The tensor's own cell size may be larger (a window
+// of a route's buffer): the kernel gathers cp bytes of every cell at the tensor's stride, so the blob (mi355_connected_pack) is a
+// function of (n, C, H, W) alone and fits every cs % 16 == 0 that holds C:
+//     frag    [mtiles][nsteps][64 lanes][16 B]: lane (m, q) of a step holds bytes 64 step + 16 q .. + 15 of filter 16 tile + m as
+//             w - 128; byte kp is channel kp % cp of cell kp / cp, i.e. the reference's weight (kp % cp) H W + kp / cp, and 0 on the
+//             spare channels C .. cp, past the last cell and in the rows past n
+//     rows    GrpRow [16 mtiles]   per filter: d = 128 - zp_w, cst = 128 sum w' + 128 K d (K = C H W), bias, the epilogue's multipliers
+#define MI355_FC_MAGIC 0x4D494643u /* "MIFC" */
+constexpr int FC_MB = 4;               // M tiles (waves) of a workgroup
+constexpr int FC_THREADS = 64 * FC_MB;
+constexpr int FC_LDS_MAX = 64 * 1024;  // staged bytes of a chunk, every image of the group
+constexpr int FC_MAX_K = 33024;        // K 255^2 < 2^31
+constexpr int FC_CUS = 256;            // workgroups the launcher tries to reach by splitting K
+constexpr int FC_MIN_STEPS = 8;        // K-steps of the shortest slice the rule makes
+struct FcBlobHeader {
+    uint32_t magic;
+    int32_t n, C, H, W, cp, mtiles, nsteps;  // cp: packed bytes a cell, round_up(C, 16)
+    int32_t pad_[2];
+    uint64_t off_frag, off_rows, total;
+};
+inline bool fc_blob_layout(int n, int C, int H, int W, int cs, FcBlobHeader *h)
+{
+    if (n < 1 || C < 1 || H < 1 || W < 1 || cs % 16 || cs < C || (long)C * H * W > FC_MAX_K || (long)H * W * cs > (1L << 24)) return false;
+    *h = FcBlobHeader{};
+    h->magic = MI355_FC_MAGIC; h->n = n; h->C = C; h->H = H; h->W = W; h->cp = (C + 15) / 16 * 16;
+    h->mtiles = (n + 15) / 16; h->nsteps = (H * W * h->cp + 63) / 64;
+    h->off_frag = (sizeof(FcBlobHeader) + 15) & ~(uint64_t)15;
+    h->off_rows = h->off_frag + (uint64_t)h->mtiles * h->nsteps * 1024;
+    h->total = h->off_rows + (uint64_t)h->mtiles * 16 * sizeof(GrpRow);
+    return true;
+}
+// split-K rule, a function of (n, K, B) alone: slices of at least FC_MIN_STEPS K-steps of the TRUE K until the grid reaches FC_CUS
+// workgroups.  The launcher cuts the packed K-steps (>= the true ones) into that many slices of equal length and drops empty ones,
+// so the rule's S bounds the launch's.
+inline int fc_split(int n, int K, int B)
+{
+    const int base = (((n + 15) / 16 + FC_MB - 1) / FC_MB) * ((B + 63) / 64);
+    const int most = ((K + 63) / 64) / FC_MIN_STEPS;
+    int s = FC_CUS / base;
+    if (s > most) s = most;
+    return s < 1 ? 1 : s;
+}
+struct FcArgs {
+    const uint8_t *x;        // input tensor, biased PHWC (cs % 16 == 0, data 16-byte aligned)
+    int in_cs, in_lead;
+    int B, H, W, C;
+    int n, ktrue, nsteps, cp;
+    const FcBlobHeader *hdr; // device copy: a launch whose header does not say (n, C, H, W) runs no workgroup past its first lines
+    const char *frag;
+    const GrpRow *rows;
+    uint8_t *y;              // [B][n][1][1]
+    int out_cs, out_lead;
+    int32_t *acc_out;
+    float *y_f32;
+    int zp_act, act, store_mode;
+    float s_act;
+    int32_t *ws_acc, *ws_sx; // S > 1: partial accumulators [S][B][npad] and partial sums of x' [S][B] (the caller's workspace)
+    // geometry (set by the launcher)
+    int mtiles, npad, fblocks;
+    int S, sps;              // K slices and K-steps a slice
+    int chunk, pitch;        // K-steps staged at a time; LDS bytes between two images (chunk bytes + 16)
+};
+int connected_launch(FcArgs &a, hipStream_t st);
+// classify.hip: the global average pool, q = floor((2 S + HW) / (2 HW)) per image and channel
+struct AvgArgs {
+    const uint8_t *x;
+    uint8_t *y;              // [B][C][1][1]
+    int in_cs, in_lead, out_cs, out_lead;
+    int B, H, W, C;
+    int nchunks, dq, dr;     // set by the launcher: 64-byte channel chunks; 64 / W and 64 % W (a lane's step of 64 cells in rows and columns)
+};
+int avgpool_launch(AvgArgs &a, hipStream_t st);
+
 // spp.hip: up to three stride-1 "same" max pools of one tensor in one launch (the SPP block of yolov3-spp / yolov4), computed as a
 // cascade: level i is the box max of size d[i] of level i - 1, level 0 being x, so that level i is x's pool of size sizes[i].
 constexpr int SPP_MAX = 3;       // levels

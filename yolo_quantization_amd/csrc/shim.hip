@@ -1297,6 +1297,111 @@ int mi355_conv_dil_forward(const mi355_conv_desc *d, const mi355_tensor *x, cons
     return rc;
 }
 
+// ------------------------------------------------------------------------------------- classifier tail (classify.hip)
+size_t mi355_connected_pack_size(int n, int C, int H, int W, int cs)
+{
+    FcBlobHeader h;
+    return fc_blob_layout(n, C, H, W, cs, &h) ? (size_t)h.total : 0;
+}
+
+int mi355_connected_pack(int n, int C, int H, int W, int cs, const uint8_t *wq, const uint8_t *zp_w, const int32_t *biases_int32,
+                         const double *M_value, const double *shift_value, void *blob)
+{
+    FcBlobHeader h;
+    if (!fc_blob_layout(n, C, H, W, cs, &h))
+        return einval("connected_pack: need n, C, H, W >= 1, cs a multiple of 16 that holds C, and K = C H W <= 33024");
+    if (!wq || !zp_w || !biases_int32 || !M_value || !shift_value || !blob) return einval("connected_pack: null");
+    for (int j = 0; j < n; ++j)
+        if (!(M_value[j] > 0.0 && M_value[j] < 1.0) || !(shift_value[j] > 0.0 && shift_value[j] <= 1.0))
+            return einval("connected_pack: need 0 < M_value < 1 and 0 < shift_value <= 1 (ref asserts 0<M<1, src/blas.c:391-392)");
+    char *base = (char *)blob;
+    memset(base, 0, (size_t)h.total);
+    memcpy(base, &h, sizeof(h));
+    const int hw = H * W, K = C * hw;
+    for (int j = 0; j < n; ++j) {
+        long sw = 0;
+        for (int i = 0; i < K; ++i) sw += (int)wq[(size_t)j * K + i] - 128;
+        const long d = 128 - (long)zp_w[j];
+        ((GrpRow *)(base + h.off_rows))[j] = GrpRow{(int32_t)d, (int32_t)(uint32_t)(128 * sw + 128 * (long)K * d), biases_int32[j], 0,
+                                                   M_value[j], shift_value[j], M_value[j] * shift_value[j]};
+        // byte kp of the packed K axis: channel kp % cp of cell kp / cp; lane (j % 16, (kp % 64) / 16) of step kp / 64
+        int8_t *fr = (int8_t *)(base + h.off_frag) + (size_t)(j / 16) * h.nsteps * 1024;
+        for (int cell = 0; cell < hw; ++cell)
+            for (int ch = 0; ch < C; ++ch) {
+                const int kp = cell * h.cp + ch;
+                fr[((size_t)(kp / 64) * 64 + (size_t)((kp % 64) / 16) * 16 + j % 16) * 16 + kp % 16] = (int8_t)(wq[(size_t)j * K + (size_t)ch * hw + cell] ^ 0x80);
+            }
+    }
+    return MI355_OK;
+}
+
+size_t mi355_connected_workspace_size(int n, int K, int B)
+{
+    if (n < 1 || K < 1 || K > FC_MAX_K || B < 1) return 0;
+    const int S = fc_split(n, K, B);
+    return S > 1 ? (size_t)S * B * ((size_t)(n + 15) / 16 * 16 + 1) * 4 : 0;
+}
+
+int mi355_connected_forward(const mi355_conv_desc *d, const mi355_tensor *x, const void *blob, const mi355_tensor *y, int32_t *acc_out,
+                            float *y_f32, void *workspace, void *stream)
+{
+    if (!d || !x || !x->data || !blob) return einval("connected_forward: null");
+    if (d->n < 1 || d->c < 1) return einval("connected_forward: need n >= 1 and c >= 1");
+    if (d->ksize != 1 || d->stride != 1 || d->pad != 0) return einval("connected_forward: desc must say ksize 1, stride 1, pad 0 (c = C H W)");
+    if (d->accum_mode != MI355_ACC_EXACT) return einval("connected_forward: MI355_ACC_EXACT only (the reference has no integer connected layer)");
+    if (d->activation != MI355_ACT_LEAKY && d->activation != MI355_ACT_RELU && d->activation != MI355_ACT_RELU6 && d->activation != MI355_ACT_LINEAR)
+        return einval("connected_forward: activation must be leaky, relu, relu6 or linear");
+    if (x->B < 1 || x->H < 1 || x->W < 1 || x->C < 1) return einval("connected_forward: empty tensor");
+    if (x->cs % 16 || x->cs < x->C) return einval("connected_forward: x.cs must be a multiple of 16 that holds the channels");
+    if ((long)x->C * x->H * x->W != d->c) return einval("connected_forward: desc.c != x.C x.H x.W (the flattened input)");
+    if (d->c > FC_MAX_K) return einval("connected_forward: K = C H W must be <= 33024 (K 255^2 stays below 2^31)");
+    if (y && (y->C != d->n || y->B != x->B || y->H != 1 || y->W != 1 || !y->data || y->cs % 16 || y->cs < d->n))
+        return einval("connected_forward: y must be a B x n x 1 x 1 tensor (y.cs a multiple of 16 that holds the filters)");
+    if (((uintptr_t)x->data & 15) || ((uintptr_t)blob & 15) || (y && ((uintptr_t)y->data & 3)))
+        return einval("connected_forward: x.data and blob must be aligned to 16 bytes, y.data to 4");
+    FcBlobHeader h;
+    if (!fc_blob_layout(d->n, x->C, x->H, x->W, x->cs, &h)) return einval("connected_forward: no blob of this shape");
+    if (fc_split(d->n, d->c, x->B) > 1 && (!workspace || ((uintptr_t)workspace & 15)))
+        return einval("connected_forward: this shape splits K: workspace of mi355_connected_workspace_size bytes, aligned to 16, is needed");
+    const char *base = (const char *)blob;
+    FcArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = (const uint8_t *)x->data; a.in_cs = x->cs; a.in_lead = x->lead;
+    a.B = x->B; a.H = x->H; a.W = x->W; a.C = x->C;
+    a.n = d->n; a.ktrue = d->c; a.nsteps = h.nsteps; a.cp = h.cp;
+    a.hdr = (const FcBlobHeader *)base;
+    a.frag = base + h.off_frag; a.rows = (const GrpRow *)(base + h.off_rows);
+    a.y = y ? (uint8_t *)y->data : nullptr; a.out_cs = y ? y->cs : 0; a.out_lead = y ? y->lead : 0;
+    a.acc_out = acc_out; a.y_f32 = y_f32;
+    a.zp_act = d->zp_act; a.act = d->activation; a.store_mode = d->store_mode; a.s_act = d->s_act;
+    a.ws_acc = (int32_t *)workspace;
+    const int rc = connected_launch(a, (hipStream_t)stream);
+    if (rc == MI355_EINVAL) return einval("connected_forward: no launch fits (the grid of this shape exceeds 2^31 workgroups, or a pointer is misaligned)");
+    if (rc != MI355_OK) return hip_fail(hipGetLastError(), "connected launch");
+    g_last_kernel = 14;
+    return rc;
+}
+
+int mi355_avgpool_forward(const mi355_tensor *x, const mi355_tensor *y, void *stream)
+{
+    if (!x || !y || !x->data || !y->data) return einval("avgpool_forward: null");
+    if (x->B < 1 || x->H < 1 || x->W < 1 || x->C < 1) return einval("avgpool_forward: empty tensor");
+    if (x->B != y->B || x->C != y->C) return einval("avgpool_forward: y has x's B and C");
+    if (x->cs % 16 || y->cs % 16 || x->cs < x->C || y->cs < y->C) return einval("avgpool_forward: cs must be a multiple of 16 that holds the channels");
+    if (y->H != 1 || y->W != 1) return einval("avgpool_forward: y must be a 1 x 1 map (the pool is global)");
+    if ((long)x->H * x->W > (1L << 22)) return einval("avgpool_forward: the map must hold at most 2^22 cells (2 S + HW stays in 32 bits)");
+    if (((uintptr_t)x->data & 15) || ((uintptr_t)y->data & 15)) return einval("avgpool_forward: x.data and y.data must be aligned to 16 bytes");
+    AvgArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = (const uint8_t *)x->data; a.y = (uint8_t *)y->data;
+    a.in_cs = x->cs; a.in_lead = x->lead; a.out_cs = y->cs; a.out_lead = y->lead;
+    a.B = x->B; a.H = x->H; a.W = x->W; a.C = x->C;
+    const int rc = avgpool_launch(a, (hipStream_t)stream);
+    if (rc == MI355_EINVAL) return einval("avgpool_forward: the grid does not fit a launch");
+    if (rc != MI355_OK) return hip_fail(hipGetLastError(), "avgpool launch");
+    return rc;
+}
+
 int mi355_conv_yolo_forward(const mi355_conv_desc *d, const mi355_tensor *x, const void *blob, const mi355_tensor *y,
                             float *y_f32, float *yolo_out, int classes, void *stream)
 {

@@ -27,8 +27,11 @@ static inline int fusion_on(const network *net) { return net->fuse_maxpool && !n
  * the plain path: that makes the dumps the expectation the fused runs are held against. */
 static inline int spp_on(const network *net) { return !net->dump_int32; }
 
-/* the two layers with a weight record, a prep and a packed blob: [convolutional] and [deconvolutional] */
-static inline int conv_like(const layer *l) { return l->type == CONVOLUTIONAL || l->type == DECONVOLUTIONAL; }
+/* layers with a weight record, a prep and a packed blob: [connected] is the 1x1 convolution of its flattened input */
+static inline int conv_like(const layer *l) { return l->type == CONVOLUTIONAL || l->type == DECONVOLUTIONAL || l->type == CONNECTED; }
+layer make_connected_layer(int batch, int h, int w, int c, int outputs, ACTIVATION activation, int batch_normalize, int quant_stop_flag,
+                           int close_quantization, int layer_quantization, int count);
+layer make_avgpool_layer(int batch, int h, int w, int c, int layer_quant_flag, int quant_stop_flag, int close_quantization, int count);
 layer make_deconvolutional_layer(int batch, int h, int w, int c, int n, int size, int stride, int padding, ACTIVATION activation,
                                  int batch_normalize, int quant_stop_flag, int close_quantization, int layer_quantization, int count);
 /* [convolutional] dilation=d > 1: the dense layer's record, prep and blob; its own output map, kernel and forward */

@@ -158,6 +158,24 @@ static void forward_dilated_layer_quant_gpu(layer l, network net)
                                        l.quant_stop_flag ? l.output_gpu : NULL, net.stream), "mi355_conv_dil_forward");
 }
 
+/* The fully connected layer: the 1x1 convolution of the flattened input on classify.hip.  Unfused, exact mode only. */
+static void forward_connected_layer_quant_gpu(layer l, network net)
+{
+    if (!l.prepared) error("forward_gpu before quantization_weights_and_activations");
+    mi355_conv_desc d;
+    memset(&d, 0, sizeof(d));
+    d.n = l.n; d.c = l.c; d.ksize = 1; d.stride = 1; d.pad = 0;
+    d.activation = l.activation;
+    d.plan = net.plan;
+    d.store_mode = net.store_mode;
+    d.accum_mode = net.accum_mode;
+    d.zp_in = l.input_data_uint8_zero_point[0];
+    d.zp_act = l.activ_data_uint8_zero_point[0];
+    d.s_act = l.activ_data_uint8_scales[0];
+    check_mi355(mi355_connected_forward(&d, net.cur_t, l.blob_gpu, &l.out_t, net.dump_int32 ? l.output_int32_gpu : NULL,
+                                        l.quant_stop_flag ? l.output_gpu : NULL, l.workspace_gpu, net.stream), "mi355_connected_forward");
+}
+
 /* quant_stop tail shared by the glue layers: l.output = (u8 - zp) * scale (ref: src/maxpool_layer.c:163-171,
  * src/upsample_layer.c:104-112) */
 static void dequant_tail(layer l, network net)
@@ -186,6 +204,13 @@ static void forward_maxpool_layer_quant_gpu(layer l, network net)
         for (int k = 0; k < l.spp_n; ++k) net.layers[l.spp_pool[k]].spp = 0;
     }
     check_mi355(mi355_maxpool_forward(net.cur_t, &l.out_t, l.size, l.stride, l.pad, net.stream), "mi355_maxpool_forward");
+    if (l.quant_stop_flag) dequant_tail(l, net);
+}
+
+/* The global average pool: round-half-up of each channel's mean, the input's record */
+static void forward_avgpool_layer_quant_gpu(layer l, network net)
+{
+    check_mi355(mi355_avgpool_forward(net.cur_t, &l.out_t, net.stream), "mi355_avgpool_forward");
     if (l.quant_stop_flag) dequant_tail(l, net);
 }
 
@@ -315,6 +340,39 @@ layer make_deconvolutional_layer(int batch, int h, int w, int c, int n, int size
     return l;
 }
 
+/* [connected], DESIGN.md 7g: the record, prep fields and weights of the convolution with c = C H W, size 1 on a 1 x 1 map; the map it
+ * flattens is kept for the packer.  The kernel is a function of the cfg alone, so conv_kernel says 14 from here on */
+layer make_connected_layer(int batch, int h, int w, int c, int outputs, ACTIVATION activation, int batch_normalize, int quant_stop_flag,
+                           int close_quantization, int layer_quantization, int count)
+{
+    layer l = make_convolutional_layer(batch, 1, 1, c * h * w, outputs, 1, 1, 1, 0, activation, batch_normalize, quant_stop_flag,
+                                       close_quantization, layer_quantization, count);
+    l.type = CONNECTED;
+    l.fc_c = c; l.fc_h = h; l.fc_w = w;
+    l.conv_kernel = 14;
+    l.forward_gpu = forward_connected_layer_quant_gpu;
+    return l;
+}
+
+/* [avgpool], DESIGN.md 7g: global, 1 x 1 x c out; no record of its own in the weights file */
+layer make_avgpool_layer(int batch, int h, int w, int c, int layer_quant_flag, int quant_stop_flag, int close_quantization, int count)
+{
+    layer l;
+    memset(&l, 0, sizeof(l));
+    l.type = AVGPOOL;
+    l.batch = batch; l.h = h; l.w = w; l.c = c; l.count = count;
+    l.out_w = 1; l.out_h = 1; l.out_c = c;
+    l.outputs = c;
+    l.inputs = h * w * c;
+    l.layer_quant_flag = layer_quant_flag; l.quant_stop_flag = quant_stop_flag;
+    l.close_quantization = close_quantization;
+    if (!layer_quant_flag) error("[avgpool] without quantized=1 is the reference's float path; not built");
+    alloc_act_record(&l);
+    l.forward = forward_cpu_not_built;
+    l.forward_gpu = forward_avgpool_layer_quant_gpu;
+    return l;
+}
+
 layer make_maxpool_layer(int batch, int h, int w, int c, int size, int stride, int padding, int layer_quant_flag,
                          int quant_stop_flag, int close_quantization, int count)
 {
@@ -432,6 +490,8 @@ void free_layer_device(layer *l)
     if (l->weights_uint8_gpu) mi355_free(l->weights_uint8_gpu);
     if (l->weight_zero_point_gpu) mi355_free(l->weight_zero_point_gpu);
     if (l->output_int32_gpu) mi355_free(l->output_int32_gpu);
+    if (l->workspace_gpu) mi355_free(l->workspace_gpu);
+    l->workspace_gpu = NULL;
     if (l->output_gpu) mi355_free(l->output_gpu);
     if (l->output_uint8_nchw_gpu) mi355_free(l->output_uint8_nchw_gpu);
     if (l->anchors_gpu) mi355_free(l->anchors_gpu);

@@ -48,6 +48,8 @@ const char *get_layer_string(LAYER_TYPE t)
     case CONVOLUTIONAL: return "CONV";
     case DECONVOLUTIONAL: return "DECONV";
     case MAXPOOL: return "MAX";
+    case CONNECTED: return "CONNECTED";
+    case AVGPOOL: return "AVG";
     case ROUTE: return "ROUTE";
     case UPSAMPLE: return "UPSAMPLE";
     case SHORTCUT: return "SHORTCUT";
@@ -171,6 +173,7 @@ static void prep_conv_layer(network *net, int i)
 static size_t conv_blob_size(const layer *l)
 {
     if (l->type == DECONVOLUTIONAL) return mi355_conv_tr_pack_size(l->n, l->c, l->size, l->stride);
+    if (l->type == CONNECTED) return mi355_connected_pack_size(l->n, l->fc_c, l->fc_h, l->fc_w, (l->fc_c + 15) / 16 * 16); /* (the blob is the same for every cell size that holds the channels: its input may be a window of a route's buffer) */
     return l->groups > 1 ? mi355_conv_dw_pack_size(l->c, l->size) : mi355_conv_pack_size(l->n, l->c, l->size);
 }
 
@@ -191,6 +194,10 @@ static void alloc_layer_device(network *net, int i)
     }
     if (l->type == YOLO || l->quant_stop_flag)
         check_mi355(mi355_alloc((void **)&l->output_gpu, (size_t)B * l->outputs * sizeof(float)), "alloc float out");
+    if (l->type == CONNECTED) { /* its own in every executor: a replica's passes run beside its parent's */
+        const size_t ws = mi355_connected_workspace_size(l->n, l->c, B);
+        if (ws) check_mi355(mi355_alloc(&l->workspace_gpu, ws), "alloc split-K workspace");
+    }
     if (conv_like(l) && net->dump_int32)
         check_mi355(mi355_alloc((void **)&l->output_int32_gpu, (size_t)B * l->outputs * sizeof(int32_t)), "alloc int32 out");
     free(l->output); free(l->output_int32); free(l->output_uint8_final);
@@ -274,6 +281,7 @@ static void plan_views(network *net)
         if (l->type != ROUTE || l->n != 1) continue;
         layer *p = &net->layers[l->input_layers[0]];
         if (l->input_layers[0] >= r || p->type == YOLO || !p->out_t.data) continue;
+        if (p->type == AVGPOOL || p->type == CONNECTED) continue; /* a route over the classifier tail copies */
         if (p->type == CONVOLUTIONAL && p->fuse_next == FUSE_POOL && !p->fuse_pool_keep && net->fuse_maxpool) continue;
         mi355_free(l->out_t.data);
         l->out_t = p->out_t;
@@ -352,6 +360,8 @@ void quantization_prep_host(network *net, float in_scale, uint8_t in_zp)
                 error("unsupported layer after a 3-filter [deconvolutional]");
             }
         }
+        if (l->type == CONNECTED && net->accum_mode == MI355_ACC_REF_F32)
+            error("[connected] runs in MI355_ACC_EXACT only: the reference has no integer connected forward whose fp32 order could be followed");
         if (conv_dilated(l) && net->accum_mode == MI355_ACC_REF_F32)
             error("[convolutional] dilation > 1 runs in MI355_ACC_EXACT only: the reference has no dilated forward whose fp32 order could be followed");
         if (l->n == 3 && ((i + 1 < net->n && net->layers[i + 1].type != CONVOLUTIONAL && net->layers[i + 1].type != ROUTE) ||
@@ -371,6 +381,11 @@ void quantization_prep_host(network *net, float in_scale, uint8_t in_zp)
         if (l->type == DECONVOLUTIONAL) { /* transposed: its own blob, no epilogue table (the planner offers it to no fusion) */
             check_mi355(mi355_conv_tr_pack(l->n, l->c, l->size, l->stride, l->weights_uint8, l->weight_data_uint8_zero_point, l->biases_int32,
                                            l->M_value, l->M0_right_shift_value, l->blob_host), "mi355_conv_tr_pack");
+            continue;
+        }
+        if (l->type == CONNECTED) { /* classify.hip: the record permuted to the input tensor's cell order */
+            check_mi355(mi355_connected_pack(l->n, l->fc_c, l->fc_h, l->fc_w, (l->fc_c + 15) / 16 * 16, l->weights_uint8, l->weight_data_uint8_zero_point,
+                                             l->biases_int32, l->M_value, l->M0_right_shift_value, l->blob_host), "mi355_connected_pack");
             continue;
         }
         if (l->groups > 1) { /* depthwise: its own blob, no epilogue table (the planner offers it to no fusion) */

@@ -183,6 +183,40 @@ static layer parse_deconvolutional(section *o, size_params p, int count)
     return l;
 }
 
+/* [connected] / [conn]: `output`, `activation`, `batch_normalize` as the reference reads them (src/parser.c:232-243), the
+ * quantisation keys of parse_convolutional */
+static layer parse_connected(section *o, size_params p, int count)
+{
+    int output = option_find_int(o, "output", 1);
+    ACTIVATION act = get_activation(option_find_str(o, "activation", "logistic"));
+    if (act == LOGISTIC) /* also the default when the key is missing */
+        error("[connected] activation=logistic (or no activation key): the reference's quantized forward stores nothing for it "
+              "(`default: break`, src/convolutional_layer.c:746); use leaky, relu6, relu or linear");
+    if (!(p.h && p.w && p.c)) error("Layer before connected layer must output image.");
+    if (p.index == 0 || p.c == 3) error("[connected] on the image or on a 3-channel tensor is not built (its 4-byte cells are not served)");
+    if (output < 1 || output == 3) error("[connected] output must be >= 1 and not 3 (a 3-channel tensor has 4-byte cells, which classify.hip does not store)");
+    if ((long)p.c * p.h * p.w > 33024)
+        error("[connected] K = c h w above 33024 is refused: K 255^2 must stay below 2^31 for the exact int32 accumulator");
+    int bn = option_find_int(o, "batch_normalize", 0);
+    int q = option_find_int(o, "quantized", 0);
+    int qs = option_find_int(o, "quant_stop", 0);
+    layer l = make_connected_layer(p.batch, p.h, p.w, p.c, output, act, bn, qs, p.close_quantization, q, count);
+    l.fisrt_time_train_fag = option_find_int(o, "first_time", 0);
+    return l;
+}
+
+/* [avgpool] / [avg]: darknet's global average pool, no keys but the quantisation ones */
+static layer parse_avgpool(section *o, size_params p, int count)
+{
+    if (!(p.h && p.w && p.c)) error("Layer before avgpool layer must output image.");
+    if (p.index == 0 || p.c == 3) error("[avgpool] on the image or on a 3-channel tensor is not built (its 4-byte cells are not served)");
+    if ((long)p.h * p.w > (1L << 22)) error("[avgpool] a map above 2^22 cells is refused: 2 S + h w must fit 32 unsigned bits");
+    int q = option_find_int(o, "quantized", 0), qs = option_find_int(o, "quant_stop", 0);
+    layer l = make_avgpool_layer(p.batch, p.h, p.w, p.c, q, qs, p.close_quantization, count);
+    l.fisrt_time_train_fag = 1; /* like a first_time [upsample]: the input's record, nothing in the weights file */
+    return l;
+}
+
 static layer parse_maxpool(section *o, size_params p, int count)
 {
     int stride = option_find_int(o, "stride", 1);
@@ -326,6 +360,8 @@ network *parse_network_cfg(char *filename, int close_quantization)
         if (!strcmp(s->type, "[convolutional]") || !strcmp(s->type, "[conv]")) l = parse_convolutional(s, p, i);
         else if (!strcmp(s->type, "[deconvolutional]") || !strcmp(s->type, "[deconv]")) l = parse_deconvolutional(s, p, i);
         else if (!strcmp(s->type, "[maxpool]") || !strcmp(s->type, "[max]")) l = parse_maxpool(s, p, i);
+        else if (!strcmp(s->type, "[connected]") || !strcmp(s->type, "[conn]")) l = parse_connected(s, p, i);
+        else if (!strcmp(s->type, "[avgpool]") || !strcmp(s->type, "[avg]")) l = parse_avgpool(s, p, i);
         else if (!strcmp(s->type, "[upsample]")) l = parse_upsample(s, p, i);
         else if (!strcmp(s->type, "[route]")) l = parse_route(s, p, net, i);
         else if (!strcmp(s->type, "[shortcut]")) l = parse_shortcut(s, p, net, i);
@@ -406,6 +442,10 @@ void load_weights(network *net, char *filename)
         layer l = net->layers[i];
         if (conv_like(&l)) load_convolutional_weights(l, fp); /* the transposed layer loads the convolution's record (ref :1232) */
         if (l.type == MAXPOOL) load_act_record(l, fp); /* always, ref :1244-1246 */
+        if (l.type == AVGPOOL && i > 0) { /* the mean of a tensor has the tensor's record */
+            l.activ_data_uint8_scales[0] = net->layers[i - 1].activ_data_uint8_scales[0];
+            l.activ_data_uint8_zero_point[0] = net->layers[i - 1].activ_data_uint8_zero_point[0];
+        }
         if (l.type == ROUTE && l.layer_quant_flag) {   /* ref :1174-1183 */
             if (l.n > 1 && !l.fisrt_time_train_fag) load_act_record(l, fp);
             else {

@@ -96,6 +96,12 @@ def layer_shapes(sections: list[dict]) -> tuple[dict, list[LayerShape]]:
             padding = size // 2 if int(s.get("pad", 0)) else int(s.get("padding", 0))
             L = LayerShape("deconv", c, h, w, n, (h - 1) * stride + size - 2 * padding, (w - 1) * stride + size - 2 * padding, n, size,
                            stride, padding, s.get("activation", "logistic"), int(s.get("batch_normalize", 0)), q, qs)
+        elif t in ("[connected]", "[conn]"):  # the 1x1 convolution of the input flattened in (c, y, x) order
+            n = int(s.get("output", 1))
+            L = LayerShape("connected", c * h * w, 1, 1, n, 1, 1, n, 1, 1, 0, s.get("activation", "logistic"),
+                           int(s.get("batch_normalize", 0)), q, qs)
+        elif t in ("[avgpool]", "[avg]"):  # global; its input's record, nothing in the weights file
+            L = LayerShape("avgpool", c, h, w, c, 1, 1, 0, 0, 1, 0, "", 0, q, qs)
         elif t == "[maxpool]":
             stride = int(s.get("stride", 1)); size = int(s.get("size", stride))
             padding = int(s.get("padding", size - 1))
@@ -170,7 +176,7 @@ def synth_weights(cfg_path: str, out_path: str, seed: int = 1234, act_gain: floa
     blob += struct.pack("<iiiQ", 0, 2, 0, 0)
     info = []
     for i, L in enumerate(layers):
-        if L.type in ("conv", "deconv"):
+        if L.type in ("conv", "deconv", "connected"):
             K = L.c // L.groups * L.size * L.size
             w = (rng.standard_normal((L.n, K)) * np.sqrt(2.0 / K)).astype(np.float32)
             if small_m_channels > 0:
@@ -202,7 +208,7 @@ def synth_weights(cfg_path: str, out_path: str, seed: int = 1234, act_gain: floa
                 rec.update(w_hat=q.copy(), weights_uint8=unflip(q), zp_w=wzp, s_w=wscale, biases=bias,
                            bn=(sc, mean, var) if L.batch_normalize else (None, None, None))
                 q, w = unflip(q), unflip(w)
-            if L.dilation > 1:  # the dense layer's record; what a check of the layer needs beside the host's prep
+            if L.dilation > 1 or L.type == "connected":  # the dense layer's record; what a check of the layer needs beside the host's prep
                 rec.update(weights_uint8=q.copy(), zp_w=wzp)
             blob += wscale.tobytes() + wzp.tobytes() + q.tobytes() + w.tobytes()
             act_q.append((a_s, a_zp))
@@ -233,7 +239,7 @@ def synth_weights(cfg_path: str, out_path: str, seed: int = 1234, act_gain: floa
             a = (np.float32((hi - lo) * 0.6 / 255.0), zp)
             blob += struct.pack("<fB", float(a[0]), int(a[1]))
             act_q.append(a)
-        else:  # yolo
+        else:  # yolo, avgpool
             act_q.append(act_q[i - 1])
     with open(out_path, "wb") as f:
         f.write(blob)
