@@ -36,7 +36,8 @@ typedef enum { LOGISTIC = 0, RELU = 1, LINEAR = 3, RELU6 = 8, LEAKY = 9 } ACTIVA
 typedef enum { CONVOLUTIONAL = 0, DECONVOLUTIONAL = 1, CONNECTED = 2, MAXPOOL = 3, ROUTE = 8, AVGPOOL = 11, SHORTCUT = 13, YOLO = 23, UPSAMPLE = 26 } LAYER_TYPE;
 
 /* layer.fuse_next: the layer after a conv that runs inside the conv's kernel.  The type of that layer decides the kind */
-enum { FUSE_NONE = 0, FUSE_POOL, FUSE_UPSAMPLE, FUSE_SHORTCUT, FUSE_YOLO };
+enum { FUSE_NONE = 0, FUSE_POOL, FUSE_UPSAMPLE, FUSE_SHORTCUT, FUSE_YOLO,
+       FUSE_SEP /* a depthwise layer and the 1x1 convolution after it in one kernel (set_fuse_separable) */ };
 
 #define QUANT_POSITIVE_LIMIT 255
 #define QUANT_NEGATIVE_LIMIT 0
@@ -262,6 +263,7 @@ struct network {
     float *od_mm_gpu;                    /* [B][2] max, min of the float path */
     void *od_const_gpu, *od_const_host;  /* mi355_l0_consts + n mi355_l0_channel */
     long host_waits;                     /* times the host library waited for the device on this network's behalf (network_host_waits) */
+    int fuse_separable;                  /* set_fuse_separable: plan_fusion may pair a depthwise layer with the 1x1 layer after it (0: never) */
 };
 
 /* ---- construction / IO ------------------------------------------------------------------------------------ */
@@ -491,6 +493,14 @@ network *network_replica_ex(network *parent, int default_stream);
  * stream, drops a captured hipGraph (it holds the other plan's kernels) and re-derives the conv + pool / upsample / yolo / residual
  * fusion flags: a launcher that declined a fused call under one plan (flag cleared at run time) is asked again under the other. */
 void network_set_plan(network *net, int plan);
+/* Opt-in fusion of depthwise-separable blocks, off by default: off, every network runs exactly as without this call.
+ * on != 0: plan_fusion pairs a depthwise layer i with layer i + 1 when that is a [convolutional] of size 1, stride 1, pad 0, groups 1,
+ * dilation 1, filters != 3 and no quant_stop that takes none of the pool / upsample / shortcut / yolo fusions itself, nothing else
+ * (route, shortcut, SPP) reads layer i, layer i is no quant_stop, and the run mode honours fusion (fuse_maxpool, no int32 dump, exact
+ * mode).  A pair is one mi355_conv_sep_forward call on the two layers' own blobs: layer i's tensor is not stored and
+ * dnq_layer_conv_kernel reports 15 for both layers.  Like network_set_plan the call waits for the executor's stream, drops a captured
+ * graph and re-plans; a replica made afterwards inherits the flag.  Returns 0. */
+int set_fuse_separable(network *net, int on);
 
 /* ---- execution ----------------------------------------------------------------------------------------------- */
 void forward_network(network *net);     /* == forward_network_gpu; dies if no device */

@@ -371,6 +371,28 @@ int mi355_connected_forward(const mi355_conv_desc *desc, const mi355_tensor *x, 
                             float *y_f32, void *workspace, void *stream);
 int mi355_avgpool_forward(const mi355_tensor *x, const mi355_tensor *y, void *stream);
 
+/* The depthwise-separable block (conv_sep.hip; Keras SeparableConv2D, the body of MobileNet / EfficientNet-lite /
+ * YOLO-Fastest): a depthwise layer and the dense 1x1 layer that reads it, in one launch.  sep(x) = pw(dw(x)) byte for byte: every output
+ * byte, accumulator and float equals mi355_conv_dw_forward(dw) into a tensor m followed by mi355_conv_forward(pw) on m in MI355_ACC_EXACT,
+ * the wrap of a wrapping depthwise store included.  The intermediate tensor m is never stored.
+ *   dw        the depthwise layer's desc: n == c == x.C >= 16, ksize 1..11, stride >= 1, pad >= 0, any of leaky / relu / relu6 / linear and
+ *             either store mode; out-of-image taps read dw.zp_in; dw.zp_act is the zero point of m
+ *   pw        the 1x1 layer's desc: c == dw.n, ksize 1, stride 1, pad 0, n >= 1 and n != 3 (a 3-filter output has 4-byte cells),
+ *             zp_in == dw.zp_act; its constants, activation, store mode and s_act make the epilogue, acc_out and y_f32 as in
+ *             mi355_conv_forward.  dw.accum_mode and pw.accum_mode must be MI355_ACC_EXACT: the 1x1 layer's step-wise fp32 sum
+ *             (MI355_ACC_REF_F32) is not reproduced in a fused K order.  pw.plan chooses the plan
+ *   blob_dw   the depthwise layer's mi355_conv_dw_pack blob;  blob_pw  the 1x1 layer's mi355_conv_pack blob: there is no packer of its own
+ *   x, y      x.cs % 16 == 0 (not the image's 4-byte cells), y.cs % 16 == 0; x.data, y.data and both blobs 16-byte aligned; y
+ *             (nullable) is the 1x1 layer's B x n x OH x OW tensor, channels >= n and pad cells of it keep their bytes;
+ *             acc_out [B][n][OH * OW] and y_f32 are the 1x1 layer's
+ * The blobs live in device memory.  The kernel compares both headers with the launch and, when one differs, reads nothing past the
+ * headers and writes nothing.  The call also reads the two headers back the first time it sees a pair of blob addresses outside a stream
+ * capture (one stream synchronisation, remembered per address) and refuses a pair that is not the launch's.
+ * Anything else returns MI355_EINVAL with a message that starts "conv_sep_forward:", nothing launched or written.  mi355_last_conv_kernel()
+ * is 15 after the call.  A new call, no struct change: MI355_ABI_VERSION is unchanged. */
+int mi355_conv_sep_forward(const mi355_conv_desc *dw, const mi355_conv_desc *pw, const mi355_tensor *x, const void *blob_dw,
+                           const void *blob_pw, const mi355_tensor *y, int32_t *acc_out, float *y_f32, void *stream);
+
 /* Tile configuration override for benchmarking (0 = auto). */
 int mi355_conv_set_tile(int bm, int bn);
 /* Development switches.  Bits 0..8 are timing ablations of the K loop (no DMA / no s_barrier / no MFMA / ...), compiled

@@ -10,6 +10,7 @@
   python tools/conv_microbench.py --group [--out FILE]  # grouped 3x3 (conv_group.hip) against its dense twin and the HBM floor
   python tools/conv_microbench.py --dil [--out FILE]  # dilated 3x3 (conv_dil.hip) against the same layer at d = 1, its stuffed twin and the HBM floor
   python tools/conv_microbench.py --fc [--out FILE]   # connected / avgpool (classify.hip) against the layer spelled as a convolution and the HBM floor
+  python tools/conv_microbench.py --sep [--out FILE]  # the fused depthwise-separable launch (conv_sep.hip) against conv_dw + the 1x1 layer and the HBM floor
 """
 import argparse
 import ctypes as C
@@ -133,6 +134,56 @@ def run_dw(iters, repeats):
                                  "dense_kernel": binding.last_conv_kernel(), "bytes_equal": same, "hbm_floor_us": floor_us,
                                  "dw_over_dense": float(np.median(t_dw) / np.median(t_dense)),
                                  "dw_over_floor": float(np.median(t_dw) / floor_us)})
+    return out
+
+
+def run_sep(iters, repeats):
+    """The fused depthwise-separable launch (conv_sep.hip) against the two-launch pair, conv_dw + the 1x1 layer, on the same buffers:
+    five MobileNet-style shapes at batch 32, 3x3 depthwise.  The two alternate, `repeats` rounds; medians and ranges in microseconds,
+    the HBM floor of input + output bytes, and equal output bytes checked in the run."""
+    S = binding.shim()
+    st = C.c_void_p(); binding.check(S.mi355_stream_create(C.byref(st)))
+    nb = 256 << 20
+    src, dst = binding.DevBuf(nb), binding.DevBuf(nb)
+    copy_us = [_time_us(lambda: binding.check(S.mi355_d2d(dst.ptr, src.ptr, nb, st), "d2d"), st, 10) for _ in range(repeats)]
+    bw = 2.0 * nb / (np.median(copy_us) * 1e-6)
+    src.free(); dst.free()
+    out = {"copy_256MiB_us": copy_us, "copy_bytes_per_s": bw, "iters": iters, "cases": []}
+    for c, hw, stride, n in ((64, 208, 1, 128), (128, 104, 2, 256), (256, 52, 1, 256), (512, 26, 1, 512), (960, 13, 1, 320)):
+        rng = np.random.default_rng(c + n)
+        B, k = 32, 3
+        x = rng.integers(0, 256, (B, c, hw, hw), dtype=np.uint8)
+        wd = rng.integers(0, 256, (c, k * k), dtype=np.uint8)
+        wp = rng.integers(0, 256, (n, c), dtype=np.uint8)
+        zd, zp = rng.integers(100, 157, c, dtype=np.uint8), rng.integers(100, 157, n, dtype=np.uint8)
+        ohw = (hw + 2 - k) // stride + 1
+        xt = binding.DevTensor.from_nchw(x, 0)
+        mid = binding.DevTensor(B, ohw, ohw, c, 23)
+        y, yf = binding.DevTensor(B, ohw, ohw, n, 23), binding.DevTensor(B, ohw, ohw, n, 23)
+        bd = binding.DevBuf.from_numpy(binding.conv_dw_pack(wd, zd, k, np.zeros(c, np.int32), np.full(c, 0.75), np.full(c, 2.0 ** -7)))
+        bp = binding.DevBuf.from_numpy(binding.conv_pack(wp, zp, c, 1, np.zeros(n, np.int32), np.full(n, 0.75), np.full(n, 2.0 ** -SHIFT)))
+        dd = binding.ConvDesc(c, c, k, stride, 1, binding.ACT["leaky"], 0, 0, 0, 23, 1.0)
+        dp = binding.ConvDesc(n, c, 1, 1, 0, binding.ACT["leaky"], 0, 0, 23, 23, 1.0)
+
+        def pair():
+            binding.check(S.mi355_conv_dw_forward(C.byref(dd), xt.ref(), bd.ptr, mid.ref(), None, None, st), "dw")
+            binding.check(S.mi355_conv_forward(C.byref(dp), mid.ref(), bp.ptr, None, None, y.ref(), None, None, st), "pw")
+
+        def fused():
+            binding.check(S.mi355_conv_sep_forward(C.byref(dd), C.byref(dp), xt.ref(), bd.ptr, bp.ptr, yf.ref(), None, None, st), "sep")
+        t_f, t_p = [], []
+        for _ in range(repeats):
+            t_f.append(_time_us(fused, st, iters)); t_p.append(_time_us(pair, st, iters))
+        pair()
+        pw_kernel = binding.last_conv_kernel()
+        fused()
+        launch = binding.last_conv_launch()
+        S.mi355_stream_sync(st)
+        same = bool(np.array_equal(y.to_nchw(), yf.to_nchw()))
+        floor_us = B * (c * hw * hw + n * ohw * ohw) / bw * 1e6
+        out["cases"].append({"c": c, "hw": hw, "stride": stride, "n": n, "batch": B, "fused_us": t_f, "pair_us": t_p, "pw_kernel": pw_kernel,
+                             "fused_launch": launch, "bytes_equal": same, "hbm_floor_us": floor_us,
+                             "fused_over_pair": float(np.median(t_f) / np.median(t_p)), "fused_over_floor": float(np.median(t_f) / floor_us)})
     return out
 
 
@@ -379,6 +430,7 @@ def run_fc(iters, repeats):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--fc", action="store_true", help="connected / avgpool against the layer spelled as a convolution and the HBM floor")
+    ap.add_argument("--sep", action="store_true", help="fused depthwise + 1x1 against the two-launch pair and the HBM floor")
     ap.add_argument("--dil", action="store_true", help="dilated 3x3 against the same layer at d = 1, its stuffed twin and the HBM floor")
     ap.add_argument("--group", action="store_true", help="grouped 3x3 against its dense twin and the HBM floor")
     ap.add_argument("--tr", action="store_true", help="transposed k4 s2 / k2 s2 against the stuffed dense twin and the HBM floor")
@@ -402,8 +454,8 @@ if __name__ == "__main__":
     binding.init(0)
     if a.dbg:
         binding.shim().mi355_debug_flags(a.dbg)
-    if a.dw or a.spp or a.tr or a.group or a.dil or a.fc:
-        fn = run_fc if a.fc else run_dil if a.dil else (run_group if a.group else (run_tr if a.tr else (run_spp if a.spp else run_dw)))
+    if a.dw or a.spp or a.tr or a.group or a.dil or a.fc or a.sep:
+        fn = run_sep if a.sep else run_fc if a.fc else run_dil if a.dil else (run_group if a.group else (run_tr if a.tr else (run_spp if a.spp else run_dw)))
         r = fn(a.iters, a.repeats)
         print(json.dumps(r))
         if a.out:

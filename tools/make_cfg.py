@@ -10,6 +10,7 @@ accepts: /root/reference/src/parser.c:170-204 (convolutional), 411-431 (maxpool)
   cfg/yolov3_quant.cfg             full YOLOv3 @608 (75 convs, 23 quantized [shortcut]s, 3 heads) -- BASELINE config[4]
   cfg/res_unit.cfg                 16x16 unit net for the quantized residual add and the glue layers' quant_stop tails
   cfg/s2_unit.cfg                  24x24 chain of stride-2 3x3 convolutions (the downsampling layers of full YOLOv3)
+  cfg/sep_unit.cfg                 24x24 net of depthwise + 1x1 pairs, fused and refused, for set_fuse_separable
   cfg/dw_unit.cfg                  24x24 depthwise-separable unit net (groups = channels layers between 1x1 convolutions)
   cfg/tr_unit.cfg                  24x24 unit net with two [deconvolutional] layers (k4 s2 p1, k2 s2 p0) and a route over one of them
   cfg/dil_unit.cfg                 20x20 small ASPP: three parallel dilated 3x3 branches (dilation 2, 3, 5) on one tensor, a route, a 1x1
@@ -97,6 +98,25 @@ def dw_unit(act="leaky"):
     s += conv(30, 1, "linear", bn=0, stop=1)          # 6
     s += yolo("0,1,2")                                # 7
     return s
+
+def sep_unit(act="leaky"):
+    """24x24 unit net of depthwise + 1x1 pairs for set_fuse_separable: three pairs the planner takes and two it refuses"""
+    s = net(24, 24)
+    s += conv(16, 3, act)                             # 0   3 -> 16
+    s += conv(16, 3, act, groups=16)                  # 1   pair: 3x3 s1 ...
+    s += conv(32, 1, act)                             # 2   ... into 1x1 leaky
+    s += conv(32, 3, "relu6", stride=2, groups=32)    # 3   pair: 3x3 s2 relu6 ...            12x12
+    s += conv(32, 1, "linear")                        # 4   ... into 1x1 linear
+    s += conv(32, 5, act, groups=32)                  # 5   pair: 5x5 s1 (pad 2) ...
+    s += conv(48, 1, act)                             # 6   ... into a 1x1 whose output a route reads
+    s += conv(48, 3, act, groups=48)                  # 7   refused: the depthwise output is also routed (layer 9)
+    s += conv(32, 1, act)                             # 8
+    s += route("-2,-3")                                # 9   48 + 48 = 96
+    s += conv(96, 3, act, groups=96)                  # 10  refused: the 1x1 after it is the head, which fuses with yolo
+    s += conv(30, 1, "linear", bn=0, stop=1)          # 11
+    s += yolo("0,1,2")
+    return s
+
 
 def deconv(filters, size, stride, padding, act, bn=1, stop=0):
     s = "[deconvolutional]\n"
@@ -236,6 +256,7 @@ if __name__ == "__main__":
     open(os.path.join(out, "yolov3_quant.cfg"), "w").write(yolov3())
     open(os.path.join(out, "res_unit.cfg"), "w").write(res_unit())
     open(os.path.join(out, "dw_unit.cfg"), "w").write(dw_unit())
+    open(os.path.join(out, "sep_unit.cfg"), "w").write(sep_unit())
     open(os.path.join(out, "tr_unit.cfg"), "w").write(tr_unit())
     open(os.path.join(out, "dil_unit.cfg"), "w").write(dil_unit())
     open(os.path.join(out, "cls_unit.cfg"), "w").write(cls_unit())

@@ -285,6 +285,9 @@ def shim():
             L.mi355_connected_workspace_size.restype = C.c_size_t
             L.mi355_connected_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(Tensor), vp, C.POINTER(Tensor), vp, vp, vp, vp]
             L.mi355_avgpool_forward.argtypes = [C.POINTER(Tensor), C.POINTER(Tensor), vp]
+        if hasattr(L, "mi355_conv_sep_forward"):  # (MI355_LIB_DIR may name an older build)
+            L.mi355_conv_sep_forward.argtypes = [C.POINTER(ConvDesc), C.POINTER(ConvDesc), C.POINTER(Tensor), vp, vp, C.POINTER(Tensor),
+                                                 vp, vp, vp]
         L.mi355_last_conv_kernel.argtypes = []
         L.mi355_last_conv_kernel.restype = ci
         if hasattr(L, "mi355_last_conv_launch"):  # (absent from older A/B builds under build_ab/)
@@ -541,6 +544,37 @@ def conv_dw_forward(x: DevTensor, wq, zp_w, ksize, biases_int32, M_value, shift_
         out["int32"] = acc.to_numpy(np.int32, cnt).reshape(x.t.B, c, OH * OW)
     if f32:
         out["f32"] = f32.to_numpy(np.float32, cnt).reshape(x.t.B, c, OH * OW)
+    return out
+
+
+def conv_sep_forward(x: DevTensor, dw, pw, store=STORE_WRAP, accum=ACC_EXACT, want_acc=True, want_f32=False, plan=0, y=None):
+    """One depthwise-separable block (a depthwise layer and the 1x1 layer that reads it) through mi355_conv_sep_forward, one launch.
+    dw = dict(wq [c, k * k], zp_w, ksize, bias, M, shift, zp_in, zp_act, activation, stride=1, pad=ksize // 2, store=STORE_WRAP),
+    pw = dict(wq [n, c], zp_w, bias, M, shift, zp_act, s_act, activation); `store` is the 1x1 layer's.  Results are the 1x1 layer's,
+    as conv_forward's: dict(u8 NCHW, int32 [B, n, HW], f32).  y: the output DevTensor to write into (default: a fresh one)."""
+    c, k = x.t.C, int(dw["ksize"])
+    n = np.asarray(pw["wq"]).shape[0]
+    blob_dw = DevBuf.from_numpy(conv_dw_pack(dw["wq"], dw["zp_w"], k, dw["bias"], dw["M"], dw["shift"]))
+    blob_pw = DevBuf.from_numpy(conv_pack(np.asarray(pw["wq"]).reshape(n, -1), pw["zp_w"], c, 1, pw["bias"], pw["M"], pw["shift"]))
+    stride, pad = int(dw.get("stride", 1)), dw.get("pad")
+    if pad is None:
+        pad = k // 2
+    OH, OW = (x.t.H + 2 * pad - k) // stride + 1, (x.t.W + 2 * pad - k) // stride + 1
+    if y is None:
+        y = DevTensor(x.t.B, OH, OW, n, pw["zp_act"])
+    cnt = x.t.B * n * OH * OW
+    acc = DevBuf(cnt * 4) if want_acc else None
+    f32 = DevBuf(cnt * 4) if want_f32 else None
+    dd = ConvDesc(c, c, k, stride, pad, dw["activation"], dw.get("store", STORE_WRAP), accum, dw["zp_in"], dw["zp_act"], 0.0, int(plan), 0)
+    dp = ConvDesc(n, c, 1, 1, 0, pw["activation"], store, accum, dw["zp_act"], pw["zp_act"], float(pw["s_act"]), int(plan), 0)
+    check(shim().mi355_conv_sep_forward(C.byref(dd), C.byref(dp), x.ref(), blob_dw.ptr, blob_pw.ptr, y.ref(),
+                                        acc.ptr if acc else None, f32.ptr if f32 else None, None), "conv_sep_forward")
+    check(shim().mi355_stream_sync(None), "sync")
+    out = {"u8": y.to_nchw(), "tensor": y}
+    if acc:
+        out["int32"] = acc.to_numpy(np.int32, cnt).reshape(x.t.B, n, OH * OW)
+    if f32:
+        out["f32"] = f32.to_numpy(np.float32, cnt).reshape(x.t.B, n, OH * OW)
     return out
 
 
@@ -879,6 +913,9 @@ def host():
         L.network_load_packed.argtypes = [vp, C.c_char_p]
         L.dnq_layer_conv_kernel.argtypes = [vp, ci]
         L.dnq_layer_conv_kernel.restype = ci
+        if hasattr(L, "set_fuse_separable"):  # (MI355_LIB_DIR may name an older build)
+            L.set_fuse_separable.argtypes = [vp, ci]
+            L.set_fuse_separable.restype = ci
         if hasattr(L, "dnq_layer_dilation"):
             L.dnq_layer_dilation.argtypes = [vp, ci]
             L.dnq_layer_dilation.restype = ci
@@ -2035,6 +2072,11 @@ class Net:
     def spp(self, i):
         """dnq_layer_spp: 0, 1 for the leading [maxpool] of a fused SPP group (it runs mi355_spp_forward for the group), 2 for a member"""
         return int(self.H.dnq_layer_spp(self.h, i))
+
+    def set_fuse_separable(self, on=True):
+        """set_fuse_separable: let the planner run a depthwise layer and the 1x1 layer after it as one mi355_conv_sep_forward call
+        (DESIGN.md 7h).  Off by default; re-plans like a change of plan."""
+        assert self.H.set_fuse_separable(self.h, int(bool(on))) == 0
 
     def is_fused(self, i):
         """conv i runs fused with the layer after it and its own uint8 tensor is not stored."""

@@ -239,6 +239,44 @@ struct DwArgs {
 constexpr int DW_RUN = 8;    // output pixels along x per lane; the tile is 2^ry_sh rows by (16 >> ry_sh) * DW_RUN columns
 int conv_dw_launch(DwArgs &a, hipStream_t st);  // MI355_EINVAL when no tile fits LDS (nothing launched)
 
+// conv_sep.hip: the depthwise-separable block: a depthwise layer (its mi355_conv_dw_pack blob) and the dense 1x1
+// layer that reads it (its mi355_conv_pack blob) in one launch; the intermediate tensor stays in LDS
+struct SepArgs {
+    const uint8_t *x;        // input tensor, biased PHWC (cs % 16 == 0, data 16-byte aligned)
+    int in_cs, in_lead;
+    int B, H, W, c;          // input map; channels == depthwise filters == the 1x1 layer's channels
+    int ksize, stride, pad, OH, OW;  // the depthwise layer's; OH x OW is also the 1x1 layer's map
+    // depthwise stage (DwBlobHeader's arrays)
+    const int16_t *wd;
+    const int32_t *dbias;
+    const double *dmval, *dsval, *dmprime;
+    const DwBlobHeader *dhdr;  // device copy: compared with the launch, and the pow2 flag
+    int zp_in, zp_mid, dact, dstore;  // zp_mid: the depthwise layer's zp_act = the 1x1 layer's zp_in
+    // pointwise stage (ConvBlobHeader's arrays)
+    int n;
+    const int8_t *wk;        // gen: general-kernel A fragments [mpad / 32][ksteps][64 lanes][16 B]; else the row plane [mpad / 16][ksteps][4][16 rows][16 B]
+    int gen, cb_sh, ksteps;  // cb_sh: log2 of the row plane's 16-channel units per K-step (cb / 16)
+    int mt32;                // 32-row tiles the plane holds: mpad / 32
+    const int32_t *cw, *dzp, *bias;
+    const double *mval, *sval, *mprime;
+    const ConvBlobHeader *hdr;  // device copy: compared with the launch, and the pow2 flag
+    uint8_t *y;
+    int out_cs, out_lead;
+    int32_t *acc_out;
+    float *y_f32;
+    int zp_act, act, store_mode;
+    float s_act;
+    int plan;
+    // tile geometry (set by the launcher): conv_dw.hip's tile and patch, and this kernel's buffers
+    int ry_sh, tiles_x, tiles_y, nchunks;
+    int ph, pw, pitch, pieces16;
+    int pbytes, pbufs;       // bytes of one patch buffer (patch, then the runtime-size path's weights); patch buffers: 1 | 2
+    int fblocks;             // filter blocks of 128 (n <= SEP_FILTERS_MS1) or 256 filters: the depthwise stage is recomputed per block
+    FastDiv fd_pw;
+};
+constexpr int SEP_FILTERS_MS1 = 128;  // up to here a wave owns 32 filters (64 accumulator registers), above 64 (128)
+int conv_sep_launch(SepArgs &a, hipStream_t st);  // MI355_EINVAL when no tile fits LDS (nothing launched)
+
 // conv_tr.hip: the transposed convolution ([deconvolutional]), split into its stride x stride output phases.  Phase
 // (ty, tx) owns the taps ky = ty + s jy, kx = tx + s jx, numbered t = jy * tr_taps(k, s, tx) + jx.  With nu = ceil(c / 16) channel
 // units, a phase's K-steps (32 bytes: two lane halves of one unit of one tap) are dense: first (unit pair up, tap t) -> step

@@ -1297,6 +1297,109 @@ int mi355_conv_dil_forward(const mi355_conv_desc *d, const mi355_tensor *x, cons
     return rc;
 }
 
+// ------------------------------------------------------------------------------------- depthwise-separable block (conv_sep.hip)
+// The pairs of blob addresses whose device headers have been read back and found to be the launch's (n, c, ksize), per device: one
+// stream synchronisation the first time a pair is seen, none after.  64 sets of 4 ways, the oldest way of a set replaced, so the blob
+// pairs of one network (13 to 17) do not evict each other.  A stale entry (a blob freed, its address reused) only loses the message:
+// the kernel compares the headers itself and does nothing on a mismatch.  Inside a stream capture nothing is read back (the kernel's
+// check stands alone); the read-back is a synchronising copy, so the first call on a pair must not run while ANOTHER thread captures
+// in hipStreamCaptureModeGlobal (this library captures thread-locally: mi355_graph_begin).
+static int sep_blobs_known(const void *bd, const void *bp, int n, int c, int k, hipStream_t st)
+{
+    struct Seen { const void *bd, *bp; int n, c, k, dev; };
+    static Seen seen[64][4];
+    static unsigned char next_way[64];
+    static std::mutex mu;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const size_t set = (((uintptr_t)bd >> 4) * 31 + ((uintptr_t)bp >> 4) + (size_t)dev) & 63;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        for (const Seen &e : seen[set])
+            if (e.bd == bd && e.bp == bp && e.n == n && e.c == c && e.k == k && e.dev == dev) return MI355_OK;
+    }
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return MI355_OK;
+    DwBlobHeader hd;
+    ConvBlobHeader hp;
+    HIPCHK(hipMemcpyAsync(&hd, bd, sizeof(hd), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&hp, bp, sizeof(hp), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (hd.magic != MI355_DW_MAGIC || hd.c != c || hd.ksize != k)
+        return einval("conv_sep_forward: blob_dw is not the mi355_conv_dw_pack blob of (dw.c, dw.ksize)");
+    if (hp.magic != MI355_BLOB_MAGIC || hp.n != n || hp.c != c || hp.ksize != 1)
+        return einval("conv_sep_forward: blob_pw is not the mi355_conv_pack blob of (pw.n, pw.c, 1)");
+    std::lock_guard<std::mutex> lk(mu);
+    seen[set][next_way[set]++ & 3] = Seen{bd, bp, n, c, k, dev};
+    return MI355_OK;
+}
+
+int mi355_conv_sep_forward(const mi355_conv_desc *dw, const mi355_conv_desc *pw, const mi355_tensor *x, const void *blob_dw,
+                           const void *blob_pw, const mi355_tensor *y, int32_t *acc_out, float *y_f32, void *stream)
+{
+    if (!dw || !pw || !x || !x->data || !blob_dw || !blob_pw) return einval("conv_sep_forward: null");
+    if (dw->n != dw->c) return einval("conv_sep_forward: depthwise means dw.n == dw.c (channel multipliers are not served)");
+    if (dw->c < 16) return einval("conv_sep_forward: need dw.c >= 16");
+    if (dw->ksize < 1 || dw->ksize > 11) return einval("conv_sep_forward: dw.ksize must be 1..11");
+    if (dw->stride < 1 || dw->pad < 0) return einval("conv_sep_forward: need dw.stride >= 1 and dw.pad >= 0");
+    if (pw->ksize != 1 || pw->stride != 1 || pw->pad != 0) return einval("conv_sep_forward: the pointwise layer is ksize 1, stride 1, pad 0");
+    if (pw->c != dw->n) return einval("conv_sep_forward: pw.c != dw.n");
+    if (pw->n < 1 || pw->n == 3) return einval("conv_sep_forward: need pw.n >= 1 and pw.n != 3 (a 3-filter output has 4-byte cells)");
+    if (pw->zp_in != dw->zp_act) return einval("conv_sep_forward: pw.zp_in != dw.zp_act (the intermediate tensor has one zero point)");
+    if (dw->accum_mode != MI355_ACC_EXACT || pw->accum_mode != MI355_ACC_EXACT)
+        return einval("conv_sep_forward: MI355_ACC_EXACT only (the pointwise layer's step-wise fp32 sum is not reproduced in a fused K order)");
+    for (const mi355_conv_desc *d : {dw, pw})
+        if (d->activation != MI355_ACT_LEAKY && d->activation != MI355_ACT_RELU && d->activation != MI355_ACT_RELU6 && d->activation != MI355_ACT_LINEAR)
+            return einval("conv_sep_forward: activation must be leaky, relu, relu6 or linear");
+    if (x->cs % 16 || x->cs < (dw->c + 15) / 16 * 16)
+        return einval("conv_sep_forward: x.cs must be a multiple of 16 that holds the channels (the 3-channel image's 4-byte cells are not served)");
+    if (x->C != dw->c) return einval("conv_sep_forward: x.C != dw.c");
+    const long OHl = ((long)x->H + 2L * dw->pad - dw->ksize) / dw->stride + 1, OWl = ((long)x->W + 2L * dw->pad - dw->ksize) / dw->stride + 1;
+    if (x->B < 1 || x->H < 1 || x->W < 1 || x->H + 2L * dw->pad < dw->ksize || x->W + 2L * dw->pad < dw->ksize || OHl < 1 || OWl < 1)
+        return einval("conv_sep_forward: the padded map is smaller than the depthwise kernel");
+    if (OHl * OWl > (1L << 30)) return einval("conv_sep_forward: the output map must stay below 2^30 pixels");
+    if (y && (y->C != pw->n || y->B != x->B || y->H != OHl || y->W != OWl || !y->data || y->cs % 16 || y->cs < pw->n))
+        return einval("conv_sep_forward: y shape (y.cs must be a multiple of 16 that holds the filters)");
+    if (((uintptr_t)x->data & 15) || ((uintptr_t)blob_dw & 15) || ((uintptr_t)blob_pw & 15) || (y && ((uintptr_t)y->data & 15)))
+        return einval("conv_sep_forward: x.data, y.data and both blobs must be aligned to 16 bytes");
+    DwBlobHeader hd;
+    ConvBlobHeader hp;
+    if (!dw_blob_layout(dw->c, dw->ksize, &hd) || blob_layout(pw->n, pw->c, 1, &hp) != MI355_OK || (hp.generic && !hp.off_gen))
+        return einval("conv_sep_forward: no blob of this shape");
+    const int known = sep_blobs_known(blob_dw, blob_pw, pw->n, pw->c, dw->ksize, (hipStream_t)stream);
+    if (known != MI355_OK) return known;
+    const char *bd = (const char *)blob_dw, *bp = (const char *)blob_pw;
+    SepArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = (const uint8_t *)x->data; a.in_cs = x->cs; a.in_lead = x->lead;
+    a.B = x->B; a.H = x->H; a.W = x->W; a.c = dw->c;
+    a.ksize = dw->ksize; a.stride = dw->stride; a.pad = dw->pad; a.OH = (int)OHl; a.OW = (int)OWl;
+    a.wd = (const int16_t *)(bd + hd.off_wd); a.dbias = (const int32_t *)(bd + hd.off_bias);
+    a.dmval = (const double *)(bd + hd.off_mval); a.dsval = (const double *)(bd + hd.off_sval);
+    a.dmprime = (const double *)(bd + hd.off_mprime);
+    a.dhdr = (const DwBlobHeader *)bd;
+    a.zp_in = dw->zp_in; a.zp_mid = dw->zp_act; a.dact = dw->activation; a.dstore = dw->store_mode;
+    a.n = pw->n;
+    a.gen = hp.generic;
+    a.wk = (const int8_t *)(bp + (hp.generic ? hp.off_gen : hp.off_wp));
+    a.ksteps = hp.ksteps; a.mt32 = hp.mpad / 32;
+    a.cb_sh = hp.generic ? 0 : (hp.cb == 64 ? 2 : (hp.cb == 32 ? 1 : 0));
+    a.cw = (const int32_t *)(bp + hp.off_cw); a.dzp = (const int32_t *)(bp + hp.off_dzp);
+    a.bias = (const int32_t *)(bp + hp.off_bias);
+    a.mval = (const double *)(bp + hp.off_mval); a.sval = (const double *)(bp + hp.off_sval);
+    a.mprime = (const double *)(bp + hp.off_mprime);
+    a.hdr = (const ConvBlobHeader *)bp;
+    a.y = y ? (uint8_t *)y->data : nullptr; a.out_cs = y ? y->cs : 0; a.out_lead = y ? y->lead : 0;
+    a.acc_out = acc_out; a.y_f32 = y_f32;
+    a.zp_act = pw->zp_act; a.act = pw->activation; a.store_mode = pw->store_mode; a.s_act = pw->s_act;
+    a.plan = pw->plan;
+    const int rc = conv_sep_launch(a, (hipStream_t)stream);
+    if (rc == MI355_EINVAL) return einval("conv_sep_forward: no tile of the kernel fits this stride and size in LDS");
+    if (rc != MI355_OK) return hip_fail(hipGetLastError(), "conv_sep launch");
+    g_last_kernel = 15;
+    return rc;
+}
+
 // ------------------------------------------------------------------------------------- classifier tail (classify.hip)
 size_t mi355_connected_pack_size(int n, int C, int H, int W, int cs)
 {

@@ -91,7 +91,8 @@ int dnq_layer_is_fused(network *net, int i)
 {
     if (i < 0 || i >= net->n) return 0;
     const layer *l = &net->layers[i];
-    return fusion_on(net) && ((l->fuse_next == FUSE_POOL && !l->fuse_pool_keep) || l->fuse_next == FUSE_UPSAMPLE || l->fuse_next == FUSE_SHORTCUT);
+    return fusion_on(net) && ((l->fuse_next == FUSE_POOL && !l->fuse_pool_keep) || l->fuse_next == FUSE_UPSAMPLE || l->fuse_next == FUSE_SHORTCUT ||
+                              l->fuse_next == FUSE_SEP);
 }
 
 /* layer i + 1 runs inside layer i's kernel (whether or not layer i's own tensor is stored as well) */

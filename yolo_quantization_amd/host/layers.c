@@ -60,7 +60,7 @@ static int conv_pool(const layer *l, const network *net, const mi355_conv_desc *
 static void forward_convolutional_layer_quant_gpu(layer l, network net)
 {
     static const char *const fused_name[] = { "mi355_conv_forward", "mi355_conv_pool_forward", "mi355_conv_upsample_forward",
-                                              "mi355_conv_shortcut_forward", "mi355_conv_yolo_forward" };
+                                              "mi355_conv_shortcut_forward", "mi355_conv_yolo_forward", "mi355_conv_sep_forward" };
     if (!l.prepared) error("forward_gpu before quantization_weights_and_activations");
     mi355_conv_desc d;
     memset(&d, 0, sizeof(d));
@@ -114,6 +114,16 @@ static void forward_convolutional_layer_quant_gpu(layer l, network net)
         if (rc == MI355_EINVAL)
             rc = mi355_conv_yolo_forward(&d, net.cur_t, l.blob_gpu, &l.out_t, l.output_gpu, next->output_gpu, next->classes, net.stream);
         break;
+    case FUSE_SEP: { /* this depthwise layer and the 1x1 layer after it in one kernel; this layer's own tensor is not stored */
+        mi355_conv_desc dp = d;
+        dp.n = next->n; dp.c = next->c; dp.ksize = 1; dp.stride = 1; dp.pad = 0;
+        dp.activation = next->activation;
+        dp.zp_in = next->input_data_uint8_zero_point[0];
+        dp.zp_act = next->activ_data_uint8_zero_point[0];
+        dp.s_act = next->activ_data_uint8_scales[0];
+        rc = mi355_conv_sep_forward(&d, &dp, net.cur_t, l.blob_gpu, next->blob_gpu, &next->out_t, NULL, NULL, net.stream);
+        break;
+    }
     }
     if (kind != FUSE_NONE) {
         if (rc != MI355_EINVAL) { check_mi355(rc, fused_name[kind]); return; }

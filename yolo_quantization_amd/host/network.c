@@ -497,6 +497,15 @@ static void plan_fusion(network *net)
         }
     }
     for (int i = 1; i < net->n;) i = net->layers[i].type == MAXPOOL ? spp_group(net, i) : i + 1;
+    /* set_fuse_separable: a depthwise layer and the 1x1 layer after it in one kernel (conv_sep.hip).  After the loops above: the 1x1
+     * layer must take none of their fusions (it is skipped on its turn), and no SPP leader may read the depthwise layer */
+    for (int i = 0; net->fuse_separable && i + 1 < net->n; ++i) {
+        layer *c = &net->layers[i], *p = &net->layers[i + 1];
+        if (c->type != CONVOLUTIONAL || c->groups <= 1 || c->c < 16 || c->quant_stop_flag || output_read_elsewhere(net, i)) continue;
+        if (p->type != CONVOLUTIONAL || p->size != 1 || p->stride != 1 || p->pad != 0 || p->groups > 1 || p->dilation > 1 || p->n == 3) continue;
+        if (p->quant_stop_flag || p->fuse_next != FUSE_NONE) continue;
+        c->fuse_next = FUSE_SEP;
+    }
 }
 
 void quantization_weights_and_activations_fixed_input(network *net, float in_scale, uint8_t in_zp)
@@ -1119,6 +1128,7 @@ static void run_layers(network *netp)
          * handed on and the layer skipped.  A yolo layer hands on the head conv's uint8 tensor and its own activations. */
         if (asked != FUSE_NONE && netp->layers[i].fuse_next == asked) {
             ++i;
+            if (asked == FUSE_SEP) netp->layers[i].conv_kernel = netp->layers[i - 1].conv_kernel; /* one kernel served both layers */
             net.cur_t = &netp->layers[asked == FUSE_YOLO ? i - 1 : i].out_t;
             net.cur_f32_gpu = asked == FUSE_YOLO ? netp->layers[i].output_gpu : NULL;
             if (ev) check_mi355(mi355_event_record(ev[i + 2], net.stream), "event");
@@ -1627,6 +1637,14 @@ static void set_plan_internal(network *net, int plan)
     if (net->prepared) plan_fusion(net);
 }
 
+int set_fuse_separable(network *net, int on)
+{
+    net->fuse_separable = on != 0;
+    set_plan_internal(net, net->plan); /* waits, drops a graph captured with the other pairing, re-plans */
+    if (!net->prepared) plan_fusion(net); /* pure host logic: readable (dnq_layer_is_fused) before a device is touched */
+    return 0;
+}
+
 void network_set_plan(network *net, int plan)
 {
     net->plan_user = plan;
@@ -1650,6 +1668,7 @@ network *network_replica_ex(network *parent, int default_stream)
     net->gpu_index = parent->gpu_index;
     net->accum_mode = parent->accum_mode; net->store_mode = parent->store_mode;
     net->fuse_maxpool = parent->fuse_maxpool; net->keep_head_float = parent->keep_head_float;
+    net->fuse_separable = parent->fuse_separable;
     net->use_graph = parent->use_graph; net->input_direct_off = parent->input_direct_off;
     net->per_image = parent->per_image; /* its own bank (allocated by its first per-image batch); layer 0's raw weights are the parent's */
     net->input_on_device = parent->input_on_device; /* its own bank, pair and status arrays and copy of the constant table */
